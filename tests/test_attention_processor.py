@@ -33,6 +33,12 @@ def test_call_signature_is_the_references():
     defaults = {k: v.default for k, v in ours.parameters.items() if v.default is not inspect._empty}
     assert defaults == dict(encoder_hidden_states=None, attention_mask=None, temb=None, inflate_self_attention=False,
                             freqs_rot=None, n_frames=None)
+    # the reference's own signature, as recorded from it (tests/golden/reference_signatures.json, oracle/make_golden_signatures.py)
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_signatures.json")) as f:
+        rec = json.load(f)["AttentionProcessor"]["__call__"]
+    assert [n for n, _, _ in rec] == names
+    assert {n: d for n, _, d in rec if d is not None} == {k: repr(v) for k, v in defaults.items()}
     if os.path.isdir(REF):
         _shim_attention()
         sys.path.insert(0, REF)

@@ -98,14 +98,16 @@ def test_copy_engine_exchange_on_real_ranks(world):
     _run(world, env_extra={"ACTIONMESH_AMD_EXCHANGE": "peer"})          # the same back-end under HipDenoiser + RCCL control plane
 
 
-def _bench(world, extra=(), bare=False):
+def _bench(world, extra=(), bare=False, full=True):
     """bench.py itself, as the driver launches it (torch.distributed.run for N > 1), with every rank on ONE device.  `bare`: N > 1
-    WITHOUT a launcher around it - bench.py re-executes itself under torch.distributed.run (round 6)."""
+    WITHOUT a launcher around it - bench.py re-executes itself under torch.distributed.run (round 6).  `full`: with --full (the
+    roofline and the N > 1 fingerprint check these tests read are left out of a plain run)."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--shape", "small", "--no-cpu-baseline", *extra]
+    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--shape", "small", *(["--full", "--no-cpu-baseline"] if full else []),
+            *extra]
     if world == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args]
     elif bare:
@@ -118,6 +120,23 @@ def _bench(world, extra=(), bare=False):
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, f"exactly ONE JSON line on rank 0, got {len(lines)}:\n" + r.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` times the steps and nothing else (no roofline, nominal, cpu_baseline or exact-shortcut timing), and
+    --dump-outputs writes the latents the timed steps produced: the array the line's fingerprint was taken from."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    d = _bench(1, ("--steps", "3", "--dump-outputs", str(tmp_path)), full=False)
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["ms_per_step"] * d["value"] - 1e3) < 0.01 * 1e3
+    assert not {"roofline", "nominal", "cpu_baseline", "with_exact_shortcuts"} & set(d)
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (1, 4, 512, 64) and np.isfinite(lat).all()
+    fp = d["latents_fingerprint"]
+    assert fp["after_steps"] == 4
+    assert abs(float(np.sqrt((lat[0, 1:].astype(np.float64) ** 2).mean())) - fp["rms"]) <= 1e-9 * max(1.0, fp["rms"])
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp8"])

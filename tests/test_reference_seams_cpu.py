@@ -1,7 +1,8 @@
-"""Seams S1 / S2 against the REFERENCE's own classes (CPU; build container only - skipped where /root/reference is absent,
-e.g. on the GPU box).
+"""Seams S1 / S2 against the REFERENCE's own classes (CPU).  2. and the overlay check need the reference checkout (REF) and are
+skipped where it is absent; 1. runs everywhere.
 
-1. `inspect.signature` equality of the drop-in surfaces with the reference classes they replace.
+1. `inspect.signature` equality of the drop-in surfaces with the reference classes they replace, as recorded from the reference in
+   tests/golden/reference_signatures.json (oracle/make_golden_signatures.py; re-checked against the live classes where present).
 2. The reference's OWN `SchedulerFlow` + `ClassifierFreeGuidance` objects (not a restated loop) drive `HipDenoiser`
    through the S2 protocol - keyword call, opaque `freqs_rot` cache handed back, batched and `split_cfg_batch=True`
    (one forward per CFG branch re-using branch 0's cache object, scheduler.py:159-168).  There is no GPU here, so the
@@ -19,7 +20,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "actionmesh")), reason="reference not present")
+HAVE_REF = os.path.isdir(os.path.join(REF, "actionmesh"))
+needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference not present")
 
 
 def _ref():
@@ -37,25 +39,51 @@ def _sig(fn):
     return [(n, p.kind, p.default) for n, p in s.parameters.items()]
 
 
-def test_signatures_equal_the_references():
+def _recorded_signatures(golden_dir):
+    import json
+    with open(os.path.join(golden_dir, "reference_signatures.json")) as f:
+        return json.load(f)
+
+
+def _rec(fn):
+    """(name, kind, repr(default) or None) - the form tests/golden/reference_signatures.json records."""
+    from oracle.make_golden_signatures import signature_record
+    return [tuple(p) for p in signature_record(fn)]
+
+
+def test_signatures_equal_the_references(golden_dir):
     import actionmesh_amd as A
-    RefDenoiser, RefCFG, RefSched = _ref()
+    rec = {cls: {m: [tuple(p) for p in sig] for m, sig in methods.items()} for cls, methods in _recorded_signatures(golden_dir).items()}
+    RefSched, RefCFG, RefDenoiser = rec["SchedulerFlow"], rec["ClassifierFreeGuidance"], rec["ActionMeshDenoiser"]
     for name in ("denoise", "get_noise", "get_schedule", "_flow_sample", "_compute_timesteps"):
-        assert _sig(getattr(A.HipSchedulerFlow, name)) == _sig(getattr(RefSched, name)), name
+        assert _rec(getattr(A.HipSchedulerFlow, name)) == RefSched[name], name
     for name in ("get_unobserved_mask", "cfg_at_inference", "aggregate_cfg"):
-        assert _sig(getattr(A.ClassifierFreeGuidance, name)) == _sig(getattr(RefCFG, name)), name
-    assert _sig(A.HipDenoiser.forward) == _sig(RefDenoiser.forward)
+        assert _rec(getattr(A.ClassifierFreeGuidance, name)) == RefCFG[name], name
+    assert _rec(A.HipDenoiser.forward) == RefDenoiser["forward"]
     # constructors: every reference field, same order and defaults (ours may append optional fields)
-    ours, ref = _sig(A.HipSchedulerFlow.__init__), _sig(RefSched.__init__)
-    assert ours[:len(ref)] == ref and all(d is not inspect._empty for _, _, d in ours[len(ref):])
-    ours, ref = _sig(A.ClassifierFreeGuidance.__init__), _sig(RefCFG.__init__)
+    ours, ref = _rec(A.HipSchedulerFlow.__init__), RefSched["__init__"]
+    assert ours[:len(ref)] == ref and all(d is not None for _, _, d in ours[len(ref):])
+    ours, ref = _rec(A.ClassifierFreeGuidance.__init__), RefCFG["__init__"]
     assert [n for n, _, _ in ours] == [n for n, _, _ in ref]
-    ours, ref = _sig(A.HipDenoiser.__init__), _sig(RefDenoiser.__init__)
-    assert all(d is not inspect._empty for _, _, d in ours[len(ref):])
+    ours, ref = _rec(A.HipDenoiser.__init__), RefDenoiser["__init__"]
+    assert all(d is not None for _, _, d in ours[len(ref):])
     for (n, k, d), (rn, rk, rd) in zip(ours, ref):
         assert (n, k) == (rn, rk)
-        if "factory" not in repr(rd):       # dataclass default_factory (inflated_layers): ours resolves None the same way
+        if "factory" not in str(rd):        # dataclass default_factory (inflated_layers): ours resolves None the same way
             assert d == rd, n
+
+
+@needs_ref
+def test_recorded_signatures_are_the_references(golden_dir):
+    """The fixture above is what the reference's classes say now (regenerate with oracle/make_golden_signatures.py)."""
+    import importlib
+    from oracle.make_golden_signatures import SURFACES
+    _ref()
+    for cls, methods in _recorded_signatures(golden_dir).items():
+        mod, name, _ = SURFACES[cls]
+        klass = getattr(importlib.import_module(mod), name)
+        for m, sig in methods.items():
+            assert _rec(getattr(klass, m)) == [tuple(p) for p in sig], (cls, m)
 
 
 class StandInEngine:
@@ -99,6 +127,7 @@ class StandInEngine:
         return e.end()
 
 
+@needs_ref
 @pytest.mark.parametrize("split", [False, True])
 def test_reference_scheduler_object_drives_hipdenoiser(golden_dir, split, monkeypatch):
     import actionmesh_amd as A
@@ -151,6 +180,7 @@ def test_window_cache_is_reused_only_for_the_same_context(monkeypatch):
     assert cache4 is not cache3 and engine.binds == 4
 
 
+@needs_ref
 def test_overlays_cover_the_reference_presets():
     """One *_mi355x.yaml overlay per preset the reference CLI can pick (inference/video_to_animated_mesh.py:199-210); each derives
     from its preset, overrides ONLY keys the reference base config has, names importable classes whose dataclass fields cover what

@@ -417,6 +417,16 @@ def _legs_worker(rank, world, port, outdir, scenario):
                                      describe=lambda r: {"ms_per_step": r["elapsed"] * 1e3},
                                      make_ctl=lambda: dist.new_group(backend="gloo", timeout=timedelta(seconds=3)))
     write({"legs": sorted(legs), "report": report})
+    # the ranks leave together: the store the verdicts travel on lives in rank 0's process, and a peer may still be reading its own
+    # verdict back from it when rank 0 is done (bounded wait, as in bench.py's pre-flight children)
+    from torch.distributed import distributed_c10d as c10d
+    st = c10d._get_default_store()
+    st.set(f"worker_done/{rank}", "1")
+    if rank == 0:
+        try:
+            st.wait([f"worker_done/{r}" for r in range(world)], timedelta(seconds=60))
+        except Exception:                            # noqa: BLE001 - the verdict is on disk already
+            pass
     os._exit(0)          # (a group whose collective timed out does not always tear down cleanly; the verdict is on disk)
 
 

@@ -17,7 +17,7 @@ OUT=$PWD/gpurun_out/prof_$NAME
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 # 1) per-kernel time of the bench command
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/bench -o bench -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-nominal > $OUT/bench.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/bench -o bench -- python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-nominal > $OUT/bench.log 2>&1
 grep '^{"metric"' $OUT/bench.log | tail -1 > gpurun_out/${NAME}_bench.json
 # 2) SQ counter passes on the kernel micro-bench (product kernels only)
 for pass in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" \
