@@ -82,6 +82,17 @@ class AmAttnArgs(C.Structure):
     ]
 
 
+class AmAttnF32Args(C.Structure):      # am_attn_f32_args
+    _fields_ = [
+        ("Q", C.c_void_p), ("ldq", C.c_int64), ("q_off", C.c_int32), ("q_hs", C.c_int32),
+        ("K", C.c_void_p), ("ldk", C.c_int64), ("k_off", C.c_int32), ("k_hs", C.c_int32),
+        ("V", C.c_void_p), ("ldv", C.c_int64), ("v_off", C.c_int32), ("v_hs", C.c_int32),
+        ("O", C.c_void_p), ("ldo", C.c_int64),
+        ("nseq", C.c_int32), ("heads", C.c_int32), ("sq", C.c_int32), ("sk", C.c_int32), ("head_dim", C.c_int32),
+        ("scale", C.c_float),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -114,6 +125,12 @@ SYMBOLS = {
     "am_displacement": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P]),
     "am_attention_fallback_count": (C.c_int, [_P]),
     "am_patchify": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "am_gemm_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "am_attention_f32": (C.c_int, [C.POINTER(AmAttnF32Args), _P]),
+    "am_layernorm_f32": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_float, _P]),
+    "am_point_embed_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "am_patchify_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "am_displacement_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P]),
     "am_nn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "am_nn_search": (C.c_int, [C.POINTER(AmNnArgs), _P, C.c_size_t, _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
@@ -185,7 +202,9 @@ def lib(kind: str = "bf16") -> C.CDLL:
 
 
 def kind_of(dtype) -> str:
-    """'bf16' / 'f16' for torch.bfloat16 / torch.float16 (or their names); anything else is an error - there is no fp32 library."""
+    """'bf16' / 'f16' for torch.bfloat16 / torch.float16 (or their names); anything else is an error.  These are the two builds of the
+    library; float32 is not a third build: the exact-fp32 entry points (am_gemm_f32, am_attention_f32, ...) live in both, and the modules
+    that offer an fp32 mode (HipAutoencoder(cross_fp32=True), HipImageEncoder(dtype="float32")) handle it before calling this."""
     name = str(dtype).replace("torch.", "")
     if name in ("bfloat16", "bf16"):
         return "bf16"

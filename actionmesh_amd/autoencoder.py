@@ -20,8 +20,12 @@ stream** as in the reference: its torch.cat of the 16-bit projected latents with
 fp32 (temporal_autoencoder.py:258), every `h + branch` under autocast then adds a 16-bit linear output into fp32, FP32LayerNorm reads
 fp32, and the query side / cross-attention block run with autocast off (:236, :265).  Here: the residual streams of the self-attention
 stack and of the query block are fp32 tensors; one kernel per branch adds the branch's 16-bit output into it and emits the next
-LayerNorm's 16-bit output (am_add_layernorm_f32).  The cross-attention block's linears and attention stay 16-bit MFMA (there is no
-fp32 matrix path in the library); `residual_fp32=False` is the round-5 all-16-bit stream.  Tolerances: tests/test_autoencoder.py.
+LayerNorm's 16-bit output (am_add_layernorm_f32).  By default the cross-attention block's linears and attention stay 16-bit MFMA;
+`cross_fp32=True` runs everything the reference runs with autocast off - the query embedding, proj_query, the whole cross-attention
+block, norm_out and proj_out - in exact fp32 (am_gemm_f32 / am_attention_f32 / am_layernorm_f32 on the fp32 MFMA) on the finished fp32
+kv stream, while the 16 self-attention blocks still follow the caller's 16-bit type (opt-in: it roughly doubles a window's time, the
+cross-attention at V vertices x T (N + 1) keys being the largest single cost).  `residual_fp32=False` is the round-5 all-16-bit stream.
+Tolerances: tests/test_autoencoder.py, tests/test_fp32_path_gpu.py.
 float16 range: activations above 65504 overflow in IEEE half; a float16 forward whose result is not finite raises.
 The 16-bit type follows the caller like the reference module's does: the reference pipeline calls Stage II inside
 torch.autocast("cuda", dtype=self._dtype) (pipeline.py:679; pipeline_with_3d.py:221), `--dtype float16` from the CLI
@@ -46,7 +50,7 @@ class HipAutoencoder:
     def __init__(self, temporal_context_size: int = 16, in_channels: int = 3, in_extra_channels: int = 3, out_dim: int = 3,
                  latent_channels: int = 64, width: int = 1024, num_layers: int = 16, num_attention_heads: int = 8,
                  embed_frequency: int = 8, embed_include_pi: bool = False, prediction_mode: str = "direct",
-                 verbose: bool = False, dtype=None, residual_fp32: bool = True, **_ignored):
+                 verbose: bool = False, dtype=None, residual_fp32: bool = True, cross_fp32: bool = False, **_ignored):
         if width % num_attention_heads or width // num_attention_heads != ops.HEAD_DIM:
             raise ValueError("HipAutoencoder: the kernels are built for head_dim 128 (width = 128 * heads)")
         if latent_channels % 64 or width % 64:
@@ -61,8 +65,12 @@ class HipAutoencoder:
         self.device = torch.device("cpu")
         self.dtype_pinned = None if dtype is None else _L.kind_of(dtype)      # None: the caller's autocast dtype (compute_kind)
         self.residual_fp32 = bool(residual_fp32)
+        self.cross_fp32 = bool(cross_fp32)
+        if self.cross_fp32 and not self.residual_fp32:
+            raise ValueError("HipAutoencoder: cross_fp32=True needs residual_fp32=True (the fp32 block reads the fp32 kv stream)")
         self._sd: Optional[Dict[str, torch.Tensor]] = None
         self._w_kind: Dict[str, Dict[str, torch.Tensor]] = {}                 # "bf16" / "f16" -> device weights, uploaded on first use
+        self._w32_cache: Optional[Dict[str, torch.Tensor]] = None             # fp32 copies of the cross_fp32 layers, uploaded on first use
         lib()      # fail loudly here if libactionmesh_amd.so is missing
 
     # ---- nn.Module-like surface ---------------------------------------------------------------------------
@@ -87,6 +95,7 @@ class HipAutoencoder:
     def to(self, device):
         self.device = torch.device(device)
         self._w_kind = {}
+        self._w32_cache = None
         return self
 
     def compute_kind(self) -> str:
@@ -109,7 +118,29 @@ class HipAutoencoder:
             raise KeyError(f"HipAutoencoder.load_state_dict: missing {missing}")
         self._sd = {k: v.detach().to("cpu", torch.float32) for k, v in sd.items()}
         self._w_kind = {}
+        self._w32_cache = None
         return self
+
+    @property
+    def _w32(self) -> Dict[str, torch.Tensor]:
+        """fp32 device copies of what the reference runs with autocast off: proj_query, the cross-attention block, norm_out, proj_out."""
+        if self._w32_cache is None:
+            sd, dev, p = self._sd, self.device, f"blocks.{self.num_layers}."
+            f32 = lambda t: t.to(dev, torch.float32).contiguous()
+            pq = torch.zeros((self.width, self.query_pad))
+            pq[:, : self.query_dim] = sd["proj_query.weight"]                   # K padded to a multiple of 64 (zero columns)
+            w = {"proj_query": f32(pq), "proj_query_b": f32(sd["proj_query.bias"]),
+                 "q": f32(sd[p + "x_attn.to_q.weight"]),
+                 "kv": f32(torch.cat([sd[p + "x_attn.to_k.weight"], sd[p + "x_attn.to_v.weight"]], 0)),   # [to_k | to_v] output columns
+                 "o": f32(sd[p + "x_attn.to_out.0.weight"]), "o_b": f32(sd[p + "x_attn.to_out.0.bias"]),
+                 "ff1": f32(sd[p + "ff.net.0.proj.weight"]), "ff1_b": f32(sd[p + "ff.net.0.proj.bias"]),
+                 "ff2": f32(sd[p + "ff.net.2.weight"]), "ff2_b": f32(sd[p + "ff.net.2.bias"]),
+                 "proj_out": f32(sd["proj_out.weight"]), "proj_out_b": f32(sd["proj_out.bias"]),
+                 "norm_out.w": f32(sd["norm_out.weight"]), "norm_out.b": f32(sd["norm_out.bias"])}
+            for n, key in (("norm_x_attn", "norm_x_attn"), ("norm_cross", "x_attn.norm_cross"), ("norm_ff", "norm_ff")):
+                w[n + ".w"], w[n + ".b"] = f32(sd[p + key + ".weight"]), f32(sd[p + key + ".bias"])
+            self._w32_cache = w
+        return self._w32_cache
 
     def _upload(self, dt16: torch.dtype) -> Dict[str, torch.Tensor]:
         sd, dev, C = self._sd, self.device, self.width
@@ -172,7 +203,7 @@ class HipAutoencoder:
 
     # the same blocks on an fp32 residual stream (residual_fp32): a branch's linear output is 16-bit, as an autocast linear's is;
     # `ops.add_layernorm_f32(h32, y, w, b)` adds it into the stream and returns the next FP32LayerNorm's output rounded to 16 bits
-    def _self_stack_f32(self, h32: torch.Tensor, dt16, B: int, T: int, L: int, rope) -> None:
+    def _self_stack_f32(self, h32: torch.Tensor, dt16, B: int, T: int, L: int, rope, finish_fp32: bool = False):
         w = self._w
         z = ops.add_layernorm_f32(h32, None, w["blocks.0.norm_s_attn.w"], w["blocks.0.norm_s_attn.b"], dtype=dt16)
         for i in range(self.num_layers):
@@ -186,6 +217,9 @@ class HipAutoencoder:
             if i + 1 < self.num_layers:
                 q = f"blocks.{i + 1}."
                 z = ops.add_layernorm_f32(h32, y, w[q + "norm_s_attn.w"], w[q + "norm_s_attn.b"])
+            elif finish_fp32:           # cross_fp32: the block takes the finished fp32 stream itself (its norm_cross runs in fp32)
+                ops.add_layernorm_f32(h32, y)
+                return h32
             else:                       # the kv cache of the cross-attention block: its norm_cross reads the finished stream
                 q = f"blocks.{self.num_layers}."
                 z = ops.add_layernorm_f32(h32, y, w[q + "norm_cross.w"], w[q + "norm_cross.b"])
@@ -204,6 +238,56 @@ class HipAutoencoder:
         f = ops.gemm(z, w[p + "ff1"], bias=w[p + "ff1_b"], gelu=True)
         y = ops.gemm(f, w[p + "ff2"], bias=w[p + "ff2_b"])
         return ops.add_layernorm_f32(qh32, y, w["norm_out.w"], w["norm_out.b"])
+
+    # the exact-fp32 query side and cross-attention block (cross_fp32; temporal_autoencoder.py:152-161 under autocast(enabled=False))
+    def _query_f32(self, query: torch.Tensor) -> torch.Tensor:
+        """FrequencyPositionalEmbedding (+ extra channels) of query (rows, 3|6) fp32 -> fp32 (rows, query_pad), zero padded (:240-243)."""
+        return ops.point_embed_f32(query, self.in_channels, self.in_extra_channels, self.embed_frequency, self.embed_include_pi,
+                                   self.query_pad)
+
+    def _cross_logits_f32(self, kv32: torch.Tensor, qh32: torch.Tensor, B: int, V: int, S: int) -> torch.Tensor:
+        """blocks[-1](queries, encoder_hidden_states=kv_cache) -> norm_out -> proj_out, all fp32.  kv32 (B*S, C): the finished residual
+        stream (any key order per batch entry); qh32 (B*V, C): proj_query's output, used as the block's residual stream (modified in
+        place).  Returns (B*V, out_dim) logits BEFORE the reference's * -1."""
+        w, H, hd = self._w32, self.heads, ops.HEAD_DIM
+        e = ops.layernorm_f32(kv32, w["norm_cross.w"], w["norm_cross.b"])             # nn.LayerNorm, eps 1e-5
+        kv = ops.gemm_f32(e, w["kv"])                                                 # (B*S, 2C) = [to_k | to_v]
+        del e
+        z = ops.layernorm_f32(qh32, w["norm_x_attn.w"], w["norm_x_attn.b"])
+        q = ops.gemm_f32(z, w["q"])
+        # attention_processor.py:111-115: head h of the concatenated projection is columns h*2hd (K) and h*2hd + hd (V)
+        a = ops.attention_f32(q, kv, kv, H, V, S, hd, q_hs=hd, k_hs=2 * hd, v_hs=2 * hd, v_off=hd)
+        del kv, q
+        ops.gemm_f32(a, w["o"], bias=w["o_b"], residual=qh32, out=qh32)
+        z = ops.layernorm_f32(qh32, w["norm_ff.w"], w["norm_ff.b"], out=z)
+        f = ops.gemm_f32(z, w["ff1"], bias=w["ff1_b"], gelu=True)
+        ops.gemm_f32(f, w["ff2"], bias=w["ff2_b"], residual=qh32, out=qh32)
+        del f
+        z = ops.layernorm_f32(qh32, w["norm_out.w"], w["norm_out.b"], out=z)
+        return ops.gemm_f32(z, w["proj_out"], bias=w["proj_out_b"])
+
+    @torch.no_grad()
+    def fwd_cross_attn(self, kv_cache: torch.Tensor, queries: torch.Tensor) -> torch.Tensor:
+        """temporal_autoencoder.py:152-161 in fp32 (cross_fp32=True only): proj_query -> last FlowMatchingBlock -> norm_out ->
+        proj_out -> * -1.  kv_cache (B, T*N + T, C) fp32 in the reference's layout (the cross-attention does not care about key order),
+        queries (B, V, query_dim) fp32 = the embedded query points.  Returns logits (B, V, out_dim) fp32."""
+        if not self.cross_fp32:
+            raise RuntimeError("HipAutoencoder.fwd_cross_attn: the fp32 cross-attention block needs cross_fp32=True")
+        if self.device.type != "cuda" or self._sd is None:
+            raise RuntimeError("HipAutoencoder: load_state_dict(...) and .to('cuda:N') first (there is no CPU path)")
+        B, S, C = kv_cache.shape
+        V, Dq = queries.shape[1], queries.shape[2]
+        if C != self.width or queries.shape[0] != B or Dq != self.query_dim:
+            raise ValueError(f"HipAutoencoder.fwd_cross_attn: kv_cache {tuple(kv_cache.shape)} / queries {tuple(queries.shape)} do not "
+                             f"match width {self.width}, query_dim {self.query_dim}")
+        dev, w = self.device, self._w32
+        with torch.cuda.device(dev):
+            kv32 = kv_cache.to(dev, torch.float32).reshape(B * S, C).contiguous()
+            qe = torch.zeros((B * V, self.query_pad), dtype=torch.float32, device=dev)
+            qe[:, :Dq] = queries.to(dev, torch.float32).reshape(B * V, Dq)           # zero-padded K (copy only)
+            qh32 = ops.gemm_f32(qe, w["proj_query"], bias=w["proj_query_b"])
+            lg = self._cross_logits_f32(kv32, qh32, B, V, S)
+            return (-lg).view(B, V, self.out_dim)
 
     # ---- forward (temporal_autoencoder.py:160-267) --------------------------------------------------------------
     @torch.no_grad()
@@ -234,17 +318,30 @@ class HipAutoencoder:
                 emb += [torch.cos(arg), torch.sin(arg)]
             alpha = torch.cat(emb, -1).to(dev, dt16)                              # (B, T_out, C)
             # query side, once: embed + proj_query
-            qe = ops.point_embed(query.to(dev, torch.float32).reshape(B * V, -1).contiguous(), self.in_channels,
-                                 self.in_extra_channels, self.embed_frequency, self.embed_include_pi, self.query_pad, dtype=dt16)
-            qh = ops.gemm(qe, w["proj_query"], bias=w["proj_query_b"])
+            q32 = query.to(dev, torch.float32).reshape(B * V, -1).contiguous()
+            if self.cross_fp32:                                                 # the query side with autocast off (:240-243), once
+                qh32_0 = ops.gemm_f32(self._query_f32(q32), self._w32["proj_query"], bias=self._w32["proj_query_b"])
+            else:
+                qe = ops.point_embed(q32, self.in_channels, self.in_extra_channels, self.embed_frequency, self.embed_include_pi,
+                                     self.query_pad, dtype=dt16)
+                qh = ops.gemm(qe, w["proj_query"], bias=w["proj_query_b"])
             out = torch.empty((B, T_out, V, self.out_dim), dtype=torch.float32, device=dev)
             if self.residual_fp32:
                 base32 = base.float()                                           # am_bf16_to_f32 would do; once per window, torch moves rows
                 alpha32 = torch.cat(emb, -1).to(dev, torch.float32)             # the alpha embedding enters the stream in fp32 (:232-235, :258)
-                qh32_0 = qh.float()
+                if not self.cross_fp32:
+                    qh32_0 = qh.float()
             for i in range(T_out):
                 if step_callback is not None:
                     step_callback(i + 1, T_out)
+                if self.cross_fp32:
+                    h32 = base32.clone()
+                    h32.view(B, T, L, C)[:, :, 0] = alpha32[:, i][:, None]
+                    kv32 = self._self_stack_f32(h32, dt16, B, T, L, rope, finish_fp32=True)
+                    lg = self._cross_logits_f32(kv32, qh32_0.clone(), B, V, T * L)
+                    for b in range(B):
+                        ops.displacement_f32(lg[b * V:(b + 1) * V], self.out_dim, out[b, i])
+                    continue
                 if self.residual_fp32:
                     h32 = base32.clone()
                     h32.view(B, T, L, C)[:, :, 0] = alpha32[:, i][:, None]

@@ -1,4 +1,4 @@
-"""`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage2-hip] [--script NAME]
+"""`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage2-hip [--stage2-cross-fp32]] [--script NAME]
                                  [--reference-root DIR] -- <the reference CLI's own arguments>`
 
 Runs the reference's UNMODIFIED command-line script (inference/video_to_animated_mesh.py:120-248, or
@@ -42,6 +42,8 @@ def split_args(argv: List[str]) -> Tuple[argparse.Namespace, List[str]]:
     ap.add_argument("--attn-dtype", choices=["bf16", "fp8", "fp8_fast"], default="bf16",
                     help="inflated self-attention arithmetic: bf16 (default), e4m3 MFMA (fp8), or its exponent-field form (fp8_fast)")
     ap.add_argument("--stage2-hip", action="store_true", help="also decode Stage II on the HIP kernels (HipAutoencoder)")
+    ap.add_argument("--stage2-cross-fp32", action="store_true",
+                    help="with --stage2-hip: Stage II's query side and cross-attention block in exact fp32, as the reference runs them")
     ap.add_argument("--script", choices=SCRIPTS, default=SCRIPTS[0])
     ap.add_argument("--reference-root", default=None)
     ap.add_argument("--amd-help", action="store_true", help="this wrapper's options (plain --help shows the reference CLI's)")
@@ -51,6 +53,8 @@ def split_args(argv: List[str]) -> Tuple[argparse.Namespace, List[str]]:
     if ours.amd_help:
         ap.print_help()
         raise SystemExit(0)
+    if ours.stage2_cross_fp32 and not ours.stage2_hip:
+        ap.error("--stage2-cross-fp32 needs --stage2-hip")
     return ours, rest
 
 
@@ -61,7 +65,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     script = find_script(ours.script, ours.reference_root)
     if ours.backend == "hip":
         from . import dropin
-        dropin.install(attn_dtype=ours.attn_dtype, stage2=ours.stage2_hip)
+        dropin.install(attn_dtype=ours.attn_dtype, stage2=ours.stage2_hip, stage2_cross_fp32=ours.stage2_cross_fp32)
     old_argv = sys.argv
     sys.argv = [script] + rest
     try:

@@ -93,11 +93,14 @@ def _wrap_load_config(orig):
     return load_config
 
 
-def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[bool] = None) -> None:
+def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[bool] = None, stage2_cross_fp32: bool = False) -> None:
     """Patch the reference in THIS process (idempotent).  After it, `ActionMeshPipeline(config_name="actionmesh.yaml", ...)` - and
     therefore the unmodified CLI - samples Stage I with HipSchedulerFlow over a HipDenoiser.
     `attn_dtype`: "bf16" (default) or "fp8" (inflated self-attention on the e4m3 MFMA kernel).  `stage2`: also run the Stage-II
-    decoder on HipAutoencoder."""
+    decoder on HipAutoencoder.  `stage2_cross_fp32`: that decoder runs its query side and cross-attention block in exact fp32, as the
+    reference does (HipAutoencoder(cross_fp32=True); needs `stage2`)."""
+    if stage2_cross_fp32 and not stage2:
+        raise ValueError("actionmesh_amd.install(): stage2_cross_fp32=True needs stage2=True")
     import actionmesh.pipeline as P      # the reference (must be importable where the reference runs)
     from .denoiser import HipDenoiser
 
@@ -121,7 +124,17 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     if stage2:
         from .autoencoder import HipAutoencoder
         saved["ActionMeshAutoencoder"] = P.ActionMeshAutoencoder
-        P.ActionMeshAutoencoder = HipAutoencoder
+        decoder = HipAutoencoder
+        if stage2_cross_fp32:
+            class _ConfiguredHipAutoencoder(HipAutoencoder):
+                """HipAutoencoder with cross_fp32 bound (the reference calls `from_pretrained(dir)` with no keyword)."""
+                def __init__(self, *a, **k):
+                    k.setdefault("cross_fp32", True)
+                    super().__init__(*a, **k)
+            _ConfiguredHipAutoencoder.__name__ = "HipAutoencoder"
+            _ConfiguredHipAutoencoder.__qualname__ = "HipAutoencoder"
+            decoder = _ConfiguredHipAutoencoder
+        P.ActionMeshAutoencoder = decoder
     _state["installed"] = True
     _state["saved"] = saved
     _state["module"] = P

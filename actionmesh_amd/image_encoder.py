@@ -24,6 +24,9 @@ the reference runs this model in fp32, outside its autocast region (pipeline.py:
 of the GEMM operands / outputs, not 24 layers of re-rounding the stream (`am_add_layernorm_f32` adds each branch's 16-bit output into
 the fp32 stream and emits the next LayerNorm's 16-bit output; `residual_fp32=False` is the round-5 all-16-bit stream).  Tolerances
 stated in tests/test_image_encoder.py.
+`dtype="float32"` runs the whole ViT in exact fp32 as the reference does (am_patchify_f32, am_gemm_f32, am_layernorm_f32,
+am_attention_f32 on the fp32 MFMA): heads of 64 channels natively (no padding), the attention reading q / k / v in place from the
+packed [query | key | value] projection, LayerScale folded into the fp32 out-projection / fc2.  Tolerances: tests/test_fp32_path_gpu.py.
 """
 from __future__ import annotations
 
@@ -94,6 +97,35 @@ def pack_weights(sd: Dict[str, torch.Tensor], cfg: Dict) -> Dict[str, torch.Tens
     return w
 
 
+def pack_weights_f32(sd: Dict[str, torch.Tensor], cfg: Dict) -> Dict[str, torch.Tensor]:
+    """Dinov2Model state dict -> the fp32 operands of dtype="float32" (fp32, CPU): [query; key; value] stacked as one linear (output
+    columns q | k | v, head h at h * hd inside each), LayerScale folded into the out-projection and fc2 in fp32, the flattened patch
+    projection padded to a multiple of 64 columns."""
+    C = cfg["hidden_size"]
+    f = lambda k: sd[k].detach().to("cpu", torch.float32)
+    w: Dict[str, torch.Tensor] = {}
+    wp = f("embeddings.patch_embeddings.projection.weight").reshape(C, -1)
+    kp = ops.round_up(wp.shape[1], 64)
+    w["patch.w"] = torch.zeros((C, kp)); w["patch.w"][:, : wp.shape[1]] = wp
+    w["patch.b"] = f("embeddings.patch_embeddings.projection.bias")
+    w["cls"] = f("embeddings.cls_token").reshape(C)
+    w["pos"] = f("embeddings.position_embeddings")[0]
+    for i in range(cfg["num_hidden_layers"]):
+        q, p = f"encoder.layer.{i}.", f"l{i}."
+        names = ("query", "key", "value")
+        w[p + "qkv.w"] = torch.cat([f(q + f"attention.attention.{n}.weight") for n in names], 0)
+        w[p + "qkv.b"] = torch.cat([f(q + f"attention.attention.{n}.bias") if q + f"attention.attention.{n}.bias" in sd else torch.zeros(C)
+                                    for n in names], 0)
+        ls1, ls2 = f(q + "layer_scale1.lambda1"), f(q + "layer_scale2.lambda1")
+        w[p + "o.w"], w[p + "o.b"] = f(q + "attention.output.dense.weight") * ls1[:, None], f(q + "attention.output.dense.bias") * ls1
+        w[p + "fc1.w"], w[p + "fc1.b"] = f(q + "mlp.fc1.weight"), f(q + "mlp.fc1.bias")
+        w[p + "fc2.w"], w[p + "fc2.b"] = f(q + "mlp.fc2.weight") * ls2[:, None], f(q + "mlp.fc2.bias") * ls2
+        for n in ("norm1", "norm2"):
+            w[p + n + ".w"], w[p + n + ".b"] = f(q + n + ".weight"), f(q + n + ".bias")
+    w["norm.w"], w["norm.b"] = f("layernorm.weight"), f("layernorm.bias")
+    return w
+
+
 def position_rows(pos: torch.Tensor, cls: torch.Tensor, trained_side: int, n_h: int, n_w: int) -> torch.Tensor:
     """(1 + n_h n_w, C) fp32: row 0 = class token + class position, rows 1.. = the (resampled) patch positions
     (Dinov2Embeddings.interpolate_pos_encoding + the cat / add of Dinov2Embeddings.forward)."""
@@ -114,11 +146,13 @@ class HipImageEncoder:
         # 16-bit storage type.  The reference encodes OUTSIDE its autocast region, in fp32 (pipeline.py:665-667): there is no caller dtype
         # to follow, so the default is bfloat16 (fp32's exponent range: safe for DINOv2's outlier tokens whatever the checkpoint) and
         # dtype="float16" selects the float16 build - 8x finer rounding, measured closer to the fp32 reference on the ViT-L/14 fixture
-        # (tests/test_image_encoder.py::test_hip_encoder_vitl_against_transformers); anything else is refused (there is no fp32 library).
-        self.kind = "bf16" if dtype is None else L.kind_of(dtype)
+        # (tests/test_image_encoder.py::test_hip_encoder_vitl_against_transformers); dtype="float32" (or torch.float32) runs the reference's
+        # own fp32 arithmetic on the exact-fp32 path of the library; anything else is refused.
+        self.fp32 = str(dtype).replace("torch.", "") in ("float32", "float", "fp32", "f32")
+        self.kind = "bf16" if (dtype is None or self.fp32) else L.kind_of(dtype)
         if self.kind == "f16":
             lib("f16")
-        self.dt16 = L.torch_dtype(self.kind)
+        self.dt16 = torch.float32 if self.fp32 else L.torch_dtype(self.kind)
         self.pretrained_dino_feature_extractor = pretrained_dino_feature_extractor
         self.pretrained_dino_model = pretrained_dino_model
         self._device = torch.device("cpu")
@@ -136,6 +170,8 @@ class HipImageEncoder:
             raise ValueError("HipImageEncoder: the SwiGLU FFN variant (DINOv2 giant) is not supported")
         if C % H or C // H > ops.HEAD_DIM or C % 64:
             raise ValueError(f"HipImageEncoder: hidden_size={C}, heads={H}: need head_dim <= 128 and width % 64 == 0")
+        if self.fp32 and C // H not in (64, 128):
+            raise ValueError(f"HipImageEncoder: dtype=float32 runs head_dim 64 or 128, got {C // H}")
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -177,7 +213,7 @@ class HipImageEncoder:
         bad = [(k, tuple(sd[k].shape), v) for k, v in want.items() if tuple(sd[k].shape) != v]
         if bad:
             raise ValueError(f"HipImageEncoder.load_state_dict: shape mismatch (key, got, expected): {bad[:4]}")
-        self._packed = pack_weights(sd, self.cfg)
+        self._packed = (pack_weights_f32 if self.fp32 else pack_weights)(sd, self.cfg)
         self._pos_cache.clear()
         if self._device.type == "cuda":
             self._upload()
@@ -220,6 +256,10 @@ class HipImageEncoder:
             raise ValueError(f"HipImageEncoder: expected {cfg['num_channels']} channels, got {Cin}")
         n_h, n_w = Hi // p, Wi // p
         npatch, S = n_h * n_w, n_h * n_w + 1
+        if self.fp32:
+            with torch.cuda.device(dev):
+                out = self._forward_f32(pixel_values.to(dev, torch.float32).contiguous(), T, n_h, n_w)
+            return out if out_dtype == out.dtype else out.to(out_dtype)
         with torch.cuda.device(dev):
             pix = pixel_values.to(dev, torch.float32).contiguous()
             pos = self._pos_rows(T, n_h, n_w)
@@ -268,6 +308,33 @@ class HipImageEncoder:
                 h = ops.gemm(f, w[q + "fc2.w"], bias=w[q + "fc2.b"], residual=h)
             y = ops.layernorm(h, w["norm.w"], w["norm.b"], eps=eps).view(T, S, C)
             return y if out_dtype == y.dtype else y.to(out_dtype)
+
+    def _forward_f32(self, pix: torch.Tensor, T: int, n_h: int, n_w: int) -> torch.Tensor:
+        """dtype="float32": Dinov2Model in fp32, every step on the exact-fp32 kernels.  Returns (T, S, C) fp32."""
+        cfg, w = self.cfg, self._w
+        C, H, p, eps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["patch_size"], cfg["layer_norm_eps"]
+        hd, npatch, S = C // H, n_h * n_w, n_h * n_w + 1
+        # embeddings: h = [cls + pos_0 | conv(pixels) + bias + pos_1..] - the patch projection's residual operand is the position rows,
+        # written in place behind each frame's class-token row
+        h = self._pos_rows32(T, n_h, n_w).clone()
+        patches = ops.patchify_f32(pix, p, w["patch.w"].shape[1])
+        for t in range(T):
+            rows = h[t * S + 1:(t + 1) * S]
+            ops.gemm_f32(patches[t * npatch:(t + 1) * npatch], w["patch.w"], bias=w["patch.b"], residual=rows, out=rows)
+        del patches
+        z = torch.empty_like(h)
+        for i in range(cfg["num_hidden_layers"]):
+            q = f"l{i}."
+            ops.layernorm_f32(h, w[q + "norm1.w"], w[q + "norm1.b"], eps=eps, out=z)
+            qkv = ops.gemm_f32(z, w[q + "qkv.w"], bias=w[q + "qkv.b"])                         # (T*S, 3C): q | k | v
+            a = ops.attention_f32(qkv, qkv, qkv, H, S, S, hd, q_off=0, k_off=C, v_off=2 * C)
+            del qkv
+            ops.gemm_f32(a, w[q + "o.w"], bias=w[q + "o.b"], residual=h, out=h)                # LayerScale folded
+            ops.layernorm_f32(h, w[q + "norm2.w"], w[q + "norm2.b"], eps=eps, out=z)
+            f = ops.gemm_f32(z, w[q + "fc1.w"], bias=w[q + "fc1.b"], gelu=True)
+            ops.gemm_f32(f, w[q + "fc2.w"], bias=w[q + "fc2.b"], residual=h, out=h)
+            del f
+        return ops.layernorm_f32(h, w["norm.w"], w["norm.b"], eps=eps, out=z).view(T, S, C)
 
     def encode_images(self, images: List) -> torch.Tensor:
         """image_encoder.py:38-55: T PIL images -> context (T, S, Dc)."""

@@ -468,3 +468,139 @@ def nn_indices_valid(*indices: torch.Tensor) -> None:
         bad = b if bad is None else (bad | b)
     if bad is not None and bool(bad):
         raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
+
+
+# ---- exact-fp32 path (csrc/am_f32.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----------------------
+def _fk(kind: str, name: str):
+    """Entry point `name` of the library build `kind` ("bf16" / "f16"): the fp32 entry points are in both."""
+    l = L.lib(kind)
+    f = getattr(l, name)
+    f._am_lib = l
+    return f
+
+
+def _rows_view(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A 2-D fp32 device tensor with unit column stride (a column slice of a packed projection output qualifies)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: actionmesh_amd kernels need a device tensor (no CPU path)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {t.dtype}")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected a 2-D tensor with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
+def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+             gelu: bool = False, out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:
+    """am_gemm_f32: out = act(a @ w.T + bias) + residual, all fp32, fp32 MFMA.  a (M, K), w (N, K) (nn.Linear layout), bias (N,),
+    residual / out (M, N); rows may be strided (unit column stride), `residual` may be `out` (in-place residual add).  K % 4 == 0."""
+    _rows_view(a, "a"); _rows_view(w, "w")
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"gemm_f32: a is (M, {K}) but w is {tuple(w.shape)}")
+    if K % 4:
+        raise ValueError(f"gemm_f32: K={K} must be a multiple of 4 (pad the operands)")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    _rows_view(out, "out")
+    if tuple(out.shape) != (M, N):
+        raise ValueError(f"gemm_f32: out {tuple(out.shape)} != ({M}, {N})")
+    if bias is not None:
+        _need(bias, torch.float32, "bias")
+        if bias.numel() != N:
+            raise ValueError(f"gemm_f32: bias has {bias.numel()} elements, N={N}")
+    if residual is not None:
+        _rows_view(residual, "residual")
+        if tuple(residual.shape) != (M, N):
+            raise ValueError(f"gemm_f32: residual {tuple(residual.shape)} != ({M}, {N})")
+    _launch(a, _fk(kind, "am_gemm_f32"), "am_gemm_f32", a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _p(bias),
+            _p(residual), residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, N, K, 1 if gelu else 0)
+    return out
+
+
+def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sq: int, sk: int, head_dim: int,
+                  q_hs: Optional[int] = None, k_hs: Optional[int] = None, v_hs: Optional[int] = None,
+                  q_off: int = 0, k_off: int = 0, v_off: int = 0, scale: Optional[float] = None,
+                  out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:
+    """am_attention_f32: softmax(Q K^T scale) V in fp32, read in place from projection outputs.  q (nseq * sq, >= ...) and k / v
+    (nseq * sk, ...) are 2-D fp32 with unit column stride; head h of row i is columns [x_off + h * x_hs, + head_dim) (x_hs defaults to
+    head_dim).  The cross-attention's concatenated [to_k | to_v] output `kv` is k = v = kv, k_hs = v_hs = 2 hd, v_off = hd.
+    Returns out (nseq * sq, heads * head_dim) fp32."""
+    _rows_view(q, "q"); _rows_view(k, "k"); _rows_view(v, "v")
+    if head_dim not in (64, 128):
+        raise ValueError(f"attention_f32: head_dim {head_dim} (64 or 128)")
+    if sq < 1 or sk < 1 or heads < 1:
+        raise ValueError(f"attention_f32: bad shape heads={heads} sq={sq} sk={sk}")
+    if q.shape[0] % sq or k.shape[0] % sk or v.shape[0] != k.shape[0] or q.shape[0] // sq != k.shape[0] // sk:
+        raise ValueError(f"attention_f32: rows q {q.shape[0]} / k {k.shape[0]} / v {v.shape[0]} do not match sq={sq}, sk={sk}")
+    q_hs, k_hs, v_hs = (head_dim if x is None else x for x in (q_hs, k_hs, v_hs))
+    for name, t, off, hs in (("q", q, q_off, q_hs), ("k", k, k_off, k_hs), ("v", v, v_off, v_hs)):
+        if off < 0 or hs < 0 or off + (heads - 1) * hs + head_dim > t.shape[1]:
+            raise ValueError(f"attention_f32: {name} has {t.shape[1]} columns, head {heads - 1} ends at {off + (heads - 1) * hs + head_dim}")
+    nseq = q.shape[0] // sq
+    if out is None:
+        out = torch.empty((nseq * sq, heads * head_dim), dtype=torch.float32, device=q.device)
+    _rows_view(out, "out")
+    if out.shape[0] != nseq * sq or out.shape[1] < heads * head_dim:
+        raise ValueError(f"attention_f32: out {tuple(out.shape)} too small for ({nseq * sq}, {heads * head_dim})")
+    a = L.AmAttnF32Args()
+    a.Q, a.ldq, a.q_off, a.q_hs = q.data_ptr(), q.stride(0), q_off, q_hs
+    a.K, a.ldk, a.k_off, a.k_hs = k.data_ptr(), k.stride(0), k_off, k_hs
+    a.V, a.ldv, a.v_off, a.v_hs = v.data_ptr(), v.stride(0), v_off, v_hs
+    a.O, a.ldo = out.data_ptr(), out.stride(0)
+    a.nseq, a.heads, a.sq, a.sk, a.head_dim = nseq, heads, sq, sk, head_dim
+    a.scale = scale if scale is not None else head_dim ** -0.5
+    _launch(q, _fk(kind, "am_attention_f32"), "am_attention_f32", C.byref(a))
+    return out
+
+
+def layernorm_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = None,
+                  kind: str = "bf16") -> torch.Tensor:
+    """am_layernorm_f32: nn.LayerNorm in fp32 over the last axis of x (fp32 in, fp32 out)."""
+    _need(x, torch.float32, "x"); _need(w, torch.float32, "w"); _need(b, torch.float32, "b")
+    Cdim = x.shape[-1]
+    if w.numel() != Cdim or b.numel() != Cdim:
+        raise ValueError(f"layernorm_f32: weight / bias of {w.numel()} / {b.numel()} elements for C={Cdim}")
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out, torch.float32, "out")
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("layernorm_f32: out may not alias x")
+    _launch(x, _fk(kind, "am_layernorm_f32"), "am_layernorm_f32", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
+            x.numel() // Cdim, Cdim, eps)
+    return out
+
+
+def point_embed_f32(query: torch.Tensor, in_channels: int, extra_channels: int, num_freqs: int, include_pi: bool,
+                    ld_out: int = 64, kind: str = "bf16") -> torch.Tensor:
+    """`point_embed` without the rounding: query (rows, >= in+extra) fp32 -> fp32 (rows, ld_out)."""
+    _need(query, torch.float32, "query")
+    if query.dim() != 2 or query.shape[1] < in_channels + extra_channels:
+        raise ValueError(f"point_embed_f32: query {tuple(query.shape)} has fewer than {in_channels + extra_channels} channels")
+    rows = query.shape[0]
+    out = torch.empty((rows, ld_out), dtype=torch.float32, device=query.device)
+    _launch(query, _fk(kind, "am_point_embed_f32"), "am_point_embed_f32", query.data_ptr(), query.stride(0), rows, in_channels,
+            extra_channels, num_freqs, int(include_pi), out.data_ptr(), ld_out)
+    return out
+
+
+def patchify_f32(pixels: torch.Tensor, patch: int, ld_out: int, kind: str = "bf16") -> torch.Tensor:
+    """`patchify` without the rounding: pixels (T, C, H, W) fp32 -> fp32 (T * (H // patch) * (W // patch), ld_out)."""
+    _need(pixels, torch.float32, "pixels")
+    if pixels.dim() != 4:
+        raise ValueError(f"patchify_f32: expected (T, C, H, W), got {tuple(pixels.shape)}")
+    T, Cin, H, W = pixels.shape
+    out = torch.empty((T * (H // patch) * (W // patch), ld_out), dtype=torch.float32, device=pixels.device)
+    _launch(pixels, _fk(kind, "am_patchify_f32"), "am_patchify_f32", pixels.data_ptr(), T, Cin, H, W, patch, out.data_ptr(), ld_out)
+    return out
+
+
+def displacement_f32(logits: torch.Tensor, out_dim: int, out: torch.Tensor, kind: str = "bf16") -> torch.Tensor:
+    """out (rows, out_dim) fp32 = 2 sigmoid(-logits[:, :out_dim]) - 1 on fp32 logits (rows may be strided)."""
+    _rows_view(logits, "logits"); _need(out, torch.float32, "out")
+    if logits.shape[1] < out_dim or out.shape != (logits.shape[0], out_dim):
+        raise ValueError(f"displacement_f32: logits {tuple(logits.shape)} / out {tuple(out.shape)} for out_dim={out_dim}")
+    _launch(logits, _fk(kind, "am_displacement_f32"), "am_displacement_f32", logits.data_ptr(), logits.stride(0), logits.shape[0], out_dim,
+            out.data_ptr())
+    return out

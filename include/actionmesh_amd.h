@@ -347,6 +347,43 @@ int am_displacement(const uint16_t* logits, int ld, int64_t rows, int out_dim, f
 int am_patchify(const float* pixels, int frames, int channels, int height, int width, int patch, uint16_t* out,
                 int ld_out, void* stream);
 
+/* ---- exact-fp32 matrix path (csrc/am_f32.hip; v_mfma_f32_32x32x2_f32: fp32 operands and accumulation) ------------------------
+ * What the reference computes with autocast off: Stage II's query embedding, proj_query, the cross-attention FlowMatchingBlock,
+ * norm_out and proj_out (temporal_autoencoder.py:152-161, 240-243, 266-267), and the DINOv2 encoder (pipeline.py:665-667,
+ * image_encoder.py:38-55).  fp32 pointers, row-major; deterministic (no split-K, no atomics); the same bits from both library builds.
+ *
+ * nn.Linear in fp32 (block.py linears, proj_query / proj_out, Dinov2 query / key / value / dense / fc1 / fc2):
+ *   C[M][ldc] = act(A[M][lda] W^T + bias[N]) + R[M][ldr], W [N][ldw] (nn.Linear layout), bias / R may be NULL, R may alias C.
+ *   act 0 = none, 1 = exact erf-GELU (F.gelu).  Any M, N; K % 4 == 0; A, W 16-byte aligned, lda, ldw multiples of 4. */
+int am_gemm_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* R, int64_t ldr,
+                float* C, int64_t ldc, int M, int N, int K, int act, void* stream);
+/* softmax(Q K^T * scale) V per (sequence, head), non-causal, fp32 (F.scaled_dot_product_attention in attention_processor.py:145,
+ * Dinov2SelfAttention).  Operands are read in place from projection outputs: element d of head h of row i of sequence n of X is
+ *   X[(n * s + i) * ldx + x_off + h * x_hs + d]     (s = sq for Q, sk for K / V)
+ * so the reference's per-head split of the CONCATENATED cross-attention projection (attention_processor.py:105-115: K of head h at
+ * column h * 2 hd of [to_k | to_v], V at h * 2 hd + hd) and transformers' h * hd split are both just strides.
+ * O [nseq * sq][ldo], heads concatenated (h * head_dim + d).  head_dim 64 or 128; sq, sk >= 1; pointers, ld*, *_off and *_hs aligned
+ * to 16 bytes.  Exact online softmax (running row max), libm expf. */
+typedef struct {
+  const float* Q; int64_t ldq; int32_t q_off, q_hs;
+  const float* K; int64_t ldk; int32_t k_off, k_hs;
+  const float* V; int64_t ldv; int32_t v_off, v_hs;
+  float* O; int64_t ldo;
+  int32_t nseq, heads, sq, sk, head_dim;
+  float scale;
+} am_attn_f32_args;
+int am_attention_f32(const am_attn_f32_args* args, void* stream);
+/* nn.LayerNorm / FP32LayerNorm in fp32 (block.py:64,83,98,107 with eps 1e-5; Dinov2Layer norm1 / norm2 / layernorm with eps 1e-6):
+ * y = (x - mean) / sqrt(var + eps) * w + b, two-pass statistics.  C % 4 == 0, C <= 4096; y may not alias x. */
+int am_layernorm_f32(const float* x, float* y, const float* w, const float* b, int64_t rows, int C, float eps, void* stream);
+/* fp32-output forms of am_point_embed / am_patchify (same element maps, no rounding) and am_displacement on fp32 logits
+ * (2 sigmoid(-logits) - 1, temporal_autoencoder.py:156-157, 267). */
+int am_point_embed_f32(const float* q_dev, int ld_in, int64_t rows, int in_channels, int extra_channels, int num_freqs,
+                       int include_pi, float* out, int ld_out, void* stream);
+int am_patchify_f32(const float* pixels, int frames, int channels, int height, int width, int patch, float* out, int ld_out,
+                    void* stream);
+int am_displacement_f32(const float* logits, int ld, int64_t rows, int out_dim, float* out, void* stream);
+
 /* ActionBench quality gate (actionbench/chamfer.py:13-86, actionbench/icp.py:94): exact nearest-neighbour
  * search, the arithmetic of scipy.spatial.KDTree(points).query(queries) and of pytorch3d's chamfer_distance.
  *   points  (batch, n_points, 3) fp32, batch stride points_bstride ELEMENTS (0 = one cloud shared by every batch entry);

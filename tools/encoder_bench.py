@@ -15,7 +15,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16"])
+    ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16", "float32"])
     a = ap.parse_args()
     from actionmesh_amd import image_encoder as IE
     dev = torch.device("cuda:0")
@@ -48,7 +48,7 @@ def main():
     ms = e0.elapsed_time(e1) / a.reps
     fl = enc.step_flops(a.frames, 224, 224)
     print(json.dumps({"metric": "context-encoder calls/sec (16 frames x 224x224, DINOv2 ViT-L/14)", "value": round(1e3 / ms, 2),
-                      "unit": "calls/s", "ms_per_call": round(ms, 3), "n_gpus": 1, "dtype": "bf16" if a.dtype == "bfloat16" else "f16", "data": "synthetic",
+                      "unit": "calls/s", "ms_per_call": round(ms, 3), "n_gpus": 1, "dtype": {"bfloat16": "bf16", "float16": "f16", "float32": "f32"}[a.dtype], "data": "synthetic",
                       "algorithmic_flops": fl, "tflops": round(fl / ms / 1e9, 1),
                       "frac_of_bf16_peak": round(fl / ms / 1e9 / 2500.0, 4),
                       "config": {"workload": f"T={a.frames} 224x224 patch 14 width 1024 heads 16x64 layers 24"}}))
