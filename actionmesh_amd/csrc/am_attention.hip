@@ -43,9 +43,10 @@
 //   * Q is pre-multiplied by scale*log2(e) once (re-rounded to bf16): scores are
 //     born in log2 units, no per-element multiply;
 //   * the running max is subtracted two elements at a time (v_pk_add_f32);
-//   * no key mask: padded K rows / V^T columns are zero (am_head_post), so a padded
-//     key scores exactly 0 (harmless in the running max) and adds nothing to O;
-//     the row sum of a chunk's partial last sub-tile is corrected once (tail);
+//   * padded K rows / V^T columns are zero (am_head_post); only a chunk's partial last
+//     sub-tile has padded keys, and there (a rare branch) they score -inf before the row
+//     max: P = 0 exactly, so they move neither the running max nor the row sum (a
+//     padded key scoring 0 would cap a row whose real scores all sit far below 0);
 //   * row max with v_max3 through inline asm (fmaxf on MFMA outputs makes hipcc
 //     canonicalise every operand with an extra v_max), four independent chains;
 //     cross-half exchange with v_permlane32_swap (no LDS round trip);
@@ -89,6 +90,14 @@ struct Geo {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+
+// The padded keys of a chunk's partial last tile score -inf before the row max: their P is exactly 0, so they move neither the
+// running max nor the row sum.  s holds keys first + (r & 3) + 8 (r >> 2) + 4 hi (r = 0..15); tv = the tile's valid keys - 4 hi.
+__device__ __forceinline__ void mask_keys(f32x16_t& s, int first, int tv) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (first + (r & 3) + 8 * (r >> 2) >= tv) s[r] = -INFINITY;
+}
 
 // SPLIT: the workgroup handles only super-tiles [z*ns/Z, (z+1)*ns/Z) (z = blockIdx.z) of query block
 // `qblk_base + blockIdx.x` and writes un-normalised fp32 (O, m, l) partials for attn_combine_kernel.
@@ -218,6 +227,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
     // ---- row max (four independent v_max3 chains), relative to the running max ------------------
     // hipcc pads no hazards for inline asm: an MFMA result needs 12 wait states before a VALU read
     asm volatile("s_nop 15" : "+v"(s[0]), "+v"(s[1]));
+    if (valid < KVBLK) {                          // rare: the partial last sub-tile of a chunk
+      mask_keys(s[0], 0, valid - 4 * hi);
+      mask_keys(s[1], 32, valid - 4 * hi);
+    }
     float mxa[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) mxa[i] = max3(s[0][i], s[1][i], s[0][i + 4]);
@@ -262,14 +275,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
     {
       const f32x2_t rs = (rsa[0] + rsa[1]) + (rsa[2] + rsa[3]);
       l_run += rs[0] + rs[1];
-    }
-    if (valid < KVBLK) {   // partial last sub-tile of a chunk: remove the padded keys' exp2(0 - m_run)
-      int cnt = 0;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) cnt += min(4, max(0, kb * 32 + 8 * g + 4 * hi + 4 - valid));
-      l_run -= (float)cnt * __builtin_amdgcn_exp2f(-m_run);
     }
     bf16x8_t pf[4];
 #pragma unroll
@@ -355,9 +360,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
 // workgroup per (frame, head) loads K and V^T once - the full 64-key tiles (at most 4) plus a SHORT tail tile of at most 16 keys -
 // and then walks all the query blocks of its sequence against LDS that nobody writes any more: no barrier and no DMA wait in the
 // loop, the next block's Q rows are fetched while the current block computes, and the tail costs 8 + 4 MFMAs instead of 32 (its QK^T
-// only multiplies key block 0, its P.V only the first 16-key step; padded keys score 0 and meet zero V^T columns, as everywhere).
+// only multiplies key block 0, its P.V only the first 16-key step; its padded keys score -inf, as everywhere).
 // Same layouts, same LDS images, same per-tile arithmetic as attn_fwd_kernel (its sub_tile, copied: that kernel's tuning is not
-// touched); the tail's row-sum correction counts 31 padded keys instead of 63, so results agree to rounding, not bit for bit.
+// touched); the tail's keys are summed in another grouping, so results agree to rounding, not bit for bit.
 // The output rows leave through a 2 KiB staging slice per wave (one 32-channel block at a time, XOR-swizzled 8-byte units): the MFMA
 // layout holds one query row per lane, so direct stores were 8-byte pieces of 32 different rows per instruction - 512 line touches per
 // block and wave, the floor of the first form of this kernel; staged, a store instruction writes 64 contiguous bytes of 16 rows.
@@ -431,10 +436,6 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
   f32x16_t zero16;
 #pragma unroll
   for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-  // padded keys among the ones this lane holds of the tail's key block 0 (keys (r & 3) + 8 (r >> 2) + 4 hi, r = 0 .. 15)
-  int tail_pad = 0;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) tail_pad += min(4, max(0, 8 * g + 4 * hi + 4 - tail_valid));
 
   // raw Q rows of the first block (the scaling to log2 units happens at the top of the block's iteration)
   u32x4_t qraw[8];
@@ -584,6 +585,7 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
 #pragma unroll
       for (int d = 0; d < 4; ++d) vf[d] = *reinterpret_cast<const bf16x8_t*>(Vt_ + ((d * 32 + l31) * 2 + hi) * 16);
       asm volatile("s_nop 15" : "+v"(s0));
+      mask_keys(s0, 0, tail_valid - 4 * hi);      // the tail holds tail_valid <= 16 real keys of its 32
       float mxa[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) mxa[i] = max3(s0[i], s0[i + 4], s0[i + 8]);
@@ -599,7 +601,7 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
         s0[r] = __builtin_amdgcn_exp2f(s0[r] - m_run);
         rs += s0[r];
       }
-      l_run += rs - (float)tail_pad * __builtin_amdgcn_exp2f(-m_run);      // the padded keys scored exactly 0
+      l_run += rs;
       u32x4_t w;
 #pragma unroll
       for (int e = 0; e < 4; ++e) w[e] = pack_bf2(s0[2 * e], s0[2 * e + 1]);
@@ -778,6 +780,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_balanced_kernel(am_attn_args 
     }
     // ---- softmax, first half: row max, rescale, exp of key block 0 ------------------------------
     asm volatile("s_nop 15" : "+v"(s[0]), "+v"(s[1]));     // MFMA result -> inline-asm VALU read hazard
+    const int valid = p.sk - c_tt * KVBLK;
+    if (++c_tt == tiles_per_chunk) c_tt = 0;
+    if (valid < KVBLK) {                                    // rare: the partial last tile of a chunk
+      mask_keys(s[0], 0, valid - 4 * hi);
+      mask_keys(s[1], 32, valid - 4 * hi);
+    }
     float mxa[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) mxa[i] = max3(s[0][i], s[1][i], s[0][i + 4]);
@@ -824,16 +832,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_balanced_kernel(am_attn_args 
     {
       const f32x2_t rs = (rsa[0] + rsa[1]) + (rsa[2] + rsa[3]);
       l_run += rs[0] + rs[1];
-    }
-    const int valid = p.sk - c_tt * KVBLK;
-    if (++c_tt == tiles_per_chunk) c_tt = 0;
-    if (valid < KVBLK) {
-      int cnt = 0;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) cnt += min(4, max(0, kb * 32 + 8 * g + 4 * hi + 4 - valid));
-      l_run -= (float)cnt * __builtin_amdgcn_exp2f(-m_run);
     }
     bf16x8_t pf[4];
 #pragma unroll

@@ -22,8 +22,8 @@
 //     K(g+1); K is fetched three tiles ahead and V^T two (LDS-DMA pieces issued one per MFMA pair inside the two
 //     light phases, source = scalar base + 32-bit lane offset), one barrier per tile with a counted
 //     s_waitcnt vmcnt(8); fragments sit in explicit rotating register sets with HOLD() keep-alives;
-//   * the padded keys of a chunk's partial last tile score exactly 0 and their exp2(-m) is removed from the
-//     row sums once, after the loop (rescales multiply it like every other term);
+//   * the padded keys of a chunk's partial last tile score -inf, in a rare branch at the top of that tile's
+//     iteration (mask_tail): P = 0 exactly, so they move neither m_run nor the row sums;
 //   * O (128) and the pre-scaled Q (64) live in AccVGPRs a[64:255], named literally in the inline asm of
 //     am_attention64_asm.inc (P.V runs as AGPR-form MFMAs, QK^T takes its B operand from the accumulator file);
 //   * two-pass form for the multi-GPU overlap (STATE): save (O, m, l) after the local key chunk, resume over
@@ -441,6 +441,26 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64_kernel(am_attn_args p, int 
     for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(z + i * 16) = u32x4_t{0u, 0u, 0u, 0u};
   }
   dma_drain_barrier();
+  // rare: the padded keys of a chunk's partial last tile (keys >= pad_valid) score -inf in both blocks' scores of that tile, before
+  // anything reads them.  Their QK^T MFMAs (inline asm) may still be in flight.
+  const int pad_valid = p.sk - (tiles_per_chunk - 1) * KVBLK;      // valid keys in a chunk's last tile
+  auto mask_tail = [&](f32x16_t (&sa)[2], f32x16_t (&sb)[2]) __attribute__((always_inline)) {
+    asm volatile("s_nop 15\n\ts_nop 15" : "+v"(sa[0]), "+v"(sa[1]), "+v"(sb[0]), "+v"(sb[1]));
+    int tv = pad_valid - 1 - 4 * hi;
+    asm volatile("" : "+v"(tv));          // computed here, in the rare branch, not held across the loop
+    // s = min(s, +-inf): the limit's sign bit is that of tv - key (set: a padded key).  Compares would leave 32 lane masks in
+    // SGPR pairs, and this kernel has no SGPRs to spare.
+    auto lim = [&](int key) __attribute__((always_inline)) { return __int_as_float(((tv - key) & (int)0x80000000) | 0x7f800000); };
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = (r & 3) + 8 * (r >> 2);
+      const float l0 = lim(key), l1 = lim(32 + key);
+      sa[0][r] = __builtin_fminf(sa[0][r], l0); sb[0][r] = __builtin_fminf(sb[0][r], l0);
+      sa[1][r] = __builtin_fminf(sa[1][r], l1); sb[1][r] = __builtin_fminf(sb[1][r], l1);
+    }
+    FENCE();
+  };
+  int c_tt = 0;                           // tile in chunk of the tile the next iteration computes
   auto first_scores = [&](f32x16_t (&s1c)[2]) __attribute__((always_inline)) {   // S(0) = K(0) Q^T
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks)
@@ -453,6 +473,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64_kernel(am_attn_args p, int 
 #pragma unroll
     for (int d = 0; d < 4; ++d) vf[0][d] = v_frag(smem + 3 * STAGE_B, d, 0);
     asm volatile("" :: "v"(negm[0]), "v"(negm[1]));     // SrcC of the first k-step stays allocated until here
+    if (LAZY && STATE != 2 && tiles_per_chunk == 1 && pad_valid < KVBLK) mask_tail(s0, s1c);   // rare: tile 0 is partial (row max below)
     if (LAZY && STATE != 2) {
       // m_run starts at the exact row max of tile 0 rounded up to a whole octave (when resuming it comes from the saved
       // state): un-normalised q.k (Stage II has no qk-norm) may sit tens of octaves away from 0, and a start that far off
@@ -517,6 +538,9 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64_kernel(am_attn_args p, int 
     if (AM_A64_PREP) { k_prep(0); v_prep(0); }
     if (!(ABL & 4)) A64_TILE_BARRIER();
     stamp(g, 1);
+    const bool last_of_chunk = c_tt == tiles_per_chunk - 1;
+    c_tt = last_of_chunk ? 0 : c_tt + 1;
+    if (last_of_chunk && pad_valid < KVBLK) mask_tail(s0, s1c);
     const unsigned char* v_st = smem + ((g + 3) & 3) * STAGE_B;   // V^T(g-1)
     const unsigned char* k_st = smem + ((g + 1) & 3) * STAGE_B;   // K(g+1)
     const unsigned char* vn_st = smem + (g & 3) * STAGE_B;        // V^T(g), for the next iteration's first step
@@ -626,6 +650,9 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64_kernel(am_attn_args p, int 
       A64_TILE_BARRIER();
     }
     stamp(g, 1);
+    const bool last_of_chunk = c_tt == tiles_per_chunk - 1;
+    c_tt = last_of_chunk ? 0 : c_tt + 1;
+    if (last_of_chunk && pad_valid < KVBLK) mask_tail(s0, s1c);
     const unsigned char* v_st = smem + ((g + 3) & 3) * STAGE_B;   // V^T(g-1)
     const unsigned char* k_st = smem + ((g + 1) & 3) * STAGE_B;   // K(g+1)
     const unsigned char* vn_st = smem + (g & 3) * STAGE_B;        // V^T(g), for the next iteration's first step
@@ -802,21 +829,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64_kernel(am_attn_args p, int 
   }
   o_read_fence();
 
-  // ---- epilogue: remove the padded keys' exp2(0 - m) (one partial tile per chunk), normalise, store ----
-  const int pad_valid = p.sk - (tiles_per_chunk - 1) * KVBLK;      // valid keys in a chunk's last tile
-  int cnt = 0;
-  if (pad_valid < KVBLK) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) cnt += min(4, max(0, kb * 32 + 8 * gq + 4 * hi + 4 - pad_valid));
-  }
+  // ---- epilogue: normalise, store ----
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    // (lazy kernel with AM_A64_DOTSUM: the row sums hold ROUNDED probabilities, a padded key's among them; its m_run is a whole number
-    // of octaves unless a resumed state says otherwise, so the rounding is the identity almost always)
-    const float p_pad = __builtin_amdgcn_exp2f(-m_run[j]);
-    float l = l_run[j] - (float)(cnt * p.nchunks) * ((LAZY && AM_A64_DOTSUM) ? rbf(p_pad) : p_pad);
+    float l = l_run[j];
     l += __shfl_xor(l, 32);
     // LAZY: m_run starts at tile 0's max (or at the saved state's) and only ever moves up by whole octaves when a row sum says so.
     // A row whose scores all sit far below it has lost its sum to underflow: let the exact kernel redo the workgroup.

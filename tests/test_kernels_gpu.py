@@ -692,7 +692,7 @@ def test_cross_attention_with_the_resident_key_stream(dev, nseq, H, sq, sk, defe
     (sequence, head), >= 128 pairs) run attn_resident_kernel - the key stream loaded into LDS once per (sequence, head), every query
     block walked against it without a barrier, the tail as 8 + 4 MFMAs.  Against the fp32 statement (the attention kernels' own
     tolerance), and against the tile-streaming kernel forced through its geometry code (defer 50 / 58: never the resident path): the two
-    differ only in the tail's padded-key correction, i.e. by rounding."""
+    differ only in the order the tail's row sum is added, i.e. by rounding."""
     from actionmesh_amd import ops
     q = (_randn((nseq, H, sq, 128), 11, dev) * 1.3).to(dtype)
     k = _randn((nseq, H, sk, 128), 12, dev).to(dtype)
