@@ -93,6 +93,23 @@ class AmAttnF32Args(C.Structure):      # am_attn_f32_args
     ]
 
 
+RENDER_MAX_CAMERAS = 16
+
+
+class AmRenderCamera(C.Structure):     # am_render_camera
+    _fields_ = [("R", C.c_float * 9), ("T", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("px", C.c_float), ("py", C.c_float)]
+
+
+class AmRenderArgs(C.Structure):       # am_render_args
+    _fields_ = [
+        ("verts", C.c_void_p), ("faces", C.c_void_p), ("faces_host", C.c_void_p),
+        ("n_frames", C.c_int32), ("n_verts", C.c_int32), ("n_faces", C.c_int32), ("n_cameras", C.c_int32),
+        ("cameras", AmRenderCamera * RENDER_MAX_CAMERAS), ("image_size", C.c_int32),
+        ("out_rgba", C.c_void_p), ("out_mask", C.c_void_p), ("out_normal", C.c_void_p),
+        ("out_face", C.c_void_p), ("out_bary", C.c_void_p),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -133,6 +150,8 @@ SYMBOLS = {
     "am_displacement_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P]),
     "am_nn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "am_nn_search": (C.c_int, [C.POINTER(AmNnArgs), _P, C.c_size_t, _P]),
+    "am_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "am_render_normals": (C.c_int, [C.POINTER(AmRenderArgs), _P, C.c_size_t, _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

@@ -1,4 +1,5 @@
-"""`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage2-hip [--stage2-cross-fp32]] [--script NAME]
+"""`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage2-hip [--stage2-cross-fp32]]
+                                 [--render {auto,hip,off}] [--script NAME]
                                  [--reference-root DIR] -- <the reference CLI's own arguments>`
 
 Runs the reference's UNMODIFIED command-line script (inference/video_to_animated_mesh.py:120-248, or
@@ -44,6 +45,9 @@ def split_args(argv: List[str]) -> Tuple[argparse.Namespace, List[str]]:
     ap.add_argument("--stage2-hip", action="store_true", help="also decode Stage II on the HIP kernels (HipAutoencoder)")
     ap.add_argument("--stage2-cross-fp32", action="store_true",
                     help="with --stage2-hip: Stage II's query side and cross-attention block in exact fp32, as the reference runs them")
+    ap.add_argument("--render", choices=["auto", "hip", "off"], default="auto",
+                    help="with --backend hip: the preview video grid_normal.* on HIP after the script: auto (default) = only when pytorch3d is not "
+                         "importable, so the reference's own video is not rendered twice; hip = always; off = never")
     ap.add_argument("--script", choices=SCRIPTS, default=SCRIPTS[0])
     ap.add_argument("--reference-root", default=None)
     ap.add_argument("--amd-help", action="store_true", help="this wrapper's options (plain --help shows the reference CLI's)")
@@ -63,15 +67,20 @@ def main(argv: Optional[List[str]] = None) -> None:
     if ours.reference_root:
         sys.path.insert(0, ours.reference_root)
     script = find_script(ours.script, ours.reference_root)
+    render = False
     if ours.backend == "hip":
         from . import dropin
-        dropin.install(attn_dtype=ours.attn_dtype, stage2=ours.stage2_hip, stage2_cross_fp32=ours.stage2_cross_fp32)
+        from . import render as R
+        render = ours.render == "hip" or (ours.render == "auto" and not R.pytorch3d_available())
+        dropin.install(attn_dtype=ours.attn_dtype, stage2=ours.stage2_hip, stage2_cross_fp32=ours.stage2_cross_fp32, render=render)
     old_argv = sys.argv
     sys.argv = [script] + rest
     try:
         runpy.run_path(script, run_name="__main__")
     finally:
         sys.argv = old_argv
+    if render:           # the preview video the reference renders only with PyTorch3D (seam S6), into the script's output directory
+        R.render_captured()
 
 
 if __name__ == "__main__":

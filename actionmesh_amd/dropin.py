@@ -11,7 +11,9 @@ The reference builds its Stage-I objects in three places, none of which takes a 
   * the denoiser is `ActionMeshDenoiser.from_pretrained(...)`, the name resolved in `actionmesh.pipeline`'s globals at call
     time (pipeline.py:180)                                                              -> that global is rebound to HipDenoiser
     (same `from_pretrained(dir)`, `.eval()`, `.to()`, `.device`, forward signature: tests/test_reference_seams_cpu.py);
-  * optionally (`stage2=True`) the Stage-II decoder, `ActionMeshAutoencoder.from_pretrained` (pipeline.py:195) -> HipAutoencoder.
+  * optionally (`stage2=True`) the Stage-II decoder, `ActionMeshAutoencoder.from_pretrained` (pipeline.py:195) -> HipAutoencoder;
+  * optionally (`render=True`) the scripts' `load_frames` / `save_deformation` are wrapped to keep what the preview video needs
+    (actionmesh_amd/render.py, seam S6).
 
 `uninstall()` restores every name.  Nothing here imports the reference at module import time: `install()` imports
 `actionmesh.pipeline` (the caller's environment must be able to - that is the environment the reference runs in).
@@ -93,12 +95,14 @@ def _wrap_load_config(orig):
     return load_config
 
 
-def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[bool] = None, stage2_cross_fp32: bool = False) -> None:
+def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[bool] = None, stage2_cross_fp32: bool = False,
+            render: bool = False) -> None:
     """Patch the reference in THIS process (idempotent).  After it, `ActionMeshPipeline(config_name="actionmesh.yaml", ...)` - and
     therefore the unmodified CLI - samples Stage I with HipSchedulerFlow over a HipDenoiser.
     `attn_dtype`: "bf16" (default) or "fp8" (inflated self-attention on the e4m3 MFMA kernel).  `stage2`: also run the Stage-II
     decoder on HipAutoencoder.  `stage2_cross_fp32`: that decoder runs its query side and cross-attention block in exact fp32, as the
-    reference does (HipAutoencoder(cross_fp32=True); needs `stage2`)."""
+    reference does (HipAutoencoder(cross_fp32=True); needs `stage2`).  `render`: also wrap the scripts' `load_frames` /
+    `save_deformation` so that `actionmesh_amd.render.render_captured()` can draw the preview video afterwards (render.install_hook)."""
     if stage2_cross_fp32 and not stage2:
         raise ValueError("actionmesh_amd.install(): stage2_cross_fp32=True needs stage2=True")
     import actionmesh.pipeline as P      # the reference (must be importable where the reference runs)
@@ -135,6 +139,9 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
             _ConfiguredHipAutoencoder.__qualname__ = "HipAutoencoder"
             decoder = _ConfiguredHipAutoencoder
         P.ActionMeshAutoencoder = decoder
+    if render:
+        from . import render as R
+        R.install_hook()
     _state["installed"] = True
     _state["saved"] = saved
     _state["module"] = P
@@ -146,6 +153,8 @@ def uninstall() -> None:
     P = _state["module"]
     for name, obj in _state["saved"].items():
         setattr(P, name, obj)
+    from . import render as R
+    R.uninstall_hook()
     _state["installed"] = False
 
 

@@ -604,3 +604,52 @@ def displacement_f32(logits: torch.Tensor, out_dim: int, out: torch.Tensor, kind
     _launch(logits, _fk(kind, "am_displacement_f32"), "am_displacement_f32", logits.data_ptr(), logits.stride(0), logits.shape[0], out_dim,
             out.data_ptr())
     return out
+
+
+def render_normals(vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequence[dict], image_size: int,
+                   fragments: bool = False, floats: bool = False) -> dict:
+    """am_render_normals: the normal-map preview of an animated mesh.  vertices (T, V, 3) fp32 on the device, faces (F, 3) integer
+    (any device: a host copy is what the library checks against V), cameras: up to 16 dicts with "R" (3, 3), "T" (3,),
+    "focal_length" (fx, fy) and "principal_point" (px, py).  Returns {"rgba": uint8 (T, C, S, S, 4)} plus, with `floats`,
+    "mask" (T, C, S, S) and "normal" (T, C, S, S, 3), and with `fragments`, "pix_to_face" int32 (T, C, 2S, 2S) and "bary"
+    (T, C, 2S, 2S, 3) - all on the device of `vertices`."""
+    _need(vertices, torch.float32, "vertices")
+    if vertices.dim() != 3 or vertices.shape[-1] != 3:
+        raise ValueError(f"render_normals: vertices must be (T, V, 3), got {tuple(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[-1] != 3 or faces.dtype.is_floating_point:
+        raise ValueError(f"render_normals: faces must be (F, 3) integers, got {tuple(faces.shape)} {faces.dtype}")
+    if not 1 <= len(cameras) <= L.RENDER_MAX_CAMERAS:
+        raise ValueError(f"render_normals: {len(cameras)} cameras, 1 .. {L.RENDER_MAX_CAMERAS} supported")
+    T, V = vertices.shape[0], vertices.shape[1]
+    F, Cn, S = faces.shape[0], len(cameras), int(image_size)
+    dev = vertices.device
+    faces_host = faces.detach().to("cpu", torch.int32).contiguous()
+    faces_dev = faces_host.to(dev)
+    out = {"rgba": torch.empty((T, Cn, S, S, 4), dtype=torch.uint8, device=dev)}
+    if floats:
+        out["mask"] = torch.empty((T, Cn, S, S), dtype=torch.float32, device=dev)
+        out["normal"] = torch.empty((T, Cn, S, S, 3), dtype=torch.float32, device=dev)
+    if fragments:
+        out["pix_to_face"] = torch.empty((T, Cn, 2 * S, 2 * S), dtype=torch.int32, device=dev)
+        out["bary"] = torch.empty((T, Cn, 2 * S, 2 * S, 3), dtype=torch.float32, device=dev)
+    a = L.AmRenderArgs()
+    a.verts, a.faces, a.faces_host = vertices.data_ptr(), faces_dev.data_ptr(), faces_host.data_ptr()
+    a.n_frames, a.n_verts, a.n_faces, a.n_cameras, a.image_size = T, V, F, Cn, S
+    for k, cam in enumerate(cameras):
+        c = a.cameras[k]
+        R = torch.as_tensor(cam["R"], dtype=torch.float32).reshape(9).tolist()
+        Tv = torch.as_tensor(cam["T"], dtype=torch.float32).reshape(3).tolist()
+        for i in range(9):
+            c.R[i] = R[i]
+        for i in range(3):
+            c.T[i] = Tv[i]
+        c.fx, c.fy = (float(x) for x in cam["focal_length"])
+        c.px, c.py = (float(x) for x in cam["principal_point"])
+    a.out_rgba = out["rgba"].data_ptr()
+    a.out_mask, a.out_normal = _p(out.get("mask")), _p(out.get("normal"))
+    a.out_face, a.out_bary = _p(out.get("pix_to_face")), _p(out.get("bary"))
+    lib = L.lib()
+    need = lib.am_render_workspace_bytes(T, V, F, Cn, S)
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    _launch(vertices, lib.am_render_normals, "am_render_normals", C.byref(a), ws.data_ptr(), need)
+    return out

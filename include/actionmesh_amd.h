@@ -407,6 +407,44 @@ typedef struct {
 size_t am_nn_workspace_bytes(int64_t n_points, int64_t n_queries, int batch, int precise);
 int am_nn_search(const am_nn_args* args, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Preview rendering (INTEGRATION seam S6; reference actionmesh/render/{renderer,visualizer}.py, PyTorch3D's
+ * MeshRasterizer + soft_normal_shading): normal maps of ONE animated mesh - n_frames vertex sets on one topology - seen by
+ * n_cameras PerspectiveCameras, every (frame, camera) image of the call in a fixed number of launches.
+ *   vertex normals: sum of the un-normalised cross(v2 - v1, v0 - v1) of every face on the vertex, in face-index order,
+ *                   normalised with eps 1e-6 (Meshes.verts_normals_packed; no float atomics: bit-identical run to run);
+ *   projection:     view = X @ R + T (row vectors), x_ndc = fx * view.x / view.z + px, y likewise, depth = view.z;
+ *   raster:         at 2S x 2S, pixel centre x = 1 - (2 col + 1) / W, y = 1 - (2 row + 1) / H; covered when the three
+ *                   perspective-corrected, unclipped barycentrics are all > 0; the nearest face wins, ties -> lowest index;
+ *   resolve to S x S: mask = covered sub-pixels / 4; normal of sub-pixel (2i, 2j) through n @ R + T / 2, normalised,
+ *                   (n + 1) / 2, clamped; rgba8 = trunc(255 * (normal * mask + 1 - mask)), alpha = trunc(255 * mask).
+ * faces_host is the host copy of `faces` (the same (n_faces, 3) array): every index is checked against n_verts on it before
+ * anything is launched.  The optional outputs (NULL = not written) are the float forms and the 2S x 2S fragments.
+ * am_render_workspace_bytes() bytes of device scratch must be passed for the same sizes. */
+#define AM_RENDER_MAX_CAMERAS 16
+typedef struct {
+  float R[9];        /* row-major 3x3: view = X @ R + T */
+  float T[3];
+  float fx, fy, px, py;
+} am_render_camera;
+typedef struct {
+  const float* verts;           /* (n_frames, n_verts, 3) fp32 */
+  const int32_t* faces;         /* (n_faces, 3) int32 */
+  const int32_t* faces_host;    /* host memory: the same (n_faces, 3) array */
+  int32_t n_frames;
+  int32_t n_verts;
+  int32_t n_faces;
+  int32_t n_cameras;            /* 1 .. AM_RENDER_MAX_CAMERAS */
+  am_render_camera cameras[AM_RENDER_MAX_CAMERAS];
+  int32_t image_size;           /* S */
+  uint8_t* out_rgba;            /* (n_frames, n_cameras, S, S, 4) */
+  float* out_mask;              /* optional (n_frames, n_cameras, S, S) */
+  float* out_normal;            /* optional (n_frames, n_cameras, S, S, 3): (n + 1) / 2 before the mask blend */
+  int32_t* out_face;            /* optional (n_frames, n_cameras, 2S, 2S): face index, -1 = empty */
+  float* out_bary;              /* optional (n_frames, n_cameras, 2S, 2S, 3): clipped barycentrics, -1 = empty */
+} am_render_args;
+size_t am_render_workspace_bytes(int n_frames, int n_verts, int n_faces, int n_cameras, int image_size);
+int am_render_normals(const am_render_args* args, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

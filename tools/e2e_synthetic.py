@@ -118,7 +118,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
     assert bool(torch.isfinite(verts).all()) and float(verts.abs().max()) <= 1.0
     lat, _ = bank.get_ordered()
     assert bool(torch.isfinite(lat).all())
-    # output files (N4): per-frame GLBs, the deformation arrays, the animated morph-target GLB; and the ActionBench Chamfer metrics
+    # output files (N4): per-frame GLBs, the deformation arrays, the animated morph-target GLB, the preview video; and the ActionBench Chamfer metrics
     # of the animation against itself shifted by one frame (a number that must be > 0 and finite: the metric path end to end)
     import shutil
     import tempfile
@@ -130,6 +130,11 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
     vp, fp = save_deformation(verts, faces, os.path.join(out_dir, "deformations"))
     create_animated_glb(vertices_npy=str(vp), faces_npy=str(fp), output_glb=os.path.join(out_dir, "animated_mesh.glb"), fps=8)
     t_out = time.perf_counter() - t0
+    # the preview video (grid_normal.*: three normal-map views per frame, the reference's visualizer call) on am_render_normals
+    from actionmesh_amd import HipVisualizer
+    t0 = time.perf_counter()
+    HipVisualizer(image_size=256).render(verts, device=dev, output_dir=out_dir, input_frames=None, faces=faces)
+    t_preview = time.perf_counter() - t0
     out_bytes = sum(os.path.getsize(os.path.join(r, f_)) for r, _, fs in os.walk(out_dir) for f_ in fs)
     shutil.rmtree(out_dir)
     (cd, cdm), t_metric = stage(lambda: (actionbench.compute_chamfer_score(verts[1], verts[0], device=dev),
@@ -141,6 +146,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             "seconds": {"context_encoder": round(t_enc, 4), "stage_I": round(t_s1, 3), "stage_II": round(t_s2, 3),
                         "model_build_and_upload": round(t_build, 1),
                         "output_files_host_side": round(t_out, 3), "chamfer_metrics": round(t_metric, 4)},
+            "preview_video_s": round(t_preview, 3),          # grid_normal.* (HipVisualizer), written into the output files above
             "output_files_mb": round(out_bytes / 1e6, 1),
             "config": {"workload": f"{frames} frames, {n_win} AR window(s) of {window}, {steps} denoise steps, N={n_tokens} tokens, "
                                    f"{vertices} vertices, {'tiny' if tiny else 'shipped'} model shapes, random-init weights"
