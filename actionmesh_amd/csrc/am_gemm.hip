@@ -1235,8 +1235,10 @@ extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
   if (a->ln_stats) {
     AM_CHECK(a->ln_colsum != nullptr, "am_gemm_bf16: ln_stats without ln_colsum");
     AM_CHECK(a->A2 == nullptr, "am_gemm_bf16: a folded LayerNorm needs one A operand");
-    // a row map on A is honoured by the 128x128 kernel only (ln_stats is indexed by the mapped A row): narrow linears such as proj_out
-    AM_CHECK(a->a_G == 0 || a->N < 256 || (a->act & 0x100), "am_gemm_bf16: a folded LayerNorm over a row-mapped A needs N < 256 (the 128x128 kernel)");
+    // a row map on A is honoured by the 128x128 kernel only (ln_stats is indexed by the mapped A row): narrow linears such as proj_out.
+    // act 0x400 sends any N to the 256x256 tile, which indexes the statistics by OUTPUT row: refused unless 0x100 (which wins) is set too
+    AM_CHECK(a->a_G == 0 || (a->act & 0x100) || (a->N < 256 && !(a->act & 0x400)),
+             "am_gemm_bf16: a folded LayerNorm over a row-mapped A needs the 128x128 kernel (N < 256 without the forced 256x256 tile)");
     AM_CHECK(!(a->act & 0x200), "am_gemm_bf16: the round-1 lockstep kernel has no folded-LayerNorm epilogue");
     AM_CHECK(((uintptr_t)a->ln_stats % 8 == 0) && ((uintptr_t)a->ln_colsum % 16 == 0) && (a->bias == nullptr || (uintptr_t)a->bias % 16 == 0) &&
              a->N % 4 == 0, "am_gemm_bf16: ln_stats / ln_colsum / bias misaligned");

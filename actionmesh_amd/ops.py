@@ -375,10 +375,11 @@ def f32_to_bf16(x: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
     return y
 
 
-def timestep_sinusoid(t: torch.Tensor, width: int) -> torch.Tensor:
+def timestep_sinusoid(t: torch.Tensor, width: int, dtype=torch.bfloat16) -> torch.Tensor:
+    """t (rows,) fp32 -> 16-bit (rows, width): [sin | cos] of t * 10000^(-i / (width / 2)); `dtype=torch.float16` runs the float16 build."""
     _need(t, torch.float32, "t")
-    y = torch.empty((t.numel(), width), dtype=torch.bfloat16, device=t.device)
-    _launch(t, L.lib().am_timestep_sinusoid, "am_timestep_sinusoid", t.data_ptr(), y.data_ptr(), t.numel(), width)
+    y = torch.empty((t.numel(), width), dtype=dtype, device=t.device)
+    _launch(t, _fn(dtype, "am_timestep_sinusoid"), "am_timestep_sinusoid", t.data_ptr(), y.data_ptr(), t.numel(), width)
     return y
 
 

@@ -277,6 +277,10 @@ def test_head_post_cross(dev):
 
 @pytest.mark.parametrize("case", ["self_qkv_tail_and_straddle", "cross_q", "no_norm_no_rope", "misaligned_falls_back", "small_falls_back"])
 def test_gemm_headpost_fused_is_bit_identical(dev, case):
+    _gemm_headpost_fused_case(dev, case)
+
+
+def _gemm_headpost_fused_case(dev, case, dtype=torch.bfloat16):
     """am_gemm_headpost_bf16 (round 3: north_star's fused RMSNorm + RoPE + QKV - the head split in the GEMM's epilogue) against
     am_gemm_bf16 followed by am_head_post: every byte of Q, K and V^T - including the pad rows / columns, and nothing written outside
     (the outputs start from a sentinel).  Shapes: (a) two sequences of 8208 rows whose boundary falls inside a 256-row tile, 32
@@ -296,8 +300,8 @@ def test_gemm_headpost_fused_is_bit_identical(dev, case):
     seq_len = Lr if nseq_frames else T * Lr
     rows = B * T * Lr
     N = heads * len(kinds) * 128
-    a = _randn((rows, Cw), 1, dev).to(torch.bfloat16)
-    w = _randn((N, Cw), 2, dev, Cw ** -0.5).to(torch.bfloat16)
+    a = _randn((rows, Cw), 1, dev).to(dtype)
+    w = _randn((N, Cw), 2, dev, Cw ** -0.5).to(dtype)
     norm = case != "no_norm_no_rope"
     wq = (_randn((128,), 3, dev) * 0.2 + 1.0) if norm else None
     wk = (_randn((128,), 4, dev) * 0.2 + 1.0) if norm else None
@@ -309,7 +313,7 @@ def test_gemm_headpost_fused_is_bit_identical(dev, case):
     sq_pad, sk_pad = ops.round_up(seq_len, 256), ops.round_up(seq_len, 64)
 
     def outs():
-        s_ = torch.full((1,), -3.0, dtype=torch.bfloat16, device=dev)
+        s_ = torch.full((1,), -3.0, dtype=dtype, device=dev)
         return (s_.expand(nseq, heads, sq_pad, 128).contiguous() if 0 in kinds else None,
                 s_.expand(nseq, heads, sk_pad, 128).contiguous() if 1 in kinds else None,
                 s_.expand(nseq, heads, 128, sk_pad).contiguous() if 2 in kinds else None)
@@ -330,22 +334,23 @@ def test_gemm_headpost_fused_is_bit_identical(dev, case):
 
 # ------------------------------------------------------------------------------------------
 def _layout(q, k, v, nchunks=1):
-    """(nseq,H,S,128) tensors -> padded kernel operands; keys split in `nchunks` equal chunks."""
+    """(nseq,H,S,128) tensors -> padded kernel operands in q's 16-bit type (bf16 for anything else); keys split in `nchunks` equal chunks."""
     from actionmesh_amd import ops
     nseq, H, sq, _ = q.shape
+    dt = q.dtype if q.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
     sk = k.shape[2]
     assert sk % nchunks == 0
     skc = sk // nchunks
     sq_pad, sk_pad = ops.round_up(sq, 256), ops.round_up(skc, 64)
     dev = q.device
-    Q = torch.zeros((nseq, H, sq_pad, 128), dtype=torch.bfloat16, device=dev)
+    Q = torch.zeros((nseq, H, sq_pad, 128), dtype=dt, device=dev)
     Q[:, :, :sq] = q
-    K = torch.zeros((nchunks, nseq, H, sk_pad, 128), dtype=torch.bfloat16, device=dev)
-    Vt = torch.zeros((nchunks, nseq, H, 128, sk_pad), dtype=torch.bfloat16, device=dev)
+    K = torch.zeros((nchunks, nseq, H, sk_pad, 128), dtype=dt, device=dev)
+    Vt = torch.zeros((nchunks, nseq, H, 128, sk_pad), dtype=dt, device=dev)
     idx = ops.perm16_index(sk_pad, dev)
     for c in range(nchunks):
         K[c, :, :, :skc] = k[:, :, c * skc:(c + 1) * skc]
-        vp = torch.zeros((nseq, H, sk_pad, 128), dtype=torch.bfloat16, device=dev)
+        vp = torch.zeros((nseq, H, sk_pad, 128), dtype=dt, device=dev)
         vp[:, :, :skc] = v[:, :, c * skc:(c + 1) * skc]
         Vt[c] = vp[:, :, idx].transpose(-1, -2)
     return Q, K, Vt, skc
@@ -558,7 +563,7 @@ def test_attention_properties_full_size(dev):
     assert (o1 - 1.0).abs().max().item() < 8e-3
 
 
-def _coverage_case(dev, sq, skc, P, H=1, score_by_tile=False):
+def _coverage_case(dev, sq, skc, P, H=1, score_by_tile=False, dtype=torch.bfloat16):
     """Operands that make every 64-key tile of the stream visible in the output: V = indicator of the key's tile (channel = global
     tile index mod 128), and either Q = 0 (uniform scores: channel c of every output row = the share of the keys that sit in tiles
     = c mod 128 - EXACT in bf16 / fp8 arithmetic: p = 1, V = 1, integer sums) or scores that depend on the key's tile only.
@@ -578,7 +583,7 @@ def _coverage_case(dev, sq, skc, P, H=1, score_by_tile=False):
         s_tile = 8.0 * b * 128 ** -0.5
     w = torch.exp(s_tile - s_tile.max())[gt]                                   # fp64 softmax weight of every key (same for all rows)
     expect = torch.zeros(128, dtype=torch.float64, device=dev).index_add_(0, gt % 128, w) / w.sum()
-    return q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), expect
+    return q.to(dtype), k.to(dtype), v.to(dtype), expect
 
 
 @pytest.mark.parametrize("form", ["one_pass", "two_pass", "forced_8wave"])
