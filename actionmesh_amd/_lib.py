@@ -110,6 +110,18 @@ class AmRenderArgs(C.Structure):       # am_render_args
     ]
 
 
+FPS_F32, FPS_F16, FPS_BF16 = 0, 1, 2    # am_fps_args.dtype
+
+
+class AmFpsArgs(C.Structure):          # am_fps_args
+    _fields_ = [
+        ("points", C.c_void_p), ("dtype", C.c_int32), ("batch", C.c_int32), ("n_points", C.c_int64),
+        ("dims", C.c_int32), ("dist_dims", C.c_int32), ("batch_stride", C.c_int64), ("point_stride", C.c_int64),
+        ("n_samples", C.c_int64), ("start_idx", C.c_void_p), ("out_index", C.c_void_p), ("out_dist", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("threads", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -152,6 +164,8 @@ SYMBOLS = {
     "am_nn_search": (C.c_int, [C.POINTER(AmNnArgs), _P, C.c_size_t, _P]),
     "am_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "am_render_normals": (C.c_int, [C.POINTER(AmRenderArgs), _P, C.c_size_t, _P]),
+    "am_fps_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "am_fps": (C.c_int, [C.POINTER(AmFpsArgs), _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

@@ -13,7 +13,10 @@ The reference builds its Stage-I objects in three places, none of which takes a 
     (same `from_pretrained(dir)`, `.eval()`, `.to()`, `.device`, forward signature: tests/test_reference_seams_cpu.py);
   * optionally (`stage2=True`) the Stage-II decoder, `ActionMeshAutoencoder.from_pretrained` (pipeline.py:195) -> HipAutoencoder;
   * optionally (`render=True`) the scripts' `load_frames` / `save_deformation` are wrapped to keep what the preview video needs
-    (actionmesh_amd/render.py, seam S6).
+    (actionmesh_amd/render.py, seam S6);
+  * optionally (`pointcloud=True`) `actionmesh.external.triposg` gets the `sample_pc` / `sample_pc_grouped` / `masked_gather` its
+    guarded PyTorch3D import left missing (triposg.py:17-23), over the HIP farthest-point sampling
+    (actionmesh_amd/pointcloud_sampling.py, seam S7).
 
 `uninstall()` restores every name.  Nothing here imports the reference at module import time: `install()` imports
 `actionmesh.pipeline` (the caller's environment must be able to - that is the environment the reference runs in).
@@ -96,16 +99,20 @@ def _wrap_load_config(orig):
 
 
 def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[bool] = None, stage2_cross_fp32: bool = False,
-            render: bool = False) -> None:
+            render: bool = False, pointcloud: bool = False) -> None:
     """Patch the reference in THIS process (idempotent).  After it, `ActionMeshPipeline(config_name="actionmesh.yaml", ...)` - and
     therefore the unmodified CLI - samples Stage I with HipSchedulerFlow over a HipDenoiser.
     `attn_dtype`: "bf16" (default) or "fp8" (inflated self-attention on the e4m3 MFMA kernel).  `stage2`: also run the Stage-II
     decoder on HipAutoencoder.  `stage2_cross_fp32`: that decoder runs its query side and cross-attention block in exact fp32, as the
     reference does (HipAutoencoder(cross_fp32=True); needs `stage2`).  `render`: also wrap the scripts' `load_frames` /
-    `save_deformation` so that `actionmesh_amd.render.render_captured()` can draw the preview video afterwards (render.install_hook)."""
+    `save_deformation` so that `actionmesh_amd.render.render_captured()` can draw the preview video afterwards (render.install_hook).
+    `pointcloud`: also give `actionmesh.external.triposg` the point-cloud sampling names it lacks without PyTorch3D
+    (pointcloud_sampling.install_into), so that `TripoSGVAE` can be built and samples its surface points on the HIP FPS kernel."""
     if stage2_cross_fp32 and not stage2:
         raise ValueError("actionmesh_amd.install(): stage2_cross_fp32=True needs stage2=True")
     import actionmesh.pipeline as P      # the reference (must be importable where the reference runs)
+    if pointcloud:                       # before anything is patched: needs the triposg package, as the reference's anchor path does
+        import actionmesh.external.triposg as T
     from .denoiser import HipDenoiser
 
     if _state.get("installed"):
@@ -142,6 +149,10 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     if render:
         from . import render as R
         R.install_hook()
+    _state["pointcloud"] = None
+    if pointcloud:
+        from . import pointcloud_sampling as S
+        _state["pointcloud"] = (T, S.install_into(T))
     _state["installed"] = True
     _state["saved"] = saved
     _state["module"] = P
@@ -155,6 +166,10 @@ def uninstall() -> None:
         setattr(P, name, obj)
     from . import render as R
     R.uninstall_hook()
+    if _state.get("pointcloud"):
+        from . import pointcloud_sampling as S
+        S.uninstall_from(*_state["pointcloud"])
+        _state["pointcloud"] = None
     _state["installed"] = False
 
 

@@ -471,6 +471,73 @@ def nn_indices_valid(*indices: torch.Tensor) -> None:
         raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
 
 
+_FPS_DTYPES = {torch.float32: L.FPS_F32, torch.float16: L.FPS_F16, torch.bfloat16: L.FPS_BF16}
+
+
+def farthest_point_sample(points: torch.Tensor, n_samples: int, start_idx=None, dist_dims: Optional[int] = None,
+                          return_dist: bool = False, check: bool = True, threads: int = 0):
+    """am_fps: exact greedy farthest-point sampling (the contract is the header's).  points (N, D) or (B, N, D), fp32 / fp16 / bf16,
+    D = 1..8, any strides whose channel axis is contiguous (x[..., :3] of a wider tensor is passed as it is, no copy).  The first
+    `dist_dims` channels enter the distance (default: all D).  `start_idx`: None (every cloud starts at point 0), an int, or an
+    integer tensor (B,).  Returns the int32 indices (B, n_samples) - (n_samples,) for a 2-D input - and with `return_dist` also
+    the fp32 squared distance each point had to the set chosen before it (+inf for the first).
+    `check` (default): one device-to-host read in front of the launch - every coordinate finite, every start index in range.
+    A caller that knows its inputs passes check=False and nothing serialises the stream.  `threads`: 0 = the library's choice of
+    workgroup size, 256 / 512 / 1024 for benchmarks (tools/kernel_bench.py fps)."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise RuntimeError("farthest_point_sample: actionmesh_amd kernels need a device tensor (no CPU path)")
+    if points.dtype not in _FPS_DTYPES:
+        raise TypeError(f"farthest_point_sample: expected float32, float16 or bfloat16 points, got {points.dtype}")
+    if points.dim() not in (2, 3):
+        raise ValueError(f"farthest_point_sample: expected (N, D) or (B, N, D) points, got {tuple(points.shape)}")
+    p3 = points if points.dim() == 3 else points.unsqueeze(0)
+    B, N, D = p3.shape
+    dd = D if dist_dims is None else int(dist_dims)
+    K = int(n_samples)
+    if B < 1 or N < 1:
+        raise ValueError(f"farthest_point_sample: empty point cloud {tuple(points.shape)}")
+    if not 1 <= D <= 8 or not 1 <= dd <= D:
+        raise ValueError(f"farthest_point_sample: needs 1 <= dist_dims ({dd}) <= D ({D}) <= 8")
+    if not 1 <= K <= N:
+        raise ValueError(f"farthest_point_sample: n_samples {K} outside 1 .. N ({N})")
+    sb, sp, sc = p3.stride()
+    if N == 1:
+        sp = D
+    if B == 1:
+        sb = 0
+    if (D > 1 and sc != 1) or sp < D or sb < 0:
+        raise ValueError(f"farthest_point_sample: the channel axis must be contiguous and points must not overlap (strides {p3.stride()})")
+    dev = p3.device
+    start = None
+    if start_idx is not None:
+        start = torch.as_tensor(start_idx, device=dev)
+        if start.is_floating_point() or start.dtype == torch.bool:
+            raise TypeError(f"farthest_point_sample: start_idx must hold integers, got {start.dtype}")
+        start = start.reshape(-1).expand(B) if start.numel() == 1 else start.reshape(-1)
+        if start.numel() != B:
+            raise ValueError(f"farthest_point_sample: start_idx has {start.numel()} entries for a batch of {B}")
+        if check and bool(((start < 0) | (start >= N)).any()):
+            raise ValueError(f"farthest_point_sample: start_idx outside [0, {N})")
+        start = start.to(torch.int32).contiguous()
+    if check and not bool(torch.isfinite(p3[..., :dd]).all()):
+        raise ValueError("farthest_point_sample: non-finite coordinates in the points")
+    idx = torch.empty((B, K), dtype=torch.int32, device=dev)
+    dist = torch.empty((B, K), dtype=torch.float32, device=dev) if return_dist else None
+    lib = L.lib()
+    need = lib.am_fps_workspace_bytes(N, B, dd)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+    a = L.AmFpsArgs()
+    a.points, a.dtype, a.batch, a.n_points = p3.data_ptr(), _FPS_DTYPES[points.dtype], B, N
+    a.dims, a.dist_dims, a.batch_stride, a.point_stride, a.n_samples = D, dd, sb, sp, K
+    a.start_idx = start.data_ptr() if start is not None else None
+    a.out_index, a.out_dist = idx.data_ptr(), (dist.data_ptr() if return_dist else None)
+    a.workspace, a.workspace_bytes, a.threads = (ws.data_ptr() if need else None), need, int(threads)
+    _launch(p3, lib.am_fps, "am_fps", C.byref(a))
+    if points.dim() == 2:
+        idx, dist = idx[0], (dist[0] if return_dist else None)
+    return (idx, dist) if return_dist else idx
+
+
 # ---- exact-fp32 path (csrc/am_f32.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----------------------
 def _fk(kind: str, name: str):
     """Entry point `name` of the library build `kind` ("bf16" / "f16"): the fp32 entry points are in both."""

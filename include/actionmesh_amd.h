@@ -445,6 +445,61 @@ typedef struct {
 size_t am_render_workspace_bytes(int n_frames, int n_verts, int n_faces, int n_cameras, int image_size);
 int am_render_normals(const am_render_args* args, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Farthest-point sampling (INTEGRATION seam S7; reference actionmesh/model/utils/pointcloud_sampling.py, which on CUDA calls
+ * pytorch3d.ops.sample_farthest_points - the reduction of 8192 surface points to 2048 tokens in front of the TripoSG VAE,
+ * actionmesh/external/triposg.py:113-151).  Exact greedy FPS, every cloud of the batch on its own, fully determined:
+ *
+ *   md[i] = +inf for all i;  cur = start_idx[b]
+ *   for k in 0 .. n_samples - 1:
+ *       out_index[k] = cur;  out_dist[k] = md[cur]             (+inf for k = 0)
+ *       d2[i] = ((d0*d0) + (d1*d1)) + (d2*d2) + ...            dc = p[i][c] - p[cur][c] in fp32, left to right over the first
+ *                                                              dist_dims channels, every product and sum rounded on its own
+ *                                                              (no fma contraction)
+ *       md[i] = min(md[i], d2[i])
+ *       cur   = the LOWEST index i with md[i] == max(md)
+ *
+ * 16-bit inputs are converted to fp32 first (exact).  A chosen point has md == 0, so it is chosen again only when every
+ * remaining point coincides with a chosen one; the lowest-index rule then returns index 0 from there on, with out_dist 0.
+ * Inputs must be finite; with non-finite inputs the call still terminates with every index inside [0, n_points), nothing more.
+ * PyTorch3D is not installable where this was written: that its CUDA kernel breaks ties the same way, and how it draws a
+ * random start point, are UNPINNED; the contract above is what the tests hold (against a numpy restatement, bit for bit).
+ *
+ *   points       device, element (b, i, c) at points[b * batch_stride + i * point_stride + c]: strides in ELEMENTS, channels
+ *                contiguous - so x[..., :3] of a (B, N, 6) tensor needs no copy, and equal chunks of one cloud can be passed
+ *                as extra batch entries of one launch;
+ *   dims         channels a point has (1 .. 8; point_stride >= dims);  dist_dims (1 .. dims): those that enter the distance -
+ *                3 for the reference's "fps", dims for "fps_full";
+ *   start_idx    device int32[batch], NULL = every cloud starts at 0 (values are clamped into [0, n_points));
+ *   out_index    device int32 (batch, n_samples);  out_dist: optional device fp32 (batch, n_samples), NULL = not written;
+ *   threads      0 = the library's choice; 256 / 512 / 1024 = workgroup size of the resident form (for benchmarks).
+ * One workgroup per cloud.  Up to 8192 points the cloud and md stay in registers for the whole launch (the resident form) and
+ * no workspace is needed; beyond that (any n_points < 2^31: the streaming form) md and an fp32 copy of the distance channels
+ * live in `workspace` - am_fps_workspace_bytes() bytes of 16-byte aligned device scratch for the same (n_points, batch,
+ * dist_dims), 0 for the resident form - and are walked once per step. */
+#define AM_FPS_F32 0
+#define AM_FPS_F16 1    /* IEEE half */
+#define AM_FPS_BF16 2
+typedef struct {
+  const void* points;
+  int32_t dtype;                /* AM_FPS_F32 / AM_FPS_F16 / AM_FPS_BF16 */
+  int32_t batch;
+  int64_t n_points;
+  int32_t dims;
+  int32_t dist_dims;
+  int64_t batch_stride;
+  int64_t point_stride;
+  int64_t n_samples;            /* K: 1 .. n_points */
+  const int32_t* start_idx;
+  int32_t* out_index;
+  float* out_dist;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t threads;
+  int32_t reserved;
+} am_fps_args;
+size_t am_fps_workspace_bytes(int64_t n_points, int batch, int dist_dims);
+int am_fps(const am_fps_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Per-kernel timing at the headline (or nominal) layer shapes, HIP events on the launch stream.
     python tools/kernel_bench.py [--shape headline|nominal] [--only attn,gemm,ln,post] [--reps 3]
-Prints one line per kernel: ms, TFLOP/s (MFMA kernels) or GB/s (HBM-bound kernels)."""
+Prints one line per kernel: ms, TFLOP/s (MFMA kernels) or GB/s (HBM-bound kernels).
+`--only fps` times the farthest-point sampling kernel against the same algorithm as a loop of torch operations and writes
+profiles/fps_bench.json (`--fps-out` for another path)."""
 import argparse
 import os
 import sys
@@ -25,6 +27,53 @@ def timeit(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def fps_torch_loop(pts, K):
+    """The FPS of include/actionmesh_amd.h as what a user has without the kernel: K iterations of torch operations on the device
+    (subtract / square / sum / minimum / argmax).  No host synchronisation inside: `cur` stays a device tensor."""
+    B, N, _ = pts.shape
+    md = torch.full((B, N), float("inf"), device=pts.device)
+    cur = torch.zeros((B, 1, 1), dtype=torch.long, device=pts.device)
+    out = torch.empty((B, K), dtype=torch.long, device=pts.device)
+    for k in range(K):
+        out[:, k] = cur[:, 0, 0]
+        d = pts - torch.gather(pts, 1, cur.expand(-1, -1, pts.shape[2]))
+        md = torch.minimum(md, (d * d).sum(-1))
+        cur = md.argmax(dim=1).view(B, 1, 1)
+    return out
+
+
+def fps_bench(dev, g, reps, out_path):
+    """am_fps at the product shape, a batch of 16 and a cloud past the resident limit; per shape: the kernel at every workgroup size
+    it carries (three interleaved rounds of `reps` launches each: the spread is part of the record), the torch loop, and whether
+    the two agree on the indices (the loop's sum may be contracted or reordered by torch: agreement is reported, not required)."""
+    import json
+    import statistics
+    reps = max(reps, 10)
+    rec = {"device": torch.cuda.get_device_name(dev), "hip": torch.version.hip, "clocks": "as found (not pinned)",
+           "timing": f"HIP events around {reps} back-to-back launches, 3 interleaved rounds per variant; torch loop: 2 runs", "shapes": []}
+    for B, N, K in ((1, 8192, 2048), (16, 8192, 2048), (1, 100_000, 4096)):
+        pts = torch.randn((B, N, 3), device=dev, generator=g)
+        variants = (0, 256, 512, 1024) if N <= 8192 else (0,)
+        rounds = {t: [] for t in variants}
+        for _ in range(3):
+            for t in variants:
+                rounds[t].append(timeit(lambda: ops.farthest_point_sample(pts, K, check=False, threads=t), reps))
+        loop_ms = [timeit(lambda: fps_torch_loop(pts, K), 1) for _ in range(2)]
+        same = bool(torch.equal(fps_torch_loop(pts, K), ops.farthest_point_sample(pts, K).long()))
+        row = {"batch": B, "n_points": N, "n_samples": K, "dims": 3, "torch_loop_ms": loop_ms, "torch_loop_same_indices": same,
+               "kernel_ms": {("default" if t == 0 else str(t)): v for t, v in rounds.items()},
+               "kernel_us_per_step": {("default" if t == 0 else str(t)): 1e3 * statistics.median(v) / K for t, v in rounds.items()}}
+        rec["shapes"].append(row)
+        for t, v in rounds.items():
+            print(f"fps B={B} N={N} K={K} threads={'default' if t == 0 else t}: {statistics.median(v):8.3f} ms (min {min(v):.3f}, max {max(v):.3f})  "
+                  f"{1e3 * statistics.median(v) / K:6.3f} us/step")
+        print(f"fps B={B} N={N} K={K} torch loop: {min(loop_ms):8.3f} ms  (same indices: {same})")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print("wrote", out_path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="headline")
@@ -43,6 +92,7 @@ def main():
                     "one shape per counter pass, so that a PMC record belongs to ONE launch shape")
     ap.add_argument("--blas", action="store_true", help="gemm: also time torch.matmul (hipBLASLt) on the same operands - the "
                     "vendor library as a same-box reference point; never on the product path")
+    ap.add_argument("--fps-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "fps_bench.json"))
     a = ap.parse_args()
     T, N, C, H, S = (16, 4096, 1024, 8, 257) if a.shape == "headline" else (16, 2048, 2048, 16, 257)
     B, L = 2, N + 1
@@ -216,6 +266,8 @@ def main():
             # 8 arithmetic lane-operations per pair (3 sub, 3 mul, 2 add) + compare / select
             print(f"nn_search  P={P} Q={Q} batch={Bn} {'fp64' if precise else 'fp32'}: {ms:8.3f} ms  {Bn * P * Q / ms / 1e6:8.1f} G pairs/s  "
                   f"{8.0 * Bn * P * Q / ms / 1e9:7.2f} TFLOP/s")
+    if "fps" in only:
+        fps_bench(dev, g, a.reps, a.fps_out)
     if "ln" in only:
         x = rnd(R, C); w = torch.ones(C, device=dev); b = torch.zeros(C, device=dev); y = torch.empty_like(x)
         ms = timeit(lambda: ops.layernorm(x, w, b, out=y), a.reps)
