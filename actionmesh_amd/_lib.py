@@ -122,6 +122,37 @@ class AmFpsArgs(C.Structure):          # am_fps_args
     ]
 
 
+class AmImageFrame(C.Structure):       # am_image_frame
+    _fields_ = [
+        ("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("src_w", C.c_int32), ("src_h", C.c_int32),
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32),
+        ("htab", C.c_int32), ("vtab", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("row_lo", C.c_int32), ("n_rows", C.c_int32),
+    ]
+
+
+class AmImageAlphaStatsArgs(C.Structure):      # am_image_alpha_stats_args
+    _fields_ = [("rgba", C.c_void_p), ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("out_stats", C.c_void_p)]
+
+
+class AmImageResampleArgs(C.Structure):        # am_image_resample_args
+    _fields_ = [
+        ("src", C.c_void_p), ("src_bytes", C.c_int64), ("src_channels", C.c_int32), ("fill", C.c_int32), ("composite", C.c_void_p),
+        ("n_frames", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("reserved", C.c_int32),
+        ("frames", C.c_void_p), ("frames_dev", C.c_void_p), ("taps", C.c_void_p), ("taps_dev", C.c_void_p), ("taps_len", C.c_int64),
+        ("norm_table", C.c_void_p), ("out_pixels", C.c_void_p), ("out_u8", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AmImageMaterializeArgs(C.Structure):     # am_image_materialize_args
+    _fields_ = [
+        ("src", C.c_void_p), ("src_bytes", C.c_int64), ("src_channels", C.c_int32), ("fill", C.c_int32), ("composite", C.c_void_p),
+        ("n_frames", C.c_int32), ("reserved", C.c_int32), ("frames", C.c_void_p), ("frames_dev", C.c_void_p),
+        ("out", C.c_void_p), ("out_bytes", C.c_int64),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -166,6 +197,10 @@ SYMBOLS = {
     "am_render_normals": (C.c_int, [C.POINTER(AmRenderArgs), _P, C.c_size_t, _P]),
     "am_fps_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "am_fps": (C.c_int, [C.POINTER(AmFpsArgs), _P]),
+    "am_image_alpha_stats": (C.c_int, [C.POINTER(AmImageAlphaStatsArgs), _P]),
+    "am_image_resample_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "am_image_resample": (C.c_int, [C.POINTER(AmImageResampleArgs), _P]),
+    "am_image_materialize": (C.c_int, [C.POINTER(AmImageMaterializeArgs), _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

@@ -1,5 +1,5 @@
 """`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage2-hip [--stage2-cross-fp32]]
-                                 [--render {auto,hip,off}] [--pointcloud {hip,off}] [--script NAME]
+                                 [--render {auto,hip,off}] [--pointcloud {hip,off}] [--preprocess {hip,off}] [--script NAME]
                                  [--reference-root DIR] -- <the reference CLI's own arguments>`
 
 Runs the reference's UNMODIFIED command-line script (inference/video_to_animated_mesh.py:120-248, or
@@ -51,6 +51,9 @@ def split_args(argv: List[str]) -> Tuple[argparse.Namespace, List[str]]:
     ap.add_argument("--pointcloud", choices=["hip", "off"], default="off",
                     help="with --backend hip: hip = give actionmesh.external.triposg the sample_pc / masked_gather it lacks without pytorch3d, "
                          "over the HIP farthest-point sampling (the {video+3D} script's anchor latent); off (default) = leave it alone")
+    ap.add_argument("--preprocess", choices=["hip", "off"], default="off",
+                    help="with --backend hip: hip = crop / pad the frames and resize / crop / normalise them for DINOv2 on the device, bit-identical "
+                         "to the reference's CPU code (HipImagePreprocessor, HipImageEncoder(preprocess='hip')); off (default) = leave both alone")
     ap.add_argument("--script", choices=SCRIPTS, default=SCRIPTS[0])
     ap.add_argument("--reference-root", default=None)
     ap.add_argument("--amd-help", action="store_true", help="this wrapper's options (plain --help shows the reference CLI's)")
@@ -77,6 +80,8 @@ def main(argv: Optional[List[str]] = None) -> None:
         render = ours.render == "hip" or (ours.render == "auto" and not R.pytorch3d_available())
         dropin.install(attn_dtype=ours.attn_dtype, stage2=ours.stage2_hip, stage2_cross_fp32=ours.stage2_cross_fp32, render=render,
                        pointcloud=ours.pointcloud == "hip")
+        if ours.preprocess == "hip":
+            dropin.install_preprocess()
     old_argv = sys.argv
     sys.argv = [script] + rest
     try:

@@ -16,7 +16,11 @@ The reference builds its Stage-I objects in three places, none of which takes a 
     (actionmesh_amd/render.py, seam S6);
   * optionally (`pointcloud=True`) `actionmesh.external.triposg` gets the `sample_pc` / `sample_pc_grouped` / `masked_gather` its
     guarded PyTorch3D import left missing (triposg.py:17-23), over the HIP farthest-point sampling
-    (actionmesh_amd/pointcloud_sampling.py, seam S7).
+    (actionmesh_amd/pointcloud_sampling.py, seam S7);
+  * optionally (`install_preprocess()` after `install()`) the frame preprocessing: `ImagePreprocessor`, a name
+    `ActionMeshPipeline.__init__` resolves in `actionmesh.pipeline`'s globals (pipeline.py:97), is rebound to HipImagePreprocessor,
+    and the composed config's `model.image_encoder` (pipeline.py:164) is pointed at HipImageEncoder with `preprocess="hip"`
+    (actionmesh_amd/image_preprocess.py, seam S8).
 
 `uninstall()` restores every name.  Nothing here imports the reference at module import time: `install()` imports
 `actionmesh.pipeline` (the caller's environment must be able to - that is the environment the reference runs in).
@@ -32,6 +36,7 @@ from typing import Any, Dict, Optional
 OVERLAY_SUFFIX = "_mi355x"
 SCHEDULER_TARGET = "actionmesh_amd.scheduler.HipSchedulerFlow"
 GUIDANCE_TARGET = "actionmesh_amd.scheduler.ClassifierFreeGuidance"
+IMAGE_ENCODER_TARGET = "actionmesh_amd.image_encoder.HipImageEncoder"
 REFERENCE_PRESETS = ("actionmesh", "actionmesh_fast", "actionmesh_lowram", "actionmesh_fast_lowram")
 
 _state: Dict[str, Any] = {}
@@ -85,14 +90,33 @@ def _retarget(cfg):
     return cfg
 
 
+def _retarget_image_encoder(cfg):
+    """After install_preprocess(): the context encoder becomes HipImageEncoder(preprocess="hip") - same two constructor fields
+    (image_encoder.py:19-23), so the node keeps them and gains one."""
+    try:
+        node = cfg["model"]["image_encoder"]
+        node["_target_"] = IMAGE_ENCODER_TARGET
+    except Exception as e:
+        raise RuntimeError(f"actionmesh_amd.install_preprocess(): the composed config has no model.image_encoder._target_ to swap: {e}") from e
+    try:
+        node["preprocess"] = "hip"
+    except Exception:                   # a struct-mode OmegaConf node refuses new keys until it is opened
+        from omegaconf import open_dict
+        with open_dict(node):
+            node["preprocess"] = "hip"
+    return cfg
+
+
 def _wrap_load_config(orig):
     def load_config(config_name: str, config_dir: str, *args, **kwargs):
         mapped = overlay_name(config_name)
         if mapped is not None:
-            return orig(mapped, merged_config_dir(config_dir), *args, **kwargs)
-        cfg = orig(config_name, config_dir, *args, **kwargs)
-        stem = config_name[:-5] if config_name.endswith(".yaml") else config_name
-        return cfg if stem.endswith(OVERLAY_SUFFIX) else _retarget(cfg)
+            cfg = orig(mapped, merged_config_dir(config_dir), *args, **kwargs)
+        else:
+            cfg = orig(config_name, config_dir, *args, **kwargs)
+            stem = config_name[:-5] if config_name.endswith(".yaml") else config_name
+            cfg = cfg if stem.endswith(OVERLAY_SUFFIX) else _retarget(cfg)
+        return _retarget_image_encoder(cfg) if _state.get("preprocess") else cfg
     load_config.__wrapped__ = orig
     load_config.__actionmesh_amd__ = True
     return load_config
@@ -107,7 +131,8 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     reference does (HipAutoencoder(cross_fp32=True); needs `stage2`).  `render`: also wrap the scripts' `load_frames` /
     `save_deformation` so that `actionmesh_amd.render.render_captured()` can draw the preview video afterwards (render.install_hook).
     `pointcloud`: also give `actionmesh.external.triposg` the point-cloud sampling names it lacks without PyTorch3D
-    (pointcloud_sampling.install_into), so that `TripoSGVAE` can be built and samples its surface points on the HIP FPS kernel."""
+    (pointcloud_sampling.install_into), so that `TripoSGVAE` can be built and samples its surface points on the HIP FPS kernel.
+    The frame preprocessing is a call of its own on top of this one: `install_preprocess()`."""
     if stage2_cross_fp32 and not stage2:
         raise ValueError("actionmesh_amd.install(): stage2_cross_fp32=True needs stage2=True")
     import actionmesh.pipeline as P      # the reference (must be importable where the reference runs)
@@ -149,6 +174,7 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     if render:
         from . import render as R
         R.install_hook()
+    _state["preprocess"] = False
     _state["pointcloud"] = None
     if pointcloud:
         from . import pointcloud_sampling as S
@@ -156,6 +182,24 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     _state["installed"] = True
     _state["saved"] = saved
     _state["module"] = P
+
+
+def install_preprocess() -> None:
+    """On top of `install()` (called with its defaults first if nothing is installed; idempotent): also crop / pad the frames
+    (`ImagePreprocessor`, pipeline.py:97, 656) and resize / crop / normalise them in front of DINOv2 on the device, bit-identical to
+    the CPU code - the name `ImagePreprocessor` in `actionmesh.pipeline` becomes HipImagePreprocessor, and every config `load_config`
+    composes from now on names HipImageEncoder(preprocess="hip") as its `model.image_encoder`.  Pipelines constructed before the call
+    keep what they have.  `uninstall()` - and therefore a later `install()` - takes it back.  A call of its own, not a keyword of
+    `install()`: that function's parameter list is pinned by tests/test_fps_cpu.py."""
+    if not _state.get("installed"):
+        install()
+    if _state.get("preprocess"):
+        return
+    from .image_preprocess import HipImagePreprocessor
+    P = _state["module"]
+    _state["saved"]["ImagePreprocessor"] = P.ImagePreprocessor
+    P.ImagePreprocessor = HipImagePreprocessor
+    _state["preprocess"] = True
 
 
 def uninstall() -> None:
@@ -170,6 +214,7 @@ def uninstall() -> None:
         from . import pointcloud_sampling as S
         S.uninstall_from(*_state["pointcloud"])
         _state["pointcloud"] = None
+    _state["preprocess"] = False
     _state["installed"] = False
 
 

@@ -6,7 +6,9 @@ module the reference calls at :53) evaluated through the C-ABI.
 The reference is Python; so is this orchestration.  Every arithmetic step is a call through the C-ABI (`am_patchify`,
 `am_gemm_bf16`, `am_layernorm_bf16`, `am_head_post`, `am_attention_bf16`); torch owns device memory and copies the T
 class-token rows.  There is no CPU / torch fallback.  The image preprocessing (`BitImageProcessor`: resize, crop,
-normalise PIL images; image_encoder.py:48-51) is CPU glue and stays on the reference's own dependency.
+normalise PIL images; image_encoder.py:48-51) runs on the reference's own dependency by default (`preprocess="pil"`); with
+`preprocess="hip"` it runs on the device, bit-identical to the PIL backend (actionmesh_amd/image_preprocess.py: the config file is
+read here, `transformers` is not imported), and `encode_frames` takes the raw RGBA frames through crop, pad, resize and the ViT.
 
 How the ViT maps onto kernels that were built for head_dim 128:
   * patch embedding: kernel = stride convolution = im2col (`am_patchify`, K = 3 p^2 padded to a multiple of 64) + one
@@ -140,8 +142,12 @@ def position_rows(pos: torch.Tensor, cls: torch.Tensor, trained_side: int, n_h: 
 class HipImageEncoder:
     def __init__(self, pretrained_dino_feature_extractor: Optional[str] = None, pretrained_dino_model: Optional[str] = None,
                  config: Optional[Dict] = None, state_dict: Optional[Dict[str, torch.Tensor]] = None, dtype=None,
-                 residual_fp32: bool = True, **_ignored):
+                 residual_fp32: bool = True, preprocess: str = "pil", **_ignored):
         lib()      # fail loudly here if libactionmesh_amd.so is missing
+        if preprocess not in ("pil", "hip"):
+            raise ValueError(f"HipImageEncoder: preprocess must be 'pil' or 'hip', got {preprocess!r}")
+        self.preprocess = preprocess
+        self._settings: Optional[Dict] = None
         self.residual_fp32 = bool(residual_fp32)
         # 16-bit storage type.  The reference encodes OUTSIDE its autocast region, in fp32 (pipeline.py:665-667): there is no caller dtype
         # to follow, so the default is bfloat16 (fp32's exponent range: safe for DINOv2's outlier tokens whatever the checkpoint) and
@@ -336,8 +342,48 @@ class HipImageEncoder:
             del f
         return ops.layernorm_f32(h, w["norm.w"], w["norm.b"], eps=eps, out=z).view(T, S, C)
 
+    def _preprocess_settings(self) -> Dict:
+        """preprocessor_config.json of the feature extractor, validated by image_preprocess.processor_settings (no `transformers`)."""
+        if self._settings is None:
+            if self.pretrained_dino_feature_extractor is None:
+                raise RuntimeError("HipImageEncoder: preprocess='hip' needs pretrained_dino_feature_extractor (the directory or dict of "
+                                   "preprocessor_config.json); use encode_pixels for preprocessed input")
+            from . import image_preprocess as IP
+            self._settings = IP.processor_settings(self.pretrained_dino_feature_extractor)
+        return self._settings
+
+    def encode_frames(self, rgba_u8: torch.Tensor, independent_cropping: bool = False, padding_ratio: float = 0.1) -> torch.Tensor:
+        """Raw frames (T, H, W, 4) uint8 -> context (T, S, Dc): ImagePreprocessor.process_images (pipeline.py:656) and
+        BitImageProcessor.preprocess (image_encoder.py:48-51) on the device, then the ViT.  Whatever `preprocess` is."""
+        from . import image_preprocess as IP
+        rgba_u8 = torch.as_tensor(rgba_u8).to(self._device)
+        with torch.cuda.device(self._device):
+            pixel_values = IP.frames_to_pixel_values(rgba_u8, self._preprocess_settings(), independent_cropping, padding_ratio)
+        return self.encode_pixels(pixel_values)
+
+    def _pixels_hip(self, images: List) -> torch.Tensor:
+        """PIL frames uploaded as uint8, then resize / crop / normalise on the device."""
+        import numpy as np
+        from . import image_preprocess as IP
+        settings = self._preprocess_settings()
+        frames = []
+        for im in images:
+            if im.mode != "RGB":
+                if not settings["do_convert_rgb"]:
+                    raise ValueError(f"HipImageEncoder: do_convert_rgb=False with a {im.mode} image is not supported")
+                im = im.convert("RGB")
+            frames.append(np.ascontiguousarray(im))
+        with torch.cuda.device(self._device):
+            if len({f.shape for f in frames}) == 1:
+                dev = torch.from_numpy(np.stack(frames)).to(self._device)
+            else:
+                dev = [torch.from_numpy(f).to(self._device) for f in frames]
+            return IP.rgb_to_pixel_values(dev, settings)
+
     def encode_images(self, images: List) -> torch.Tensor:
         """image_encoder.py:38-55: T PIL images -> context (T, S, Dc)."""
+        if self.preprocess == "hip":
+            return self.encode_pixels(self._pixels_hip(images))
         if self._processor is None:
             if self.pretrained_dino_feature_extractor is None:
                 raise RuntimeError("HipImageEncoder.encode_images needs pretrained_dino_feature_extractor "

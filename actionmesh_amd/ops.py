@@ -538,6 +538,86 @@ def farthest_point_sample(points: torch.Tensor, n_samples: int, start_idx=None, 
     return (idx, dist) if return_dist else idx
 
 
+# ---- image preprocessing (csrc/am_image.hip; the contract is the header's, the geometry and the tables are image_preprocess.py's) ----
+def image_alpha_stats(rgba: torch.Tensor) -> torch.Tensor:
+    """am_image_alpha_stats: rgba (T, H, W, 4) uint8 -> int32 (T, 8) = [count(alpha > 127), min col, min row, max col, max row of
+    alpha > 0, 0, 0, 0] per frame, on the device (the caller reads it)."""
+    _need(rgba, torch.uint8, "image_alpha_stats: rgba")
+    if rgba.dim() != 4 or rgba.shape[-1] != 4 or rgba.numel() == 0:
+        raise ValueError(f"image_alpha_stats: expected non-empty (T, H, W, 4) uint8 frames, got {tuple(rgba.shape)}")
+    stats = torch.empty((rgba.shape[0], 8), dtype=torch.int32, device=rgba.device)
+    a = L.AmImageAlphaStatsArgs()
+    a.rgba, a.n_frames, a.height, a.width, a.out_stats = rgba.data_ptr(), rgba.shape[0], rgba.shape[1], rgba.shape[2], stats.data_ptr()
+    lib = L.lib()
+    _launch(rgba, lib.am_image_alpha_stats, "am_image_alpha_stats", C.byref(a))
+    return stats
+
+
+def _image_src(a, src: torch.Tensor, channels: int, composite: Optional[torch.Tensor], fill: int, frames, frames_dev: torch.Tensor) -> None:
+    """The fields am_image_resample_args and am_image_materialize_args share.  `frames`: a ctypes array of AmImageFrame (host);
+    `frames_dev`: the same bytes on the device."""
+    _need(src, torch.uint8, "image: src")
+    _need(frames_dev, torch.uint8, "image: frames_dev")
+    if frames_dev.numel() != C.sizeof(frames):
+        raise ValueError("image: frames_dev is not a copy of frames")
+    if channels == 4:
+        if composite is None:
+            raise ValueError("image: an RGBA source needs the composite table")
+        _need(composite, torch.uint8, "image: composite")
+        if composite.numel() != 65536:
+            raise ValueError(f"image: the composite table has 65536 entries, got {composite.numel()}")
+    a.src, a.src_bytes, a.src_channels, a.fill = src.data_ptr(), src.numel(), int(channels), int(fill)
+    a.composite = composite.data_ptr() if channels == 4 else None
+    a.n_frames, a.frames, a.frames_dev = len(frames), C.addressof(frames), frames_dev.data_ptr()
+
+
+def image_resample(src: torch.Tensor, channels: int, frames, frames_dev: torch.Tensor, taps, taps_dev: torch.Tensor, out_h: int,
+                   out_w: int, composite: Optional[torch.Tensor] = None, fill: int = 255, norm_table: Optional[torch.Tensor] = None,
+                   want_u8: bool = False) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """am_image_resample over frames described by `frames` (ctypes array of AmImageFrame) with the int32 tap tables `taps` (a
+    contiguous numpy array; `taps_dev` its device copy).  Returns (pixel_values (T, 3, out_h, out_w) fp32 or None without a
+    norm_table, the uint8 crop (T, out_h, out_w, 3) or None unless `want_u8`)."""
+    T = len(frames)
+    if norm_table is None and not want_u8:
+        raise ValueError("image_resample: nothing to compute (no norm_table and want_u8=False)")
+    _need(taps_dev, torch.int32, "image_resample: taps_dev")
+    if taps.dtype.name != "int32" or not taps.flags["C_CONTIGUOUS"] or taps.size != taps_dev.numel():
+        raise ValueError("image_resample: taps must be a contiguous int32 array and taps_dev its copy")
+    a = L.AmImageResampleArgs()
+    _image_src(a, src, channels, composite, fill, frames, frames_dev)
+    a.out_w, a.out_h = int(out_w), int(out_h)
+    a.taps, a.taps_dev, a.taps_len = taps.ctypes.data, taps_dev.data_ptr(), taps.size
+    pix = u8 = None
+    if norm_table is not None:
+        _need(norm_table, torch.float32, "image_resample: norm_table")
+        if norm_table.numel() != 768:
+            raise ValueError(f"image_resample: the normalisation table is (3, 256), got {tuple(norm_table.shape)}")
+        pix = torch.empty((T, 3, out_h, out_w), dtype=torch.float32, device=src.device)
+        a.norm_table, a.out_pixels = norm_table.data_ptr(), pix.data_ptr()
+    if want_u8:
+        u8 = torch.empty((T, out_h, out_w, 3), dtype=torch.uint8, device=src.device)
+        a.out_u8 = u8.data_ptr()
+    lib = L.lib()
+    need = lib.am_image_resample_workspace_bytes(T, max(f.n_rows for f in frames), int(out_w))
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=src.device)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    _launch(src, lib.am_image_resample, "am_image_resample", C.byref(a))
+    return pix, u8
+
+
+def image_materialize(src: torch.Tensor, channels: int, frames, frames_dev: torch.Tensor, out_bytes: int,
+                      composite: Optional[torch.Tensor] = None, fill: int = 255) -> torch.Tensor:
+    """am_image_materialize: the padded (and, for RGBA, composited) frames as flat uint8; frame t is (h + 2 pad_y, w + 2 pad_x, 3) at
+    its dst_offset."""
+    a = L.AmImageMaterializeArgs()
+    _image_src(a, src, channels, composite, fill, frames, frames_dev)
+    out = torch.empty((int(out_bytes),), dtype=torch.uint8, device=src.device)
+    a.out, a.out_bytes = out.data_ptr(), out.numel()
+    lib = L.lib()
+    _launch(src, lib.am_image_materialize, "am_image_materialize", C.byref(a))
+    return out
+
+
 # ---- exact-fp32 path (csrc/am_f32.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----------------------
 def _fk(kind: str, name: str):
     """Entry point `name` of the library build `kind` ("bf16" / "f16"): the fp32 entry points are in both."""

@@ -500,6 +500,101 @@ typedef struct {
 size_t am_fps_workspace_bytes(int64_t n_points, int batch, int dist_dims);
 int am_fps(const am_fps_args* args, void* stream);
 
+/* Image preprocessing in front of the context encoder (INTEGRATION seam S8): the reference's `ImagePreprocessor`
+ * (actionmesh/preprocessing/image_processor.py:15-146: validity of the alpha mask, composite on white, bounding box, square padding)
+ * and the PIL backend of transformers' `BitImageProcessor` (image_encoder.py:48-51: resize of the shortest edge, centre crop,
+ * rescale, normalise), restated as integer / table arithmetic so that the device result is BIT-IDENTICAL to theirs.
+ *
+ * Alpha statistics (am_image_alpha_stats).  rgba: (n_frames, height, width, 4) uint8, contiguous, 4-byte aligned.  Per frame the
+ * eight int32 of out_stats[t] are { count(alpha > 127), min column, min row, max column, max row of alpha > 0, 0, 0, 0 }; a frame
+ * without any alpha > 0 has min = INT32_MAX and max = -1.  The entry initialises out_stats itself.  Only integer atomics are used
+ * (one add / min / max per workgroup), so the result does not depend on scheduling.  The caller reads these rows on the host and
+ * decides (image_processor.py:15-23): a frame is valid when count >= int(H W 0.01) and H W - count >= int(H W 0.01); the bounding
+ * box is (x, y, w, h) = (min col, min row, max col - min col + 1, max row - min row + 1); frames share the union box unless cropped
+ * independently; with m = max(w, h): pad = int(m * padding_ratio), pad_x = pad + (m - w) / 2, pad_y = pad + (m - h) / 2 (integer
+ * division), fill value 255 - so the padded frame is (w + 2 pad_x) x (h + 2 pad_y), which may be off square by one pixel.
+ *
+ * The virtual source image.  Every entry below reads its input through one description per frame (am_image_frame): the window
+ * (x0, y0, w, h) of a stored frame of src_w x src_h pixels, surrounded by pad_x columns and pad_y rows of `fill` on each side.
+ * With src_channels == 4 the stored pixel is RGBA and each colour byte c with alpha a reads as composite[c * 256 + a], a 64 KiB
+ * table the caller supplies: uint8(float32 expression * 255) of image_processor.py:44-52 evaluated by numpy over all 65536 pairs
+ * (it differs from floor of the exact blend in 454 pairs, so it is a table, not a formula).  With src_channels == 3 the stored
+ * pixel is RGB and is read as it is.  The padded, composited frames never exist in memory unless am_image_materialize writes them.
+ *
+ * Resample (am_image_resample): PIL's antialiased bicubic resize of 8-bit images followed by a crop, per frame
+ *   in = w + 2 pad (width, height); one 1-D pass from `in` to `out` samples: scale = in / out, fs = max(scale, 1), support = 2 fs;
+ *   for output i: c = (i + 0.5) scale, taps j in [max(0, trunc(c - support + 0.5)), min(in, trunc(c + support + 0.5))),
+ *   w_j = cubic((j - c + 0.5) / fs) (Keys, a = -0.5) divided by their fp64 sum, k_j = trunc(w_j 2^22 + 0.5 sign(w_j));
+ *   output = clip_0^255((2^21 + sum_j k_j p_j) >> 22) in int32 with an arithmetic shift.
+ * The horizontal pass runs first into a uint8 image (the workspace), the vertical pass on that image; only the rows and columns the
+ * crop window (left, top, out_w, out_h of the resized image) needs are computed.  The tap tables are built by the caller in fp64
+ * (they depend on (in, out) only) and live in one int32 array `taps`; a table starts at the frame's htab / vtab offset and is
+ *   { in, out, ksize, 0,  (first tap, tap count) x out,  k[out][ksize] }.
+ * The vertical pass writes out_u8 (n_frames, out_h, out_w, 3) and / or out_pixels (n_frames, 3, out_h, out_w) fp32 =
+ * norm_table[channel * 256 + value]: t[v] = (fp32(v * rescale_factor) - fp32(mean)) / fp32(std), built by the caller.
+ * Frames may differ in every field but the output size, and a frame's result does not depend on which other frames share the call.
+ *
+ * frames / taps are HOST arrays (validated before anything is launched: every window inside its frame, every tap inside its image,
+ * every offset inside its buffer); frames_dev / taps_dev are the caller's device copies of the same bytes, which the kernels read.
+ * Launches only: no allocation, no copy, no synchronisation.  Two launches per am_image_resample and per am_image_alpha_stats, one
+ * per am_image_materialize, whatever n_frames is. */
+typedef struct {
+  int64_t src_offset;           /* bytes from `src` to the frame's first stored pixel (a multiple of 4) */
+  int64_t dst_offset;           /* am_image_materialize: bytes from `out` to the frame's first output pixel (a multiple of 4) */
+  int32_t src_w, src_h;         /* stored frame, pixels; rows are src_w * src_channels bytes apart */
+  int32_t x0, y0, w, h;         /* window of the stored frame */
+  int32_t pad_x, pad_y;         /* columns / rows of `fill` on each side */
+  int32_t htab, vtab;           /* offsets (in int32) of the two tap tables in `taps` */
+  int32_t left, top;            /* crop origin in the resized image */
+  int32_t row_lo, n_rows;       /* rows of the padded image the vertical pass reads: [row_lo, row_lo + n_rows) */
+} am_image_frame;
+
+typedef struct {
+  const uint8_t* rgba;          /* device (n_frames, height, width, 4) */
+  int32_t n_frames, height, width;
+  int32_t reserved;
+  int32_t* out_stats;           /* device (n_frames, 8) */
+} am_image_alpha_stats_args;
+int am_image_alpha_stats(const am_image_alpha_stats_args* args, void* stream);
+
+typedef struct {
+  const uint8_t* src;           /* device, 4-byte aligned */
+  int64_t src_bytes;
+  int32_t src_channels;         /* 4: RGBA through `composite`; 3: RGB */
+  int32_t fill;                 /* 0 .. 255 */
+  const uint8_t* composite;     /* device uint8[65536] (src_channels == 4), else NULL */
+  int32_t n_frames;
+  int32_t out_w, out_h;         /* size of the crop = of the output */
+  int32_t reserved;
+  const am_image_frame* frames;      /* host, n_frames */
+  const am_image_frame* frames_dev;  /* device copy */
+  const int32_t* taps;          /* host */
+  const int32_t* taps_dev;      /* device copy */
+  int64_t taps_len;             /* int32 entries */
+  const float* norm_table;      /* device fp32[3 * 256]; needed with out_pixels */
+  float* out_pixels;            /* optional device (n_frames, 3, out_h, out_w) */
+  uint8_t* out_u8;              /* optional device (n_frames, out_h, out_w, 3) */
+  void* workspace;              /* device, 16-byte aligned, am_image_resample_workspace_bytes(n_frames, max n_rows, out_w) */
+  size_t workspace_bytes;
+} am_image_resample_args;
+size_t am_image_resample_workspace_bytes(int n_frames, int max_rows, int out_w);
+int am_image_resample(const am_image_resample_args* args, void* stream);
+
+typedef struct {
+  const uint8_t* src;           /* as in am_image_resample_args */
+  int64_t src_bytes;
+  int32_t src_channels;
+  int32_t fill;
+  const uint8_t* composite;
+  int32_t n_frames;
+  int32_t reserved;
+  const am_image_frame* frames;      /* host: src_offset, dst_offset, src_w, src_h, x0, y0, w, h, pad_x, pad_y are read */
+  const am_image_frame* frames_dev;
+  uint8_t* out;                 /* device, 4-byte aligned: frame t is (h + 2 pad_y, w + 2 pad_x, 3) uint8 at dst_offset */
+  int64_t out_bytes;
+} am_image_materialize_args;
+int am_image_materialize(const am_image_materialize_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,14 +76,35 @@ def build(tiny: bool, dev):
     return enc, denoiser, vae, HipSchedulerFlow, ClassifierFreeGuidance, n_tokens, window, side
 
 
-def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44, clip: str = None, label: str = None):
+def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44, clip: str = None, label: str = None,
+        raw_frames: bool = False):
     from actionmesh_amd import LatentBank, generate_3d_latents, generate_vertex_animation
     t_build = time.perf_counter()
     enc, denoiser, vae, Sched, CFG, n_tokens, window, side = build(tiny, dev)
     torch.cuda.synchronize(dev)
     t_build = time.perf_counter() - t_build
     g = torch.Generator().manual_seed(1)
-    if clip:           # a real clip as the context encoder receives it (oracle/make_golden_frames.py)
+    t_pre = None
+    if clip and raw_frames:        # from the raw RGBA frames (tests/golden/frames_raw): crop, pad, resize, normalise on the device
+        import numpy as np
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from make_golden_frames_raw import load_clip
+        from actionmesh_amd import image_preprocess as IP
+        settings = IP.processor_settings({"size": {"shortest_edge": 256}, "crop_size": {"height": side, "width": side}, "resample": 3,
+                                          "image_mean": [0.485, 0.456, 0.406], "image_std": [0.229, 0.224, 0.225]})
+        raw = load_clip(clip)
+        assert raw.shape[0] >= frames, (raw.shape, frames)
+        IP.frames_to_pixel_values(torch.from_numpy(raw[:1]).to(dev), settings)          # the library's first call, outside the stage
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        pixels = IP.frames_to_pixel_values(torch.from_numpy(raw[:frames]).to(dev), settings)   # the upload is part of the stage
+        torch.cuda.synchronize(dev)
+        t_pre = time.perf_counter() - t0
+        if frames == raw.shape[0] and side == 224 and os.path.exists(os.path.join(ROOT, "tests", "golden", "frames", f"{clip}_16x224.npz")):
+            from oracle.make_golden_frames import frames_to_pixels
+            rgb = np.load(os.path.join(ROOT, "tests", "golden", "frames", f"{clip}_16x224.npz"))["rgb_u8"]
+            assert float((pixels.cpu() - frames_to_pixels(rgb)).abs().max()) < 1e-6      # the frames the committed fixture holds
+    elif clip:           # a real clip as the context encoder receives it (oracle/make_golden_frames.py)
         import numpy as np
         from oracle.make_golden_frames import frames_to_pixels          # the rescale + normalise half of BitImageProcessor (data handling only)
         rgb = np.load(os.path.join(ROOT, "tests", "golden", "frames", f"{clip}_16x224.npz"))["rgb_u8"]
@@ -145,6 +166,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             "unit": "s", "higher_is_better": False, "n_gpus": 1, "dtype": "bf16", "data": "synthetic",
             "seconds": {"context_encoder": round(t_enc, 4), "stage_I": round(t_s1, 3), "stage_II": round(t_s2, 3),
                         "model_build_and_upload": round(t_build, 1),
+                        **({"preprocess_s": round(t_pre, 4)} if t_pre is not None else {}),
                         "output_files_host_side": round(t_out, 3), "chamfer_metrics": round(t_metric, 4)},
             "preview_video_s": round(t_preview, 3),          # grid_normal.* (HipVisualizer), written into the output files above
             "output_files_mb": round(out_bytes / 1e6, 1),
@@ -162,8 +184,12 @@ def main():
     ap.add_argument("--vertices", type=int, default=50000)
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--clip", default=None, choices=["davis_camel", "panda"], help="frames of a reference example clip (tests/golden/frames/) instead of noise")
+    ap.add_argument("--raw-frames", action="store_true",
+                    help="with --clip: start from the raw RGBA frames (tests/golden/frames_raw/) and preprocess them on the device; adds preprocess_s")
     ap.add_argument("--config", type=int, default=None, choices=[1, 3], help="BASELINE.json configs[1] / configs[3] as a plumbing record (see the module docstring)")
     a = ap.parse_args()
+    if a.raw_frames and not (a.clip or a.config):
+        ap.error("--raw-frames needs --clip (or --config)")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     label = None
@@ -174,7 +200,7 @@ def main():
         a.clip, a.frames, a.steps = "panda", 16, 50
         label = ("configs[3]: {video+3D}->4D panda path, 16 frames, 1 x MI355X - PLUMBING on random-init weights; differs from configs[1] only in the "
                  "anchor latent's source (Stage 0, reference path), which is seeded noise in both records")
-    print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label)))
+    print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames)))
 
 
 if __name__ == "__main__":
