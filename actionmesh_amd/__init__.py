@@ -13,7 +13,7 @@ from .denoiser import HipDenoiser, HipEngine, WindowCache  # noqa: F401
 from .mesh_io import create_animated_glb, load_glb, save_deformation, save_meshes  # noqa: F401
 from . import actionbench  # noqa: F401
 from .render import HipRenderer, HipVisualizer, uniform_cameras  # noqa: F401
-from .dropin import install, install_preprocess, uninstall  # noqa: F401
+from .dropin import install, install_mask_refine, install_preprocess, uninstall  # noqa: F401
 from .scheduler import ClassifierFreeGuidance, HipSchedulerFlow  # noqa: F401
 from .sharding import FrameShardPlan  # noqa: F401
 from .windows import LatentBank, chunk_from, denoise_window, generate_3d_latents, generate_vertex_animation  # noqa: F401
@@ -22,4 +22,4 @@ __all__ = ["HipAutoencoder", "HipImageEncoder", "HipDenoiser", "HipEngine", "Hip
            "FrameShardPlan", "WindowCache", "HipLibraryMissing", "LIB_PATH",
            "LatentBank", "chunk_from", "denoise_window", "generate_3d_latents", "generate_vertex_animation", "save_deformation",
            "save_meshes", "create_animated_glb", "load_glb", "actionbench", "install", "uninstall", "HipRenderer", "HipVisualizer",
-           "uniform_cameras", "HipImagePreprocessor", "frames_to_pixel_values", "install_preprocess"]
+           "uniform_cameras", "HipImagePreprocessor", "frames_to_pixel_values", "install_preprocess", "install_mask_refine"]

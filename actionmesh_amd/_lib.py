@@ -153,6 +153,21 @@ class AmImageMaterializeArgs(C.Structure):     # am_image_materialize_args
     ]
 
 
+class AmMaskRefineArgs(C.Structure):           # am_mask_refine_args
+    _fields_ = [
+        ("mask", C.c_void_p), ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("min_size", C.c_int32),
+        ("threshold", C.c_int32), ("reserved", C.c_int32), ("out_mask", C.c_void_p), ("out_labels", C.c_void_p), ("out_stats", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AmGraphArgs(C.Structure):                # am_graph_args
+    _fields_ = [
+        ("n_nodes", C.c_int64), ("n_edges", C.c_int64), ("edges", C.c_void_p), ("out_label", C.c_void_p), ("out_size", C.c_void_p),
+        ("out_flag", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -201,6 +216,10 @@ SYMBOLS = {
     "am_image_resample_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "am_image_resample": (C.c_int, [C.POINTER(AmImageResampleArgs), _P]),
     "am_image_materialize": (C.c_int, [C.POINTER(AmImageMaterializeArgs), _P]),
+    "am_mask_refine_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "am_mask_refine": (C.c_int, [C.POINTER(AmMaskRefineArgs), _P]),
+    "am_graph_components_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "am_graph_components": (C.c_int, [C.POINTER(AmGraphArgs), _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

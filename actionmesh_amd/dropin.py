@@ -20,7 +20,10 @@ The reference builds its Stage-I objects in three places, none of which takes a 
   * optionally (`install_preprocess()` after `install()`) the frame preprocessing: `ImagePreprocessor`, a name
     `ActionMeshPipeline.__init__` resolves in `actionmesh.pipeline`'s globals (pipeline.py:97), is rebound to HipImagePreprocessor,
     and the composed config's `model.image_encoder` (pipeline.py:164) is pointed at HipImageEncoder with `preprocess="hip"`
-    (actionmesh_amd/image_preprocess.py, seam S8).
+    (actionmesh_amd/image_preprocess.py, seam S8);
+  * optionally (`install_mask_refine()` after `install()`) the mask refinement behind the background remover: `refine_mask`, a name
+    `BackgroundRemover.forward` resolves in `actionmesh.preprocessing.background_removal`'s globals (background_removal.py:109), is
+    rebound to the HIP labelling (actionmesh_amd/mask_refine.py, seam S9).
 
 `uninstall()` restores every name.  Nothing here imports the reference at module import time: `install()` imports
 `actionmesh.pipeline` (the caller's environment must be able to - that is the environment the reference runs in).
@@ -132,7 +135,8 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     `save_deformation` so that `actionmesh_amd.render.render_captured()` can draw the preview video afterwards (render.install_hook).
     `pointcloud`: also give `actionmesh.external.triposg` the point-cloud sampling names it lacks without PyTorch3D
     (pointcloud_sampling.install_into), so that `TripoSGVAE` can be built and samples its surface points on the HIP FPS kernel.
-    The frame preprocessing is a call of its own on top of this one: `install_preprocess()`."""
+    The frame preprocessing and the mask refinement are calls of their own on top of this one: `install_preprocess()`,
+    `install_mask_refine()`."""
     if stage2_cross_fp32 and not stage2:
         raise ValueError("actionmesh_amd.install(): stage2_cross_fp32=True needs stage2=True")
     import actionmesh.pipeline as P      # the reference (must be importable where the reference runs)
@@ -175,6 +179,7 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
         from . import render as R
         R.install_hook()
     _state["preprocess"] = False
+    _state["mask_refine"] = None
     _state["pointcloud"] = None
     if pointcloud:
         from . import pointcloud_sampling as S
@@ -202,12 +207,32 @@ def install_preprocess() -> None:
     _state["preprocess"] = True
 
 
+def install_mask_refine() -> None:
+    """On top of `install()` (called with its defaults first if nothing is installed; idempotent): `refine_mask` in
+    `actionmesh.preprocessing.background_removal` - Otsu threshold, connected components, removal of the small ones, on every frame
+    that arrives without a usable alpha channel (background_removal.py:109) - becomes `actionmesh_amd.mask_refine.refine_mask`: same
+    name, signature and return convention, computed by the HIP labelling kernels.  `uninstall()` - and therefore a later
+    `install()` - takes it back.  A call of its own, like `install_preprocess()`: `install()` keeps its parameter list."""
+    if not _state.get("installed"):
+        install()
+    if _state.get("mask_refine"):
+        return
+    import actionmesh.preprocessing.background_removal as B      # the reference's module (its own imports must resolve)
+    from .mask_refine import refine_mask
+    _state["mask_refine"] = (B, B.refine_mask)
+    B.refine_mask = refine_mask
+
+
 def uninstall() -> None:
     if not _state.get("installed"):
         return
     P = _state["module"]
     for name, obj in _state["saved"].items():
         setattr(P, name, obj)
+    if _state.get("mask_refine"):
+        B, orig = _state["mask_refine"]
+        B.refine_mask = orig
+        _state["mask_refine"] = None
     from . import render as R
     R.uninstall_hook()
     if _state.get("pointcloud"):

@@ -618,6 +618,82 @@ def image_materialize(src: torch.Tensor, channels: int, frames, frames_dev: torc
     return out
 
 
+# ---- connected components (csrc/am_components.hip; the contract is the header's) -----------------------------------------------------
+def mask_refine(mask: torch.Tensor, min_size: int = 200, threshold: int = -1, return_labels: bool = False, return_stats: bool = False):
+    """am_mask_refine: mask (T, H, W) uint8 on the device -> (out_mask uint8 (T, H, W) of 0 / 255, labels int32 (T, H, W) or None,
+    stats int32 (T, 4) = [threshold used, foreground pixels, components, components kept] or None), all on the device, nothing read
+    back.  `threshold`: -1 = Otsu per frame, 0..255 = that value for every frame.  The argument checks come before the device check,
+    so they hold for any tensor."""
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError(f"mask_refine: expected a torch tensor, got {type(mask).__name__}")
+    if mask.dtype != torch.uint8:
+        raise TypeError(f"mask_refine: expected a uint8 mask, got {mask.dtype}")
+    if mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError(f"mask_refine: expected a non-empty (T, H, W) mask, got {tuple(mask.shape)}")
+    if not mask.is_contiguous():
+        raise ValueError("mask_refine: the mask must be contiguous")
+    min_size, threshold = int(min_size), int(threshold)
+    if min_size < 0:
+        raise ValueError(f"mask_refine: min_size {min_size} is negative")
+    if not -1 <= threshold <= 255:
+        raise ValueError(f"mask_refine: threshold {threshold} outside -1 .. 255")
+    T, H, W = mask.shape
+    if H * W >= 2 ** 31 - 1:
+        raise ValueError(f"mask_refine: {H} x {W} pixels per frame do not fit a 32-bit label")
+    if not mask.is_cuda:
+        raise RuntimeError("mask_refine: actionmesh_amd kernels need a device tensor (no CPU path)")
+    dev = mask.device
+    out = torch.empty_like(mask)
+    labels = torch.empty((T, H, W), dtype=torch.int32, device=dev) if return_labels else None
+    stats = torch.empty((T, 4), dtype=torch.int32, device=dev) if return_stats else None
+    lib = L.lib()
+    need = lib.am_mask_refine_workspace_bytes(T, H, W)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    a = L.AmMaskRefineArgs()
+    a.mask, a.n_frames, a.height, a.width, a.min_size, a.threshold = mask.data_ptr(), T, H, W, min_size, threshold
+    a.out_mask, a.out_labels, a.out_stats = out.data_ptr(), _p(labels), _p(stats)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    _launch(mask, lib.am_mask_refine, "am_mask_refine", C.byref(a))
+    return out, labels, stats
+
+
+def graph_components(n_nodes: int, edges: torch.Tensor, return_size: bool = False):
+    """am_graph_components: the connected components of an undirected graph of `n_nodes` nodes.  edges (E, 2) int32 on the device
+    (self-loops and duplicates allowed, E may be 0).  Returns the int32 label of every node - the smallest node index of its
+    component - and with `return_size` also the int32 size of every node's component.  The edge list is validated on the device;
+    ONE device-to-host read behind the launch (the flag, which shares the labels' buffer) turns a node index outside [0, n_nodes)
+    into a ValueError."""
+    if not isinstance(edges, torch.Tensor):
+        raise TypeError(f"graph_components: expected a torch tensor of edges, got {type(edges).__name__}")
+    if edges.dtype != torch.int32:
+        raise TypeError(f"graph_components: expected int32 edges, got {edges.dtype}")
+    if edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError(f"graph_components: expected (E, 2) edges, got {tuple(edges.shape)}")
+    if not edges.is_contiguous():
+        raise ValueError("graph_components: the edges must be contiguous")
+    n = int(n_nodes)
+    if not 1 <= n < 2 ** 31 - 1:
+        raise ValueError(f"graph_components: n_nodes {n} outside 1 .. 2^31 - 2")
+    if not edges.is_cuda:
+        raise RuntimeError("graph_components: actionmesh_amd kernels need a device tensor (no CPU path)")
+    dev = edges.device
+    E = edges.shape[0]
+    buf = torch.empty((n + 1,), dtype=torch.int32, device=dev)       # labels, then the flag
+    size = torch.empty((n,), dtype=torch.int32, device=dev) if return_size else None
+    lib = L.lib()
+    need = lib.am_graph_components_workspace_bytes(n, E)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    a = L.AmGraphArgs()
+    a.n_nodes, a.n_edges, a.edges = n, E, (edges.data_ptr() if E else None)
+    a.out_label, a.out_size, a.out_flag = buf.data_ptr(), _p(size), buf.data_ptr() + 4 * n
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    _launch(edges, lib.am_graph_components, "am_graph_components", C.byref(a))
+    if bool(buf[n]):
+        raise ValueError(f"graph_components: an edge names a node outside [0, {n})")
+    label = buf[:n]
+    return (label, size) if return_size else label
+
+
 # ---- exact-fp32 path (csrc/am_f32.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----------------------
 def _fk(kind: str, name: str):
     """Entry point `name` of the library build `kind` ("bf16" / "f16"): the fp32 entry points are in both."""

@@ -595,6 +595,73 @@ typedef struct {
 } am_image_materialize_args;
 int am_image_materialize(const am_image_materialize_args* args, void* stream);
 
+/* Connected components (INTEGRATION seam S9).  Two entries over one union-find whose root is the SMALLEST index of its component, so
+ * every result is fully determined; only integer atomics are used (min on labels, add on sizes and counters) and nothing depends on
+ * scheduling.  Launches only: no allocation, no copy, no synchronisation, a number of launches that does not depend on the sizes;
+ * no kernel waits for another workgroup (the unions are lock-free atomic-min retries, which end because labels only decrease).
+ *
+ * Mask refinement: the reference's `refine_mask` (actionmesh/preprocessing/background_removal.py:20-38: cv2's Otsu threshold,
+ * skimage.measure.label, skimage.morphology.remove_small_objects), per frame:
+ *
+ *   h[0..255] = histogram of the frame;  N = height * width                       (threshold == -1; else max_val = threshold)
+ *   scale = 1.0 / N;  mu = (sum_i i*h[i]) * scale;  mu1 = q1 = max_sigma = 0;  max_val = 0                      all in fp64
+ *   for i in 0 .. 255:
+ *       p = h[i]*scale;  mu1 *= q1;  q1 += p;  q2 = 1.0 - q1
+ *       if min(q1, q2) < FLT_EPSILON or max(q1, q2) > 1.0 - FLT_EPSILON: continue
+ *       mu1 = (mu1 + i*p)/q1;  mu2 = (mu - q1*mu1)/q2
+ *       sigma = q1*q2*(mu1 - mu2)*(mu1 - mu2)                                      left to right, no fused multiply-add anywhere
+ *       if sigma > max_sigma: max_sigma = sigma; max_val = i
+ *   foreground = pixel > max_val                                                   (a constant frame: max_val = 0)
+ *   components of the foreground under 8-connectivity (skimage's default in 2-D; its input holds only 0 and 255, so labelling
+ *   equal-valued regions is labelling the foreground);  size = pixels of a component
+ *   out_mask = foreground and size >= min_size ? 255 : 0                           (remove_small_objects drops size < min_size)
+ *
+ * The loop restates OpenCV's getThreshVal_Otsu_8u followed by THRESH_BINARY.  OpenCV is not installable where this was written:
+ * that cv2.threshold returns this very value for every histogram is UNPINNED; the loop above is the contract, and the tests hold
+ * the device to a numpy restatement of it exactly, and the labelling to scipy.ndimage.label bit for bit.
+ *
+ *   mask        device uint8 (n_frames, height, width), contiguous;  height * width < 2^31 - 1, offsets across frames are 64-bit;
+ *   out_mask    device uint8, same shape, values 0 / 255 (may be `mask` itself);
+ *   out_labels  optional device int32, same shape: 0 on background, 1 + min(y * width + x) over the pixel's component on foreground
+ *               - the components BEFORE small ones are removed;
+ *   out_stats   optional device int32 (n_frames, 4) = { threshold used, foreground pixels, components, components kept };
+ *   workspace   16-byte aligned device scratch of the workspace function's size for the same (n_frames, height, width).
+ * A frame's result does not depend on which frames share the call.
+ *
+ * Graph components: n_nodes nodes and an explicit undirected edge list (self-loops and duplicates allowed, n_edges may be 0).
+ *   edges       device int32 (n_edges, 2);
+ *   out_label   device int32[n_nodes]: the smallest node index of the node's component;
+ *   out_size    optional device int32[n_nodes]: the size of the node's component, written at every node;
+ *   out_flag    device int32[1]: 0, or 1 when an edge names a node outside [0, n_nodes) - such an edge is skipped (never
+ *               dereferenced) and the caller, who reads the flag together with the result, treats the call as failed. */
+typedef struct {
+  const uint8_t* mask;
+  int32_t n_frames, height, width;
+  int32_t min_size;             /* >= 0 */
+  int32_t threshold;            /* -1: Otsu per frame; 0 .. 255: that value for every frame */
+  int32_t reserved;
+  uint8_t* out_mask;
+  int32_t* out_labels;
+  int32_t* out_stats;
+  void* workspace;
+  size_t workspace_bytes;
+} am_mask_refine_args;
+size_t am_mask_refine_workspace_bytes(int n_frames, int height, int width);
+int am_mask_refine(const am_mask_refine_args* args, void* stream);
+
+typedef struct {
+  int64_t n_nodes;              /* 1 .. 2^31 - 2 */
+  int64_t n_edges;
+  const int32_t* edges;
+  int32_t* out_label;
+  int32_t* out_size;
+  int32_t* out_flag;
+  void* workspace;              /* device, 16-byte aligned, am_graph_components_workspace_bytes(n_nodes, n_edges) */
+  size_t workspace_bytes;
+} am_graph_args;
+size_t am_graph_components_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+int am_graph_components(const am_graph_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
