@@ -1271,6 +1271,9 @@ extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
   // get four times as many 128x128 workgroups instead
   const bool big = !force_small && args.N >= 8 && args.M >= 1 &&
                    (force_big || (args.N >= 256 && args.M >= 1024 && (int64_t)ceil_div(args.M, B2) * ceil_div(args.N, B2) >= 192));
+  // both 256x256 kernels (and gemm_tail_kernel behind them) fetch the bias four floats per lane as one f32x4_t: a 16-byte access.
+  // The 128x128 kernel reads it float by float and takes any bias
+  AM_CHECK(!big || (uintptr_t)args.bias % 16 == 0, "am_gemm_bf16: the 256x256 tile needs a 16-byte aligned bias");
   args.act |= abl;          // kernels test `act & 0xff`; bits 11 / 12 are the store / residual timing ablations
   // ln_part: full 256-row tiles of the ping-pong kernel write their slices from the store loop (N % 256 == 0); every other row -
   // edge tiles, the 128x128 kernel's rows, the lockstep kernel - gets them from am_row_part below, reading C back

@@ -314,8 +314,9 @@ __global__ __launch_bounds__(256) void head_post_kernel(am_headpost_args p, int 
       const int s = s0 + pass * 16 + tok_in_pass;
       if (s < s_min) continue;          // partial launch: this token's row was written by the fused GEMM epilogue
       if (s >= p.seq_len) {             // uniform per 16-lane group
-        // K rows of the padded tail of the last key tile must be zero: the attention kernel
-        // relies on score(padded key) == 0 instead of masking (am_attention.hip, tail_fix)
+        // K rows of the padded tail of the last key tile are written as zeros ("pad rows zero").  The
+        // attention kernels no longer depend on score(padded key) == 0: they set the scores of the keys past `sk` to -inf
+        // (P = 0 exactly).  The pads are still loaded and multiplied, so they have to stay finite
         if (kind == 1 && s < s_pad) {
           bf16_t* dst = out + (((int64_t)sidx * p.heads + head) * s_pad + s) * 128 + sub * 8;
           *reinterpret_cast<u32x4_t*>(dst) = u32x4_t{0u, 0u, 0u, 0u};

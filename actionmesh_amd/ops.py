@@ -56,8 +56,30 @@ def _need(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     return t
 
 
+def _need_rows(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
+    """A 2-D device tensor of `dtype` with unit column stride: an operand whose leading dimension (t.stride(0)) goes to the library,
+    so rows may be padded or be a column slice of a wider buffer.  Contiguous 2-D tensors qualify.  `_rows_view` is the fp32 twin."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: actionmesh_amd kernels need a device tensor (no CPU path)")
+    if (t.dtype not in dtype) if isinstance(dtype, tuple) else (t.dtype != dtype):
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected a 2-D tensor with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
 def round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
+
+
+def _out_rows(out: Optional[torch.Tensor], rows: int, ld_out: int, dtype, device, name: str) -> torch.Tensor:
+    """The (rows, ld_out) output of a kernel that writes whole rows of `ld_out` elements: a fresh tensor, or the caller's `out`."""
+    if out is None:
+        return torch.empty((rows, ld_out), dtype=dtype, device=device)
+    _need(out, dtype, f"{name}: out")
+    if tuple(out.shape) != (rows, ld_out):
+        raise ValueError(f"{name}: out {tuple(out.shape)} != ({rows}, {ld_out})")
+    return out
 
 
 def perm16_index(n: int, device=None) -> torch.Tensor:
@@ -80,7 +102,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     a_map / c_map = (G, group_stride, offset) row maps (G=0: identity).
     ln = (stats (M, 2) fp32, colsum (N,) fp32): the LayerNorm of `a` folded into the linear (w, bias from ln_fold_weight; see
     am_gemm_args in include/actionmesh_amd.h).  ln_part (M, ceil(N / 256), 2) fp32: receives the per-slice (mean, M2) of the output rows."""
-    _need(a, H16, "a"); _need(w, a.dtype, "w")
+    _need_rows(a, H16, "a"); _need_rows(w, a.dtype, "w")
     K1 = a.shape[1]
     K = w.shape[1]
     N = w.shape[0]
@@ -88,18 +110,18 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
         M = a.shape[0]
     if out is None:
         out = torch.empty((M, N), dtype=a.dtype, device=a.device)
-    _need(out, a.dtype, "out")
+    _need_rows(out, a.dtype, "out")
     g = L.AmGemmArgs()
     g.A1 = a.data_ptr(); g.lda1 = a.stride(0); g.K1 = K1
     g.A2 = _p(a2); g.lda2 = a2.stride(0) if a2 is not None else 0
     if a2 is not None:
-        _need(a2, a.dtype, "a2")
+        _need_rows(a2, a.dtype, "a2")
         assert K1 + a2.shape[1] == K
     else:
         assert K1 == K
     g.W = w.data_ptr(); g.ldw = w.stride(0)
     g.bias = _p(_need(bias, torch.float32, "bias")) if bias is not None else None
-    g.residual = _p(_need(residual, a.dtype, "residual")) if residual is not None else None
+    g.residual = _p(_need_rows(residual, a.dtype, "residual")) if residual is not None else None
     g.C = out.data_ptr(); g.ldc = out.stride(0)
     g.M, g.N, g.K = M, N, K
     # 0x100: force the 128x128 register-staged kernel (the small-problem path; tests compare the two tilings);
@@ -142,14 +164,20 @@ def row_stats_finalize(part: torch.Tensor, Cdim: int, eps: float = 1e-5, out: Op
     return out
 
 
-def ln_fold_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: Optional[torch.Tensor] = None):
+def ln_fold_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
     """One-time preparation of a linear that absorbs the LayerNorm in front of it: returns (wf, colsum, d) for gemm(a, wf, bias=d,
     ln=(row_stats(a), colsum)) == gemm(layernorm(a, gamma, beta), w, bias) up to the bf16 rounding of the normalised activation."""
     _need(w, H16, "w"); _need(gamma, torch.float32, "gamma"); _need(beta, torch.float32, "beta")
     N, K = w.shape
-    wf = torch.empty_like(w)
-    colsum = torch.empty((N,), dtype=torch.float32, device=w.device)
-    d = torch.empty((N,), dtype=torch.float32, device=w.device)
+    if out is None:
+        wf = torch.empty_like(w)
+        colsum = torch.empty((N,), dtype=torch.float32, device=w.device)
+        d = torch.empty((N,), dtype=torch.float32, device=w.device)
+    else:       # caller-owned (wf (N, K), colsum (N,), d (N,))
+        wf, colsum, d = _need(out[0], w.dtype, "out wf"), _need(out[1], torch.float32, "out colsum"), _need(out[2], torch.float32, "out d")
+        if tuple(wf.shape) != (N, K) or colsum.numel() != N or d.numel() != N:
+            raise ValueError(f"ln_fold_weight: out shapes {tuple(wf.shape)} / {colsum.numel()} / {d.numel()} for N={N}, K={K}")
     _launch(w, _fn(w, "am_ln_fold_weight"), "am_ln_fold_weight", w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
             _p(_need(bias, torch.float32, "bias")) if bias is not None else None, wf.data_ptr(), colsum.data_ptr(), d.data_ptr(), N, K)
     return wf, colsum, d
@@ -206,7 +234,7 @@ def head_post(x: torch.Tensor, heads: int, kinds: Sequence[int], seq_len: int, r
     """Split heads of x (rows, heads*len(kinds)*128), apply qk-RMSNorm (+RoPE), and write the
     attention operand layouts.  Returns (Q, K, Vt) (None for absent kinds):
       Q  (nseq, H, sq_pad, 128), K (nseq, H, sk_pad, 128), Vt (nseq, H, 128, sk_pad)."""
-    _need(x, H16, "x")
+    _need_rows(x, H16, "x")
     rows = x.shape[0]
     nseq = rows // seq_len
     sq_pad, sk_pad = round_up(seq_len, 256), round_up(seq_len, 64)
@@ -249,6 +277,7 @@ def gemm_head_post(a: torch.Tensor, w: torch.Tensor, heads: int, kinds: Sequence
     assert N == heads * len(kinds) * HEAD_DIM and w.shape[1] == K
     if x is None:
         x = torch.empty((rows, N), dtype=a.dtype, device=a.device)
+    _need_rows(x, a.dtype, "x")
     nseq = rows // seq_len
     sq_pad, sk_pad = round_up(seq_len, 256), round_up(seq_len, 64)
     dev = a.device
@@ -304,6 +333,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: i
     sk_pad = k.shape[-2]
     if out is None:
         out = torch.empty((nseq * sq, H * HEAD_DIM), dtype=q.dtype, device=q.device)
+    _need_rows(out, q.dtype, "out")
     a = L.AmAttnArgs()
     a.Q, a.K, a.Vt, a.O = q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
     a.nseq, a.heads, a.sq, a.sq_pad, a.sk, a.sk_pad = nseq, H, sq, sq_pad, sk, sk_pad
@@ -325,15 +355,18 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, s
                   out: Optional[torch.Tensor] = None, nchunks: int = 1, scale: Optional[float] = None,
                   quantized: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, ablate: int = 0,
                   rows: int = 0, state_mode: int = 0, state: Optional[torch.Tensor] = None, chunk_first: int = 0,
-                  chunk_total: int = 0, **_ignored) -> torch.Tensor:
+                  chunk_total: int = 0, quantize_out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                  **_ignored) -> torch.Tensor:
     """fp8 (e4m3) attention on the bf16 operand layouts of `attention`: quantise (unless `quantized` = (q8, k8, vt8) from an
     earlier call is passed), then QK^T / P.V on the MX-scaled fp8 MFMA.  Returns out (nseq * sq, H * 128) bf16.
-    rows / state_mode / state / chunk_first / chunk_total: the two-pass forms, as in `attention`."""
+    rows / state_mode / state / chunk_first / chunk_total: the two-pass forms, as in `attention`.  `quantize_out`: caller-owned uint8
+    (q8, k8, vt8) of the shapes of q / k / vt that receive the quantisation (default: fresh tensors)."""
     _need(q, H16, "q"); _need(k, q.dtype, "k"); _need(vt, q.dtype, "vt")
     nseq, H, sq_pad, _ = q.shape
     sk_pad = k.shape[-2]
     if out is None:
         out = torch.empty((nseq * sq, H * HEAD_DIM), dtype=q.dtype, device=q.device)
+    _need_rows(out, q.dtype, "out")
     a = L.AmAttnArgs()
     a.Q, a.K, a.Vt, a.O = q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
     a.nseq, a.heads, a.sq, a.sq_pad, a.sk, a.sk_pad = nseq, H, sq, sq_pad, sk, sk_pad
@@ -348,9 +381,14 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, s
         assert state.numel() >= nseq * H * sq_pad * STATE_LD
         a.state = state.data_ptr()
     if quantized is None:
-        q8 = torch.empty(q.shape, dtype=torch.uint8, device=q.device)
-        k8 = torch.empty(k.shape, dtype=torch.uint8, device=q.device)
-        vt8 = torch.empty(vt.shape, dtype=torch.uint8, device=q.device)
+        if quantize_out is not None:
+            q8, k8, vt8 = (_need(t, torch.uint8, "quantize_out") for t in quantize_out)
+            if q8.shape != q.shape or k8.shape != k.shape or vt8.shape != vt.shape:
+                raise ValueError("attention_fp8: quantize_out must have the shapes of q, k, vt")
+        else:
+            q8 = torch.empty(q.shape, dtype=torch.uint8, device=q.device)
+            k8 = torch.empty(k.shape, dtype=torch.uint8, device=q.device)
+            vt8 = torch.empty(vt.shape, dtype=torch.uint8, device=q.device)
         _launch(q, _fn(q, "am_attention_quantize_fp8"), "am_attention_quantize_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(),
                 vt8.data_ptr())
     else:
@@ -367,46 +405,50 @@ def attention_fallback_count() -> int:
     return int(n.value)
 
 
-def f32_to_bf16(x: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+def f32_to_bf16(x: torch.Tensor, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 -> the 16-bit type (round to nearest even); `dtype=torch.float16` runs the float16 build of the library."""
     _need(x, torch.float32, "x")
-    y = torch.empty(x.shape, dtype=dtype, device=x.device)
+    y = torch.empty(x.shape, dtype=dtype, device=x.device) if out is None else _need(out, dtype, "out")
+    if y.numel() != x.numel():
+        raise ValueError(f"f32_to_bf16: out has {y.numel()} elements for {x.numel()} inputs")
     _launch(x, _fn(dtype, "am_f32_to_bf16"), "am_f32_to_bf16", x.data_ptr(), y.data_ptr(), x.numel())
     return y
 
 
-def timestep_sinusoid(t: torch.Tensor, width: int, dtype=torch.bfloat16) -> torch.Tensor:
+def timestep_sinusoid(t: torch.Tensor, width: int, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """t (rows,) fp32 -> 16-bit (rows, width): [sin | cos] of t * 10000^(-i / (width / 2)); `dtype=torch.float16` runs the float16 build."""
     _need(t, torch.float32, "t")
-    y = torch.empty((t.numel(), width), dtype=dtype, device=t.device)
+    y = torch.empty((t.numel(), width), dtype=dtype, device=t.device) if out is None else _need(out, dtype, "out")
+    if tuple(y.shape) != (t.numel(), width):
+        raise ValueError(f"timestep_sinusoid: out {tuple(y.shape)} != ({t.numel()}, {width})")
     _launch(t, _fn(dtype, "am_timestep_sinusoid"), "am_timestep_sinusoid", t.data_ptr(), y.data_ptr(), t.numel(), width)
     return y
 
 
 def point_embed(query: torch.Tensor, in_channels: int, extra_channels: int, num_freqs: int, include_pi: bool,
-                ld_out: int = 64, dtype=torch.bfloat16) -> torch.Tensor:
-    """query (rows, >= in+extra) fp32 -> 16-bit (rows, ld_out): FrequencyPositionalEmbedding + extras, zero padded."""
-    _need(query, torch.float32, "query")
+                ld_out: int = 64, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """query (rows, >= in+extra) fp32, rows may be strided -> 16-bit (rows, ld_out): FrequencyPositionalEmbedding + extras, zero padded."""
+    _rows_view(query, "query")
     rows = query.shape[0]
-    out = torch.empty((rows, ld_out), dtype=dtype, device=query.device)
+    out = _out_rows(out, rows, ld_out, dtype, query.device, "point_embed")
     _launch(query, _fn(dtype, "am_point_embed"), "am_point_embed", query.data_ptr(), query.stride(0), rows, in_channels, extra_channels, num_freqs,
                                    int(include_pi), out.data_ptr(), ld_out)
     return out
 
 
-def patchify(pixels: torch.Tensor, patch: int, ld_out: int, dtype=torch.bfloat16) -> torch.Tensor:
+def patchify(pixels: torch.Tensor, patch: int, ld_out: int, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pixels (T, C, H, W) fp32 -> 16-bit (T * (H // patch) * (W // patch), ld_out): rows of the kernel = stride patch
     convolution in flattened-Conv2d-weight column order, zero padded."""
     _need(pixels, torch.float32, "pixels")
     T, Cin, H, W = pixels.shape
-    out = torch.empty((T * (H // patch) * (W // patch), ld_out), dtype=dtype, device=pixels.device)
+    out = _out_rows(out, T * (H // patch) * (W // patch), ld_out, dtype, pixels.device, "patchify")
     _launch(pixels, _fn(dtype, "am_patchify"), "am_patchify", pixels.data_ptr(), T, Cin, H, W, patch, out.data_ptr(), ld_out)
     return out
 
 
 def displacement(logits: torch.Tensor, out_dim: int, out: torch.Tensor) -> torch.Tensor:
     """out (rows, out_dim) fp32 = 2 sigmoid(-logits[:, :out_dim]) - 1."""
-    _need(logits, H16, "logits"); _need(out, torch.float32, "out")
+    _need_rows(logits, H16, "logits"); _need(out, torch.float32, "out")
     _launch(logits, _fn(logits, "am_displacement"), "am_displacement", logits.data_ptr(), logits.stride(0), logits.shape[0], out_dim, out.data_ptr())
     return out
 
@@ -797,25 +839,25 @@ def layernorm_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float 
 
 
 def point_embed_f32(query: torch.Tensor, in_channels: int, extra_channels: int, num_freqs: int, include_pi: bool,
-                    ld_out: int = 64, kind: str = "bf16") -> torch.Tensor:
-    """`point_embed` without the rounding: query (rows, >= in+extra) fp32 -> fp32 (rows, ld_out)."""
-    _need(query, torch.float32, "query")
+                    ld_out: int = 64, kind: str = "bf16", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`point_embed` without the rounding: query (rows, >= in+extra) fp32, rows may be strided -> fp32 (rows, ld_out)."""
+    _rows_view(query, "query")
     if query.dim() != 2 or query.shape[1] < in_channels + extra_channels:
         raise ValueError(f"point_embed_f32: query {tuple(query.shape)} has fewer than {in_channels + extra_channels} channels")
     rows = query.shape[0]
-    out = torch.empty((rows, ld_out), dtype=torch.float32, device=query.device)
+    out = _out_rows(out, rows, ld_out, torch.float32, query.device, "point_embed_f32")
     _launch(query, _fk(kind, "am_point_embed_f32"), "am_point_embed_f32", query.data_ptr(), query.stride(0), rows, in_channels,
             extra_channels, num_freqs, int(include_pi), out.data_ptr(), ld_out)
     return out
 
 
-def patchify_f32(pixels: torch.Tensor, patch: int, ld_out: int, kind: str = "bf16") -> torch.Tensor:
+def patchify_f32(pixels: torch.Tensor, patch: int, ld_out: int, kind: str = "bf16", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`patchify` without the rounding: pixels (T, C, H, W) fp32 -> fp32 (T * (H // patch) * (W // patch), ld_out)."""
     _need(pixels, torch.float32, "pixels")
     if pixels.dim() != 4:
         raise ValueError(f"patchify_f32: expected (T, C, H, W), got {tuple(pixels.shape)}")
     T, Cin, H, W = pixels.shape
-    out = torch.empty((T * (H // patch) * (W // patch), ld_out), dtype=torch.float32, device=pixels.device)
+    out = _out_rows(out, T * (H // patch) * (W // patch), ld_out, torch.float32, pixels.device, "patchify_f32")
     _launch(pixels, _fk(kind, "am_patchify_f32"), "am_patchify_f32", pixels.data_ptr(), T, Cin, H, W, patch, out.data_ptr(), ld_out)
     return out
 

@@ -179,7 +179,11 @@ double am_step_flops(am_handle h, int B, int T_total, int N, int S);
  *   A may be split in two column blocks (A1: first K1 cols, A2: rest) = the
  *   torch.cat([skip, h]) of block.py:131 without materialising it.
  *   Row maps: physical_row(r) = (r / G) * gs + off + r % G  (G = 0 => identity).
- *   residual uses C's row map and leading dimension; may alias C.            */
+ *   residual uses C's row map and leading dimension; may alias C.
+ *   Layout: A1, A2, W, C, residual 16-byte aligned; lda1, lda2, ldw, ldc multiples of 8
+ *   elements; K and K1 multiples of 64, N a multiple of 8.  bias: 16-byte aligned on the
+ *   256x256 tile (N >= 256 and M >= 1024 on a grid of >= 192 tiles) and under ln_stats, any
+ *   float pointer on the 128x128 tile.  Only C[r][0 .. N) of the M mapped rows is written.  */
 typedef struct {
   const uint16_t* A1; int32_t lda1; int32_t K1;
   const uint16_t* A2; int32_t lda2;
