@@ -35,6 +35,15 @@ class AmConfig(C.Structure):
     ]
 
 
+# am_gemm_args.act: the activation code in the low byte; the bits above it are diagnostic and test switches, never product options
+# (the AM_GEMM_* defines of include/actionmesh_amd.h; tests/test_host_cpu.py holds the two lists equal)
+GEMM_ACT_MASK, GEMM_ACT_GELU = 0xff, 1
+GEMM_FORCE_128, GEMM_LOCKSTEP, GEMM_FORCE_256 = 0x100, 0x200, 0x400
+GEMM_ABLATE_STORE, GEMM_ABLATE_READ, GEMM_ABLATE_MASK = 0x800, 0x1000, 0x1800
+GEMM_SKEW_SHIFT, GEMM_SKEW_MASK = 13, 0xe000
+GEMM_NO_GELU_TABLE = 0x10000
+
+
 class AmGemmArgs(C.Structure):
     _fields_ = [
         ("A1", C.c_void_p), ("lda1", C.c_int32), ("K1", C.c_int32),
@@ -180,6 +189,16 @@ class AmPeerRing(C.Structure):          # include/actionmesh_amd_sharded.h
         ("ev_fork", C.c_void_p), ("ev_pushed", C.c_void_p),
     ]
 
+
+# every struct include/*.h declares: C typedef name -> ctypes mirror (tests/test_host_cpu.py compares the names with the headers and
+# every size and field offset with what a C compiler makes of them)
+STRUCTS = {
+    "am_config": AmConfig, "am_gemm_args": AmGemmArgs, "am_headpost_args": AmHeadPostArgs, "am_attn_args": AmAttnArgs,
+    "am_attn_f32_args": AmAttnF32Args, "am_nn_args": AmNnArgs, "am_render_camera": AmRenderCamera, "am_render_args": AmRenderArgs,
+    "am_fps_args": AmFpsArgs, "am_image_frame": AmImageFrame, "am_image_alpha_stats_args": AmImageAlphaStatsArgs,
+    "am_image_resample_args": AmImageResampleArgs, "am_image_materialize_args": AmImageMaterializeArgs,
+    "am_mask_refine_args": AmMaskRefineArgs, "am_graph_args": AmGraphArgs, "am_peer_ring": AmPeerRing,
+}
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = C.c_void_p

@@ -127,8 +127,14 @@ extern "C" int am_timestep_sinusoid(const float* t_dev, uint16_t* out, int rows,
 // ---- Stage II (temporal_autoencoder.py) input / output featurisation -------------------------------------------
 // FrequencyPositionalEmbedding (embeddings.py:14-52, logspace, include_input) + the extra channels (normals):
 //   out[row] = [x (3) | sin(x_c f_j), c-major (3F) | cos(x_c f_j) (3F) | extra | 0-pad], f_j = 2^j (* pi)
+// point_embed_kernel and patchify_kernel compute in fp32 and are templates over the output type: T = bf16_t rounds to the 16-bit type
+// (am_point_embed, am_patchify), T = float stores the value as it is (am_point_embed_f32, am_patchify_f32: the exact-fp32 path).
+static __device__ inline void put(bf16_t* o, float v) { *o = f2bf(v); }
+static __device__ inline void put(float* o, float v) { *o = v; }
+
+template <typename T>
 __global__ void point_embed_kernel(const float* __restrict__ q, int ld_in, int64_t rows, int in_ch, int extra, int nfreq,
-                                   float fscale, bf16_t* __restrict__ out, int ld_out) {
+                                   float fscale, T* __restrict__ out, int ld_out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows * ld_out) return;
   const int64_t row = i / ld_out;
@@ -142,7 +148,7 @@ __global__ void point_embed_kernel(const float* __restrict__ q, int ld_in, int64
     const float a = x[e / nfreq] * (fscale * (float)(1 << (e % nfreq)));
     v = c < in_ch + nf ? sinf(a) : cosf(a);
   } else if (c < in_ch + 2 * nf + extra) v = x[in_ch + (c - in_ch - 2 * nf)];
-  out[i] = f2bf(v);
+  put(out + i, v);
 }
 // temporal_autoencoder.py:156-157, 267: logits * -1, then 2 * sigmoid - 1
 __global__ void displacement_kernel(const bf16_t* __restrict__ logits, int ld, int64_t rows, int out_dim, float* __restrict__ out) {
@@ -155,9 +161,10 @@ __global__ void displacement_kernel(const bf16_t* __restrict__ logits, int ld, i
 
 // ---- context encoder (transformers Dinov2PatchEmbeddings: Conv2d with kernel = stride = patch) ------------------------
 // im2col of the stride = kernel convolution: out[t * nh * nw + py * nw + px][c * p * p + ky * p + kx] = pix[t][c][py p + ky][px p + kx]
-// (the column order of a flattened Conv2d weight), bf16, zero padded to ld_out so the patch projection is one GEMM.
+// (the column order of a flattened Conv2d weight), zero padded to ld_out so the patch projection is one GEMM.
+template <typename T>
 __global__ void patchify_kernel(const float* __restrict__ pix, int ch, int H, int W, int patch, int nh, int nw, int64_t rows,
-                                bf16_t* __restrict__ out, int ld_out) {
+                                T* __restrict__ out, int ld_out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows * ld_out) return;
   const int64_t row = i / ld_out;
@@ -171,34 +178,53 @@ __global__ void patchify_kernel(const float* __restrict__ pix, int ch, int H, in
     const int ky = k / patch, kx = k - ky * patch;
     v = pix[((t * ch + cc) * H + py * patch + ky) * (int64_t)W + px * patch + kx];
   }
-  out[i] = f2bf(v);
+  put(out + i, v);
 }
 
-extern "C" int am_patchify(const float* pixels, int frames, int channels, int height, int width, int patch, uint16_t* out,
-                           int ld_out, void* stream) {
-  AM_CHECK(pixels && out && frames > 0 && channels > 0 && patch > 0, "am_patchify: bad args");
-  AM_CHECK(height >= patch && width >= patch, "am_patchify: image %dx%d smaller than one patch (%d)", height, width, patch);
-  AM_CHECK(ld_out >= channels * patch * patch, "am_patchify: ld_out=%d too small", ld_out);
+// the 16-bit and the fp32 entry points differ in the output type and in the name their messages carry
+template <typename T>
+static int patchify(const char* what, const float* pixels, int frames, int channels, int height, int width, int patch, T* out, int ld_out,
+                    void* stream) {
+  AM_CHECK(pixels && out && frames > 0 && channels > 0 && patch > 0, "%s: bad args", what);
+  AM_CHECK(height >= patch && width >= patch, "%s: image %dx%d smaller than one patch (%d)", what, height, width, patch);
+  AM_CHECK(ld_out >= channels * patch * patch, "%s: ld_out=%d too small", what, ld_out);
   const int nh = height / patch, nw = width / patch;
   const int64_t rows = (int64_t)frames * nh * nw;
   const int64_t n = rows * ld_out;
-  hipLaunchKernelGGL(patchify_kernel, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, pixels,
+  hipLaunchKernelGGL(patchify_kernel<T>, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, pixels,
                      channels, height, width, patch, nh, nw, rows, out, ld_out);
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
+extern "C" int am_patchify(const float* pixels, int frames, int channels, int height, int width, int patch, uint16_t* out,
+                           int ld_out, void* stream) {
+  return patchify("am_patchify", pixels, frames, channels, height, width, patch, out, ld_out, stream);
+}
+extern "C" int am_patchify_f32(const float* pixels, int frames, int channels, int height, int width, int patch, float* out, int ld_out,
+                               void* stream) {
+  return patchify("am_patchify_f32", pixels, frames, channels, height, width, patch, out, ld_out, stream);
+}
 
-extern "C" int am_point_embed(const float* q_dev, int ld_in, int64_t rows, int in_channels, int extra_channels, int num_freqs,
-                              int include_pi, uint16_t* out, int ld_out, void* stream) {
-  AM_CHECK(q_dev && out && rows > 0, "am_point_embed: bad args");
+template <typename T>
+static int point_embed(const char* what, const float* q_dev, int ld_in, int64_t rows, int in_channels, int extra_channels, int num_freqs,
+                       int include_pi, T* out, int ld_out, void* stream) {
+  AM_CHECK(q_dev && out && rows > 0, "%s: bad args", what);
   AM_CHECK(in_channels > 0 && extra_channels >= 0 && num_freqs > 0 && num_freqs < 24 && ld_in >= in_channels + extra_channels,
-           "am_point_embed: bad channel counts");
-  AM_CHECK(ld_out >= in_channels * (2 * num_freqs + 1) + extra_channels, "am_point_embed: ld_out=%d too small", ld_out);
+           "%s: bad channel counts", what);
+  AM_CHECK(ld_out >= in_channels * (2 * num_freqs + 1) + extra_channels, "%s: ld_out=%d too small", what, ld_out);
   const int64_t n = rows * ld_out;
-  hipLaunchKernelGGL(point_embed_kernel, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, q_dev, ld_in,
+  hipLaunchKernelGGL(point_embed_kernel<T>, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, q_dev, ld_in,
                      rows, in_channels, extra_channels, num_freqs, include_pi ? 3.14159265358979323846f : 1.0f, out, ld_out);
   AM_HIP(hipGetLastError());
   return AM_OK;
+}
+extern "C" int am_point_embed(const float* q_dev, int ld_in, int64_t rows, int in_channels, int extra_channels, int num_freqs,
+                              int include_pi, uint16_t* out, int ld_out, void* stream) {
+  return point_embed("am_point_embed", q_dev, ld_in, rows, in_channels, extra_channels, num_freqs, include_pi, out, ld_out, stream);
+}
+extern "C" int am_point_embed_f32(const float* q_dev, int ld_in, int64_t rows, int in_channels, int extra_channels, int num_freqs,
+                                  int include_pi, float* out, int ld_out, void* stream) {
+  return point_embed("am_point_embed_f32", q_dev, ld_in, rows, in_channels, extra_channels, num_freqs, include_pi, out, ld_out, stream);
 }
 
 extern "C" int am_displacement(const uint16_t* logits, int ld, int64_t rows, int out_dim, float* out, void* stream) {

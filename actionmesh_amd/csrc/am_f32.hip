@@ -4,7 +4,8 @@
 //   am_gemm_f32        C = A W^T (+ bias) (GELU) (+ R), R may alias C                       (nn.Linear in fp32)
 //   am_attention_f32   non-causal SDPA, head_dim 64 / 128, operands read in place from packed projection outputs
 //   am_layernorm_f32   nn.LayerNorm in fp32
-//   am_point_embed_f32 / am_patchify_f32 / am_displacement_f32: the fp32-output forms of the small featurisation ops.
+//   am_displacement_f32: the fp32-input form of am_displacement (am_point_embed_f32 / am_patchify_f32 are in am_elementwise.hip,
+//   next to the 16-bit forms they share their kernels with).
 // Deterministic: no split-K, no atomics; every launch of the same shape computes the same bits (both library builds compile this
 // file the same way - nothing in it depends on the 16-bit type).  Built without the SLP vectoriser (csrc/Makefile).
 #include <math.h>
@@ -326,41 +327,6 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
   }
 }
 
-// ---- fp32-output forms of the featurisation ops (same element maps as am_point_embed / am_patchify / am_displacement) -----------
-__global__ void point_embed_f32_kernel(const float* __restrict__ q, int ld_in, int64_t rows, int in_ch, int extra, int nfreq,
-                                       float fscale, float* __restrict__ out, int ld_out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * ld_out) return;
-  const int64_t row = i / ld_out;
-  const int c = (int)(i - row * ld_out);
-  const float* x = q + row * ld_in;
-  const int nf = in_ch * nfreq;
-  float v = 0.f;
-  if (c < in_ch) v = x[c];
-  else if (c < in_ch + 2 * nf) {
-    const int e = (c - in_ch) % nf;
-    const float a = x[e / nfreq] * (fscale * (float)(1 << (e % nfreq)));
-    v = c < in_ch + nf ? sinf(a) : cosf(a);
-  } else if (c < in_ch + 2 * nf + extra) v = x[in_ch + (c - in_ch - 2 * nf)];
-  out[i] = v;
-}
-__global__ void patchify_f32_kernel(const float* __restrict__ pix, int ch, int H, int W, int patch, int nh, int nw, int64_t rows,
-                                    float* __restrict__ out, int ld_out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * ld_out) return;
-  const int64_t row = i / ld_out;
-  const int c = (int)(i - row * ld_out);
-  float v = 0.f;
-  if (c < ch * patch * patch) {
-    const int64_t t = row / (nh * nw);
-    const int pr = (int)(row - t * nh * nw);
-    const int py = pr / nw, px = pr - py * nw;
-    const int cc = c / (patch * patch), k = c - cc * patch * patch;
-    const int ky = k / patch, kx = k - ky * patch;
-    v = pix[((t * ch + cc) * H + py * patch + ky) * (int64_t)W + px * patch + kx];
-  }
-  out[i] = v;
-}
 // temporal_autoencoder.py:156-157, 267 on fp32 logits: 2 sigmoid(-logits) - 1, libm expf
 __global__ void displacement_f32_kernel(const float* __restrict__ logits, int ld, int64_t rows, int out_dim, float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -432,33 +398,6 @@ extern "C" int am_layernorm_f32(const float* x, float* y, const float* w, const 
   else if (nch <= 4) hipLaunchKernelGGL(layernorm_f32_kernel<4>, grid, block, 0, s, x, y, w, b, rows, C, eps);
   else if (nch <= 8) hipLaunchKernelGGL(layernorm_f32_kernel<8>, grid, block, 0, s, x, y, w, b, rows, C, eps);
   else hipLaunchKernelGGL(layernorm_f32_kernel<16>, grid, block, 0, s, x, y, w, b, rows, C, eps);
-  AM_HIP(hipGetLastError());
-  return AM_OK;
-}
-
-extern "C" int am_point_embed_f32(const float* q_dev, int ld_in, int64_t rows, int in_channels, int extra_channels, int num_freqs,
-                                  int include_pi, float* out, int ld_out, void* stream) {
-  AM_CHECK(q_dev && out && rows > 0, "am_point_embed_f32: bad args");
-  AM_CHECK(in_channels > 0 && extra_channels >= 0 && num_freqs > 0 && num_freqs < 24 && ld_in >= in_channels + extra_channels,
-           "am_point_embed_f32: bad channel counts");
-  AM_CHECK(ld_out >= in_channels * (2 * num_freqs + 1) + extra_channels, "am_point_embed_f32: ld_out=%d too small", ld_out);
-  const int64_t n = rows * ld_out;
-  hipLaunchKernelGGL(point_embed_f32_kernel, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, q_dev, ld_in,
-                     rows, in_channels, extra_channels, num_freqs, include_pi ? 3.14159265358979323846f : 1.0f, out, ld_out);
-  AM_HIP(hipGetLastError());
-  return AM_OK;
-}
-
-extern "C" int am_patchify_f32(const float* pixels, int frames, int channels, int height, int width, int patch, float* out, int ld_out,
-                               void* stream) {
-  AM_CHECK(pixels && out && frames > 0 && channels > 0 && patch > 0, "am_patchify_f32: bad args");
-  AM_CHECK(height >= patch && width >= patch, "am_patchify_f32: image %dx%d smaller than one patch (%d)", height, width, patch);
-  AM_CHECK(ld_out >= channels * patch * patch, "am_patchify_f32: ld_out=%d too small", ld_out);
-  const int nh = height / patch, nw = width / patch;
-  const int64_t rows = (int64_t)frames * nh * nw;
-  const int64_t n = rows * ld_out;
-  hipLaunchKernelGGL(patchify_f32_kernel, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, pixels,
-                     channels, height, width, patch, nh, nw, rows, out, ld_out);
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(am_gemm_args p, int t
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = rbf(v[e] + bv[e]);     // nn.Linear result in bf16
         }
-        if ((p.act & 0xff) == 1) {
+        if ((p.act & AM_GEMM_ACT_MASK) == AM_GEMM_ACT_GELU) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = rbf(gelu_erf(v[e]));   // F.gelu on bf16 -> bf16
         }
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(512) void gemm_tail_kernel(am_gemm_args p, int m_ba
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + bv[e]);
   }
-  if ((p.act & 0xff) == 1) {
+  if ((p.act & AM_GEMM_ACT_MASK) == AM_GEMM_ACT_GELU) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = rbf(gelu_erf(v[e]));
   }
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(512) void gemm_tail_kernel(am_gemm_args p, int m_ba
 // Shared tail of the 256x256 kernels: the bf16 tile staged in LDS (row = 512 B, 8-byte unit u of row m at u ^ (m & 15))
 // goes out as row-contiguous 16-byte stores with the residual added on the way.
 #ifndef AM_GEMM_NT
-#define AM_GEMM_NT 1        // non-temporal residual loads and C stores: both are touched once per GEMM and would only evict the A / W panels the
+#define AM_GEMM_NT 1   // non-temporal residual loads and C stores: both are touched once per GEMM and would only evict the A / W panels the
 #endif                      // XCD's other workgroups are about to re-read from L2 (0 = the A/B build, tools/build_gemm_variants.sh)
 // The residual operand of a full, identity-mapped tile, fetched BEFORE the accumulators are staged through LDS (round 4): 16 loads of
 // 16 bytes per thread in flight at once, their HBM latency under the staging pass and its barrier.  Before, the store loop issued them
@@ -304,7 +304,7 @@ struct ResidualPrefetch {
   bool on;
 };
 __device__ __forceinline__ bool residual_prefetchable(const am_gemm_args& p, int tid, int m0, int n0) {
-  return p.residual != nullptr && p.c_G <= 0 && m0 + B2 <= p.M && n0 + (tid & 31) * 8 < p.N && !(p.act & 0x1800);
+  return p.residual != nullptr && p.c_G <= 0 && m0 + B2 <= p.M && n0 + (tid & 31) * 8 < p.N && !(p.act & AM_GEMM_ABLATE_MASK);
 }
 __device__ __forceinline__ void residual_prefetch(const am_gemm_args& p, int tid, int m0, int n0, ResidualPrefetch& r) {
   r.on = residual_prefetchable(p, tid, m0, n0);
@@ -369,7 +369,7 @@ __device__ __forceinline__ void store_staged_tile(const am_gemm_args& p, const u
         for (int e = 0; e < 4; ++e) sv[e] = pack_bf2(bflo(sv[e]) + bflo(rv[e]), bfhi(sv[e]) + bfhi(rv[e]));
         return sv;
       };
-      const bool abl_nostore = (p.act & 0x800) != 0, abl_nores = (p.act & 0x1000) != 0;   // timing ablations (tools/kernel_bench.py)
+      const bool abl_nostore = (p.act & AM_GEMM_ABLATE_STORE) != 0, abl_nores = (p.act & AM_GEMM_ABLATE_READ) != 0;   // timing ablations (tools/kernel_bench.py)
       if (abl_nostore) {
         u32x4_t keep = fetch(0);
 #pragma unroll 4
@@ -446,7 +446,7 @@ __device__ __forceinline__ void store_staged_tile_headpost(const am_gemm_args& p
                                                            int tid, int m0, int n0) {
   const int k16 = tid & 31, r16 = tid >> 5;
   const int half = k16 >> 4, sub = k16 & 15;
-  const bool abl_noqk = (p.act & 0x800) != 0, abl_nov = (p.act & 0x1000) != 0;      // timing ablations (tools/kernel_bench.py --ablate-gemm)
+  const bool abl_noqk = (p.act & AM_GEMM_ABLATE_STORE) != 0, abl_nov = (p.act & AM_GEMM_ABLATE_READ) != 0;   // timing ablations (tools/kernel_bench.py --ablate-gemm)
   if (!abl_noqk) {
     const int pi = (n0 >> 7) + half;                           // (head, part) slice of this thread's 128-column half
     const int head = pi / hp.nparts, part = pi - head * hp.nparts;
@@ -760,7 +760,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_bf16_kernel(am_gemm_args p, in
       for (int i = 0; i < 4; ++i) {
         const int ml = wm * 128 + i * 32 + l31;
         u32x2_t w;
-        if ((p.act & 0xff) == 1) {                               // F.gelu on the bf16 linear output -> bf16
+        if ((p.act & AM_GEMM_ACT_MASK) == AM_GEMM_ACT_GELU) {   // F.gelu on the bf16 linear output -> bf16
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = gelu_erf(rbf(acc[i][j][4 * g + e]));
@@ -862,14 +862,14 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_bf16_kernel(am_gemm_args p, 
 
   const int nb = tiles_m * tiles_n;
   const int bid = blockIdx.x;
-  {   // Per-XCD start skew (round 3): the first round's workgroups of XCD x start x * units * 1.5 us late (act bits 13-15, set by
+  {   // Per-XCD start skew (round 3): the first round's workgroups of XCD x start x * units * 1.5 us late (act's AM_GEMM_SKEW field, set by
       // am_gemm_bf16), and every later round inherits the offset.  All workgroups of a round take the same time, so without it the
       // 256 epilogues (C stores + residual loads: 64-96 MB) hit HBM in one burst while the main loops leave it idle; whole-XCD
       // offsets spread the bursts and keep each XCD's 32 workgroups in lockstep, so they still share their A / W panels through its
       // L2 (per-WORKGROUP offsets, tried in round 2, lost that sharing and were slower).  Same tiles, same arithmetic: bit-identical.
       // Measured same-box, warm (profiles/r03h_gemm_skew.txt, "off" vs best): qkv 0.828 -> 0.756 ms, ff1+GELU 1.262 -> 1.164, ff2 0.951 -> 0.936;
       // nominal qkv 1.369 -> 1.302.
-    const int units = (p.act >> 13) & 7;
+    const int units = (p.act & AM_GEMM_SKEW_MASK) >> AM_GEMM_SKEW_SHIFT;
     // (an additional INTRA-XCD skew - the XCD's workgroups entering their epilogues at four different times - was measured in round 4
     // and dropped: no gain at 0.5-2 us, 1.5-4 % slower at 4-8 us; tools/experiments/gemm_subskew.patch, profiles/r04m_gemm_subskew.txt)
     if (units && units < 7 && bid < 256) {
@@ -1100,11 +1100,11 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_bf16_kernel(am_gemm_args p, 
         *reinterpret_cast<u32x2_t*>(stage + ml * 512 + u * 8) = w;
       }
   };
-  if ((p.act & 0xff) == 1 && gelu_tab != nullptr) {             // F.gelu on the bf16 linear output -> bf16, by table (see GT_LO)
+  if ((p.act & AM_GEMM_ACT_MASK) == AM_GEMM_ACT_GELU && gelu_tab != nullptr) {   // F.gelu on the bf16 linear output -> bf16, by table (see GT_LO)
     stage_pass([&](const f32x4_t& a) __attribute__((always_inline)) {
       return u32x2_t{gelu_table_pair(pack_bf2(a[0], a[1]), smem + GT_OFF, gelu_bad), gelu_table_pair(pack_bf2(a[2], a[3]), smem + GT_OFF, gelu_bad)};
     });
-  } else if ((p.act & 0xff) == 1) {                              // the arithmetic form (float16 build; table unavailable)
+  } else if ((p.act & AM_GEMM_ACT_MASK) == AM_GEMM_ACT_GELU) {   // the arithmetic form (float16 build; table unavailable)
     stage_pass([&](const f32x4_t& a) __attribute__((always_inline)) {
       float v[4];
 #pragma unroll
@@ -1141,7 +1141,7 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_bf16_kernel(am_gemm_args p, 
 
 }  // namespace
 
-// Per-XCD start skew of the big GEMMs: how many 1.5 us units XCD x's first round starts late (kernel: act bits 13-15).  The
+// Per-XCD start skew of the big GEMMs: how many 1.5 us units XCD x's first round starts late (kernel: act's AM_GEMM_SKEW field).  The
 // kernel's `blockIdx & 7 == XCD` mapping, the 100 MHz wall clock and the 256-workgroup first round describe ONE part in ONE
 // partition mode: an MI355X (gfx950) in SPX mode - 256 CUs visible as one device.  Anywhere else (CPX / DPX partitions, CU-masked
 // streams shrink multiProcessorCount; other parts) the skew would be pure added latency, so it is 0 there; the environment
@@ -1236,10 +1236,11 @@ extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
     AM_CHECK(a->ln_colsum != nullptr, "am_gemm_bf16: ln_stats without ln_colsum");
     AM_CHECK(a->A2 == nullptr, "am_gemm_bf16: a folded LayerNorm needs one A operand");
     // a row map on A is honoured by the 128x128 kernel only (ln_stats is indexed by the mapped A row): narrow linears such as proj_out.
-    // act 0x400 sends any N to the 256x256 tile, which indexes the statistics by OUTPUT row: refused unless 0x100 (which wins) is set too
-    AM_CHECK(a->a_G == 0 || (a->act & 0x100) || (a->N < 256 && !(a->act & 0x400)),
+    // AM_GEMM_FORCE_256 sends any N to the 256x256 tile, which indexes the statistics by OUTPUT row: refused unless AM_GEMM_FORCE_128
+    // (which wins) is set too
+    AM_CHECK(a->a_G == 0 || (a->act & AM_GEMM_FORCE_128) || (a->N < 256 && !(a->act & AM_GEMM_FORCE_256)),
              "am_gemm_bf16: a folded LayerNorm over a row-mapped A needs the 128x128 kernel (N < 256 without the forced 256x256 tile)");
-    AM_CHECK(!(a->act & 0x200), "am_gemm_bf16: the round-1 lockstep kernel has no folded-LayerNorm epilogue");
+    AM_CHECK(!(a->act & AM_GEMM_LOCKSTEP), "am_gemm_bf16: the round-1 lockstep kernel has no folded-LayerNorm epilogue");
     AM_CHECK(((uintptr_t)a->ln_stats % 8 == 0) && ((uintptr_t)a->ln_colsum % 16 == 0) && (a->bias == nullptr || (uintptr_t)a->bias % 16 == 0) &&
              a->N % 4 == 0, "am_gemm_bf16: ln_stats / ln_colsum / bias misaligned");
   }
@@ -1257,16 +1258,15 @@ extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
     AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256pp_bf16_kernel<true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2PP_BYTES));
   });
-  // act bit 8 (0x100) forces the 128x128 register-staged kernel (tests compare the two tilings); bit 9 (0x200) the round-1
-  // lockstep main loop of the 256x256 tile (same-box A/B against the ping-pong loop)
+  // the switches of `act` (AM_GEMM_* in include/actionmesh_amd.h): tests compare the two tilings and the two GELU forms, A/B runs the loops
   am_gemm_args args = *a;
-  const bool force_small = (args.act & 0x100) != 0;
-  const bool legacy = (args.act & 0x200) != 0;
-  const bool force_big = (args.act & 0x400) != 0;       // tests: the 256x256 tile whatever the grid size
-  const int abl = args.act & 0xF800;     // bits 11 / 12: timing ablations; bits 13-15: per-XCD start skew (experiment)
-  const bool no_gelu_table = (args.act & 0x10000) != 0;   // tests / A/B: the arithmetic GELU epilogue in the 256x256 tile as well
-  args.act &= 0xff;
-  AM_CHECK(args.act == 0 || args.act == 1, "am_gemm_bf16: unknown activation %d", args.act);
+  const bool force_small = (args.act & AM_GEMM_FORCE_128) != 0;
+  const bool legacy = (args.act & AM_GEMM_LOCKSTEP) != 0;
+  const bool force_big = (args.act & AM_GEMM_FORCE_256) != 0;
+  const int abl = args.act & (AM_GEMM_ABLATE_MASK | AM_GEMM_SKEW_MASK);   // the kernels read these two fields themselves
+  const bool no_gelu_table = (args.act & AM_GEMM_NO_GELU_TABLE) != 0;
+  args.act &= AM_GEMM_ACT_MASK;
+  AM_CHECK(args.act == 0 || args.act == AM_GEMM_ACT_GELU, "am_gemm_bf16: unknown activation %d", args.act);
   // the 256x256 tiles need a grid that fills the 256 CUs; mid-sized problems (the context encoder's 16 x 257 rows)
   // get four times as many 128x128 workgroups instead
   const bool big = !force_small && args.N >= 8 && args.M >= 1 &&
@@ -1274,17 +1274,17 @@ extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
   // both 256x256 kernels (and gemm_tail_kernel behind them) fetch the bias four floats per lane as one f32x4_t: a 16-byte access.
   // The 128x128 kernel reads it float by float and takes any bias
   AM_CHECK(!big || (uintptr_t)args.bias % 16 == 0, "am_gemm_bf16: the 256x256 tile needs a 16-byte aligned bias");
-  args.act |= abl;          // kernels test `act & 0xff`; bits 11 / 12 are the store / residual timing ablations
+  args.act |= abl;
   // ln_part: full 256-row tiles of the ping-pong kernel write their slices from the store loop (N % 256 == 0); every other row -
   // edge tiles, the 128x128 kernel's rows, the lockstep kernel - gets them from am_row_part below, reading C back
   float* const ln_part = args.ln_part;
   int64_t part_done = 0;                                       // rows [0, part_done) are covered by the fused epilogue
   args.ln_part = nullptr;
-  if (big && (abl >> 13) == 0) {
+  if (big && (abl & AM_GEMM_SKEW_MASK) == 0) {
     // start skew per XCD in units of 1.5 us: the more rounds of workgroups a GEMM has, the better the 7-unit tail amortises
-    // (24-32 rounds: 6 us per XCD; 8 rounds: 1.5 us); act bits 13-15 = 7 turn it off (A/B runs)
+    // (24-32 rounds: 6 us per XCD; 8 rounds: 1.5 us); a skew field of 7 turns it off (A/B runs)
     const int rounds = (int)(((int64_t)ceil_div(args.M, B2) * ceil_div(args.N, B2)) / 256);
-    args.act |= gemm_skew_units(rounds) << 13;
+    args.act |= gemm_skew_units(rounds) << AM_GEMM_SKEW_SHIFT;
   }
   if (big) {
     // M = B*T*(N+1) is 256*k + a small remainder for every reference shape (the +1 time token per
@@ -1298,12 +1298,12 @@ extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
                          (hipStream_t)stream, args, tiles_m, tiles_n, 0);
     } else {
       am_gemm_args main_args = args;
-      if (ln_part && args.N % B2 == 0 && !(args.act & 0x1800)) {
+      if (ln_part && args.N % B2 == 0 && !(args.act & AM_GEMM_ABLATE_MASK)) {
         main_args.ln_part = ln_part;
         part_done = (int64_t)(args.M / B2) * B2;               // the kernel emits for tiles with m0 + 256 <= M only
         if (part_done > m_main) part_done = m_main;
       }
-      const uint16_t* gt = ((main_args.act & 0xff) == 1 && !no_gelu_table) ? gelu_table((hipStream_t)stream) : nullptr;
+      const uint16_t* gt = ((main_args.act & AM_GEMM_ACT_MASK) == AM_GEMM_ACT_GELU && !no_gelu_table) ? gelu_table((hipStream_t)stream) : nullptr;
       hipLaunchKernelGGL(gemm256pp_bf16_kernel<false>, dim3(tiles_m * tiles_n), dim3(512), gt ? SMEM2PP_GELU_BYTES : SMEM2PP_BYTES,
                          (hipStream_t)stream, main_args, tiles_m, tiles_n, 0, am_headpost_args{}, gt);
     }
@@ -1334,10 +1334,10 @@ extern "C" int am_gemm_headpost_bf16(const am_gemm_args* g, const am_headpost_ar
   const int rem = g->M % B2;
   const bool tail_split = rem != 0 && rem <= 128 && g->M > 8 * B2;
   AM_CHECK(g->ln_part == nullptr, "am_gemm_headpost_bf16: no row statistics of a head-split output");
-  const bool fuse = (g->act & 0xff) == 0 && !g->residual && (!g->bias || g->ln_stats) && !g->A2 && g->a_G == 0 && g->c_G == 0 && g->N % 256 == 0 && g->M % 16 == 0 &&
+  const bool fuse = (g->act & AM_GEMM_ACT_MASK) == 0 && !g->residual && (!g->bias || g->ln_stats) && !g->A2 && g->a_G == 0 && g->c_G == 0 && g->N % 256 == 0 && g->M % 16 == 0 &&
                     g->N >= 256 && g->M >= 1024 && (int64_t)ceil_div(g->M, B2) * ceil_div(g->N, B2) >= 192 &&
                     (!has_v || hp->seq_len % 16 == 0) && (!tail_split || rem <= hp->seq_len) && hp->rows % hp->seq_len == 0 &&
-                    !(g->act & 0x700) && getenv("ACTIONMESH_AMD_NO_FUSED_QKV") == nullptr;
+                    !(g->act & (AM_GEMM_FORCE_128 | AM_GEMM_LOCKSTEP | AM_GEMM_FORCE_256)) && getenv("ACTIONMESH_AMD_NO_FUSED_QKV") == nullptr;
   if (!fuse) {
     AM_TRY(am_gemm_bf16(g, stream));
     return am_head_post(hp, stream);
@@ -1353,12 +1353,12 @@ extern "C" int am_gemm_headpost_bf16(const am_gemm_args* g, const am_headpost_ar
     AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES));
   });
   am_gemm_args args = *g;
-  args.act = g->act & 0x1800;                 // the epilogue's timing ablations (tools/kernel_bench.py); 0 on the product path
+  args.act = g->act & AM_GEMM_ABLATE_MASK;   // the epilogue's timing ablations (tools/kernel_bench.py); 0 on the product path
   const int m_main = tail_split ? args.M - rem : args.M;
   const int tiles_m = ceil_div(m_main, B2), tiles_n = ceil_div(args.N, B2);
   {
     const int rounds = (int)(((int64_t)tiles_m * tiles_n) / 256);
-    args.act |= gemm_skew_units(rounds) << 13;
+    args.act |= gemm_skew_units(rounds) << AM_GEMM_SKEW_SHIFT;
   }
   am_gemm_args main_args = args;
   main_args.M = m_main;                      // the fused epilogue bounds its rows by M: the main grid owns [0, m_main)

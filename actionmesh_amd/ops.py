@@ -16,41 +16,53 @@ from . import _lib as L
 HEAD_DIM = 128
 
 
-def _stream(device=None) -> int:
-    """torch's current stream of `device` (default: the current device)."""
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _launch(t: torch.Tensor, fn, what: str, *args) -> None:
-    """Call a C-ABI kernel entry point on the device that owns `t`: the device is made current for the call (the
-    library launches on the current device) and the stream is torch's current stream OF THAT DEVICE, so a tensor on a
-    non-current device is neither launched on device 0's stream nor unordered with the work that produced it."""
-    with torch.cuda.device(t.device):
-        L.check(fn(*args, _stream(t.device)), what, getattr(fn, "_am_lib", None))
-
-
 H16 = (torch.bfloat16, torch.float16)       # the two 16-bit storage types: each has its own build of the library (_lib.lib(kind))
 
 
-def _fn(t_or_dtype, name: str):
-    """Entry point `name` of the library whose 16-bit type is that of the tensor (or dtype) given: bfloat16 -> libactionmesh_amd.so,
-    float16 -> libactionmesh_amd_f16.so (the same sources built with -DAM_F16)."""
-    dt = t_or_dtype.dtype if isinstance(t_or_dtype, torch.Tensor) else t_or_dtype
-    l = L.lib("f16" if dt == torch.float16 else "bf16")
-    f = getattr(l, name)
-    f._am_lib = l
-    return f
+def _entry(key, name: str):
+    """(library, its entry point `name`).  `key` picks the build: a tensor or dtype (float16 -> libactionmesh_amd_f16.so, the same sources
+    built with -DAM_F16; anything else -> libactionmesh_amd.so), a kind "bf16" / "f16" (the fp32 entry points are in both builds: the
+    caller says which one runs them), or None for the entry points that have no 16-bit code (the bfloat16 build)."""
+    if isinstance(key, torch.Tensor):
+        key = key.dtype
+    l = L.lib(key if isinstance(key, str) else "f16" if key == torch.float16 else "bf16")
+    return l, getattr(l, name)
+
+
+def _call(t: torch.Tensor, key, name: str, *args) -> None:
+    """Call the C-ABI kernel entry point `name` (of the build `key` picks, see _entry) on the device that owns `t`: the device is made
+    current for the call (the library launches on the current device) and the stream, the entry point's last argument, is torch's
+    current stream OF THAT DEVICE, so a tensor on a non-current device is neither launched on device 0's stream nor unordered with the
+    work that produced it.  A non-zero status raises with the am_last_error of the library that ran."""
+    l, fn = _entry(key, name)
+    with torch.cuda.device(t.device):
+        L.check(fn(*args, torch.cuda.current_stream(t.device).cuda_stream), name, l)
+
+
+def _workspace(device, query: str, *dims, at_least: int = 0) -> Tuple[Optional[torch.Tensor], int]:
+    """The scratch buffer of an entry point: (uint8 tensor, the byte count to declare to the library) for the size its `query`
+    function (am_*_workspace_bytes) returns for `dims`.  `at_least`: the smallest buffer allocated whatever the size - an entry point
+    that refuses a null workspace gets a real pointer for a size of 0; with 0, a size of 0 allocates nothing (tensor None)."""
+    need = _entry(None, query)[1](*dims)
+    size = max(need, at_least)
+    return (torch.empty((size,), dtype=torch.uint8, device=device) if size else None), need
 
 
 def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def _need(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
+def _on_device(t: torch.Tensor, dtype, name: str) -> None:
+    """The check every operand passes: a device tensor of `dtype` (one dtype or a tuple of them)."""
     if not t.is_cuda:
         raise RuntimeError(f"{name}: actionmesh_amd kernels need a device tensor (no CPU path)")
     if (t.dtype not in dtype) if isinstance(dtype, tuple) else (t.dtype != dtype):
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+
+
+def _need(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
+    """A contiguous device tensor of `dtype`."""
+    _on_device(t, dtype, name)
     if not t.is_contiguous():
         raise ValueError(f"{name}: must be contiguous")
     return t
@@ -58,11 +70,8 @@ def _need(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
 
 def _need_rows(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     """A 2-D device tensor of `dtype` with unit column stride: an operand whose leading dimension (t.stride(0)) goes to the library,
-    so rows may be padded or be a column slice of a wider buffer.  Contiguous 2-D tensors qualify.  `_rows_view` is the fp32 twin."""
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: actionmesh_amd kernels need a device tensor (no CPU path)")
-    if (t.dtype not in dtype) if isinstance(dtype, tuple) else (t.dtype != dtype):
-        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    so rows may be padded or be a column slice of a wider buffer (of a packed projection output, say).  Contiguous 2-D tensors qualify."""
+    _on_device(t, dtype, name)
     if t.dim() != 2 or t.stride(1) != 1:
         raise ValueError(f"{name}: expected a 2-D tensor with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
     return t
@@ -86,6 +95,15 @@ def perm16_index(n: int, device=None) -> torch.Tensor:
     """position -> key index map of the V^T layout (bit2 <-> bit3 inside each 16-group)."""
     k = torch.arange(n, device=device)
     return (k & ~0xC) | ((k & 4) << 1) | ((k & 8) >> 1)
+
+
+def _fold_args(g, bias: Optional[torch.Tensor], ln: Optional[Tuple[torch.Tensor, torch.Tensor]]) -> None:
+    """The bias and the folded LayerNorm (`ln` = (stats, colsum)) of a linear into its AmGemmArgs."""
+    if bias is not None:
+        g.bias = _need(bias, torch.float32, "bias").data_ptr()
+    if ln is not None:
+        g.ln_stats = _need(ln[0], torch.float32, "ln stats").data_ptr()
+        g.ln_colsum = _need(ln[1], torch.float32, "ln colsum").data_ptr()
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -120,26 +138,23 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     else:
         assert K1 == K
     g.W = w.data_ptr(); g.ldw = w.stride(0)
-    g.bias = _p(_need(bias, torch.float32, "bias")) if bias is not None else None
+    _fold_args(g, bias, ln)
     g.residual = _p(_need_rows(residual, a.dtype, "residual")) if residual is not None else None
     g.C = out.data_ptr(); g.ldc = out.stride(0)
     g.M, g.N, g.K = M, N, K
-    # 0x100: force the 128x128 register-staged kernel (the small-problem path; tests compare the two tilings);
-    # 0x200: the round-1 lockstep main loop of the 256x256 tile (same-box A/B); 0x400: the 256x256 tile at any grid size (tests)
-    # 0x10000: the arithmetic GELU epilogue in the 256x256 tile too (default: the bit-identical LDS table, am_gemm.hip GT_LO)
-    g.act = (1 if gelu else 0) | (0x100 if force_small else 0) | (0x200 if legacy else 0) | (0x400 if force_big else 0) | (ablate & 0xF800) \
-        | (0 if gelu_table else 0x10000)
+    # beside the activation, the diagnostic and test switches of `act` (AM_GEMM_* in include/actionmesh_amd.h): the kernel choice, the
+    # timing ablations and start skew of `ablate`, the arithmetic GELU epilogue
+    g.act = (L.GEMM_ACT_GELU if gelu else 0) | (L.GEMM_FORCE_128 if force_small else 0) | (L.GEMM_LOCKSTEP if legacy else 0) \
+        | (L.GEMM_FORCE_256 if force_big else 0) | (ablate & (L.GEMM_ABLATE_MASK | L.GEMM_SKEW_MASK)) | (0 if gelu_table else L.GEMM_NO_GELU_TABLE)
     g.a_G, g.a_gs, g.a_off = a_map
     g.c_G, g.c_gs, g.c_off = c_map
     if ln is not None:
-        g.ln_stats = _need(ln[0], torch.float32, "ln stats").data_ptr()
-        g.ln_colsum = _need(ln[1], torch.float32, "ln colsum").data_ptr()
         assert ln[0].numel() >= 2 * M and ln[1].numel() == N
     if ln_part is not None:
         _need(ln_part, torch.float32, "ln_part")
         assert ln_part.numel() >= 2 * M * ((N + 255) // 256)
         g.ln_part = ln_part.data_ptr()
-    _launch(a, _fn(a, "am_gemm_bf16"), "am_gemm_bf16", C.byref(g))
+    _call(a, a, "am_gemm_bf16", C.byref(g))
     return out
 
 
@@ -150,7 +165,7 @@ def row_stats(x: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = 
     rows = x.numel() // Cdim
     if out is None:
         out = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-    _launch(x, _fn(x, "am_row_stats_bf16"), "am_row_stats_bf16", x.data_ptr(), _need(out, torch.float32, "out").data_ptr(), rows, Cdim, eps)
+    _call(x, x, "am_row_stats_bf16", x.data_ptr(), _need(out, torch.float32, "out").data_ptr(), rows, Cdim, eps)
     return out
 
 
@@ -160,7 +175,7 @@ def row_stats_finalize(part: torch.Tensor, Cdim: int, eps: float = 1e-5, out: Op
     rows, nparts = part.shape[0], part.shape[1]
     if out is None:
         out = torch.empty((rows, 2), dtype=torch.float32, device=part.device)
-    _launch(part, _fn(kind, "am_row_stats_finalize"), "am_row_stats_finalize", part.data_ptr(), nparts, Cdim, out.data_ptr(), rows, eps)
+    _call(part, kind, "am_row_stats_finalize", part.data_ptr(), nparts, Cdim, out.data_ptr(), rows, eps)
     return out
 
 
@@ -178,7 +193,7 @@ def ln_fold_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bia
         wf, colsum, d = _need(out[0], w.dtype, "out wf"), _need(out[1], torch.float32, "out colsum"), _need(out[2], torch.float32, "out d")
         if tuple(wf.shape) != (N, K) or colsum.numel() != N or d.numel() != N:
             raise ValueError(f"ln_fold_weight: out shapes {tuple(wf.shape)} / {colsum.numel()} / {d.numel()} for N={N}, K={K}")
-    _launch(w, _fn(w, "am_ln_fold_weight"), "am_ln_fold_weight", w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+    _call(w, w, "am_ln_fold_weight", w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
             _p(_need(bias, torch.float32, "bias")) if bias is not None else None, wf.data_ptr(), colsum.data_ptr(), d.data_ptr(), N, K)
     return wf, colsum, d
 
@@ -192,10 +207,10 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e
     if out is None:
         out = torch.empty_like(x)
     if stats_out is not None:
-        _launch(x, _fn(x, "am_layernorm_stats_bf16"), "am_layernorm_stats_bf16", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
+        _call(x, x, "am_layernorm_stats_bf16", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
                 rows, Cdim, eps, _need(stats_out, torch.float32, "stats_out").data_ptr())
         return out
-    _launch(x, _fn(x, "am_layernorm_bf16"), "am_layernorm_bf16", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
+    _call(x, x, "am_layernorm_bf16", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
                                       rows, Cdim, eps)
     return out
 
@@ -215,83 +230,24 @@ def add_layernorm_f32(h32: torch.Tensor, y: Optional[torch.Tensor] = None, w: Op
         dtype = y.dtype
     if w is None:
         assert y is not None, "add_layernorm_f32: nothing to do"
-        _launch(h32, _fn(dtype, "am_add_layernorm_f32"), "am_add_layernorm_f32", h32.data_ptr(), y.data_ptr(), None, None, None, rows, Cdim, eps)
+        _call(h32, dtype, "am_add_layernorm_f32", h32.data_ptr(), y.data_ptr(), None, None, None, rows, Cdim, eps)
         return None
     assert dtype in H16, "add_layernorm_f32: the 16-bit output type must be given when there is no branch to take it from"
     _need(w, torch.float32, "w"); _need(b, torch.float32, "b")
     if out is None:
         out = torch.empty(h32.shape, dtype=dtype, device=h32.device)
-    _launch(h32, _fn(dtype, "am_add_layernorm_f32"), "am_add_layernorm_f32", h32.data_ptr(), _p(y), _need(out, dtype, "out").data_ptr(),
+    _call(h32, dtype, "am_add_layernorm_f32", h32.data_ptr(), _p(y), _need(out, dtype, "out").data_ptr(),
             w.data_ptr(), b.data_ptr(), rows, Cdim, eps)
     return out
 
 
-def head_post(x: torch.Tensor, heads: int, kinds: Sequence[int], seq_len: int, rows_per_frame: int,
-              w_q: Optional[torch.Tensor] = None, w_k: Optional[torch.Tensor] = None,
-              rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, eps: float = 1e-6,
-              out_q: Optional[torch.Tensor] = None, out_k: Optional[torch.Tensor] = None,
-              out_vt: Optional[torch.Tensor] = None):
-    """Split heads of x (rows, heads*len(kinds)*128), apply qk-RMSNorm (+RoPE), and write the
-    attention operand layouts.  Returns (Q, K, Vt) (None for absent kinds):
-      Q  (nseq, H, sq_pad, 128), K (nseq, H, sk_pad, 128), Vt (nseq, H, 128, sk_pad)."""
-    _need_rows(x, H16, "x")
+def _head_post_args(x: torch.Tensor, heads: int, kinds: Sequence[int], seq_len: int, rows_per_frame: int, w_q, w_k, rope, eps: float,
+                    out_q, out_k, out_vt):
+    """(AmHeadPostArgs of the head split of x (rows, heads * len(kinds) * 128), (Q, K, Vt)): the caller's outputs, or fresh ZERO-filled
+    ones padded to the attention kernels' tiles for the kinds present (the pad rows and columns are read by the kernels)."""
     rows = x.shape[0]
     nseq = rows // seq_len
     sq_pad, sk_pad = round_up(seq_len, 256), round_up(seq_len, 64)
-    dev = x.device
-    a = L.AmHeadPostArgs()
-    a.X = x.data_ptr(); a.ldx = x.stride(0)
-    a.rows = rows; a.seq_len = seq_len; a.rows_per_frame = rows_per_frame
-    a.heads = heads; a.nparts = len(kinds)
-    for i, k in enumerate(kinds):
-        a.kinds[i] = k
-    a.w_q = _p(w_q); a.w_k = _p(w_k); a.eps = eps
-    if rope is not None:
-        a.rope_cos = _need(rope[0], torch.float32, "rope_cos").data_ptr()
-        a.rope_sin = _need(rope[1], torch.float32, "rope_sin").data_ptr()
-    if 0 in kinds and out_q is None:
-        out_q = torch.zeros((nseq, heads, sq_pad, HEAD_DIM), dtype=x.dtype, device=dev)
-    if 1 in kinds and out_k is None:
-        out_k = torch.zeros((nseq, heads, sk_pad, HEAD_DIM), dtype=x.dtype, device=dev)
-    if 2 in kinds and out_vt is None:
-        out_vt = torch.zeros((nseq, heads, HEAD_DIM, sk_pad), dtype=x.dtype, device=dev)
-    a.out_q = _p(out_q); a.sq_pad = out_q.shape[2] if out_q is not None else 0
-    a.out_k = _p(out_k); a.out_vt = _p(out_vt)
-    a.sk_pad = out_k.shape[2] if out_k is not None else (out_vt.shape[3] if out_vt is not None else 0)
-    _launch(x, _fn(x, "am_head_post"), "am_head_post", C.byref(a))
-    return out_q, out_k, out_vt
-
-
-def gemm_head_post(a: torch.Tensor, w: torch.Tensor, heads: int, kinds: Sequence[int], seq_len: int, rows_per_frame: int,
-                   w_q: Optional[torch.Tensor] = None, w_k: Optional[torch.Tensor] = None,
-                   rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, eps: float = 1e-6,
-                   out_q: Optional[torch.Tensor] = None, out_k: Optional[torch.Tensor] = None,
-                   out_vt: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None,
-                   bias: Optional[torch.Tensor] = None, ln: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ablate: int = 0):
-    """am_gemm_headpost_bf16: (a @ w.T) -> head split / qk-RMSNorm / RoPE / attention layouts in ONE launch; the arguments of `gemm`
-    (no bias, no activation) and of `head_post`.  `x` (rows, N) is the linear's output buffer the un-fused pair would use (only the
-    tile grid's remainder rows are written to it).  Returns (Q, K, Vt) like head_post."""
-    _need(a, H16, "a"); _need(w, a.dtype, "w")
-    rows, K = a.shape
-    N = w.shape[0]
-    assert N == heads * len(kinds) * HEAD_DIM and w.shape[1] == K
-    if x is None:
-        x = torch.empty((rows, N), dtype=a.dtype, device=a.device)
-    _need_rows(x, a.dtype, "x")
-    nseq = rows // seq_len
-    sq_pad, sk_pad = round_up(seq_len, 256), round_up(seq_len, 64)
-    dev = a.device
-    g = L.AmGemmArgs()
-    g.A1 = a.data_ptr(); g.lda1 = a.stride(0); g.K1 = K
-    g.W = w.data_ptr(); g.ldw = w.stride(0)
-    g.C = x.data_ptr(); g.ldc = x.stride(0)
-    g.M, g.N, g.K = rows, N, K
-    g.act = ablate & 0x1800      # timing ablations of the fused epilogue (0x800: no Q / K rows, 0x1000: no V^T read-back); never on the product path
-    if bias is not None:
-        g.bias = _need(bias, torch.float32, "bias").data_ptr()
-    if ln is not None:       # LayerNorm folded into the projection (gemm's `ln`)
-        g.ln_stats = _need(ln[0], torch.float32, "ln stats").data_ptr()
-        g.ln_colsum = _need(ln[1], torch.float32, "ln colsum").data_ptr()
     h = L.AmHeadPostArgs()
     h.X = x.data_ptr(); h.ldx = x.stride(0)
     h.rows = rows; h.seq_len = seq_len; h.rows_per_frame = rows_per_frame
@@ -303,31 +259,66 @@ def gemm_head_post(a: torch.Tensor, w: torch.Tensor, heads: int, kinds: Sequence
         h.rope_cos = _need(rope[0], torch.float32, "rope_cos").data_ptr()
         h.rope_sin = _need(rope[1], torch.float32, "rope_sin").data_ptr()
     if 0 in kinds and out_q is None:
-        out_q = torch.zeros((nseq, heads, sq_pad, HEAD_DIM), dtype=a.dtype, device=dev)
+        out_q = torch.zeros((nseq, heads, sq_pad, HEAD_DIM), dtype=x.dtype, device=x.device)
     if 1 in kinds and out_k is None:
-        out_k = torch.zeros((nseq, heads, sk_pad, HEAD_DIM), dtype=a.dtype, device=dev)
+        out_k = torch.zeros((nseq, heads, sk_pad, HEAD_DIM), dtype=x.dtype, device=x.device)
     if 2 in kinds and out_vt is None:
-        out_vt = torch.zeros((nseq, heads, HEAD_DIM, sk_pad), dtype=a.dtype, device=dev)
+        out_vt = torch.zeros((nseq, heads, HEAD_DIM, sk_pad), dtype=x.dtype, device=x.device)
     h.out_q = _p(out_q); h.sq_pad = out_q.shape[2] if out_q is not None else 0
     h.out_k = _p(out_k); h.out_vt = _p(out_vt)
     h.sk_pad = out_k.shape[2] if out_k is not None else (out_vt.shape[3] if out_vt is not None else 0)
-    _launch(a, _fn(a, "am_gemm_headpost_bf16"), "am_gemm_headpost_bf16", C.byref(g), C.byref(h))
-    return out_q, out_k, out_vt
+    return h, (out_q, out_k, out_vt)
+
+
+def head_post(x: torch.Tensor, heads: int, kinds: Sequence[int], seq_len: int, rows_per_frame: int,
+              w_q: Optional[torch.Tensor] = None, w_k: Optional[torch.Tensor] = None,
+              rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, eps: float = 1e-6,
+              out_q: Optional[torch.Tensor] = None, out_k: Optional[torch.Tensor] = None,
+              out_vt: Optional[torch.Tensor] = None):
+    """Split heads of x (rows, heads*len(kinds)*128), apply qk-RMSNorm (+RoPE), and write the
+    attention operand layouts.  Returns (Q, K, Vt) (None for absent kinds):
+      Q  (nseq, H, sq_pad, 128), K (nseq, H, sk_pad, 128), Vt (nseq, H, 128, sk_pad)."""
+    _need_rows(x, H16, "x")
+    h, outs = _head_post_args(x, heads, kinds, seq_len, rows_per_frame, w_q, w_k, rope, eps, out_q, out_k, out_vt)
+    _call(x, x, "am_head_post", C.byref(h))
+    return outs
+
+
+def gemm_head_post(a: torch.Tensor, w: torch.Tensor, heads: int, kinds: Sequence[int], seq_len: int, rows_per_frame: int,
+                   w_q: Optional[torch.Tensor] = None, w_k: Optional[torch.Tensor] = None,
+                   rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, eps: float = 1e-6,
+                   out_q: Optional[torch.Tensor] = None, out_k: Optional[torch.Tensor] = None,
+                   out_vt: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None,
+                   bias: Optional[torch.Tensor] = None, ln: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ablate: int = 0):
+    """am_gemm_headpost_bf16: (a @ w.T) -> head split / qk-RMSNorm / RoPE / attention layouts in ONE launch; the arguments of `gemm`
+    (no activation; `ln`: the LayerNorm folded into the projection, as gemm's) and of `head_post`.  `x` (rows, N) is the linear's output
+    buffer the un-fused pair would use (only the tile grid's remainder rows are written to it).  Returns (Q, K, Vt) like head_post."""
+    _need(a, H16, "a"); _need(w, a.dtype, "w")
+    rows, K = a.shape
+    N = w.shape[0]
+    assert N == heads * len(kinds) * HEAD_DIM and w.shape[1] == K
+    if x is None:
+        x = torch.empty((rows, N), dtype=a.dtype, device=a.device)
+    _need_rows(x, a.dtype, "x")
+    g = L.AmGemmArgs()
+    g.A1 = a.data_ptr(); g.lda1 = a.stride(0); g.K1 = K
+    g.W = w.data_ptr(); g.ldw = w.stride(0)
+    g.C = x.data_ptr(); g.ldc = x.stride(0)
+    g.M, g.N, g.K = rows, N, K
+    g.act = ablate & L.GEMM_ABLATE_MASK      # timing ablations of the fused epilogue (no Q / K rows, no V^T read-back); never on the product path
+    _fold_args(g, bias, ln)
+    h, outs = _head_post_args(x, heads, kinds, seq_len, rows_per_frame, w_q, w_k, rope, eps, out_q, out_k, out_vt)
+    _call(a, a, "am_gemm_headpost_bf16", C.byref(g), C.byref(h))
+    return outs
 
 
 STATE_LD = 132   # floats per row of a two-pass attention state: O[128], m, l, pad
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: int,
-              out: Optional[torch.Tensor] = None, nchunks: int = 1, defer_log2: int = 8,
-              scale: Optional[float] = None, rows: int = 0, state_mode: int = 0,
-              state: Optional[torch.Tensor] = None, chunk_first: int = 0, chunk_total: int = 0) -> torch.Tensor:
-    """softmax(q k^T * scale) v on pre-laid-out operands.
-      q (nseq, H, sq_pad, 128); k ([chunks,] nseq, H, sk_pad, 128); vt ([chunks,] nseq, H, 128, sk_pad)
-      -> out (nseq * sq, H * 128)
-    Two-pass form (am_attn_args in include/actionmesh_amd.h): `rows` selects the query blocks (1 = the full blocks,
-    2 = the rest), `state_mode` 1 saves / 2 resumes the (O, m, l) of the full blocks in `state`
-    (nseq * H, sq_pad, STATE_LD) fp32, and the chunks walked are (chunk_first + i) % chunk_total."""
+def _attn_args(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: int, out: Optional[torch.Tensor], nchunks: int,
+               scale: Optional[float], defer_log2: int, rows: int, state_mode: int, state: Optional[torch.Tensor], chunk_first: int,
+               chunk_total: int):
+    """(AmAttnArgs, out) of an attention over the operand layouts of `attention`; `defer_log2` is the field as each kernel family reads it."""
     _need(q, H16, "q"); _need(k, q.dtype, "k"); _need(vt, q.dtype, "vt")
     nseq, H, sq_pad, _ = q.shape
     sk_pad = k.shape[-2]
@@ -347,7 +338,21 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: i
         _need(state, torch.float32, "state")
         assert state.numel() >= nseq * H * sq_pad * STATE_LD
         a.state = state.data_ptr()
-    _launch(q, _fn(q, "am_attention_bf16"), "am_attention_bf16", C.byref(a))
+    return a, out
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: int,
+              out: Optional[torch.Tensor] = None, nchunks: int = 1, defer_log2: int = 8,
+              scale: Optional[float] = None, rows: int = 0, state_mode: int = 0,
+              state: Optional[torch.Tensor] = None, chunk_first: int = 0, chunk_total: int = 0) -> torch.Tensor:
+    """softmax(q k^T * scale) v on pre-laid-out operands.
+      q (nseq, H, sq_pad, 128); k ([chunks,] nseq, H, sk_pad, 128); vt ([chunks,] nseq, H, 128, sk_pad)
+      -> out (nseq * sq, H * 128)
+    Two-pass form (am_attn_args in include/actionmesh_amd.h): `rows` selects the query blocks (1 = the full blocks,
+    2 = the rest), `state_mode` 1 saves / 2 resumes the (O, m, l) of the full blocks in `state`
+    (nseq * H, sq_pad, STATE_LD) fp32, and the chunks walked are (chunk_first + i) % chunk_total."""
+    a, out = _attn_args(q, k, vt, sq, sk, out, nchunks, scale, defer_log2, rows, state_mode, state, chunk_first, chunk_total)
+    _call(q, q, "am_attention_bf16", C.byref(a))
     return out
 
 
@@ -361,25 +366,9 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, s
     earlier call is passed), then QK^T / P.V on the MX-scaled fp8 MFMA.  Returns out (nseq * sq, H * 128) bf16.
     rows / state_mode / state / chunk_first / chunk_total: the two-pass forms, as in `attention`.  `quantize_out`: caller-owned uint8
     (q8, k8, vt8) of the shapes of q / k / vt that receive the quantisation (default: fresh tensors)."""
-    _need(q, H16, "q"); _need(k, q.dtype, "k"); _need(vt, q.dtype, "vt")
-    nseq, H, sq_pad, _ = q.shape
-    sk_pad = k.shape[-2]
-    if out is None:
-        out = torch.empty((nseq * sq, H * HEAD_DIM), dtype=q.dtype, device=q.device)
-    _need_rows(out, q.dtype, "out")
-    a = L.AmAttnArgs()
-    a.Q, a.K, a.Vt, a.O = q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
-    a.nseq, a.heads, a.sq, a.sq_pad, a.sk, a.sk_pad = nseq, H, sq, sq_pad, sk, sk_pad
-    a.nchunks = nchunks
-    a.chunk_stride = nseq * H * sk_pad * HEAD_DIM
-    a.ldo = out.stride(0)
-    a.scale = scale if scale is not None else HEAD_DIM ** -0.5
-    a.defer_log2 = 5000 + ablate if ablate else 0        # timing ablations of the kernel (tools/kernel_bench.py)
-    a.rows, a.state_mode, a.chunk_first, a.chunk_total = rows, state_mode, chunk_first, chunk_total
-    if state is not None:
-        _need(state, torch.float32, "state")
-        assert state.numel() >= nseq * H * sq_pad * STATE_LD
-        a.state = state.data_ptr()
+    # defer_log2 carries the timing ablations of the fp8 kernel (tools/kernel_bench.py)
+    a, out = _attn_args(q, k, vt, sq, sk, out, nchunks, scale, 5000 + ablate if ablate else 0, rows, state_mode, state, chunk_first,
+                        chunk_total)
     if quantized is None:
         if quantize_out is not None:
             q8, k8, vt8 = (_need(t, torch.uint8, "quantize_out") for t in quantize_out)
@@ -389,11 +378,10 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, s
             q8 = torch.empty(q.shape, dtype=torch.uint8, device=q.device)
             k8 = torch.empty(k.shape, dtype=torch.uint8, device=q.device)
             vt8 = torch.empty(vt.shape, dtype=torch.uint8, device=q.device)
-        _launch(q, _fn(q, "am_attention_quantize_fp8"), "am_attention_quantize_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(),
-                vt8.data_ptr())
+        _call(q, q, "am_attention_quantize_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(), vt8.data_ptr())
     else:
         q8, k8, vt8 = quantized
-    _launch(q, _fn(q, "am_attention_fp8"), "am_attention_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(), vt8.data_ptr())
+    _call(q, q, "am_attention_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(), vt8.data_ptr())
     attention_fp8.last_quantized = (q8, k8, vt8)
     return out
 
@@ -411,7 +399,7 @@ def f32_to_bf16(x: torch.Tensor, dtype=torch.bfloat16, out: Optional[torch.Tenso
     y = torch.empty(x.shape, dtype=dtype, device=x.device) if out is None else _need(out, dtype, "out")
     if y.numel() != x.numel():
         raise ValueError(f"f32_to_bf16: out has {y.numel()} elements for {x.numel()} inputs")
-    _launch(x, _fn(dtype, "am_f32_to_bf16"), "am_f32_to_bf16", x.data_ptr(), y.data_ptr(), x.numel())
+    _call(x, dtype, "am_f32_to_bf16", x.data_ptr(), y.data_ptr(), x.numel())
     return y
 
 
@@ -421,36 +409,49 @@ def timestep_sinusoid(t: torch.Tensor, width: int, dtype=torch.bfloat16, out: Op
     y = torch.empty((t.numel(), width), dtype=dtype, device=t.device) if out is None else _need(out, dtype, "out")
     if tuple(y.shape) != (t.numel(), width):
         raise ValueError(f"timestep_sinusoid: out {tuple(y.shape)} != ({t.numel()}, {width})")
-    _launch(t, _fn(dtype, "am_timestep_sinusoid"), "am_timestep_sinusoid", t.data_ptr(), y.data_ptr(), t.numel(), width)
+    _call(t, dtype, "am_timestep_sinusoid", t.data_ptr(), y.data_ptr(), t.numel(), width)
     return y
+
+
+def _point_embed(what: str, key, out_dtype, query, in_channels, extra_channels, num_freqs, include_pi, ld_out, out) -> torch.Tensor:
+    """point_embed / point_embed_f32 behind their checks: entry point am_<what> of the build `key` picks, output of `out_dtype`."""
+    rows = query.shape[0]
+    out = _out_rows(out, rows, ld_out, out_dtype, query.device, what)
+    _call(query, key, "am_" + what, query.data_ptr(), query.stride(0), rows, in_channels, extra_channels, num_freqs, int(include_pi),
+          out.data_ptr(), ld_out)
+    return out
+
+
+def _patchify(what: str, key, out_dtype, pixels, patch, ld_out, out) -> torch.Tensor:
+    T, Cin, H, W = pixels.shape
+    out = _out_rows(out, T * (H // patch) * (W // patch), ld_out, out_dtype, pixels.device, what)
+    _call(pixels, key, "am_" + what, pixels.data_ptr(), T, Cin, H, W, patch, out.data_ptr(), ld_out)
+    return out
+
+
+def _displacement(what: str, key, logits, out_dim, out) -> torch.Tensor:
+    _call(logits, key, "am_" + what, logits.data_ptr(), logits.stride(0), logits.shape[0], out_dim, out.data_ptr())
+    return out
 
 
 def point_embed(query: torch.Tensor, in_channels: int, extra_channels: int, num_freqs: int, include_pi: bool,
                 ld_out: int = 64, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """query (rows, >= in+extra) fp32, rows may be strided -> 16-bit (rows, ld_out): FrequencyPositionalEmbedding + extras, zero padded."""
-    _rows_view(query, "query")
-    rows = query.shape[0]
-    out = _out_rows(out, rows, ld_out, dtype, query.device, "point_embed")
-    _launch(query, _fn(dtype, "am_point_embed"), "am_point_embed", query.data_ptr(), query.stride(0), rows, in_channels, extra_channels, num_freqs,
-                                   int(include_pi), out.data_ptr(), ld_out)
-    return out
+    _need_rows(query, torch.float32, "query")
+    return _point_embed("point_embed", dtype, dtype, query, in_channels, extra_channels, num_freqs, include_pi, ld_out, out)
 
 
 def patchify(pixels: torch.Tensor, patch: int, ld_out: int, dtype=torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pixels (T, C, H, W) fp32 -> 16-bit (T * (H // patch) * (W // patch), ld_out): rows of the kernel = stride patch
     convolution in flattened-Conv2d-weight column order, zero padded."""
     _need(pixels, torch.float32, "pixels")
-    T, Cin, H, W = pixels.shape
-    out = _out_rows(out, T * (H // patch) * (W // patch), ld_out, dtype, pixels.device, "patchify")
-    _launch(pixels, _fn(dtype, "am_patchify"), "am_patchify", pixels.data_ptr(), T, Cin, H, W, patch, out.data_ptr(), ld_out)
-    return out
+    return _patchify("patchify", dtype, dtype, pixels, patch, ld_out, out)
 
 
 def displacement(logits: torch.Tensor, out_dim: int, out: torch.Tensor) -> torch.Tensor:
     """out (rows, out_dim) fp32 = 2 sigmoid(-logits[:, :out_dim]) - 1."""
     _need_rows(logits, H16, "logits"); _need(out, torch.float32, "out")
-    _launch(logits, _fn(logits, "am_displacement"), "am_displacement", logits.data_ptr(), logits.stride(0), logits.shape[0], out_dim, out.data_ptr())
-    return out
+    return _displacement("displacement", logits, logits, out_dim, out)
 
 
 def flow_step(v: torch.Tensor, latents: torch.Tensor, scales: Sequence[float], dt: float,
@@ -462,7 +463,7 @@ def flow_step(v: torch.Tensor, latents: torch.Tensor, scales: Sequence[float], d
     un = None
     if unobserved is not None:
         un = (C.c_uint8 * T)(*[1 if u else 0 for u in unobserved])
-    _launch(v, _fn(v, "am_flow_step"), "am_flow_step", v.data_ptr(), latents.data_ptr(), nb, sc, float(dt), 1 if is_additive else 0,
+    _call(v, v, "am_flow_step", v.data_ptr(), latents.data_ptr(), nb, sc, float(dt), 1 if is_additive else 0,
                                  un, T, N, D)
 
 
@@ -488,15 +489,13 @@ def nearest_neighbors(points: torch.Tensor, queries: torch.Tensor, precise: bool
     out_shape = (batch, Q) if (points.dim() == 3 or queries.dim() == 3) else (Q,)
     idx = torch.empty(out_shape, dtype=torch.int32, device=queries.device)
     d2 = torch.empty(out_shape, dtype=torch.float64 if precise else torch.float32, device=queries.device)
-    lib = L.lib()
-    need = lib.am_nn_workspace_bytes(P, Q, batch, 1 if precise else 0)
-    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=queries.device)
+    ws, need = _workspace(queries.device, "am_nn_workspace_bytes", P, Q, batch, 1 if precise else 0, at_least=1)
     a = L.AmNnArgs()
     a.points, a.n_points, a.points_bstride = points.data_ptr(), P, (P * 3 if points.dim() == 3 else 0)
     a.queries, a.n_queries, a.queries_bstride = queries.data_ptr(), Q, (Q * 3 if queries.dim() == 3 else 0)
     a.batch, a.precise = batch, 1 if precise else 0
     a.out_index, a.out_d2 = idx.data_ptr(), d2.data_ptr()
-    _launch(queries, lib.am_nn_search, "am_nn_search", C.byref(a), ws.data_ptr(), need)
+    _call(queries, None, "am_nn_search", C.byref(a), ws.data_ptr(), need)
     if check and bool((idx < 0).any()):
         # the kernel's strict `<` never fires for a query whose distances are all NaN: index -1 would wrap in a later gather
         raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
@@ -565,16 +564,14 @@ def farthest_point_sample(points: torch.Tensor, n_samples: int, start_idx=None, 
         raise ValueError("farthest_point_sample: non-finite coordinates in the points")
     idx = torch.empty((B, K), dtype=torch.int32, device=dev)
     dist = torch.empty((B, K), dtype=torch.float32, device=dev) if return_dist else None
-    lib = L.lib()
-    need = lib.am_fps_workspace_bytes(N, B, dd)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+    ws, need = _workspace(dev, "am_fps_workspace_bytes", N, B, dd)
     a = L.AmFpsArgs()
     a.points, a.dtype, a.batch, a.n_points = p3.data_ptr(), _FPS_DTYPES[points.dtype], B, N
     a.dims, a.dist_dims, a.batch_stride, a.point_stride, a.n_samples = D, dd, sb, sp, K
     a.start_idx = start.data_ptr() if start is not None else None
     a.out_index, a.out_dist = idx.data_ptr(), (dist.data_ptr() if return_dist else None)
-    a.workspace, a.workspace_bytes, a.threads = (ws.data_ptr() if need else None), need, int(threads)
-    _launch(p3, lib.am_fps, "am_fps", C.byref(a))
+    a.workspace, a.workspace_bytes, a.threads = _p(ws), need, int(threads)
+    _call(p3, None, "am_fps", C.byref(a))
     if points.dim() == 2:
         idx, dist = idx[0], (dist[0] if return_dist else None)
     return (idx, dist) if return_dist else idx
@@ -590,8 +587,7 @@ def image_alpha_stats(rgba: torch.Tensor) -> torch.Tensor:
     stats = torch.empty((rgba.shape[0], 8), dtype=torch.int32, device=rgba.device)
     a = L.AmImageAlphaStatsArgs()
     a.rgba, a.n_frames, a.height, a.width, a.out_stats = rgba.data_ptr(), rgba.shape[0], rgba.shape[1], rgba.shape[2], stats.data_ptr()
-    lib = L.lib()
-    _launch(rgba, lib.am_image_alpha_stats, "am_image_alpha_stats", C.byref(a))
+    _call(rgba, None, "am_image_alpha_stats", C.byref(a))
     return stats
 
 
@@ -639,11 +635,9 @@ def image_resample(src: torch.Tensor, channels: int, frames, frames_dev: torch.T
     if want_u8:
         u8 = torch.empty((T, out_h, out_w, 3), dtype=torch.uint8, device=src.device)
         a.out_u8 = u8.data_ptr()
-    lib = L.lib()
-    need = lib.am_image_resample_workspace_bytes(T, max(f.n_rows for f in frames), int(out_w))
-    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=src.device)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), need
-    _launch(src, lib.am_image_resample, "am_image_resample", C.byref(a))
+    ws, need = _workspace(src.device, "am_image_resample_workspace_bytes", T, max(f.n_rows for f in frames), int(out_w), at_least=16)
+    a.workspace, a.workspace_bytes = _p(ws), need
+    _call(src, None, "am_image_resample", C.byref(a))
     return pix, u8
 
 
@@ -655,8 +649,7 @@ def image_materialize(src: torch.Tensor, channels: int, frames, frames_dev: torc
     _image_src(a, src, channels, composite, fill, frames, frames_dev)
     out = torch.empty((int(out_bytes),), dtype=torch.uint8, device=src.device)
     a.out, a.out_bytes = out.data_ptr(), out.numel()
-    lib = L.lib()
-    _launch(src, lib.am_image_materialize, "am_image_materialize", C.byref(a))
+    _call(src, None, "am_image_materialize", C.byref(a))
     return out
 
 
@@ -688,14 +681,12 @@ def mask_refine(mask: torch.Tensor, min_size: int = 200, threshold: int = -1, re
     out = torch.empty_like(mask)
     labels = torch.empty((T, H, W), dtype=torch.int32, device=dev) if return_labels else None
     stats = torch.empty((T, 4), dtype=torch.int32, device=dev) if return_stats else None
-    lib = L.lib()
-    need = lib.am_mask_refine_workspace_bytes(T, H, W)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    ws, need = _workspace(dev, "am_mask_refine_workspace_bytes", T, H, W)
     a = L.AmMaskRefineArgs()
     a.mask, a.n_frames, a.height, a.width, a.min_size, a.threshold = mask.data_ptr(), T, H, W, min_size, threshold
     a.out_mask, a.out_labels, a.out_stats = out.data_ptr(), _p(labels), _p(stats)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), need
-    _launch(mask, lib.am_mask_refine, "am_mask_refine", C.byref(a))
+    a.workspace, a.workspace_bytes = _p(ws), need
+    _call(mask, None, "am_mask_refine", C.byref(a))
     return out, labels, stats
 
 
@@ -722,45 +713,24 @@ def graph_components(n_nodes: int, edges: torch.Tensor, return_size: bool = Fals
     E = edges.shape[0]
     buf = torch.empty((n + 1,), dtype=torch.int32, device=dev)       # labels, then the flag
     size = torch.empty((n,), dtype=torch.int32, device=dev) if return_size else None
-    lib = L.lib()
-    need = lib.am_graph_components_workspace_bytes(n, E)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    ws, need = _workspace(dev, "am_graph_components_workspace_bytes", n, E)
     a = L.AmGraphArgs()
     a.n_nodes, a.n_edges, a.edges = n, E, (edges.data_ptr() if E else None)
     a.out_label, a.out_size, a.out_flag = buf.data_ptr(), _p(size), buf.data_ptr() + 4 * n
-    a.workspace, a.workspace_bytes = ws.data_ptr(), need
-    _launch(edges, lib.am_graph_components, "am_graph_components", C.byref(a))
+    a.workspace, a.workspace_bytes = _p(ws), need
+    _call(edges, None, "am_graph_components", C.byref(a))
     if bool(buf[n]):
         raise ValueError(f"graph_components: an edge names a node outside [0, {n})")
     label = buf[:n]
     return (label, size) if return_size else label
 
 
-# ---- exact-fp32 path (csrc/am_f32.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----------------------
-def _fk(kind: str, name: str):
-    """Entry point `name` of the library build `kind` ("bf16" / "f16"): the fp32 entry points are in both."""
-    l = L.lib(kind)
-    f = getattr(l, name)
-    f._am_lib = l
-    return f
-
-
-def _rows_view(t: torch.Tensor, name: str) -> torch.Tensor:
-    """A 2-D fp32 device tensor with unit column stride (a column slice of a packed projection output qualifies)."""
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: actionmesh_amd kernels need a device tensor (no CPU path)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected torch.float32, got {t.dtype}")
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise ValueError(f"{name}: expected a 2-D tensor with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
-    return t
-
-
+# ---- exact-fp32 path (csrc/am_f32.hip, am_elementwise.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              gelu: bool = False, out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:
     """am_gemm_f32: out = act(a @ w.T + bias) + residual, all fp32, fp32 MFMA.  a (M, K), w (N, K) (nn.Linear layout), bias (N,),
     residual / out (M, N); rows may be strided (unit column stride), `residual` may be `out` (in-place residual add).  K % 4 == 0."""
-    _rows_view(a, "a"); _rows_view(w, "w")
+    _need_rows(a, torch.float32, "a"); _need_rows(w, torch.float32, "w")
     M, K = a.shape
     N = w.shape[0]
     if w.shape[1] != K:
@@ -769,7 +739,7 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
         raise ValueError(f"gemm_f32: K={K} must be a multiple of 4 (pad the operands)")
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    _rows_view(out, "out")
+    _need_rows(out, torch.float32, "out")
     if tuple(out.shape) != (M, N):
         raise ValueError(f"gemm_f32: out {tuple(out.shape)} != ({M}, {N})")
     if bias is not None:
@@ -777,10 +747,10 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
         if bias.numel() != N:
             raise ValueError(f"gemm_f32: bias has {bias.numel()} elements, N={N}")
     if residual is not None:
-        _rows_view(residual, "residual")
+        _need_rows(residual, torch.float32, "residual")
         if tuple(residual.shape) != (M, N):
             raise ValueError(f"gemm_f32: residual {tuple(residual.shape)} != ({M}, {N})")
-    _launch(a, _fk(kind, "am_gemm_f32"), "am_gemm_f32", a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _p(bias),
+    _call(a, kind, "am_gemm_f32", a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _p(bias),
             _p(residual), residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), M, N, K, 1 if gelu else 0)
     return out
 
@@ -793,7 +763,7 @@ def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     (nseq * sk, ...) are 2-D fp32 with unit column stride; head h of row i is columns [x_off + h * x_hs, + head_dim) (x_hs defaults to
     head_dim).  The cross-attention's concatenated [to_k | to_v] output `kv` is k = v = kv, k_hs = v_hs = 2 hd, v_off = hd.
     Returns out (nseq * sq, heads * head_dim) fp32."""
-    _rows_view(q, "q"); _rows_view(k, "k"); _rows_view(v, "v")
+    _need_rows(q, torch.float32, "q"); _need_rows(k, torch.float32, "k"); _need_rows(v, torch.float32, "v")
     if head_dim not in (64, 128):
         raise ValueError(f"attention_f32: head_dim {head_dim} (64 or 128)")
     if sq < 1 or sk < 1 or heads < 1:
@@ -807,7 +777,7 @@ def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     nseq = q.shape[0] // sq
     if out is None:
         out = torch.empty((nseq * sq, heads * head_dim), dtype=torch.float32, device=q.device)
-    _rows_view(out, "out")
+    _need_rows(out, torch.float32, "out")
     if out.shape[0] != nseq * sq or out.shape[1] < heads * head_dim:
         raise ValueError(f"attention_f32: out {tuple(out.shape)} too small for ({nseq * sq}, {heads * head_dim})")
     a = L.AmAttnF32Args()
@@ -817,7 +787,7 @@ def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     a.O, a.ldo = out.data_ptr(), out.stride(0)
     a.nseq, a.heads, a.sq, a.sk, a.head_dim = nseq, heads, sq, sk, head_dim
     a.scale = scale if scale is not None else head_dim ** -0.5
-    _launch(q, _fk(kind, "am_attention_f32"), "am_attention_f32", C.byref(a))
+    _call(q, kind, "am_attention_f32", C.byref(a))
     return out
 
 
@@ -833,7 +803,7 @@ def layernorm_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float 
     _need(out, torch.float32, "out")
     if out.data_ptr() == x.data_ptr():
         raise ValueError("layernorm_f32: out may not alias x")
-    _launch(x, _fk(kind, "am_layernorm_f32"), "am_layernorm_f32", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
+    _call(x, kind, "am_layernorm_f32", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
             x.numel() // Cdim, Cdim, eps)
     return out
 
@@ -841,14 +811,10 @@ def layernorm_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float 
 def point_embed_f32(query: torch.Tensor, in_channels: int, extra_channels: int, num_freqs: int, include_pi: bool,
                     ld_out: int = 64, kind: str = "bf16", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`point_embed` without the rounding: query (rows, >= in+extra) fp32, rows may be strided -> fp32 (rows, ld_out)."""
-    _rows_view(query, "query")
+    _need_rows(query, torch.float32, "query")
     if query.dim() != 2 or query.shape[1] < in_channels + extra_channels:
         raise ValueError(f"point_embed_f32: query {tuple(query.shape)} has fewer than {in_channels + extra_channels} channels")
-    rows = query.shape[0]
-    out = _out_rows(out, rows, ld_out, torch.float32, query.device, "point_embed_f32")
-    _launch(query, _fk(kind, "am_point_embed_f32"), "am_point_embed_f32", query.data_ptr(), query.stride(0), rows, in_channels,
-            extra_channels, num_freqs, int(include_pi), out.data_ptr(), ld_out)
-    return out
+    return _point_embed("point_embed_f32", kind, torch.float32, query, in_channels, extra_channels, num_freqs, include_pi, ld_out, out)
 
 
 def patchify_f32(pixels: torch.Tensor, patch: int, ld_out: int, kind: str = "bf16", out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -856,20 +822,15 @@ def patchify_f32(pixels: torch.Tensor, patch: int, ld_out: int, kind: str = "bf1
     _need(pixels, torch.float32, "pixels")
     if pixels.dim() != 4:
         raise ValueError(f"patchify_f32: expected (T, C, H, W), got {tuple(pixels.shape)}")
-    T, Cin, H, W = pixels.shape
-    out = _out_rows(out, T * (H // patch) * (W // patch), ld_out, torch.float32, pixels.device, "patchify_f32")
-    _launch(pixels, _fk(kind, "am_patchify_f32"), "am_patchify_f32", pixels.data_ptr(), T, Cin, H, W, patch, out.data_ptr(), ld_out)
-    return out
+    return _patchify("patchify_f32", kind, torch.float32, pixels, patch, ld_out, out)
 
 
 def displacement_f32(logits: torch.Tensor, out_dim: int, out: torch.Tensor, kind: str = "bf16") -> torch.Tensor:
     """out (rows, out_dim) fp32 = 2 sigmoid(-logits[:, :out_dim]) - 1 on fp32 logits (rows may be strided)."""
-    _rows_view(logits, "logits"); _need(out, torch.float32, "out")
+    _need_rows(logits, torch.float32, "logits"); _need(out, torch.float32, "out")
     if logits.shape[1] < out_dim or out.shape != (logits.shape[0], out_dim):
         raise ValueError(f"displacement_f32: logits {tuple(logits.shape)} / out {tuple(out.shape)} for out_dim={out_dim}")
-    _launch(logits, _fk(kind, "am_displacement_f32"), "am_displacement_f32", logits.data_ptr(), logits.stride(0), logits.shape[0], out_dim,
-            out.data_ptr())
-    return out
+    return _displacement("displacement_f32", kind, logits, out_dim, out)
 
 
 def render_normals(vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequence[dict], image_size: int,
@@ -914,8 +875,6 @@ def render_normals(vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequenc
     a.out_rgba = out["rgba"].data_ptr()
     a.out_mask, a.out_normal = _p(out.get("mask")), _p(out.get("normal"))
     a.out_face, a.out_bary = _p(out.get("pix_to_face")), _p(out.get("bary"))
-    lib = L.lib()
-    need = lib.am_render_workspace_bytes(T, V, F, Cn, S)
-    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
-    _launch(vertices, lib.am_render_normals, "am_render_normals", C.byref(a), ws.data_ptr(), need)
+    ws, need = _workspace(dev, "am_render_workspace_bytes", T, V, F, Cn, S, at_least=1)
+    _call(vertices, None, "am_render_normals", C.byref(a), ws.data_ptr(), need)
     return out

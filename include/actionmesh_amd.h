@@ -192,7 +192,21 @@ typedef struct {
   const uint16_t* residual;
   uint16_t* C; int32_t ldc;
   int32_t M, N, K;
-  int32_t act;                 /* 0 none, 1 exact-erf GELU */
+  /* act: the activation code in the low byte (0 none, 1 exact-erf GELU).  The bits above it are DIAGNOSTIC AND TEST SWITCHES, not
+   * product options: a product caller passes 0 or AM_GEMM_ACT_GELU.  Every choice they make gives the same result (the tests hold
+   * the tilings and the two GELU forms bit-identical); the ablations skip work and give a wrong one, for timing only. */
+  int32_t act;
+#define AM_GEMM_ACT_MASK      0xff     /* the activation code */
+#define AM_GEMM_ACT_GELU      1
+#define AM_GEMM_FORCE_128     0x100    /* the 128x128 register-staged kernel at any size (wins over FORCE_256) */
+#define AM_GEMM_LOCKSTEP      0x200    /* the lockstep main loop of the 256x256 tile instead of the ping-pong loop (A/B runs) */
+#define AM_GEMM_FORCE_256     0x400    /* the 256x256 tile at any grid size */
+#define AM_GEMM_ABLATE_STORE  0x800    /* timing: no C store (am_gemm_headpost_bf16: no Q / K rows) */
+#define AM_GEMM_ABLATE_READ   0x1000   /* timing: no residual read (am_gemm_headpost_bf16: no V^T read-back) */
+#define AM_GEMM_ABLATE_MASK   0x1800
+#define AM_GEMM_SKEW_SHIFT    13       /* bits 13-15: per-XCD start skew of the 256x256 grid in 1.5 us units; 0 = the library's */
+#define AM_GEMM_SKEW_MASK     0xe000   /* choice, 7 = none */
+#define AM_GEMM_NO_GELU_TABLE 0x10000  /* the arithmetic GELU epilogue in the 256x256 tile too (default: the bit-identical table) */
   int32_t a_G, a_gs, a_off;
   int32_t c_G, c_gs, c_off;
   /* LayerNorm folded into the linear that consumes it (block.py:138,146,152: norm -> to_q|k|v / to_q / ff.net.0): with

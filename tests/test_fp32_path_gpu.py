@@ -233,6 +233,27 @@ def test_point_embed_patchify_displacement_f32():
     assert err <= 4 * 2.0 ** -24
 
 
+@pytest.mark.parametrize("padded", [False, True], ids=["natural", "padded"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_point_embed_patchify_16bit_is_the_rounded_fp32(dtype, padded):
+    """point_embed / patchify and their _f32 forms are ONE kernel template over the output type: the 16-bit form is the fp32 form
+    rounded to nearest even, bit for bit, at the natural and at a padded leading dimension (finite inputs: no other conversion rule)."""
+    from actionmesh_amd import ops
+    g = _gen(4)
+    bits = lambda t: t.view(torch.int16)
+    q = torch.rand((37, 6), generator=g, device=DEV) * 2 - 1
+    ld = 64 if padded else 54
+    for include_pi in (False, True):
+        e16, e32 = ops.point_embed(q, 3, 3, 8, include_pi, ld, dtype), ops.point_embed_f32(q, 3, 3, 8, include_pi, ld)
+        assert e16.dtype == dtype and e16.shape == e32.shape == (37, ld) and bool(torch.isfinite(e32).all())
+        assert torch.equal(bits(e16), bits(e32.to(dtype)))
+    pix = torch.randn((2, 3, 28, 42), generator=g, device=DEV)
+    ld = 640 if padded else 588
+    p16, p32 = ops.patchify(pix, 14, ld, dtype), ops.patchify_f32(pix, 14, ld)
+    assert p16.dtype == dtype and p16.shape == p32.shape == (2 * 2 * 3, ld)
+    assert torch.equal(bits(p16), bits(p32.to(dtype)))
+
+
 # ---- Stage II --------------------------------------------------------------------------------------------------------------------
 def _ae_case(golden_dir):
     from oracle import autoencoder_oracle as AO

@@ -18,9 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("kind", ["bf16", "f16"])
 def test_library_loads_and_exports_every_declared_symbol(kind):
     """Both builds of the sources: libactionmesh_amd.so (bfloat16) and libactionmesh_amd_f16.so (-DAM_F16: `--dtype float16`)."""
-    inc = os.path.join(ROOT, "include")
-    header = "".join(open(os.path.join(inc, f)).read() for f in sorted(os.listdir(inc)) if f.endswith(".h"))
-    declared = set(re.findall(r"\b(am_[a-z0-9_]+)\s*\(", header))
+    declared = set(re.findall(r"\b(am_[a-z0-9_]+)\s*\(", _headers()))
     declared -= {"am_status"}
     assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
     lib = _lib.lib(kind)        # raises if the .so is missing / lacks a symbol / ABI mismatch
@@ -29,28 +27,53 @@ def test_library_loads_and_exports_every_declared_symbol(kind):
     assert lib.am_abi_version() == _lib.ABI_VERSION
 
 
-def test_struct_layouts_match_header(tmp_path):
-    """ctypes mirrors vs the C header, measured by compiling a probe with gcc against include/."""
+def _headers():
+    inc = os.path.join(ROOT, "include")
+    return "".join(open(os.path.join(inc, f)).read() for f in sorted(os.listdir(inc)) if f.endswith(".h"))
+
+
+def _probe(tmp_path, lines):
+    """Compile and run a C program of `lines` (printf calls of "key value" pairs) against include/: {key: int(value)}."""
     import subprocess
-    structs = {"am_config": _lib.AmConfig, "am_gemm_args": _lib.AmGemmArgs,
-               "am_headpost_args": _lib.AmHeadPostArgs, "am_attn_args": _lib.AmAttnArgs, "am_nn_args": _lib.AmNnArgs,
-               "am_peer_ring": _lib.AmPeerRing}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "actionmesh_amd.h"', '#include "actionmesh_amd_sharded.h"', 'int main(void){']
-    for cname, cls in structs.items():
+    src, exe = tmp_path / "probe.c", tmp_path / "probe"
+    src.write_text("\n".join(['#include <stdio.h>', '#include <stddef.h>', '#include "actionmesh_amd.h"', '#include "actionmesh_amd_sharded.h"',
+                              'int main(void){'] + lines + ['return 0;}']))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    return {k: int(v) for k, v in (l.split() for l in out.splitlines() if l)}
+
+
+def test_struct_layouts_match_header(tmp_path):
+    """Every struct typedef of include/*.h has a ctypes mirror in _lib.STRUCTS, and each mirror's size and field offsets are the ones a C
+    compiler gives the header's struct (measured by compiling a probe with gcc against include/)."""
+    declared = set(re.findall(r"^\}\s*(am_\w+);", _headers(), re.M)) - {"am_status"}
+    assert declared == set(_lib.STRUCTS), declared ^ set(_lib.STRUCTS)
+    lines = []
+    for cname, cls in _lib.STRUCTS.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
         for fname, _t in cls._fields_:
             lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += ['return 0;}']
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    got = dict(l.split() for l in out if l)
-    for cname, cls in structs.items():
-        assert int(got[cname]) == ctypes.sizeof(cls), cname
+    got = _probe(tmp_path, lines)
+    print(f"{len(_lib.STRUCTS)} structs, {len(got) - len(_lib.STRUCTS)} fields: {' '.join(_lib.STRUCTS)}")
+    for cname, cls in _lib.STRUCTS.items():
+        assert got[cname] == ctypes.sizeof(cls), cname
         for fname, _t in cls._fields_:
-            assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
+            assert got[f"{cname}.{fname}"] == getattr(cls, fname).offset, f"{cname}.{fname}"
+
+
+def test_header_constants_match_the_binding(tmp_path):
+    """The bits of am_gemm_args.act (the header's AM_GEMM_* defines) and the camera limit, as a C compiler evaluates them, against the
+    constants of _lib: the same names without the AM_ prefix, none missing on either side."""
+    names = set(re.findall(r"^#define (AM_GEMM_\w+)", _headers(), re.M))
+    assert names == {"AM_" + n for n in dir(_lib) if n.startswith("GEMM_")}, names
+    got = _probe(tmp_path, [f'printf("{n} %d\\n", (int)({n}));' for n in sorted(names | {"AM_RENDER_MAX_CAMERAS"})])
+    for n, v in got.items():
+        assert v == getattr(_lib, n[3:]), n
+    assert _lib.GEMM_ABLATE_MASK == _lib.GEMM_ABLATE_STORE | _lib.GEMM_ABLATE_READ
+    assert _lib.GEMM_SKEW_MASK == 7 << _lib.GEMM_SKEW_SHIFT
+    bits = [_lib.GEMM_ACT_MASK, _lib.GEMM_FORCE_128, _lib.GEMM_LOCKSTEP, _lib.GEMM_FORCE_256, _lib.GEMM_ABLATE_MASK, _lib.GEMM_SKEW_MASK,
+            _lib.GEMM_NO_GELU_TABLE]
+    assert all(a & b == 0 for i, a in enumerate(bits) for b in bits[i + 1:])       # the fields do not overlap
 
 
 def test_argument_validation_without_gpu():

@@ -1,11 +1,10 @@
 """Host side of the HIP image preprocessing (actionmesh_amd/image_preprocess.py; contract: include/actionmesh_amd.h, am_image_*).
 No GPU: the tables and the geometry against the code they restate - PIL itself, numpy's float32 expression, the reference's own
-functions, transformers' PIL backend - plus the refusals, the drop-in seam and the ctypes layouts.  "Bit-identical" is zero differing
+functions, transformers' PIL backend - plus the refusals and the drop-in seam.  "Bit-identical" is zero differing
 bytes over the whole output; nothing is masked or sampled."""
 import ctypes
 import importlib.util
 import os
-import subprocess
 import sys
 import types
 
@@ -16,7 +15,6 @@ from PIL import Image
 from actionmesh_amd import _lib
 from actionmesh_amd import image_preprocess as IP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 HAVE_REF = os.path.isfile(os.path.join(REF, "actionmesh", "preprocessing", "image_processor.py"))
 needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference not present")
@@ -247,26 +245,6 @@ def test_cli_flag():
     assert cli.split_args([])[0].preprocess == "off"
     ours, rest = cli.split_args(["--preprocess", "hip", "--", "--input", "x"])
     assert ours.preprocess == "hip" and rest == ["--input", "x"]
-
-
-def test_struct_layouts_match_header(tmp_path):
-    structs = {"am_image_frame": _lib.AmImageFrame, "am_image_alpha_stats_args": _lib.AmImageAlphaStatsArgs,
-               "am_image_resample_args": _lib.AmImageResampleArgs, "am_image_materialize_args": _lib.AmImageMaterializeArgs}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "actionmesh_amd.h"', 'int main(void){']
-    for cname, cls in structs.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _t in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += ['return 0;}']
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n") if l)
-    for cname, cls in structs.items():
-        assert int(got[cname]) == ctypes.sizeof(cls), cname
-        for fname, _t in cls._fields_:
-            assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
 
 
 def test_entry_points_validate_before_launch():
