@@ -177,6 +177,30 @@ class AmGraphArgs(C.Structure):                # am_graph_args
     ]
 
 
+class AmVertexNormalsArgs(C.Structure):        # am_vertex_normals_args
+    _fields_ = [
+        ("vertices", C.c_void_p), ("vertices_f64", C.c_int32), ("n_frames", C.c_int32), ("n_vertices", C.c_int64), ("n_faces", C.c_int64),
+        ("frame_stride", C.c_int64), ("faces", C.c_void_p), ("offsets", C.c_void_p), ("corners", C.c_void_p),
+        ("out_features", C.c_void_p), ("out_normals", C.c_void_p), ("out_face_normals", C.c_void_p), ("out_flag", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AmFaceAreasArgs(C.Structure):            # am_face_areas_args
+    _fields_ = [
+        ("vertices", C.c_void_p), ("vertices_f64", C.c_int32), ("reserved", C.c_int32), ("n_vertices", C.c_int64), ("n_faces", C.c_int64),
+        ("faces", C.c_void_p), ("out_areas", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
+class AmSurfaceSampleArgs(C.Structure):        # am_surface_sample_args
+    _fields_ = [
+        ("vertices", C.c_void_p), ("vertices_f64", C.c_int32), ("reserved", C.c_int32), ("n_vertices", C.c_int64), ("n_faces", C.c_int64),
+        ("n_samples", C.c_int64), ("faces", C.c_void_p), ("cdf", C.c_void_p), ("u_face", C.c_void_p), ("u_bary", C.c_void_p),
+        ("out_points", C.c_void_p), ("out_face_index", C.c_void_p), ("out_normals", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -197,7 +221,8 @@ STRUCTS = {
     "am_attn_f32_args": AmAttnF32Args, "am_nn_args": AmNnArgs, "am_render_camera": AmRenderCamera, "am_render_args": AmRenderArgs,
     "am_fps_args": AmFpsArgs, "am_image_frame": AmImageFrame, "am_image_alpha_stats_args": AmImageAlphaStatsArgs,
     "am_image_resample_args": AmImageResampleArgs, "am_image_materialize_args": AmImageMaterializeArgs,
-    "am_mask_refine_args": AmMaskRefineArgs, "am_graph_args": AmGraphArgs, "am_peer_ring": AmPeerRing,
+    "am_mask_refine_args": AmMaskRefineArgs, "am_graph_args": AmGraphArgs, "am_vertex_normals_args": AmVertexNormalsArgs,
+    "am_face_areas_args": AmFaceAreasArgs, "am_surface_sample_args": AmSurfaceSampleArgs, "am_peer_ring": AmPeerRing,
 }
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
@@ -239,6 +264,10 @@ SYMBOLS = {
     "am_mask_refine": (C.c_int, [C.POINTER(AmMaskRefineArgs), _P]),
     "am_graph_components_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "am_graph_components": (C.c_int, [C.POINTER(AmGraphArgs), _P]),
+    "am_vertex_normals_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "am_vertex_normals": (C.c_int, [C.POINTER(AmVertexNormalsArgs), _P]),
+    "am_face_areas": (C.c_int, [C.POINTER(AmFaceAreasArgs), _P]),
+    "am_surface_sample": (C.c_int, [C.POINTER(AmSurfaceSampleArgs), _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

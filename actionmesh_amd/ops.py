@@ -725,6 +725,142 @@ def graph_components(n_nodes: int, edges: torch.Tensor, return_size: bool = Fals
     return (label, size) if return_size else label
 
 
+# ---- anchor-mesh preparation (csrc/am_mesh.hip; the contract is the header's, the tensor interface is mesh_prep.py's) ----------------
+_MESH_MAX = (2 ** 31 - 1) // 3
+_MESH_FLAGS = {1: "a face names a vertex outside [0, {V})", 2: "the vertex -> corner CSR does not belong to these faces"}
+
+
+def _mesh_operands(what: str, vertices: torch.Tensor, faces: torch.Tensor, frames: bool):
+    """The (vertices, faces) checks the three mesh entry points share; they come before the device check, so they hold for any
+    tensor.  Returns (T, V, F, frame stride in elements)."""
+    if not isinstance(vertices, torch.Tensor) or not isinstance(faces, torch.Tensor):
+        raise TypeError(f"{what}: expected torch tensors")
+    if vertices.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what}: expected float32 or float64 vertices, got {vertices.dtype}")
+    if faces.dtype != torch.int32:
+        raise TypeError(f"{what}: expected int32 faces, got {faces.dtype}")
+    if vertices.dim() not in ((2, 3) if frames else (2,)) or vertices.shape[-1] != 3 or vertices.numel() == 0:
+        raise ValueError(f"{what}: expected non-empty {'(V, 3) or (T, V, 3)' if frames else '(V, 3)'} vertices, got {tuple(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: expected (F, 3) faces, got {tuple(faces.shape)}")
+    if not faces.is_contiguous():
+        raise ValueError(f"{what}: the faces must be contiguous")
+    V, F = vertices.shape[-2], faces.shape[0]
+    T = vertices.shape[0] if vertices.dim() == 3 else 1
+    if V > _MESH_MAX or F > _MESH_MAX or T > 65535:
+        raise ValueError(f"{what}: {T} frames of {V} vertices and {F} faces are more than one call covers")
+    stride = vertices.stride()
+    if stride[-1] != 1 or (V > 1 and stride[-2] != 3) or (vertices.dim() == 3 and T > 1 and stride[0] < 3 * V):
+        raise ValueError(f"{what}: a frame's vertices must be contiguous and frames must not overlap (strides {stride})")
+    if not vertices.is_cuda or not faces.is_cuda:
+        raise RuntimeError(f"{what}: actionmesh_amd kernels need a device tensor (no CPU path)")
+    if faces.device != vertices.device:
+        raise ValueError(f"{what}: vertices on {vertices.device}, faces on {faces.device}")
+    return T, V, F, (stride[0] if vertices.dim() == 3 and T > 1 else 3 * V)
+
+
+def _mesh_flag(what: str, flag: torch.Tensor, V: int) -> None:
+    """ONE device-to-host read behind the launch: a set bit of the entry point's flag is a ValueError."""
+    bits = int(flag)
+    if bits:
+        raise ValueError(f"{what}: " + "; ".join(msg.format(V=V) for bit, msg in _MESH_FLAGS.items() if bits & bit))
+
+
+def _mesh_out(what: str, out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    """A fresh contiguous output, or the caller's of the same shape and dtype."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _need(out, dtype, what)
+    if tuple(out.shape) != tuple(shape) or out.device != device:
+        raise ValueError(f"{what}: {tuple(out.shape)} on {out.device}, expected {tuple(shape)} on {device}")
+    return out
+
+
+def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, topology=None, features: bool = False, return_face_normals: bool = False,
+                   out: Optional[torch.Tensor] = None, out_face_normals: Optional[torch.Tensor] = None):
+    """am_vertex_normals: trimesh's angle-weighted vertex normals followed by the reference's fp32 F.normalize (the contract is the
+    header's).  vertices (V, 3) or (T, V, 3), fp32 or fp64, frames that share `faces` (F, 3) int32; a frame stride above 3 V is passed
+    as it is (no copy).  `topology`: the vertex -> corner CSR of the faces, an object with int32 device tensors `.offsets` (V + 1)
+    and `.corners` (3 F) - a `mesh_prep.MeshTopology`, built here when None; a caller that keeps its faces keeps it too.
+    Returns fp32 normals (..., V, 3), or with `features` (..., V, 6) = position rounded to fp32 | normal; with `return_face_normals`
+    also the fp64 unit face normals (..., F, 3).  Faces and CSR are validated on the device: ONE device-to-host read behind the
+    launch (the flag) turns a vertex index outside [0, V) into a ValueError.  `out` / `out_face_normals`: the caller's buffers."""
+    T, V, F, stride = _mesh_operands("vertex_normals", vertices, faces, frames=True)
+    if topology is None:
+        from .mesh_prep import MeshTopology
+        topology = MeshTopology(faces, V)
+    offsets = _need(topology.offsets, torch.int32, "vertex_normals: topology.offsets")
+    corners = _need(topology.corners, torch.int32, "vertex_normals: topology.corners")
+    if offsets.numel() != V + 1 or corners.numel() != 3 * F:
+        raise ValueError(f"vertex_normals: the topology is of {offsets.numel() - 1} vertices and {corners.numel() // 3} faces, the mesh "
+                         f"has {V} and {F}")
+    dev = vertices.device
+    lead = tuple(vertices.shape[:-2])
+    out = _mesh_out("vertex_normals: out", out, lead + (V, 6 if features else 3), torch.float32, dev)
+    face_normals = None
+    if return_face_normals:
+        face_normals = _mesh_out("vertex_normals: out_face_normals", out_face_normals, lead + (F, 3), torch.float64, dev)
+    flag = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws, need = _workspace(dev, "am_vertex_normals_workspace_bytes", T, F)
+    a = L.AmVertexNormalsArgs()
+    a.vertices, a.vertices_f64, a.n_frames = vertices.data_ptr(), int(vertices.dtype == torch.float64), T
+    a.n_vertices, a.n_faces, a.frame_stride = V, F, stride
+    a.faces, a.offsets, a.corners = (faces.data_ptr() if F else None), offsets.data_ptr(), (corners.data_ptr() if F else None)
+    a.out_features, a.out_normals = (out.data_ptr(), None) if features else (None, out.data_ptr())
+    a.out_face_normals, a.out_flag = _p(face_normals), flag.data_ptr()
+    a.workspace, a.workspace_bytes = _p(ws), need
+    _call(vertices, None, "am_vertex_normals", C.byref(a))
+    _mesh_flag("vertex_normals", flag, V)
+    return (out, face_normals) if return_face_normals else out
+
+
+def face_areas(vertices: torch.Tensor, faces: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_face_areas: the fp64 area (F,) of every face of one frame.  vertices (V, 3) fp32 or fp64, faces (F, 3) int32, F >= 1.
+    ONE device-to-host read behind the launch (the flag) turns a vertex index outside [0, V) into a ValueError."""
+    _, V, F, _ = _mesh_operands("face_areas", vertices, faces, frames=False)
+    if F < 1:
+        raise ValueError("face_areas: the mesh has no faces")
+    out = _mesh_out("face_areas: out", out, (F,), torch.float64, vertices.device)
+    flag = torch.empty((1,), dtype=torch.int32, device=vertices.device)
+    a = L.AmFaceAreasArgs()
+    a.vertices, a.vertices_f64, a.n_vertices, a.n_faces = vertices.data_ptr(), int(vertices.dtype == torch.float64), V, F
+    a.faces, a.out_areas, a.out_flag = faces.data_ptr(), out.data_ptr(), flag.data_ptr()
+    _call(vertices, None, "am_face_areas", C.byref(a))
+    _mesh_flag("face_areas", flag, V)
+    return out
+
+
+def surface_sample(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tensor, u_face: torch.Tensor, u_bary: torch.Tensor,
+                   with_normals: bool = True, out_points: Optional[torch.Tensor] = None, out_face_index: Optional[torch.Tensor] = None,
+                   out_normals: Optional[torch.Tensor] = None):
+    """am_surface_sample: trimesh.sample.sample_surface with the caller's uniforms (the contract is the header's).  vertices (V, 3)
+    fp32 or fp64, faces (F, 3) int32, cdf (F,) fp64 (the prefix sum of the face areas), u_face (n,) and u_bary (n, 2) fp64 in
+    [0, 1).  Returns (points (n, 3) fp64, face_index (n,) int32, the unit face normals (n, 3) fp64 or None).  ONE device-to-host
+    read behind the launch (the flag) turns a vertex index outside [0, V) in a picked face into a ValueError."""
+    _, V, F, _ = _mesh_operands("surface_sample", vertices, faces, frames=False)
+    if F < 1:
+        raise ValueError("surface_sample: the mesh has no faces")
+    _need(cdf, torch.float64, "surface_sample: cdf")
+    _need(u_face, torch.float64, "surface_sample: u_face")
+    _need(u_bary, torch.float64, "surface_sample: u_bary")
+    n = u_face.numel()
+    if cdf.numel() != F or n < 1 or n > _MESH_MAX or tuple(u_bary.shape) != (n, 2):
+        raise ValueError(f"surface_sample: cdf {tuple(cdf.shape)}, u_face {tuple(u_face.shape)}, u_bary {tuple(u_bary.shape)} "
+                         f"do not fit {F} faces and (n,), (n, 2) uniforms")
+    dev = vertices.device
+    points = _mesh_out("surface_sample: out_points", out_points, (n, 3), torch.float64, dev)
+    normals = _mesh_out("surface_sample: out_normals", out_normals, (n, 3), torch.float64, dev) if with_normals else None
+    idx = _mesh_out("surface_sample: out_face_index", out_face_index, (n,), torch.int32, dev)
+    flag = torch.empty((1,), dtype=torch.int32, device=dev)
+    a = L.AmSurfaceSampleArgs()
+    a.vertices, a.vertices_f64, a.n_vertices, a.n_faces, a.n_samples = vertices.data_ptr(), int(vertices.dtype == torch.float64), V, F, n
+    a.faces, a.cdf, a.u_face, a.u_bary = faces.data_ptr(), cdf.data_ptr(), u_face.data_ptr(), u_bary.data_ptr()
+    a.out_points, a.out_face_index, a.out_normals, a.out_flag = points.data_ptr(), idx.data_ptr(), _p(normals), flag.data_ptr()
+    _call(vertices, None, "am_surface_sample", C.byref(a))
+    _mesh_flag("surface_sample", flag, V)
+    return points, idx, normals
+
+
 # ---- exact-fp32 path (csrc/am_f32.hip, am_elementwise.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              gelu: bool = False, out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:

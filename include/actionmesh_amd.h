@@ -680,6 +680,107 @@ typedef struct {
 size_t am_graph_components_workspace_bytes(int64_t n_nodes, int64_t n_edges);
 int am_graph_components(const am_graph_args* args, void* stream);
 
+/* Anchor-mesh preparation (INTEGRATION seam S10): the geometry behind the reference's `get_mesh_features` and `sample_surface`
+ * (actionmesh/preprocessing/mesh_processor.py:85-101, 245-285), which go through trimesh's `vertex_normals`, `area_faces`,
+ * `face_normals` and `sample.sample_surface`.  ALL geometry is fp64, every operation below rounded on its own in the order written
+ * (no fused multiply-add anywhere); a sum of three terms is (x + y) + z.  Vertices are fp32 or fp64 (vertices_f64 = 0 / 1; fp32 is
+ * widened first, exact), faces are int32 (n_faces, 3).  n_vertices, n_faces and n_samples are at most (2^31 - 1) / 3.
+ *
+ * Per face (v0, v1, v2 its three vertices):
+ *   e1 = v1 - v0;  e2 = v2 - v0;  c = e1 x e2 = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x);  |c| = sqrt(c . c)
+ *   unit face normal = c / |c| (three divisions), or (0, 0, 0) when |c| <= AM_MESH_ZERO;   area = |c| / 2
+ *   corner angles (trimesh.triangles.angles):  u = e1 / |e1|;  v = e2 / |e2|;  w = (v2 - v1) / |v2 - v1|
+ *     a0 = acos(clip(u . v, -1, 1));  a1 = acos(clip(-(u . w), -1, 1));  a2 = (pi - a0) - a1;   all three 0 for a zero-normal face
+ * AM_MESH_ZERO is a recollection of trimesh's `tol.zero` (trimesh is not installable where this was written: UNPINNED).
+ *
+ * Vertex normals (am_vertex_normals), for n_frames frames that share one topology.  The caller supplies the vertex -> corner CSR
+ * of the faces: corner id = 3 * face + k names vertex faces[face][k]; the corners of vertex v are corners[offsets[v] ..
+ * offsets[v + 1]), in ASCENDING corner id (one stable sort of the flattened faces).  Per frame and vertex:
+ *   s = (0, 0, 0);  for each corner in that order:  s = s + angle[corner] * unit face normal[corner / 3]       (per component)
+ *   n = s / |s| (three divisions), or (0, 0, 0) when |s| <= AM_MESH_ZERO;  n32 = fp32(n)
+ *   normal = n32 / max(sqrtf((n32x n32x + n32y n32y) + n32z n32z), 1e-12f)                 in fp32: the reference's F.normalize
+ * A vertex of valence 0, or one that only zero-normal faces touch, gets exactly (0, 0, 0).  The sum is a gather in CSR order:
+ * no floating-point atomics, the same two launches (behind a 4-byte memset of the flag) whatever the valences are, so the result
+ * is the same bits on every run.
+ *   vertices          device, frame t vertex i component c at vertices[t * frame_stride + 3 * i + c] (stride in ELEMENTS,
+ *                     >= 3 * n_vertices; ignored with one frame);
+ *   offsets, corners  device int32[n_vertices + 1], int32[3 * n_faces];
+ *   out_features      optional device fp32 (n_frames, n_vertices, 6) = position rounded to fp32 | normal;
+ *   out_normals       optional device fp32 (n_frames, n_vertices, 3);
+ *   out_face_normals  optional device fp64 (n_frames, n_faces, 3): the unit face normals;       at least one output is required
+ *   out_flag          device int32[1]: 0, or bit 0 when a face names a vertex outside [0, n_vertices), bit 1 when the CSR is not
+ *                     one of these faces (offsets not ascending inside [0, 3 n_faces], a corner outside [0, 3 n_faces) or one that
+ *                     does not name the vertex it is listed under).  Every index is compared with its bound BEFORE it is used as
+ *                     an address: a bad face contributes zeros, a bad corner nothing, and the caller, who reads the flag together
+ *                     with the result, treats the call as failed;
+ *   workspace         16-byte aligned device scratch of am_vertex_normals_workspace_bytes(n_frames, n_faces) bytes.
+ *
+ * Face areas (am_face_areas): out_areas[f] = |c| / 2 as fp64; out_flag as above (bit 0; such a face gets area 0).
+ *
+ * Surface samples (am_surface_sample): trimesh.sample.sample_surface with the random draws supplied by the caller.
+ *   cdf       device fp64[n_faces]: the inclusive prefix sum of the face areas (the caller's: any non-decreasing weights do);
+ *   u_face    device fp64[n_samples] in [0, 1);   u_bary: device fp64 (n_samples, 2) in [0, 1).  Per sample:
+ *   pick = u_face * cdf[n_faces - 1];  face = the first index with cdf[face] >= pick        (np.searchsorted, side left; the last
+ *                                                                                            face if there is none)
+ *   (r0, r1) = u_bary;  if r0 + r1 > 1: r0 = r0 - 1, r1 = r1 - 1;  r0 = |r0|, r1 = |r1|
+ *   point = (v0 + (v1 - v0) * r0) + (v2 - v0) * r1                                           per component
+ *   out_points      device fp64 (n_samples, 3);   out_face_index: device int32[n_samples];
+ *   out_normals     optional device fp64 (n_samples, 3): the unit face normal of the picked face as defined above;
+ *   out_flag        as above (bit 0): the sample of a face with a bad index is (0, 0, 0).
+ * A face of zero area has cdf[face] == cdf[face - 1] and is never picked (face 0 is picked by pick == 0 whatever its area).
+ * That trimesh draws and combines its uniforms this way is a recollection, UNPINNED; the tests hold the device to a numpy
+ * restatement of the lines above: points and face indices exactly, the normals to the rounding of sqrt and acos. */
+#define AM_MESH_ZERO 1e-13
+typedef struct {
+  const void* vertices;
+  int32_t vertices_f64;         /* 0: fp32, 1: fp64 */
+  int32_t n_frames;             /* 1 .. 65535 */
+  int64_t n_vertices;
+  int64_t n_faces;              /* may be 0: every normal is zero */
+  int64_t frame_stride;
+  const int32_t* faces;
+  const int32_t* offsets;
+  const int32_t* corners;
+  float* out_features;
+  float* out_normals;
+  double* out_face_normals;
+  int32_t* out_flag;
+  void* workspace;
+  size_t workspace_bytes;
+} am_vertex_normals_args;
+size_t am_vertex_normals_workspace_bytes(int n_frames, int64_t n_faces);
+int am_vertex_normals(const am_vertex_normals_args* args, void* stream);
+
+typedef struct {
+  const void* vertices;         /* one frame, contiguous (n_vertices, 3) */
+  int32_t vertices_f64;
+  int32_t reserved;
+  int64_t n_vertices;
+  int64_t n_faces;              /* >= 1 */
+  const int32_t* faces;
+  double* out_areas;
+  int32_t* out_flag;
+} am_face_areas_args;
+int am_face_areas(const am_face_areas_args* args, void* stream);
+
+typedef struct {
+  const void* vertices;         /* one frame, contiguous (n_vertices, 3) */
+  int32_t vertices_f64;
+  int32_t reserved;
+  int64_t n_vertices;
+  int64_t n_faces;              /* >= 1 */
+  int64_t n_samples;            /* >= 1 */
+  const int32_t* faces;
+  const double* cdf;
+  const double* u_face;
+  const double* u_bary;
+  double* out_points;
+  int32_t* out_face_index;
+  double* out_normals;
+  int32_t* out_flag;
+} am_surface_sample_args;
+int am_surface_sample(const am_surface_sample_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,9 @@
     latents + anchor vertices   --generate_vertex_animation (Stage II: ActionMeshAutoencoder per window)-->  vertices per frame
 
 at the shipped shapes (Stage I: N = 2048 tokens, width 2048, 16 heads, 21 layers; Stage II: width 1024, 16 + 1 blocks) with
-random-init weights.  What stays on the reference's CPU path (and is not timed here): background removal, TripoSG
-Stage 0, mesh post-processing / vertex normals (trimesh), GLB export.  Prints one JSON line (secondary metric:
+random-init weights.  The anchor is a torus mesh; its per-window vertex features (positions + angle-weighted vertex normals) are
+`actionmesh_amd.VertexFeatures` on the device (`--features analytic`: the earlier stand-in, normalised positions, no kernel).  What
+stays on the reference's CPU path (and is not timed here): background removal, TripoSG Stage 0, quadric decimation.  Prints one JSON line (secondary metric:
 BASELINE.json's "end-to-end video->4D wall-clock" restricted to the stages this repository implements).
 
     python tools/e2e_synthetic.py [--frames 16] [--steps 30] [--vertices 50000] [--tiny]
@@ -16,7 +17,10 @@ BASELINE.json's "end-to-end video->4D wall-clock" restricted to the stages this 
     python tools/e2e_synthetic.py --config 3      configs[3]: the panda clip; in the reference this path (pipeline_with_3d) differs from configs[1]
                                                   ONLY in where the anchor latent / mesh come from (a given panda.glb through the TripoSG VAE
                                                   encoder instead of TripoSG's image-to-3D sampler) - both are Stage 0, on the reference path;
-                                                  here the anchor latent is seeded noise in both, so the two records time the same GPU chain
+                                                  here the anchor latent is seeded noise in both; the given mesh is a deliberately DIRTY torus
+                                                  (duplicated seam vertices, degenerate and duplicate faces, GLB units) that goes through
+                                                  merge_and_clean_mesh -> normalize_mesh -> sample_surface(16384) in front of Stage II and
+                                                  through denormalize_mesh + expand_to_original behind it (pipeline_with_3d.py:92-104, 229-238)
 Both are PLUMBING records on random-init weights (no checkpoint is reachable offline): not BASELINE's end-to-end metric.
 """
 import argparse
@@ -76,9 +80,49 @@ def build(tiny: bool, dev):
     return enc, denoiser, vae, HipSchedulerFlow, ClassifierFreeGuidance, n_tokens, window, side
 
 
+def torus_mesh(vertices: int):
+    """A torus of exactly `vertices` vertices (rows x cols, rows the largest divisor of `vertices` up to its square root) inside the
+    0.8 cube: fp64 (V, 3), int64 (2 V, 3), numpy; and cols."""
+    import numpy as np
+    rows = max((d for d in range(3, int(vertices ** 0.5) + 1) if vertices % d == 0), default=0)
+    if rows == 0:
+        raise ValueError(f"--vertices {vertices} must be rows x cols with both at least 3")
+    cols = vertices // rows
+    a, b = np.meshgrid(2 * np.pi * np.arange(rows) / rows, 2 * np.pi * np.arange(cols) / cols, indexing="ij")
+    v = np.stack(((0.55 + 0.25 * np.cos(a)) * np.cos(b), (0.55 + 0.25 * np.cos(a)) * np.sin(b), 0.25 * np.sin(a)), -1).reshape(-1, 3)
+    i, j = (x.reshape(-1) for x in np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij"))
+    p00, p01 = i * cols + j, i * cols + (j + 1) % cols
+    p10, p11 = (i + 1) % rows * cols + j, (i + 1) % rows * cols + (j + 1) % cols
+    return v, np.concatenate((np.stack((p00, p01, p11), 1), np.stack((p00, p11, p10), 1))).astype(np.int64), cols
+
+
+def dirty_mesh(v, f, cols: int, seed: int = 2):
+    """What a GLB loader hands over: the vertices of the seam column duplicated (half of them moved by up to 2e-9) with the faces
+    on one side of the seam naming the copies, eight faces with a repeated index and eight repeated faces with reversed winding
+    scattered through the face array, everything in model units (x 3, shifted)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    seam = np.arange(0, len(v), cols)                                   # column 0 of every row
+    moved = v[seam] + rng.uniform(-2e-9, 2e-9, (len(seam), 3)) * (rng.random((len(seam), 1)) < 0.5)
+    v2 = np.concatenate((v, moved)) * 3.0 + (5.0, -2.0, 1.0)
+    same_key = (np.round(v2[len(v):] * 1e8) == np.round(v2[seam] * 1e8)).all(1, keepdims=True)
+    v2[len(v):] = np.where(same_key, v2[len(v):], v2[seam])             # a copy the 1e-8 grid would separate stays exact
+    copy_of = np.arange(len(v))
+    copy_of[seam] = len(v) + np.arange(len(seam))
+    f2 = f.copy()
+    wrap = (f % cols == cols - 1).any(1)                                # faces that reach the seam from the last column
+    f2[wrap] = np.where(np.isin(f[wrap], seam), copy_of[f[wrap]], f[wrap])
+    extra = [(a, b, a) for a, b in rng.integers(0, len(v2), (8, 2)) if a != b]
+    extra += [tuple(f2[k][::-1]) for k in rng.integers(0, len(f2), 8)]
+    for face in extra:
+        f2 = np.insert(f2, rng.integers(len(f2) // 2, len(f2) + 1), face, axis=0)      # behind the face it repeats, or anywhere
+    return v2, f2
+
+
 def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44, clip: str = None, label: str = None,
-        raw_frames: bool = False):
+        raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False):
     from actionmesh_amd import LatentBank, generate_3d_latents, generate_vertex_animation
+    from actionmesh_amd import mesh_prep as MP
     t_build = time.perf_counter()
     enc, denoiser, vae, Sched, CFG, n_tokens, window, side = build(tiny, dev)
     torch.cuda.synchronize(dev)
@@ -114,8 +158,28 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
         pixels = torch.randn((frames, 3, side, side), generator=g).to(dev)
     timesteps = torch.arange(frames, dtype=torch.float32)
     anchor_latent = torch.randn((1, n_tokens, 64), generator=g).to(dev)
-    pts = torch.nn.functional.normalize(torch.randn((vertices, 3), generator=g), dim=-1) * 0.8        # a sphere of radius 0.8
-    features = lambda v: torch.cat([v, torch.nn.functional.normalize(v, dim=-1)], dim=-1)              # its normals
+    clean_v, clean_f, cols = torus_mesh(vertices)
+    t_prep = None
+    if mesh_prep:          # the {video+3D} front end: dirty mesh -> clean-up -> normalise -> surface samples, all on the device
+        raw_v, raw_f = (torch.from_numpy(x).to(dev) for x in dirty_mesh(clean_v, clean_f, cols))
+        warm_v, warm_f, _, _ = MP.merge_and_clean_mesh(raw_v, raw_f)     # the library's first calls, outside the stage
+        MP.sample_surface(MP.normalize_mesh(warm_v)[0], warm_f, 16, seed=0)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        anchor_v, faces, merge_map, pre_faces = MP.merge_and_clean_mesh(raw_v, raw_f)
+        anchor_v, norm_params = MP.normalize_mesh(anchor_v)
+        cloud = MP.sample_surface(anchor_v, faces, 16384, seed=0, with_normals=True, dtype=torch.bfloat16)   # the VAE encoder's input
+        torch.cuda.synchronize(dev)
+        t_prep = time.perf_counter() - t0
+        assert anchor_v.shape[0] == vertices and faces.shape[0] == len(clean_f) and raw_v.shape[0] > vertices, (anchor_v.shape, faces.shape)
+        assert cloud.shape == (1, 16384, 6) and bool(torch.isfinite(cloud.float()).all())
+        pts = anchor_v.float()
+    else:
+        pts, faces = torch.from_numpy(clean_v).float().to(dev), torch.from_numpy(clean_f).to(dev)
+    if features == "hip":
+        features = MP.VertexFeatures(faces)                            # positions | angle-weighted vertex normals, per window
+    else:                                                              # the earlier stand-in: the normalised position as a normal
+        features = lambda v: torch.cat([v, torch.nn.functional.normalize(v, dim=-1)], dim=-1)
     sched, cfg = Sched(num_inference_steps=steps, shift=3.0, is_additive=True), CFG(True, [[0, 1], [1, 1]], [7.5])
     slide = window - 1
 
@@ -132,7 +196,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
     bank, t_s1 = stage(lambda: generate_3d_latents(denoiser, sched, cfg, timesteps, context, bank, 0, window, slide,
                                                    (n_tokens, 64), seed=seed, device=dev))
     vbank = LatentBank(empty_dims=(vertices, 3), device=str(dev))
-    vbank.update(timesteps[:1], pts[None].to(dev))
+    vbank.update(timesteps[:1], pts[None])
     vbank, t_s2 = stage(lambda: generate_vertex_animation(vae, bank, vbank, features, 0, window, slide, device=dev))
     verts, ts = vbank.get_ordered()
     assert ts.tolist() == timesteps.tolist() and verts.shape == (frames, vertices, 3)
@@ -144,7 +208,12 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
     import shutil
     import tempfile
     from actionmesh_amd import actionbench, create_animated_glb, save_deformation, save_meshes
-    faces = torch.arange(vertices - vertices % 3).view(-1, 3)                  # any triangulation will do for the writers
+    t_back = None
+    if mesh_prep:          # back to the given mesh: model units, the original (pre-merge) topology
+        (verts_out, t_back) = stage(lambda: MP.expand_to_original(MP.denormalize_mesh(verts.double(), norm_params), merge_map).float())
+        assert verts_out.shape == (frames, raw_v.shape[0], 3) and float((verts_out[0] - raw_v).abs().max()) < 1e-5
+        verts, faces = verts_out, pre_faces
+    faces = faces.cpu()
     out_dir = tempfile.mkdtemp(prefix="am_e2e_")
     t0 = time.perf_counter()
     save_meshes(verts, faces, os.path.join(out_dir, "meshes"))
@@ -167,6 +236,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             "seconds": {"context_encoder": round(t_enc, 4), "stage_I": round(t_s1, 3), "stage_II": round(t_s2, 3),
                         "model_build_and_upload": round(t_build, 1),
                         **({"preprocess_s": round(t_pre, 4)} if t_pre is not None else {}),
+                        **({"mesh_prep": round(t_prep, 4), "mesh_back_to_original": round(t_back, 4)} if mesh_prep else {}),
                         "output_files_host_side": round(t_out, 3), "chamfer_metrics": round(t_metric, 4)},
             "preview_video_s": round(t_preview, 3),          # grid_normal.* (HipVisualizer), written into the output files above
             "output_files_mb": round(out_bytes / 1e6, 1),
@@ -186,6 +256,9 @@ def main():
     ap.add_argument("--clip", default=None, choices=["davis_camel", "panda"], help="frames of a reference example clip (tests/golden/frames/) instead of noise")
     ap.add_argument("--raw-frames", action="store_true",
                     help="with --clip: start from the raw RGBA frames (tests/golden/frames_raw/) and preprocess them on the device; adds preprocess_s")
+    ap.add_argument("--features", default="hip", choices=["hip", "analytic"],
+                    help="Stage II's vertex features: VertexFeatures on the device (default), or the earlier stand-in (normalised positions)")
+    ap.add_argument("--mesh-prep", action="store_true", help="start from a dirty mesh and run the {video+3D} mesh glue around Stage II (implied by --config 3)")
     ap.add_argument("--config", type=int, default=None, choices=[1, 3], help="BASELINE.json configs[1] / configs[3] as a plumbing record (see the module docstring)")
     a = ap.parse_args()
     if a.raw_frames and not (a.clip or a.config):
@@ -197,10 +270,12 @@ def main():
         a.clip, a.frames, a.steps = "davis_camel", 16, 50
         label = "configs[1]: davis_camel 16 frames, full 50-step scheduler, bf16, 1 x MI355X - PLUMBING on random-init weights, not the end-to-end metric"
     elif a.config == 3:
-        a.clip, a.frames, a.steps = "panda", 16, 50
+        a.clip, a.frames, a.steps, a.mesh_prep = "panda", 16, 50, True
         label = ("configs[3]: {video+3D}->4D panda path, 16 frames, 1 x MI355X - PLUMBING on random-init weights; differs from configs[1] only in the "
-                 "anchor latent's source (Stage 0, reference path), which is seeded noise in both records")
-    print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames)))
+                 "anchor latent's source (Stage 0, reference path), which is seeded noise in both records, and in the mesh glue around Stage II "
+                 "(dirty mesh -> merge_and_clean_mesh -> normalize_mesh -> sample_surface; denormalize_mesh + expand_to_original at the end)")
+    print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames,
+                         features=a.features, mesh_prep=a.mesh_prep)))
 
 
 if __name__ == "__main__":
