@@ -201,6 +201,43 @@ class AmSurfaceSampleArgs(C.Structure):        # am_surface_sample_args
     ]
 
 
+DECIMATE_NO_KEY = 2 ** 63 - 1               # AM_DECIMATE_NO_KEY
+DECIMATE_BAD_FACE, DECIMATE_BAD_CSR, DECIMATE_BAD_EDGE, DECIMATE_BAD_KEPT = 1, 2, 4, 8      # am_decimate_*'s out_flag bits
+
+
+class AmDecimateQuadricsArgs(C.Structure):     # am_decimate_quadrics_args
+    _fields_ = [
+        ("positions", C.c_void_p), ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("faces", C.c_void_p), ("offsets", C.c_void_p),
+        ("corners", C.c_void_p), ("out_quadrics", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
+class AmDecimateEdgesArgs(C.Structure):        # am_decimate_edges_args
+    _fields_ = [
+        ("positions", C.c_void_p), ("quadrics", C.c_void_p), ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("n_edges", C.c_int64),
+        ("faces", C.c_void_p), ("offsets", C.c_void_p), ("corners", C.c_void_p), ("edges", C.c_void_p), ("half_edge_to_edge", C.c_void_p),
+        ("edge_count", C.c_void_p), ("out_positions", C.c_void_p), ("out_cost", C.c_void_p), ("out_key", C.c_void_p),
+        ("out_flag", C.c_void_p),
+    ]
+
+
+class AmDecimateSelectArgs(C.Structure):       # am_decimate_select_args
+    _fields_ = [
+        ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("n_edges", C.c_int64), ("faces", C.c_void_p), ("offsets", C.c_void_p),
+        ("corners", C.c_void_p), ("edges", C.c_void_p), ("half_edge_to_edge", C.c_void_p), ("keys", C.c_void_p), ("out_m1", C.c_void_p),
+        ("out_m2", C.c_void_p), ("out_selected", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
+class AmDecimateApplyArgs(C.Structure):        # am_decimate_apply_args
+    _fields_ = [
+        ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("n_edges", C.c_int64), ("n_kept", C.c_int64), ("kept", C.c_void_p),
+        ("edges", C.c_void_p), ("candidates", C.c_void_p), ("offsets", C.c_void_p), ("corners", C.c_void_p), ("positions", C.c_void_p),
+        ("quadrics", C.c_void_p), ("faces", C.c_void_p), ("vertex_map", C.c_void_p), ("out_face_dead", C.c_void_p),
+        ("out_flag", C.c_void_p),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -222,7 +259,9 @@ STRUCTS = {
     "am_fps_args": AmFpsArgs, "am_image_frame": AmImageFrame, "am_image_alpha_stats_args": AmImageAlphaStatsArgs,
     "am_image_resample_args": AmImageResampleArgs, "am_image_materialize_args": AmImageMaterializeArgs,
     "am_mask_refine_args": AmMaskRefineArgs, "am_graph_args": AmGraphArgs, "am_vertex_normals_args": AmVertexNormalsArgs,
-    "am_face_areas_args": AmFaceAreasArgs, "am_surface_sample_args": AmSurfaceSampleArgs, "am_peer_ring": AmPeerRing,
+    "am_face_areas_args": AmFaceAreasArgs, "am_surface_sample_args": AmSurfaceSampleArgs,
+    "am_decimate_quadrics_args": AmDecimateQuadricsArgs, "am_decimate_edges_args": AmDecimateEdgesArgs,
+    "am_decimate_select_args": AmDecimateSelectArgs, "am_decimate_apply_args": AmDecimateApplyArgs, "am_peer_ring": AmPeerRing,
 }
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
@@ -268,6 +307,10 @@ SYMBOLS = {
     "am_vertex_normals": (C.c_int, [C.POINTER(AmVertexNormalsArgs), _P]),
     "am_face_areas": (C.c_int, [C.POINTER(AmFaceAreasArgs), _P]),
     "am_surface_sample": (C.c_int, [C.POINTER(AmSurfaceSampleArgs), _P]),
+    "am_decimate_quadrics": (C.c_int, [C.POINTER(AmDecimateQuadricsArgs), _P]),
+    "am_decimate_edges": (C.c_int, [C.POINTER(AmDecimateEdgesArgs), _P]),
+    "am_decimate_select": (C.c_int, [C.POINTER(AmDecimateSelectArgs), _P]),
+    "am_decimate_apply": (C.c_int, [C.POINTER(AmDecimateApplyArgs), _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

@@ -1,0 +1,460 @@
+// Mesh decimation: the kernels of one round of the parallel quadric edge collapse (actionmesh_amd/mesh_decimate.py), which stands in
+// for the reference's trimesh.simplify_quadric_decimation (actionmesh/preprocessing/mesh_processor.py:128-161).  The contract is
+// include/actionmesh_amd.h's; all geometry is fp64, every operation rounded on its own (the file is built with -ffp-contract=off), so
+// positions, quadrics, costs and keys are compared bit for bit with a numpy restatement.
+//
+//   am_decimate_quadrics   one thread per vertex: the area-weighted plane quadrics of its faces, summed in CSR order (a gather)
+//   am_decimate_edges      one thread per edge: lock and link tests, the Cramer solve or the u / v / midpoint fallback, the cost,
+//                          the no-flip test over both stars, the 64-bit key
+//   am_decimate_select     one thread per vertex, twice (m1: min key of its edges; m2: min of m1 over its closed neighbourhood), then
+//                          one thread per edge (selected iff its key is m2 at both ends)
+//   am_decimate_apply      one thread per kept edge: moves u, adds the quadrics, rewrites v -> u in v's corners, marks the two faces
+// No floating-point atomics anywhere (the only atomic is the OR into the flag word).  No index read from memory is ever used as an
+// address before it has been compared with its bound; loops over corners run between CSR offsets that were validated first.
+#include "am_common.h"
+
+#pragma clang fp contract(off)      // the helpers below too, whatever flags the file is built with
+
+namespace {
+
+constexpr int DEC_THREADS = 256;
+constexpr int64_t DEC_MAX = (((int64_t)1 << 31) - 1) / 3;       // 3 * n fits an int32 corner id
+constexpr int64_t NO_KEY = AM_DECIMATE_NO_KEY;
+
+struct vec3 {
+  double x, y, z;
+};
+
+__device__ __forceinline__ vec3 load3(const double* p, int v) {
+  const int64_t o = (int64_t)v * 3;
+  return {p[o], p[o + 1], p[o + 2]};
+}
+__device__ __forceinline__ vec3 sub3(vec3 a, vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ double dot3(vec3 a, vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ vec3 cross3(vec3 a, vec3 b) {
+  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ bool in_range(int i, int64_t n) { return i >= 0 && (int64_t)i < n; }
+
+__device__ __forceinline__ uint32_t mix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// what every kernel knows of the mesh
+struct mesh_view {
+  int64_t n_vertices, n_faces, n_edges;
+  const int32_t* faces;
+  const int32_t* offsets;
+  const int32_t* corners;
+  const int32_t* edges;
+  const int32_t* he2e;
+  int32_t* flag;
+};
+
+// the validated corner range of vertex v (v already inside [0, n_vertices)); an invalid one is empty and raises the flag
+__device__ __forceinline__ bool csr_range(const mesh_view& m, int v, int& begin, int& end) {
+  begin = m.offsets[v];
+  end = m.offsets[v + 1];
+  if (begin < 0 || end < begin || (int64_t)end > 3 * m.n_faces) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_CSR);
+    begin = end = 0;
+    return false;
+  }
+  return true;
+}
+
+// corner j of the range of vertex v: the corner id, or -1 (flag raised) when it is outside [0, 3 n_faces) or names another vertex
+__device__ __forceinline__ int corner_at(const mesh_view& m, int j, int v) {
+  const int c = m.corners[j];
+  if (c < 0 || (int64_t)c >= 3 * m.n_faces || m.faces[c] != v) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_CSR);
+    return -1;
+  }
+  return c;
+}
+
+// the other two vertices of the face of corner c, in face order behind the corner; false (flag raised) when one is out of range
+__device__ __forceinline__ bool corner_others(const mesh_view& m, int c, int& w1, int& w2) {
+  const int f3 = c - c % 3, k = c % 3;
+  w1 = m.faces[f3 + (k + 1) % 3];
+  w2 = m.faces[f3 + (k + 2) % 3];
+  if (!in_range(w1, m.n_vertices) || !in_range(w2, m.n_vertices)) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_FACE);
+    return false;
+  }
+  return true;
+}
+
+// the edge index of half-edge h, which runs between vertices a and b; -1 (flag raised) when the table does not say so
+__device__ __forceinline__ int edge_of(const mesh_view& m, int h, int a, int b) {
+  const int e = m.he2e[h];
+  const int lo = a < b ? a : b, hi = a < b ? b : a;
+  if (!in_range(e, m.n_edges) || m.edges[2 * (int64_t)e] != lo || m.edges[2 * (int64_t)e + 1] != hi) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+    return -1;
+  }
+  return e;
+}
+
+// is w one of the neighbours of v (whose corner range [begin, end) is valid)?
+__device__ bool adjacent(const mesh_view& m, int v, int begin, int end, int w) {
+  bool found = false;
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, v);
+    if (c < 0) continue;
+    const int f3 = c - c % 3, k = c % 3;
+    found = found || m.faces[f3 + (k + 1) % 3] == w || m.faces[f3 + (k + 2) % 3] == w;
+  }
+  return found;
+}
+
+__global__ __launch_bounds__(DEC_THREADS) void decimate_quadrics_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                        double* __restrict__ out_quadrics) {
+#pragma clang fp contract(off)
+  const int64_t v = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  if (v >= m.n_vertices) return;
+  double q[10];
+  for (int i = 0; i < 10; ++i) q[i] = 0.0;
+  int begin, end;
+  csr_range(m, (int)v, begin, end);
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, (int)v);
+    if (c < 0) continue;
+    const int f3 = c - c % 3;
+    const int i0 = m.faces[f3], i1 = m.faces[f3 + 1], i2 = m.faces[f3 + 2];
+    if (!in_range(i0, m.n_vertices) || !in_range(i1, m.n_vertices) || !in_range(i2, m.n_vertices)) {
+      atomicOr(m.flag, AM_DECIMATE_BAD_FACE);
+      continue;
+    }
+    const vec3 p0 = load3(positions, i0), p1 = load3(positions, i1), p2 = load3(positions, i2);
+    const vec3 cr = cross3(sub3(p1, p0), sub3(p2, p0));
+    const double len = sqrt(dot3(cr, cr));
+    if (!(len > AM_MESH_ZERO)) continue;
+    const vec3 n = {cr.x / len, cr.y / len, cr.z / len};
+    const double d = -dot3(n, p0);
+    const double w = len / 2.0;
+    const double p[4] = {n.x, n.y, n.z, d};
+    int t = 0;
+    for (int a = 0; a < 4; ++a)
+      for (int b = a; b < 4; ++b, ++t) q[t] = q[t] + (w * p[a]) * p[b];
+  }
+  for (int i = 0; i < 10; ++i) out_quadrics[v * 10 + i] = q[i];
+}
+
+// y^T Q y with y = (y0, y1, y2, 1)
+__device__ __forceinline__ double quadric_cost(const double* q, vec3 y) {
+  const double r0 = ((q[0] * y.x + q[1] * y.y) + q[2] * y.z) + q[3];
+  const double r1 = ((q[1] * y.x + q[4] * y.y) + q[5] * y.z) + q[6];
+  const double r2 = ((q[2] * y.x + q[5] * y.y) + q[7] * y.z) + q[8];
+  const double r3 = ((q[3] * y.x + q[6] * y.y) + q[8] * y.z) + q[9];
+  return ((r0 * y.x + r1 * y.y) + r2 * y.z) + r3;
+}
+
+// One walk over the corners of endpoint s (partner o) for the lock and - on u's side, with v's range - the link counts.
+// Returns false when the endpoint is locked or a table is inconsistent.
+__device__ bool walk_topology(const mesh_view& m, const int32_t* __restrict__ edge_count, int s, int begin, int end, int o, bool count_link,
+                              int obegin, int oend, int* apex, int& n_apex, int& shared) {
+  bool ok = true;
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, s);
+    if (c < 0) {
+      ok = false;
+      continue;
+    }
+    int w1, w2;
+    if (!corner_others(m, c, w1, w2)) {
+      ok = false;
+      continue;
+    }
+    const int f3 = c - c % 3, k = c % 3;
+    const int e1 = edge_of(m, c, s, w1), e2 = edge_of(m, f3 + (k + 2) % 3, w2, s);
+    if (e1 < 0 || e2 < 0 || edge_count[e1] != 2 || edge_count[e2] != 2) ok = false;
+    if (!count_link) continue;
+    if (w1 == o || w2 == o) {
+      if (n_apex < 2) apex[n_apex] = w1 == o ? w2 : w1;
+      ++n_apex;
+    }
+    if (w1 != o && adjacent(m, o, obegin, oend, w1)) ++shared;
+    if (w2 != o && adjacent(m, o, obegin, oend, w2)) ++shared;
+  }
+  return ok;
+}
+
+// The no-flip test over the faces of s that do not hold o, with s moved to x; also refuses a face that holds both apexes.
+__device__ bool walk_flips(const mesh_view& m, const double* __restrict__ positions, int s, int begin, int end, int o, int a0, int a1,
+                           vec3 x) {
+#pragma clang fp contract(off)
+  bool ok = true;
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, s);
+    if (c < 0) {
+      ok = false;
+      continue;
+    }
+    int w1, w2;
+    if (!corner_others(m, c, w1, w2)) {
+      ok = false;
+      continue;
+    }
+    if (w1 == o || w2 == o) continue;
+    if ((w1 == a0 && w2 == a1) || (w1 == a1 && w2 == a0)) ok = false;
+    const int k = c % 3;
+    vec3 p[3];
+    p[k] = load3(positions, s);
+    p[(k + 1) % 3] = load3(positions, w1);
+    p[(k + 2) % 3] = load3(positions, w2);
+    const vec3 c0 = cross3(sub3(p[1], p[0]), sub3(p[2], p[0]));
+    p[k] = x;
+    const vec3 c1 = cross3(sub3(p[1], p[0]), sub3(p[2], p[0]));
+    if (!(dot3(c0, c1) > (AM_DECIMATE_FLIP * sqrt(dot3(c0, c0))) * sqrt(dot3(c1, c1)))) ok = false;
+  }
+  return ok;
+}
+
+__global__ __launch_bounds__(DEC_THREADS) void decimate_edges_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                     const double* __restrict__ quadrics,
+                                                                     const int32_t* __restrict__ edge_count,
+                                                                     double* __restrict__ out_positions, double* __restrict__ out_cost,
+                                                                     int64_t* __restrict__ out_key) {
+#pragma clang fp contract(off)
+  const int64_t e = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  if (e >= m.n_edges) return;
+  const int u = m.edges[2 * e], v = m.edges[2 * e + 1];
+  vec3 x = {0.0, 0.0, 0.0};
+  double cost = 0.0;
+  int64_t key = NO_KEY;
+  bool ok = true;
+  if (!in_range(u, m.n_vertices) || !in_range(v, m.n_vertices) || u > v) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+    ok = false;
+  }
+  ok = ok && u != v && edge_count[e] == 2;
+  int ub = 0, ue = 0, vb = 0, ve = 0;
+  if (ok) {
+    const bool ru = csr_range(m, u, ub, ue), rv = csr_range(m, v, vb, ve);
+    ok = ru && rv;
+  }
+  int apex[2] = {-1, -1};
+  int n_apex = 0, shared = 0;
+  if (ok) {
+    const bool tu = walk_topology(m, edge_count, u, ub, ue, v, true, vb, ve, apex, n_apex, shared);
+    const bool tv = walk_topology(m, edge_count, v, vb, ve, u, false, 0, 0, apex, n_apex, shared);
+    ok = tu && tv && n_apex == 2 && shared == 4;
+  }
+  if (ok) {
+    const int a0 = apex[0], a1 = apex[1];           // inside [0, n_vertices): corner_others checked them
+    ok = a0 != a1 && a0 != u && a0 != v && a1 != u && a1 != v && m.offsets[a0 + 1] - m.offsets[a0] > 3 &&
+         m.offsets[a1 + 1] - m.offsets[a1] > 3;
+  }
+  if (ok) {
+    double q[10];
+    for (int i = 0; i < 10; ++i) q[i] = quadrics[(int64_t)u * 10 + i] + quadrics[(int64_t)v * 10 + i];
+    const vec3 pu = load3(positions, u), pv = load3(positions, v);
+    const vec3 mid = {(pu.x + pv.x) * 0.5, (pu.y + pv.y) * 0.5, (pu.z + pv.z) * 0.5};
+    const vec3 E = sub3(pv, pu);
+    const double a = q[0], b = q[1], c = q[2], d = q[4], ee = q[5], f = q[7];
+    const double r0 = -q[3], r1 = -q[6], r2 = -q[8];
+    const double m0 = d * f - ee * ee, m1 = b * f - ee * c, m2 = b * ee - d * c;
+    const double det = (a * m0 - b * m1) + c * m2;
+    const double s = r1 * f - ee * r2, t = r1 * ee - d * r2, g = b * r2 - r1 * c;
+    const double dx = (r0 * m0 - b * s) + c * t;
+    const double dy = (a * s - r0 * m1) + c * g;
+    const double dz = (a * (d * r2 - r1 * ee) - b * g) + r0 * m2;
+    const double tr = (a + d) + f;
+    bool solved = false;
+    if (fabs(det) > AM_DECIMATE_COND * ((tr * tr) * tr)) {
+      const vec3 y = {dx / det, dy / det, dz / det};
+      const vec3 off = sub3(y, mid);
+      if (dot3(off, off) <= AM_DECIMATE_REACH * dot3(E, E)) {
+        x = y;
+        cost = quadric_cost(q, y);
+        solved = true;
+      }
+    }
+    if (!solved) {
+      x = pu;
+      cost = quadric_cost(q, pu);
+      const double cv = quadric_cost(q, pv), cm = quadric_cost(q, mid);
+      if (cv < cost) {
+        x = pv;
+        cost = cv;
+      }
+      if (cm < cost) {
+        x = mid;
+        cost = cm;
+      }
+    }
+    cost = cost > 0.0 ? cost : 0.0;
+    const bool fu = walk_flips(m, positions, u, ub, ue, v, apex[0], apex[1], x);
+    const bool fv = walk_flips(m, positions, v, vb, ve, u, apex[0], apex[1], x);
+    if (fu && fv) key = (int64_t)(((uint64_t)__float_as_uint((float)cost) << 32) | (uint64_t)mix32((uint32_t)e));
+  }
+  out_positions[3 * e] = x.x;
+  out_positions[3 * e + 1] = x.y;
+  out_positions[3 * e + 2] = x.z;
+  out_cost[e] = cost;
+  out_key[e] = key;
+}
+
+// pass 0: m1[v] = min key of v's edges;  pass 1: m2[v] = min of m1 over v and its neighbours
+__global__ __launch_bounds__(DEC_THREADS) void decimate_min_kernel(mesh_view m, int pass, const int64_t* __restrict__ in,
+                                                                   int64_t* __restrict__ out) {
+  const int64_t v = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  if (v >= m.n_vertices) return;
+  int64_t best = pass == 0 ? NO_KEY : in[v];
+  int begin, end;
+  csr_range(m, (int)v, begin, end);
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, (int)v);
+    if (c < 0) continue;
+    int w1, w2;
+    if (!corner_others(m, c, w1, w2)) continue;
+    int64_t k1, k2;
+    if (pass == 0) {
+      const int f3 = c - c % 3, k = c % 3;
+      const int e1 = edge_of(m, c, (int)v, w1), e2 = edge_of(m, f3 + (k + 2) % 3, w2, (int)v);
+      k1 = e1 < 0 ? NO_KEY : in[e1];
+      k2 = e2 < 0 ? NO_KEY : in[e2];
+    } else {
+      k1 = in[w1];
+      k2 = in[w2];
+    }
+    best = k1 < best ? k1 : best;
+    best = k2 < best ? k2 : best;
+  }
+  out[v] = best;
+}
+
+__global__ __launch_bounds__(DEC_THREADS) void decimate_pick_kernel(mesh_view m, const int64_t* __restrict__ keys,
+                                                                    const int64_t* __restrict__ m2, uint8_t* __restrict__ out_selected) {
+  const int64_t e = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  if (e >= m.n_edges) return;
+  const int u = m.edges[2 * e], v = m.edges[2 * e + 1];
+  uint8_t sel = 0;
+  if (!in_range(u, m.n_vertices) || !in_range(v, m.n_vertices) || u > v) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+  } else {
+    const int64_t k = keys[e];
+    sel = (k != NO_KEY && k == m2[u] && k == m2[v]) ? 1 : 0;
+  }
+  out_selected[e] = sel;
+}
+
+__global__ __launch_bounds__(DEC_THREADS) void decimate_apply_kernel(mesh_view m, int64_t n_kept, const int32_t* __restrict__ kept,
+                                                                     const double* __restrict__ candidates, double* positions,
+                                                                     double* quadrics, int32_t* faces, int32_t* __restrict__ vertex_map,
+                                                                     uint8_t* __restrict__ out_face_dead) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  if (i >= n_kept) return;
+  const int e = kept[i];
+  if (!in_range(e, m.n_edges)) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_KEPT);
+    return;
+  }
+  const int u = m.edges[2 * (int64_t)e], v = m.edges[2 * (int64_t)e + 1];
+  if (!in_range(u, m.n_vertices) || !in_range(v, m.n_vertices) || u >= v) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+    return;
+  }
+  int begin, end;
+  if (!csr_range(m, v, begin, end)) return;
+  for (int c3 = 0; c3 < 3; ++c3) positions[(int64_t)u * 3 + c3] = candidates[(int64_t)e * 3 + c3];
+  for (int t = 0; t < 10; ++t) quadrics[(int64_t)u * 10 + t] = quadrics[(int64_t)u * 10 + t] + quadrics[(int64_t)v * 10 + t];
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, v);       // m.faces is `faces`: this thread alone rewrites the corners of v
+    if (c < 0) continue;
+    const int f3 = c - c % 3, k = c % 3;
+    if (faces[f3 + (k + 1) % 3] == u || faces[f3 + (k + 2) % 3] == u)
+      out_face_dead[f3 / 3] = 1;
+    else
+      faces[c] = u;
+  }
+  vertex_map[v] = u;
+}
+
+unsigned dec_blocks(int64_t n) { return (unsigned)((n + DEC_THREADS - 1) / DEC_THREADS); }
+
+int check_mesh(const char* who, int64_t n_vertices, int64_t n_faces) {
+  AM_CHECK(n_vertices >= 1 && n_vertices <= DEC_MAX, "%s: %lld vertices outside 1 .. (2^31 - 1) / 3", who, (long long)n_vertices);
+  AM_CHECK(n_faces >= 1 && n_faces <= DEC_MAX, "%s: %lld faces outside 1 .. (2^31 - 1) / 3", who, (long long)n_faces);
+  return AM_OK;
+}
+
+int check_edges(const char* who, int64_t n_edges) {
+  AM_CHECK(n_edges >= 1 && n_edges <= (((int64_t)1 << 31) - 1), "%s: %lld edges outside 1 .. 2^31 - 1", who, (long long)n_edges);
+  return AM_OK;
+}
+
+}  // namespace
+
+extern "C" int am_decimate_quadrics(const am_decimate_quadrics_args* a, void* stream) {
+  AM_CHECK(a != nullptr, "am_decimate_quadrics: null arguments");
+  AM_TRY(check_mesh("am_decimate_quadrics", a->n_vertices, a->n_faces));
+  AM_CHECK(a->positions && a->faces && a->offsets && a->corners && a->out_quadrics && a->out_flag, "am_decimate_quadrics: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, 0, a->faces, a->offsets, a->corners, nullptr, nullptr, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(decimate_quadrics_kernel, dim3(dec_blocks(a->n_vertices)), dim3(DEC_THREADS), 0, st, m, a->positions, a->out_quadrics);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+extern "C" int am_decimate_edges(const am_decimate_edges_args* a, void* stream) {
+  AM_CHECK(a != nullptr, "am_decimate_edges: null arguments");
+  AM_TRY(check_mesh("am_decimate_edges", a->n_vertices, a->n_faces));
+  AM_TRY(check_edges("am_decimate_edges", a->n_edges));
+  AM_CHECK(a->positions && a->quadrics && a->faces && a->offsets && a->corners && a->edges && a->half_edge_to_edge && a->edge_count &&
+               a->out_positions && a->out_cost && a->out_key && a->out_flag,
+           "am_decimate_edges: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(decimate_edges_kernel, dim3(dec_blocks(a->n_edges)), dim3(DEC_THREADS), 0, st, m, a->positions, a->quadrics,
+                     a->edge_count, a->out_positions, a->out_cost, a->out_key);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+extern "C" int am_decimate_select(const am_decimate_select_args* a, void* stream) {
+  AM_CHECK(a != nullptr, "am_decimate_select: null arguments");
+  AM_TRY(check_mesh("am_decimate_select", a->n_vertices, a->n_faces));
+  AM_TRY(check_edges("am_decimate_select", a->n_edges));
+  AM_CHECK(a->faces && a->offsets && a->corners && a->edges && a->half_edge_to_edge && a->keys && a->out_m1 && a->out_m2 &&
+               a->out_selected && a->out_flag,
+           "am_decimate_select: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(decimate_min_kernel, dim3(dec_blocks(a->n_vertices)), dim3(DEC_THREADS), 0, st, m, 0, a->keys, a->out_m1);
+  hipLaunchKernelGGL(decimate_min_kernel, dim3(dec_blocks(a->n_vertices)), dim3(DEC_THREADS), 0, st, m, 1, (const int64_t*)a->out_m1,
+                     a->out_m2);
+  hipLaunchKernelGGL(decimate_pick_kernel, dim3(dec_blocks(a->n_edges)), dim3(DEC_THREADS), 0, st, m, a->keys, (const int64_t*)a->out_m2,
+                     a->out_selected);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+extern "C" int am_decimate_apply(const am_decimate_apply_args* a, void* stream) {
+  AM_CHECK(a != nullptr, "am_decimate_apply: null arguments");
+  AM_TRY(check_mesh("am_decimate_apply", a->n_vertices, a->n_faces));
+  AM_TRY(check_edges("am_decimate_apply", a->n_edges));
+  AM_CHECK(a->n_kept >= 1 && a->n_kept <= a->n_edges, "am_decimate_apply: %lld kept edges outside 1 .. %lld", (long long)a->n_kept,
+           (long long)a->n_edges);
+  AM_CHECK(a->kept && a->edges && a->candidates && a->offsets && a->corners && a->positions && a->quadrics && a->faces && a->vertex_map &&
+               a->out_face_dead && a->out_flag,
+           "am_decimate_apply: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, nullptr, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  AM_HIP(hipMemsetAsync(a->out_face_dead, 0, (size_t)a->n_faces, st));
+  hipLaunchKernelGGL(decimate_apply_kernel, dim3(dec_blocks(a->n_kept)), dim3(DEC_THREADS), 0, st, m, a->n_kept, a->kept, a->candidates,
+                     a->positions, a->quadrics, a->faces, a->vertex_map, a->out_face_dead);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}

@@ -1,0 +1,167 @@
+"""Mesh decimation on tensors: `decimate_mesh`, the reference's `MeshPostprocessor` step that brings every Stage-0 mesh down to
+`face_decimation` faces (actionmesh/preprocessing/mesh_processor.py:128-161, through `trimesh.simplify_quadric_decimation` and
+`fast_simplification`), as rounds of independent quadric edge collapses.  A sequential priority queue does not map to a GPU; a
+round here evaluates every edge at once, picks a set of edges whose closed stars share no face, and collapses them all:
+
+  per mesh   quadrics: every vertex sums the area-weighted plane quadrics of its faces                       ops.decimate_quadrics
+  per round  1. torch plumbing on the mesh's device (it also runs on CPU tensors): the vertex -> corner CSR of the live faces
+                (`mesh_prep.MeshTopology`) and their unique undirected edges - one `torch.unique` of the 3 F half-edge keys, with
+                the inverse (half-edge -> edge) and the use count of every edge;
+             2. every edge gets a candidate position, a cost and a 64-bit key (cost as fp32 bits, then a bijective hash of the
+                edge index), or "not a candidate" when an endpoint is on a border or a non-manifold edge, the link condition
+                fails, or a face of either star would flip or degenerate                                      ops.decimate_edges
+             3. an edge is selected when its key is the smallest among all edges within one edge of either endpoint (two
+                gathers, no atomics): selected edges have neither equal nor adjacent endpoints                ops.decimate_select
+             4. if all of them would undershoot the target, only the ceil((F - target) / 2) smallest keys are kept (one sort);
+             5. the kept edges collapse in place, u <- v with u < v: new position, summed quadrics, v's corners renamed, the
+                edge's two faces dropped                                                                      ops.decimate_apply
+The arithmetic of the four kernels is written out in include/actionmesh_amd.h (csrc/am_decimate.hip); it is fp64 without fused
+multiply-adds and without floating-point atomics, so the result is the same bits on every run and equals a numpy restatement of
+the header (tests/test_mesh_decimate_*).  Every permitted collapse removes exactly two faces, so a mesh that reaches the target ends
+with `target_faces` or `target_faces - 1` faces.  A round that selects nothing ends the loop: the mesh comes back with more faces
+than asked and a logged warning, not an exception (two glued tetrahedra and a mesh that is all border are such inputs).
+
+The kernel calls go through one small backend object (`HipBackend`), so the tests can run the same loop on CPU tensors with a numpy
+restatement in its place.  No CPU backend is shipped.
+
+Device-to-host reads: one for the quadrics' flag, then ONE per round - the flag words of the round's kernels together with the
+number of selected edges, which sizes the apply launch and, as every collapse removes two faces, gives the next face count.
+
+UNPINNED: parity with `fast_simplification` is not attempted.  That library collapses sequentially by a dirty-flag threshold
+schedule and uses unweighted planes; this one uses area-weighted planes and the round schedule above.  What is pinned is the
+header's contract, the invariants (manifoldness, Euler characteristic, no flipped or degenerate face) and the surface distance
+against a sequential greedy decimation with the same cost (profiles/mesh_decimate.json).
+"""
+from __future__ import annotations
+
+import logging
+from typing import Optional
+
+import torch
+
+from . import _lib as L
+from . import mesh_cleanup, ops
+from .mesh_prep import MeshTopology
+
+logger = logging.getLogger(__name__)
+
+NO_KEY = L.DECIMATE_NO_KEY
+MAX_ROUNDS = 4096               # far above what any mesh needs (tens): a guard against a loop that cannot end
+
+
+class HipBackend:
+    """The four kernels of a round (csrc/am_decimate.hip).  `flag`: the caller's int32 (1,) word, which it reads with the round's
+    other figures; quadrics reads its own."""
+
+    quadrics = staticmethod(ops.decimate_quadrics)
+    edges = staticmethod(ops.decimate_edges)
+    select = staticmethod(ops.decimate_select)
+    apply = staticmethod(ops.decimate_apply)
+
+
+class EdgeTables:
+    """The unique undirected edges of a face array: `edges` (E, 2) int32 with u < v in ascending (u, v), `half_edge_to_edge` (3 F,)
+    int32 - half-edge 3 f + k runs from faces[f][k] to faces[f][(k + 1) % 3] - and `edge_count` (E,) int32, the number of half-edges
+    of every edge.  One `torch.unique` (a sort) of the 3 F keys u * n_vertices + v."""
+
+    def __init__(self, faces: torch.Tensor, n_vertices: int):
+        f = faces.long()
+        a, b = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)
+        key = torch.minimum(a, b) * int(n_vertices) + torch.maximum(a, b)
+        uniq, inverse, counts = torch.unique(key, return_inverse=True, return_counts=True)
+        self.edges = torch.stack((uniq // int(n_vertices), uniq % int(n_vertices)), dim=1).to(torch.int32).contiguous()
+        self.half_edge_to_edge = inverse.to(torch.int32).contiguous()
+        self.edge_count = counts.to(torch.int32).contiguous()
+
+
+def _compact_faces(faces: torch.Tensor, dead: torch.Tensor, n_live: int) -> torch.Tensor:
+    """The faces with dead == 0, in order, as a fresh (n_live, 3) tensor, without reading the device: every face is written to its
+    rank among the live ones, a dead one (or one beyond n_live) to a spare row that is cut off."""
+    live = dead == 0
+    rank = torch.cumsum(live, 0) - 1
+    dest = torch.where(live & (rank < n_live), rank, torch.full_like(rank, n_live))
+    out = torch.empty((n_live + 1, 3), dtype=faces.dtype, device=faces.device)
+    out.index_copy_(0, dest, faces)
+    return out[:n_live].contiguous()
+
+
+def decimate_rounds(positions: torch.Tensor, faces: torch.Tensor, target_faces: int, backend=None, observer=None):
+    """The round loop on fp64 positions (V, 3) and int32 faces (F, 3), both contiguous.  Returns (positions (V, 3) fp64 - the
+    original vertex numbering, moved vertices in place -, live faces (F', 3) int32, vertex map (V,) int64: every vertex to the one
+    it was merged into, rounds run).  `observer(round, state dict)` is called after every selection (tests)."""
+    backend = HipBackend if backend is None else backend
+    V, dev = positions.shape[0], positions.device
+    positions, faces = positions.clone(), faces.clone()
+    topology = MeshTopology(faces, V)
+    quadrics = backend.quadrics(positions, faces, topology)
+    merged = torch.arange(V, device=dev)
+    flags = torch.zeros((3,), dtype=torch.int32, device=dev)           # edges, select, apply (the last round's)
+    rounds = 0
+    while faces.shape[0] > target_faces and rounds < MAX_ROUNDS:
+        F = faces.shape[0]
+        if rounds:
+            topology = MeshTopology(faces, V)
+        tables = EdgeTables(faces, V)
+        cand, cost, key = backend.edges(positions, quadrics, faces, topology, tables.edges, tables.half_edge_to_edge, tables.edge_count,
+                                        flag=flags[0:1])
+        m1, m2, selected = backend.select(V, faces, topology, tables.edges, tables.half_edge_to_edge, key, flag=flags[1:2])
+        f_edges, f_select, f_apply, n_selected = torch.cat((flags.long(), selected.sum().reshape(1))).tolist()     # the round's one read
+        if f_edges | f_select | f_apply:
+            raise ValueError("decimate_mesh: " + ops.decimate_flag_message(f_edges | f_select | f_apply, V))
+        if observer is not None:
+            observer(rounds, dict(positions=positions, quadrics=quadrics, faces=faces, topology=topology, tables=tables,
+                                  candidates=cand, cost=cost, key=key, m1=m1, m2=m2, selected=selected))
+        if n_selected == 0:
+            logger.warning("decimate_mesh: no edge can collapse any more; the mesh keeps %d faces, %d were asked for", F, target_faces)
+            break
+        n_kept = min(n_selected, (F - target_faces + 1) // 2)
+        masked = torch.where(selected != 0, key, torch.full_like(key, NO_KEY))
+        kept = torch.sort(masked).indices[:n_kept].to(torch.int32).contiguous()         # the smallest keys first
+        round_map = torch.arange(V, device=dev, dtype=torch.int32)
+        dead = backend.apply(positions, quadrics, faces, topology, tables.edges, cand, kept, round_map, flag=flags[2:3])
+        merged = round_map.long()[merged]
+        faces = _compact_faces(faces, dead, F - 2 * n_kept)
+        rounds += 1
+    bits = int(flags[2])
+    if bits:
+        raise ValueError("decimate_mesh: " + ops.decimate_flag_message(bits, V))
+    return positions, faces, merged, rounds
+
+
+def decimate_mesh(vertices: torch.Tensor, faces: torch.Tensor, target_faces: int = 40_000, return_map: bool = False, backend=None,
+                  return_rounds: bool = False):
+    """Decimate a mesh to `target_faces` faces by quadric edge collapse (the module docstring has the algorithm).  vertices (V, 3)
+    floating point, faces (F, 3) integer, on one device.  As the reference, a mesh with `target_faces` faces or fewer comes back
+    as it is - the same tensors.  Otherwise returns (vertices', faces') in the input dtypes: surviving vertices in their original
+    relative order (an unmoved one keeps its bits), vertices no face references dropped, `target_faces` or `target_faces - 1` faces
+    when the target can be reached.  Border vertices and vertices on non-manifold edges are never moved or removed; a mesh that runs
+    out of permitted collapses comes back with more faces than asked and a logged warning.  With `return_map` also an int64 (V,) map
+    in the ORIGINAL numbering from every vertex to the surviving vertex it was merged into (survivors map to themselves:
+    `map[map] == map`, and `vertices'` are the final positions of the referenced fixed points, in order); with `return_rounds` the
+    number of rounds run.  A face index outside [0, V) raises ValueError.  `backend`: the kernels (tests)."""
+    mesh_cleanup._check_faces(faces, "decimate_mesh")
+    if (not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1
+            or not vertices.is_floating_point()):
+        raise ValueError(f"decimate_mesh: expected non-empty floating-point (V, 3) vertices, got {tuple(getattr(vertices, 'shape', ()))}")
+    if faces.device != vertices.device:
+        raise ValueError(f"decimate_mesh: vertices on {vertices.device}, faces on {faces.device}")
+    target_faces = int(target_faces)
+    if target_faces < 0:
+        raise ValueError(f"decimate_mesh: target_faces {target_faces} is negative")
+    V, dev = vertices.shape[0], vertices.device
+    if faces.shape[0] <= target_faces:
+        out = (vertices, faces)
+        rounds = 0
+        merged = torch.arange(V, device=dev) if return_map else None
+    else:
+        positions, live, merged, rounds = decimate_rounds(vertices.double().contiguous(), faces.to(torch.int32).contiguous(), target_faces,
+                                                          backend=backend)
+        used = torch.zeros(V, dtype=torch.bool, device=dev)
+        used[live.long().reshape(-1)] = True
+        remap = torch.cumsum(used, 0) - 1
+        out = (positions[used].to(vertices.dtype), remap[live.long()].to(faces.dtype))
+    if return_map:
+        out = out + (merged,)
+    if return_rounds:
+        out = out + (rounds,)
+    return out

@@ -4,7 +4,8 @@
 works on instead of a `trimesh.Trimesh`.  Everything stays on the input's device: the geometry (vertex normals, face areas, surface
 samples) is HIP (`ops.vertex_normals`, `ops.face_areas`, `ops.surface_sample`, csrc/am_mesh.hip, contract in
 include/actionmesh_amd.h); the vertex merge, the face filters and the re-indexing are integer keys - `torch.unique` / `sort` /
-`scatter_reduce` on the same device, which also run on CPU tensors.
+`scatter_reduce` on the same device, which also run on CPU tensors.  `process_mesh(..., decimation="hip")` decimates through
+`mesh_decimate.decimate_mesh` (csrc/am_decimate.hip) between the clean-up and the floater removal; without the keyword it does not.
 
 What is PINNED: the contract written in the header and in the docstrings here, against numpy fp64 restatements (tests/test_mesh_prep_*).
 trimesh is not installable where this was written, so these are a recollection of its behaviour and UNPINNED:
@@ -163,16 +164,24 @@ def merge_and_clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, return_ind
     return new_vertices, new_faces, merge_map, faces
 
 
-def process_mesh(vertices: torch.Tensor, faces: torch.Tensor, face_decimation: int = -1, floaters_threshold: float = 0.0):
-    """`MeshPostprocessor.process_mesh` on tensors: the four clean-up steps of `merge_and_clean_mesh`, then - as the reference, only
-    with floaters_threshold > 0 - `mesh_cleanup.remove_floaters`.  Returns (vertices, faces).  Quadric decimation is not built: a
-    `face_decimation` other than -1 below the mesh's face count raises NotImplementedError (at or above it the reference skips the
-    decimation too)."""
+def process_mesh(vertices: torch.Tensor, faces: torch.Tensor, face_decimation: int = -1, floaters_threshold: float = 0.0,
+                 decimation: Optional[str] = None):
+    """`MeshPostprocessor.process_mesh` on tensors, in the reference's order: the four clean-up steps of `merge_and_clean_mesh`, the
+    quadric decimation to `face_decimation` faces, then - as the reference, only with floaters_threshold > 0 -
+    `mesh_cleanup.remove_floaters`.  Returns (vertices, faces).  `decimation` says who decimates: None (the default) nobody - a
+    `face_decimation` other than -1 below the mesh's face count then raises NotImplementedError (at or above it the reference skips
+    the decimation too); "hip": `mesh_decimate.decimate_mesh`, rounds of parallel edge collapses on the mesh's device (not the
+    reference's `fast_simplification` schedule: mesh_decimate.py)."""
     _check_mesh(vertices, faces, "process_mesh")
+    if decimation not in (None, "hip"):
+        raise ValueError(f"process_mesh: decimation must be None or 'hip', got {decimation!r}")
     vertices, faces, _, _ = _clean(vertices, faces)
     if face_decimation != -1 and faces.shape[0] > face_decimation:
-        raise NotImplementedError(f"process_mesh: face_decimation={face_decimation} asks for quadric decimation of a mesh of "
-                                  f"{faces.shape[0]} faces, which is not built; pass face_decimation=-1")
+        if decimation is None:
+            raise NotImplementedError(f"process_mesh: face_decimation={face_decimation} asks for quadric decimation of a mesh of "
+                                      f"{faces.shape[0]} faces; pass decimation='hip' for it, or face_decimation=-1")
+        from . import mesh_decimate
+        vertices, faces = mesh_decimate.decimate_mesh(vertices, faces, target_faces=face_decimation)
     if floaters_threshold > 0.0:
         vertices, faces = mesh_cleanup.remove_floaters(vertices, faces, threshold=floaters_threshold)
     return vertices, faces

@@ -861,6 +861,186 @@ def surface_sample(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tenso
     return points, idx, normals
 
 
+# ---- mesh decimation (csrc/am_decimate.hip; the contract is the header's, the round loop is mesh_decimate.py's) ----------------------
+_DECIMATE_FLAGS = {L.DECIMATE_BAD_FACE: "a face names a vertex outside [0, {V})",
+                   L.DECIMATE_BAD_CSR: "the vertex -> corner CSR does not belong to these faces",
+                   L.DECIMATE_BAD_EDGE: "the edge tables do not belong to these faces",
+                   L.DECIMATE_BAD_KEPT: "a kept edge index is outside the edge list"}
+
+
+def decimate_flag_message(bits: int, V: int) -> str:
+    """What the set bits of an am_decimate_* flag word say."""
+    return "; ".join(msg.format(V=V) for bit, msg in _DECIMATE_FLAGS.items() if bits & bit)
+
+
+def _decimate_flag(what: str, flag: Optional[torch.Tensor], dev) -> Tuple[torch.Tensor, bool]:
+    """The flag word of one call: the caller's int32 (1,) tensor - who then reads it, together with whatever else it needs from the
+    device - or a fresh one that the wrapper reads itself."""
+    if flag is None:
+        return torch.empty((1,), dtype=torch.int32, device=dev), True
+    _need(flag, torch.int32, f"{what}: flag")
+    if flag.numel() != 1 or flag.device != dev:
+        raise ValueError(f"{what}: the flag must be one int32 on {dev}")
+    return flag, False
+
+
+def _decimate_mesh(what: str, faces: torch.Tensor, topology, V: int) -> int:
+    """The checks on (faces, CSR) the four entry points share.  Returns F."""
+    if not isinstance(faces, torch.Tensor):
+        raise TypeError(f"{what}: expected torch tensors")
+    _need(faces, torch.int32, f"{what}: faces")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"{what}: expected non-empty (F, 3) faces, got {tuple(faces.shape)}")
+    F = faces.shape[0]
+    if not 1 <= V <= _MESH_MAX or F > _MESH_MAX:
+        raise ValueError(f"{what}: {V} vertices and {F} faces are outside 1 .. (2^31 - 1) / 3")
+    offsets = _need(topology.offsets, torch.int32, f"{what}: topology.offsets")
+    corners = _need(topology.corners, torch.int32, f"{what}: topology.corners")
+    if offsets.numel() != V + 1 or corners.numel() != 3 * F:
+        raise ValueError(f"{what}: the topology is of {offsets.numel() - 1} vertices and {corners.numel() // 3} faces, the mesh has "
+                         f"{V} and {F}")
+    if offsets.device != faces.device or corners.device != faces.device:
+        raise ValueError(f"{what}: the topology is not on {faces.device}")
+    return F
+
+
+def _decimate_rows(what: str, t: torch.Tensor, dtype, shape, dev) -> torch.Tensor:
+    _need(t, dtype, what)
+    if tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError(f"{what}: {tuple(t.shape)} on {t.device}, expected {tuple(shape)} on {dev}")
+    return t
+
+
+def _decimate_edge_tables(what: str, a, edges: torch.Tensor, half_edge_to_edge: Optional[torch.Tensor], F: int, dev) -> int:
+    """Checks and sets edges (E, 2) and, when given, half_edge_to_edge (3 F).  Returns E."""
+    if not isinstance(edges, torch.Tensor) or edges.dim() != 2 or edges.shape[1] != 2 or edges.shape[0] < 1:
+        raise ValueError(f"{what}: expected non-empty (E, 2) edges, got {tuple(getattr(edges, 'shape', ()))}")
+    E = edges.shape[0]
+    _decimate_rows(f"{what}: edges", edges, torch.int32, (E, 2), dev)
+    a.n_edges, a.edges = E, edges.data_ptr()
+    if half_edge_to_edge is not None:
+        a.half_edge_to_edge = _decimate_rows(f"{what}: half_edge_to_edge", half_edge_to_edge, torch.int32, (3 * F,), dev).data_ptr()
+    return E
+
+
+def decimate_quadrics(positions: torch.Tensor, faces: torch.Tensor, topology, out: Optional[torch.Tensor] = None,
+                      flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_decimate_quadrics: the area-weighted plane quadrics (V, 10) fp64 of every vertex, summed over its faces in the CSR order
+    of `topology` (a `mesh_prep.MeshTopology` of `faces`).  positions (V, 3) fp64, faces (F, 3) int32.  Without `flag`, ONE
+    device-to-host read behind the launch turns a bad face index or CSR into a ValueError; with the caller's int32 (1,) `flag`
+    nothing is read here."""
+    what = "decimate_quadrics"
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
+        raise ValueError(f"{what}: expected non-empty (V, 3) positions, got {tuple(getattr(positions, 'shape', ()))}")
+    V, dev = positions.shape[0], positions.device
+    _need(positions, torch.float64, f"{what}: positions")
+    F = _decimate_mesh(what, faces, topology, V)
+    if faces.device != dev:
+        raise ValueError(f"{what}: positions on {dev}, faces on {faces.device}")
+    out = _mesh_out(f"{what}: out", out, (V, 10), torch.float64, dev)
+    flag, own = _decimate_flag(what, flag, dev)
+    a = L.AmDecimateQuadricsArgs()
+    a.positions, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), V, F, faces.data_ptr()
+    a.offsets, a.corners, a.out_quadrics, a.out_flag = topology.offsets.data_ptr(), topology.corners.data_ptr(), out.data_ptr(), flag.data_ptr()
+    _call(positions, None, "am_decimate_quadrics", C.byref(a))
+    if own and int(flag):
+        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    return out
+
+
+def decimate_edges(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch.Tensor, topology, edges: torch.Tensor,
+                   half_edge_to_edge: torch.Tensor, edge_count: torch.Tensor, out_positions: Optional[torch.Tensor] = None,
+                   out_cost: Optional[torch.Tensor] = None, out_key: Optional[torch.Tensor] = None,
+                   flag: Optional[torch.Tensor] = None):
+    """am_decimate_edges: for every undirected edge (E, 2) int32 of the live faces, the position a collapse would give the
+    surviving vertex (E, 3) fp64, its quadric cost (E,) fp64, and the int64 key (E,) - `_lib.DECIMATE_NO_KEY` where the edge is not a
+    candidate (the tests are the header's).  half_edge_to_edge (3 F,) and edge_count (E,) int32.  `flag` as in decimate_quadrics."""
+    what = "decimate_edges"
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
+        raise ValueError(f"{what}: expected non-empty (V, 3) positions, got {tuple(getattr(positions, 'shape', ()))}")
+    V, dev = positions.shape[0], positions.device
+    _need(positions, torch.float64, f"{what}: positions")
+    _decimate_rows(f"{what}: quadrics", quadrics, torch.float64, (V, 10), dev)
+    F = _decimate_mesh(what, faces, topology, V)
+    if faces.device != dev:
+        raise ValueError(f"{what}: positions on {dev}, faces on {faces.device}")
+    a = L.AmDecimateEdgesArgs()
+    E = _decimate_edge_tables(what, a, edges, half_edge_to_edge, F, dev)
+    a.edge_count = _decimate_rows(f"{what}: edge_count", edge_count, torch.int32, (E,), dev).data_ptr()
+    cand = _mesh_out(f"{what}: out_positions", out_positions, (E, 3), torch.float64, dev)
+    cost = _mesh_out(f"{what}: out_cost", out_cost, (E,), torch.float64, dev)
+    key = _mesh_out(f"{what}: out_key", out_key, (E,), torch.int64, dev)
+    flag, own = _decimate_flag(what, flag, dev)
+    a.positions, a.quadrics, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), quadrics.data_ptr(), V, F, faces.data_ptr()
+    a.offsets, a.corners = topology.offsets.data_ptr(), topology.corners.data_ptr()
+    a.out_positions, a.out_cost, a.out_key, a.out_flag = cand.data_ptr(), cost.data_ptr(), key.data_ptr(), flag.data_ptr()
+    _call(positions, None, "am_decimate_edges", C.byref(a))
+    if own and int(flag):
+        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    return cand, cost, key
+
+
+def decimate_select(n_vertices: int, faces: torch.Tensor, topology, edges: torch.Tensor, half_edge_to_edge: torch.Tensor,
+                    keys: torch.Tensor, out_m1: Optional[torch.Tensor] = None, out_m2: Optional[torch.Tensor] = None,
+                    out_selected: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None):
+    """am_decimate_select: the independent set of one round.  Returns (m1 (V,) int64: the smallest key among a vertex's edges, m2
+    (V,) int64: the smallest m1 over its closed neighbourhood, selected (E,) uint8: 1 where the edge's key is m2 at both of its ends).
+    `flag` as in decimate_quadrics."""
+    what = "decimate_select"
+    V = int(n_vertices)
+    F = _decimate_mesh(what, faces, topology, V)
+    dev = faces.device
+    a = L.AmDecimateSelectArgs()
+    E = _decimate_edge_tables(what, a, edges, half_edge_to_edge, F, dev)
+    _decimate_rows(f"{what}: keys", keys, torch.int64, (E,), dev)
+    m1 = _mesh_out(f"{what}: out_m1", out_m1, (V,), torch.int64, dev)
+    m2 = _mesh_out(f"{what}: out_m2", out_m2, (V,), torch.int64, dev)
+    sel = _mesh_out(f"{what}: out_selected", out_selected, (E,), torch.uint8, dev)
+    flag, own = _decimate_flag(what, flag, dev)
+    a.n_vertices, a.n_faces, a.faces, a.offsets, a.corners = V, F, faces.data_ptr(), topology.offsets.data_ptr(), topology.corners.data_ptr()
+    a.keys, a.out_m1, a.out_m2, a.out_selected, a.out_flag = keys.data_ptr(), m1.data_ptr(), m2.data_ptr(), sel.data_ptr(), flag.data_ptr()
+    _call(faces, None, "am_decimate_select", C.byref(a))
+    if own and int(flag):
+        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    return m1, m2, sel
+
+
+def decimate_apply(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch.Tensor, topology, edges: torch.Tensor,
+                   candidates: torch.Tensor, kept: torch.Tensor, vertex_map: torch.Tensor, out_face_dead: Optional[torch.Tensor] = None,
+                   flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_decimate_apply: collapse the edges `kept` (K,) int32 - indices into `edges`, a subset of ONE decimate_select's selection -
+    IN PLACE: positions[u] = candidates[e], quadrics[u] += quadrics[v], v -> u in the faces of v, vertex_map[v] = u (vertex_map (V,)
+    int32).  `topology` is the CSR of the faces BEFORE the call.  Returns face_dead (F,) uint8: 1 on the two faces of every collapsed
+    edge, which the caller drops.  `flag` as in decimate_quadrics."""
+    what = "decimate_apply"
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
+        raise ValueError(f"{what}: expected non-empty (V, 3) positions, got {tuple(getattr(positions, 'shape', ()))}")
+    V, dev = positions.shape[0], positions.device
+    _need(positions, torch.float64, f"{what}: positions")
+    _decimate_rows(f"{what}: quadrics", quadrics, torch.float64, (V, 10), dev)
+    F = _decimate_mesh(what, faces, topology, V)
+    if faces.device != dev:
+        raise ValueError(f"{what}: positions on {dev}, faces on {faces.device}")
+    a = L.AmDecimateApplyArgs()
+    E = _decimate_edge_tables(what, a, edges, None, F, dev)
+    _decimate_rows(f"{what}: candidates", candidates, torch.float64, (E, 3), dev)
+    if not isinstance(kept, torch.Tensor) or kept.dim() != 1 or not 1 <= kept.numel() <= E:
+        raise ValueError(f"{what}: expected 1 .. {E} kept edge indices, got {tuple(getattr(kept, 'shape', ()))}")
+    K = kept.numel()
+    _decimate_rows(f"{what}: kept", kept, torch.int32, (K,), dev)
+    _decimate_rows(f"{what}: vertex_map", vertex_map, torch.int32, (V,), dev)
+    dead = _mesh_out(f"{what}: out_face_dead", out_face_dead, (F,), torch.uint8, dev)
+    flag, own = _decimate_flag(what, flag, dev)
+    a.n_vertices, a.n_faces, a.n_kept, a.kept, a.candidates = V, F, K, kept.data_ptr(), candidates.data_ptr()
+    a.offsets, a.corners = topology.offsets.data_ptr(), topology.corners.data_ptr()
+    a.positions, a.quadrics, a.faces, a.vertex_map = positions.data_ptr(), quadrics.data_ptr(), faces.data_ptr(), vertex_map.data_ptr()
+    a.out_face_dead, a.out_flag = dead.data_ptr(), flag.data_ptr()
+    _call(positions, None, "am_decimate_apply", C.byref(a))
+    if own and int(flag):
+        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    return dead
+
+
 # ---- exact-fp32 path (csrc/am_f32.hip, am_elementwise.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              gelu: bool = False, out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:

@@ -781,6 +781,153 @@ typedef struct {
 } am_surface_sample_args;
 int am_surface_sample(const am_surface_sample_args* args, void* stream);
 
+/* Mesh decimation (INTEGRATION seam S10): the four kernels behind one ROUND of the parallel quadric edge collapse of
+ * actionmesh_amd/mesh_decimate.py, which stands in for the reference's `trimesh.simplify_quadric_decimation`
+ * (mesh_processor.py:128-161).  The round loop, the sorts and the compaction are the caller's; a round is
+ *   edge evaluation (am_decimate_edges) -> selection of an independent set (am_decimate_select) -> apply (am_decimate_apply),
+ * behind am_decimate_quadrics once per mesh.  ALL arithmetic is fp64, every operation rounded on its own in the order written (no
+ * fused multiply-add), a sum of three terms is (x + y) + z, a dot product is (ax bx + ay by) + az bz, a cross product
+ * a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx).  There are no floating-point atomics: the result is the same bits on every
+ * run, and a numpy restatement of the lines below reproduces it bit for bit (tests/test_mesh_decimate_*).
+ *
+ * Tables the caller supplies (device, int32 unless noted; n_vertices, n_faces <= (2^31 - 1) / 3, n_edges <= 2^31 - 1):
+ *   positions  fp64 (n_vertices, 3);   quadrics fp64 (n_vertices, 10);   faces (n_faces, 3), the LIVE faces;
+ *   offsets, corners   the vertex -> corner CSR of `faces` as am_vertex_normals defines it (ascending corner id);
+ *   edges      (n_edges, 2): the unique undirected edges { u, v } of the faces with u < v (a face with a repeated index may give
+ *              u == v: such an edge is never a candidate);
+ *   half_edge_to_edge  [3 n_faces]: half-edge 3 f + k runs from faces[f][k] to faces[f][(k + 1) % 3]; the entry is the index of its
+ *              undirected edge;
+ *   edge_count [n_edges]: how many half-edges map to the edge.
+ *
+ * A quadric is the symmetric 4 x 4 matrix of a weighted squared plane distance, stored as its upper triangle
+ *   q = { xx, xy, xz, xw, yy, yz, yw, zz, zw, ww },   indices (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3).
+ * am_decimate_quadrics, per vertex:  Q = 0;  for each corner of the vertex in CSR order, with (p0, p1, p2) the vertices of its face
+ * in face order:
+ *   c = (p1 - p0) x (p2 - p0);  len = sqrt(c . c);  a face with len <= AM_MESH_ZERO adds nothing;  n = c / len (three divisions)
+ *   d = -(n . p0);  w = len / 2;  p = (nx, ny, nz, d);  Q[i,j] = Q[i,j] + (w * p[i]) * p[j]     for the ten (i, j) in the order above.
+ * Quadrics are never recomputed: a collapse u <- v sets Q_u = Q_u + Q_v, element by element.
+ *
+ * am_decimate_edges, per edge e = (u, v).  `neighbours of s` are the other two vertices of every face of s; the `apexes` a0, a1
+ * are the third vertices of the faces that hold both u and v.  The edge passes the TOPOLOGY tests when all of these hold:
+ *   lock   u < v, edge_count[e] == 2, and every edge of every face of u and of v that touches u respectively v (the half-edges
+ *          3 f + k and 3 f + (k + 2) % 3 of a corner 3 f + k) has edge_count == 2: a vertex on a border or on a non-manifold edge is
+ *          never moved or removed;
+ *   link   exactly two faces hold both u and v, a0 != a1, neither apex is u or v; over the corners of u, the neighbours w != v that
+ *          are also neighbours of v number exactly 4 (each shared neighbour is met twice, so: the apexes and nobody else); both
+ *          apexes have valence offsets[a + 1] - offsets[a] > 3; and no OTHER face of u or v holds both apexes.
+ * An edge that fails them gets out_positions = (0, 0, 0), out_cost = 0 and the key AM_DECIMATE_NO_KEY.  Otherwise, with
+ * Q = Q_u + Q_v (ten additions), pu, pv the endpoints, mid = (pu + pv) * 0.5 per component, E = pv - pu:
+ *   the 3 x 3 block and right-hand side:  a = Q0, b = Q1, c = Q2, d = Q4, e = Q5, f = Q7;  r = (-Q3, -Q6, -Q8)
+ *   m0 = d f - e e;  m1 = b f - e c;  m2 = b e - d c;  det = (a m0 - b m1) + c m2;   s = r1 f - e r2;  t = r1 e - d r2;  g = b r2 - r1 c
+ *   dx = (r0 m0 - b s) + c t;   dy = (a s - r0 m1) + c g;   dz = (a (d r2 - r1 e) - b g) + r0 m2;   x = (dx, dy, dz) / det
+ *   conditioning rule (scale-free):  tr = (a + d) + f;  the solve is used only when |det| > AM_DECIMATE_COND * ((tr tr) tr)
+ *   and (x - mid) . (x - mid) <= AM_DECIMATE_REACH * (E . E)        (a NaN fails the comparison: within two edge lengths of mid)
+ *   cost(y) = ((r0 y0 + r1 y1) + r2 y2) + r3,  r_i = ((Q[i,0] y0 + Q[i,1] y1) + Q[i,2] y2) + Q[i,3]          (y^T Q y, y = (y0 y1 y2 1))
+ *   otherwise x = pu, replaced by pv when cost(pv) < cost(x), then by mid when cost(mid) < cost(x)      (ties: u, v, mid)
+ *   out_cost = cost(x) when that is > 0, else 0.
+ *   no flip: for every face of u without v, and of v without u, with (p0, p1, p2) its vertices in face order and (p0', p1', p2')
+ *   the same with the endpoint replaced by x:  c0 = (p1 - p0) x (p2 - p0), c1 likewise;  the edge survives only when
+ *   c0 . c1 > (AM_DECIMATE_FLIP * sqrt(c0 . c0)) * sqrt(c1 . c1) for each of them (a degenerate old or new face fails it).
+ *   out_key = (uint32 bits of (float)out_cost) << 32 | mix32(e) as int64 when the edge survives, else AM_DECIMATE_NO_KEY (the
+ *   position and cost stay).  The fp32 bits of a non-negative number order as the number does, and
+ *   mix32(h):     h ^= h >> 16;  h *= 0x85ebca6b;  h ^= h >> 13;  h *= 0xc2b2ae35;  h ^= h >> 16                (uint32, wrapping)
+ *   is a bijection, so keys are unique; the hash keeps equal costs (flat regions, regular tessellations) from ordering the
+ *   selection along the edge numbering.
+ *
+ * am_decimate_select (three launches, gathers only):  m1[v] = min key over the edges that touch v (NO_KEY without one);
+ *   m2[v] = min(m1[v], m1[w]) over the neighbours w of v;   out_selected[e] = 1 when key[e] != NO_KEY and key[e] == m2[u] == m2[v],
+ *   else 0.  Endpoints of two selected edges are neither equal nor adjacent, so their closed stars share no face.
+ *
+ * am_decimate_apply, per kept edge index kept[i] = e = (u, v), for a caller-chosen SUBSET of the selected edges: positions[u] =
+ *   candidate[e];  quadrics[u] = quadrics[u] + quadrics[v];  every face of v that also holds u gets out_face_dead = 1, in every
+ *   other face of v the corner v becomes u;  vertex_map[v] = u.  positions, quadrics, faces and vertex_map are updated in place;
+ *   out_face_dead is cleared first.  Edges that were not selected together may race: that is the caller's responsibility, but no
+ *   index is used unchecked.
+ *
+ * out_flag, device int32[1], cleared by each call; the caller reads it with the result and treats a non-zero value as failure:
+ *   AM_DECIMATE_BAD_FACE  a face names a vertex outside [0, n_vertices);
+ *   AM_DECIMATE_BAD_CSR   offsets not ascending inside [0, 3 n_faces], a corner outside [0, 3 n_faces) or one that does not name the
+ *                         vertex it is listed under;
+ *   AM_DECIMATE_BAD_EDGE  an edge endpoint outside [0, n_vertices) or u > v, a half_edge_to_edge entry outside [0, n_edges) or one
+ *                         whose edge is not that half-edge's;
+ *   AM_DECIMATE_BAD_KEPT  a kept index outside [0, n_edges).
+ * Every index read from memory is compared with its bound BEFORE it is used as an address; what a bad index would have
+ * contributed is left out. */
+#define AM_DECIMATE_COND 1e-10
+#define AM_DECIMATE_REACH 4.0
+#define AM_DECIMATE_FLIP 0.2
+#define AM_DECIMATE_NO_KEY INT64_MAX
+#define AM_DECIMATE_BAD_FACE 1
+#define AM_DECIMATE_BAD_CSR 2
+#define AM_DECIMATE_BAD_EDGE 4
+#define AM_DECIMATE_BAD_KEPT 8
+typedef struct {
+  const double* positions;
+  int64_t n_vertices;           /* >= 1 */
+  int64_t n_faces;              /* >= 1 */
+  const int32_t* faces;
+  const int32_t* offsets;
+  const int32_t* corners;
+  double* out_quadrics;         /* (n_vertices, 10) */
+  int32_t* out_flag;
+} am_decimate_quadrics_args;
+int am_decimate_quadrics(const am_decimate_quadrics_args* args, void* stream);
+
+typedef struct {
+  const double* positions;
+  const double* quadrics;
+  int64_t n_vertices;
+  int64_t n_faces;
+  int64_t n_edges;              /* >= 1 */
+  const int32_t* faces;
+  const int32_t* offsets;
+  const int32_t* corners;
+  const int32_t* edges;
+  const int32_t* half_edge_to_edge;
+  const int32_t* edge_count;
+  double* out_positions;        /* (n_edges, 3) */
+  double* out_cost;             /* [n_edges] */
+  int64_t* out_key;             /* [n_edges] */
+  int32_t* out_flag;
+} am_decimate_edges_args;
+int am_decimate_edges(const am_decimate_edges_args* args, void* stream);
+
+typedef struct {
+  int64_t n_vertices;
+  int64_t n_faces;
+  int64_t n_edges;
+  const int32_t* faces;
+  const int32_t* offsets;
+  const int32_t* corners;
+  const int32_t* edges;
+  const int32_t* half_edge_to_edge;
+  const int64_t* keys;
+  int64_t* out_m1;              /* [n_vertices] */
+  int64_t* out_m2;              /* [n_vertices] */
+  uint8_t* out_selected;        /* [n_edges] */
+  int32_t* out_flag;
+} am_decimate_select_args;
+int am_decimate_select(const am_decimate_select_args* args, void* stream);
+
+typedef struct {
+  int64_t n_vertices;
+  int64_t n_faces;
+  int64_t n_edges;
+  int64_t n_kept;               /* >= 1 */
+  const int32_t* kept;          /* [n_kept] edge indices */
+  const int32_t* edges;
+  const double* candidates;     /* (n_edges, 3): am_decimate_edges' out_positions */
+  const int32_t* offsets;
+  const int32_t* corners;
+  double* positions;            /* in place */
+  double* quadrics;             /* in place */
+  int32_t* faces;               /* in place */
+  int32_t* vertex_map;          /* [n_vertices], in place */
+  uint8_t* out_face_dead;       /* [n_faces] */
+  int32_t* out_flag;
+} am_decimate_apply_args;
+int am_decimate_apply(const am_decimate_apply_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@
 at the shipped shapes (Stage I: N = 2048 tokens, width 2048, 16 heads, 21 layers; Stage II: width 1024, 16 + 1 blocks) with
 random-init weights.  The anchor is a torus mesh; its per-window vertex features (positions + angle-weighted vertex normals) are
 `actionmesh_amd.VertexFeatures` on the device (`--features analytic`: the earlier stand-in, normalised positions, no kernel).  What
-stays on the reference's CPU path (and is not timed here): background removal, TripoSG Stage 0, quadric decimation.  Prints one JSON line (secondary metric:
+stays on the reference's CPU path (and is not timed here): background removal, TripoSG Stage 0.  Prints one JSON line (secondary metric:
 BASELINE.json's "end-to-end video->4D wall-clock" restricted to the stages this repository implements).
 
     python tools/e2e_synthetic.py [--frames 16] [--steps 30] [--vertices 50000] [--tiny]
@@ -21,6 +21,11 @@ BASELINE.json's "end-to-end video->4D wall-clock" restricted to the stages this 
                                                   (duplicated seam vertices, degenerate and duplicate faces, GLB units) that goes through
                                                   merge_and_clean_mesh -> normalize_mesh -> sample_surface(16384) in front of Stage II and
                                                   through denormalize_mesh + expand_to_original behind it (pipeline_with_3d.py:92-104, 229-238)
+    python tools/e2e_synthetic.py --config 3 --face-decimation N      opt-in: the dirty torus goes through the reference's Stage-0 post-processing
+                                                  instead - process_mesh(face_decimation=N, decimation="hip"): clean-up, then the quadric decimation
+                                                  on the device (actionmesh_amd/mesh_decimate.py; MeshPostprocessor.process_mesh, pipeline.py:418) -
+                                                  and Stage II animates the decimated mesh; a decimated mesh has no map back to the given one, so
+                                                  the animation stays on it
 Both are PLUMBING records on random-init weights (no checkpoint is reachable offline): not BASELINE's end-to-end metric.
 """
 import argparse
@@ -120,7 +125,7 @@ def dirty_mesh(v, f, cols: int, seed: int = 2):
 
 
 def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44, clip: str = None, label: str = None,
-        raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False):
+        raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False, face_decimation: int = 0):
     from actionmesh_amd import LatentBank, generate_3d_latents, generate_vertex_animation
     from actionmesh_amd import mesh_prep as MP
     t_build = time.perf_counter()
@@ -166,12 +171,20 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
         MP.sample_surface(MP.normalize_mesh(warm_v)[0], warm_f, 16, seed=0)
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
-        anchor_v, faces, merge_map, pre_faces = MP.merge_and_clean_mesh(raw_v, raw_f)
+        if face_decimation:    # the reference's Stage-0 post-processing: clean-up, then the quadric decimation, both on the device
+            anchor_v, faces = MP.process_mesh(raw_v, raw_f, face_decimation=face_decimation, decimation="hip")
+            merge_map = pre_faces = None
+        else:
+            anchor_v, faces, merge_map, pre_faces = MP.merge_and_clean_mesh(raw_v, raw_f)
         anchor_v, norm_params = MP.normalize_mesh(anchor_v)
         cloud = MP.sample_surface(anchor_v, faces, 16384, seed=0, with_normals=True, dtype=torch.bfloat16)   # the VAE encoder's input
         torch.cuda.synchronize(dev)
         t_prep = time.perf_counter() - t0
-        assert anchor_v.shape[0] == vertices and faces.shape[0] == len(clean_f) and raw_v.shape[0] > vertices, (anchor_v.shape, faces.shape)
+        if face_decimation:
+            assert faces.shape[0] in (face_decimation, face_decimation - 1) and int(faces.max()) == anchor_v.shape[0] - 1, (anchor_v.shape, faces.shape)
+            vertices = anchor_v.shape[0]
+        else:
+            assert anchor_v.shape[0] == vertices and faces.shape[0] == len(clean_f) and raw_v.shape[0] > vertices, (anchor_v.shape, faces.shape)
         assert cloud.shape == (1, 16384, 6) and bool(torch.isfinite(cloud.float()).all())
         pts = anchor_v.float()
     else:
@@ -209,7 +222,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
     import tempfile
     from actionmesh_amd import actionbench, create_animated_glb, save_deformation, save_meshes
     t_back = None
-    if mesh_prep:          # back to the given mesh: model units, the original (pre-merge) topology
+    if mesh_prep and merge_map is not None:          # back to the given mesh: model units, the original (pre-merge) topology
         (verts_out, t_back) = stage(lambda: MP.expand_to_original(MP.denormalize_mesh(verts.double(), norm_params), merge_map).float())
         assert verts_out.shape == (frames, raw_v.shape[0], 3) and float((verts_out[0] - raw_v).abs().max()) < 1e-5
         verts, faces = verts_out, pre_faces
@@ -236,13 +249,15 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             "seconds": {"context_encoder": round(t_enc, 4), "stage_I": round(t_s1, 3), "stage_II": round(t_s2, 3),
                         "model_build_and_upload": round(t_build, 1),
                         **({"preprocess_s": round(t_pre, 4)} if t_pre is not None else {}),
-                        **({"mesh_prep": round(t_prep, 4), "mesh_back_to_original": round(t_back, 4)} if mesh_prep else {}),
+                        **({"mesh_prep": round(t_prep, 4)} if mesh_prep else {}),
+                        **({"mesh_back_to_original": round(t_back, 4)} if t_back is not None else {}),
                         "output_files_host_side": round(t_out, 3), "chamfer_metrics": round(t_metric, 4)},
             "preview_video_s": round(t_preview, 3),          # grid_normal.* (HipVisualizer), written into the output files above
             "output_files_mb": round(out_bytes / 1e6, 1),
             "config": {"workload": f"{frames} frames, {n_win} AR window(s) of {window}, {steps} denoise steps, N={n_tokens} tokens, "
                                    f"{vertices} vertices, {'tiny' if tiny else 'shipped'} model shapes, random-init weights"
-                                   + (f", frames = the reference's {clip} clip" if clip else ", random frames")},
+                                   + (f", frames = the reference's {clip} clip" if clip else ", random frames")
+                                   + (f", decimated to {faces.shape[0]} faces on the device" if face_decimation else "")},
             **({"baseline_config": label} if label else {}),
             "context_rms": round(float(context.float().pow(2).mean().sqrt()), 4), "latents_rms": round(float(lat[1:].float().pow(2).mean().sqrt()), 4)}
 
@@ -259,10 +274,14 @@ def main():
     ap.add_argument("--features", default="hip", choices=["hip", "analytic"],
                     help="Stage II's vertex features: VertexFeatures on the device (default), or the earlier stand-in (normalised positions)")
     ap.add_argument("--mesh-prep", action="store_true", help="start from a dirty mesh and run the {video+3D} mesh glue around Stage II (implied by --config 3)")
+    ap.add_argument("--face-decimation", type=int, default=0,
+                    help="with --mesh-prep / --config 3: decimate the cleaned mesh to this many faces on the device (process_mesh(decimation='hip'))")
     ap.add_argument("--config", type=int, default=None, choices=[1, 3], help="BASELINE.json configs[1] / configs[3] as a plumbing record (see the module docstring)")
     a = ap.parse_args()
     if a.raw_frames and not (a.clip or a.config):
         ap.error("--raw-frames needs --clip (or --config)")
+    if a.face_decimation and not (a.mesh_prep or a.config == 3):
+        ap.error("--face-decimation needs --mesh-prep (or --config 3)")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     label = None
@@ -275,7 +294,7 @@ def main():
                  "anchor latent's source (Stage 0, reference path), which is seeded noise in both records, and in the mesh glue around Stage II "
                  "(dirty mesh -> merge_and_clean_mesh -> normalize_mesh -> sample_surface; denormalize_mesh + expand_to_original at the end)")
     print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames,
-                         features=a.features, mesh_prep=a.mesh_prep)))
+                         features=a.features, mesh_prep=a.mesh_prep, face_decimation=a.face_decimation)))
 
 
 if __name__ == "__main__":
