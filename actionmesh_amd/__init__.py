@@ -13,10 +13,11 @@ from .denoiser import HipDenoiser, HipEngine, WindowCache  # noqa: F401
 from .mesh_prep import (MeshTopology, NormalizationParams, VertexFeatures, denormalize_mesh, expand_to_original,  # noqa: F401
                         get_mesh_features, merge_and_clean_mesh, normalize_mesh, normalize_mesh_to_bounds, process_mesh, sample_surface)
 from .mesh_decimate import decimate_mesh  # noqa: F401
+from .isosurface import extract_isosurface, hierarchical_extract_geometry  # noqa: F401
 from .mesh_io import create_animated_glb, load_glb, save_deformation, save_meshes  # noqa: F401
 from . import actionbench  # noqa: F401
 from .render import HipRenderer, HipVisualizer, uniform_cameras  # noqa: F401
-from .dropin import install, install_mask_refine, install_preprocess, uninstall  # noqa: F401
+from .dropin import install, install_isosurface, install_mask_refine, install_preprocess, uninstall  # noqa: F401
 from .scheduler import ClassifierFreeGuidance, HipSchedulerFlow  # noqa: F401
 from .sharding import FrameShardPlan  # noqa: F401
 from .windows import LatentBank, chunk_from, denoise_window, generate_3d_latents, generate_vertex_animation  # noqa: F401
@@ -27,4 +28,5 @@ __all__ = ["HipAutoencoder", "HipImageEncoder", "HipDenoiser", "HipEngine", "Hip
            "save_meshes", "create_animated_glb", "load_glb", "actionbench", "install", "uninstall", "HipRenderer", "HipVisualizer",
            "uniform_cameras", "HipImagePreprocessor", "frames_to_pixel_values", "install_preprocess", "install_mask_refine",
            "MeshTopology", "NormalizationParams", "VertexFeatures", "get_mesh_features", "merge_and_clean_mesh", "process_mesh", "decimate_mesh",
-           "normalize_mesh", "denormalize_mesh", "normalize_mesh_to_bounds", "sample_surface", "expand_to_original"]
+           "normalize_mesh", "denormalize_mesh", "normalize_mesh_to_bounds", "sample_surface", "expand_to_original",
+           "extract_isosurface", "hierarchical_extract_geometry", "install_isosurface"]

@@ -238,6 +238,33 @@ class AmDecimateApplyArgs(C.Structure):        # am_decimate_apply_args
     ]
 
 
+ISO_BAD_VERTEX_OFFSET, ISO_BAD_TRI_OFFSET, ISO_BAD_TABLE = 1, 2, 4      # am_iso_vertices' / am_iso_triangles' out_flag bits
+
+
+class AmIsoClassifyArgs(C.Structure):          # am_iso_classify_args
+    _fields_ = [
+        ("values", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("level", C.c_double),
+        ("inside_above", C.c_int32), ("reserved", C.c_int32), ("out_mask", C.c_void_p), ("out_count", C.c_void_p),
+    ]
+
+
+class AmIsoVerticesArgs(C.Structure):          # am_iso_vertices_args
+    _fields_ = [
+        ("values", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("level", C.c_double),
+        ("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("mask", C.c_void_p), ("vertex_offset", C.c_void_p),
+        ("n_vertices", C.c_int64), ("out_vertices", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
+class AmIsoTrianglesArgs(C.Structure):         # am_iso_triangles_args
+    _fields_ = [
+        ("values", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("level", C.c_double),
+        ("inside_above", C.c_int32), ("reserved", C.c_int32), ("mask", C.c_void_p), ("count", C.c_void_p),
+        ("vertex_offset", C.c_void_p), ("tri_offset", C.c_void_p), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64),
+        ("out_faces", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -261,7 +288,9 @@ STRUCTS = {
     "am_mask_refine_args": AmMaskRefineArgs, "am_graph_args": AmGraphArgs, "am_vertex_normals_args": AmVertexNormalsArgs,
     "am_face_areas_args": AmFaceAreasArgs, "am_surface_sample_args": AmSurfaceSampleArgs,
     "am_decimate_quadrics_args": AmDecimateQuadricsArgs, "am_decimate_edges_args": AmDecimateEdgesArgs,
-    "am_decimate_select_args": AmDecimateSelectArgs, "am_decimate_apply_args": AmDecimateApplyArgs, "am_peer_ring": AmPeerRing,
+    "am_decimate_select_args": AmDecimateSelectArgs, "am_decimate_apply_args": AmDecimateApplyArgs,
+    "am_iso_classify_args": AmIsoClassifyArgs, "am_iso_vertices_args": AmIsoVerticesArgs, "am_iso_triangles_args": AmIsoTrianglesArgs,
+    "am_peer_ring": AmPeerRing,
 }
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
@@ -311,6 +340,9 @@ SYMBOLS = {
     "am_decimate_edges": (C.c_int, [C.POINTER(AmDecimateEdgesArgs), _P]),
     "am_decimate_select": (C.c_int, [C.POINTER(AmDecimateSelectArgs), _P]),
     "am_decimate_apply": (C.c_int, [C.POINTER(AmDecimateApplyArgs), _P]),
+    "am_iso_classify": (C.c_int, [C.POINTER(AmIsoClassifyArgs), _P]),
+    "am_iso_vertices": (C.c_int, [C.POINTER(AmIsoVerticesArgs), _P]),
+    "am_iso_triangles": (C.c_int, [C.POINTER(AmIsoTrianglesArgs), _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

@@ -23,7 +23,10 @@ The reference builds its Stage-I objects in three places, none of which takes a 
     (actionmesh_amd/image_preprocess.py, seam S8);
   * optionally (`install_mask_refine()` after `install()`) the mask refinement behind the background remover: `refine_mask`, a name
     `BackgroundRemover.forward` resolves in `actionmesh.preprocessing.background_removal`'s globals (background_removal.py:109), is
-    rebound to the HIP labelling (actionmesh_amd/mask_refine.py, seam S9).
+    rebound to the HIP labelling (actionmesh_amd/mask_refine.py, seam S9);
+  * optionally (`install_isosurface()` after `install()`) the iso-surface extraction behind the Stage-0 VAE:
+    `hierarchical_extract_geometry`, a name `TripoSGVAE.decode_latents` resolves in `actionmesh.external.triposg`'s globals
+    (triposg.py:13, 193), is rebound to the HIP marching tetrahedra (actionmesh_amd/isosurface.py, seam S11).
 
 `uninstall()` restores every name.  Nothing here imports the reference at module import time: `install()` imports
 `actionmesh.pipeline` (the caller's environment must be able to - that is the environment the reference runs in).
@@ -135,8 +138,8 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     `save_deformation` so that `actionmesh_amd.render.render_captured()` can draw the preview video afterwards (render.install_hook).
     `pointcloud`: also give `actionmesh.external.triposg` the point-cloud sampling names it lacks without PyTorch3D
     (pointcloud_sampling.install_into), so that `TripoSGVAE` can be built and samples its surface points on the HIP FPS kernel.
-    The frame preprocessing and the mask refinement are calls of their own on top of this one: `install_preprocess()`,
-    `install_mask_refine()`."""
+    The frame preprocessing, the mask refinement and the iso-surface extraction are calls of their own on top of this one:
+    `install_preprocess()`, `install_mask_refine()`, `install_isosurface()`."""
     if stage2_cross_fp32 and not stage2:
         raise ValueError("actionmesh_amd.install(): stage2_cross_fp32=True needs stage2=True")
     import actionmesh.pipeline as P      # the reference (must be importable where the reference runs)
@@ -181,6 +184,7 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
     _state["preprocess"] = False
     _state["mask_refine"] = None
     _state["pointcloud"] = None
+    _state["isosurface"] = None
     if pointcloud:
         from . import pointcloud_sampling as S
         _state["pointcloud"] = (T, S.install_into(T))
@@ -223,6 +227,21 @@ def install_mask_refine() -> None:
     B.refine_mask = refine_mask
 
 
+def install_isosurface() -> None:
+    """On top of `install()` (called with its defaults first if nothing is installed; idempotent): `hierarchical_extract_geometry`
+    in `actionmesh.external.triposg` - and, with it, in the `triposg` pipeline module that imported the same name - becomes
+    `actionmesh_amd.isosurface.hierarchical_extract_geometry`: the call site's name and keywords, marching tetrahedra on the HIP
+    kernels instead of the `diso` wheel.  `uninstall()` - and therefore a later `install()` - takes it back.  A call of its own, like
+    `install_preprocess()`: `install()` keeps its parameter list."""
+    if not _state.get("installed"):
+        install()
+    if _state.get("isosurface"):
+        return
+    import actionmesh.external.triposg as T      # the reference's module (needs the triposg package, as its anchor path does)
+    from . import isosurface as I
+    _state["isosurface"] = (T, I.install_into(T))
+
+
 def uninstall() -> None:
     if not _state.get("installed"):
         return
@@ -239,6 +258,10 @@ def uninstall() -> None:
         from . import pointcloud_sampling as S
         S.uninstall_from(*_state["pointcloud"])
         _state["pointcloud"] = None
+    if _state.get("isosurface"):
+        from . import isosurface as I
+        I.uninstall_from(*_state["isosurface"])
+        _state["isosurface"] = None
     _state["preprocess"] = False
     _state["installed"] = False
 

@@ -1,0 +1,252 @@
+"""Iso-surface extraction on tensors (INTEGRATION seam S11): the step that turns the Stage-0 VAE's field into the anchor mesh.  The
+reference reaches it through TripoSG's `hierarchical_extract_geometry` (actionmesh/external/triposg.py:13, 193-199), which runs the
+`diso` package's dual marching cubes - a CUDA-only wheel that does not build for ROCm.  Here it is marching tetrahedra on the regular
+grid: every cell is cut into the six Kuhn tetrahedra, whose diagonals agree between neighbouring cells, so the output is always a
+combinatorial 2-manifold with one orientation (closed wherever the surface stays inside the evaluated points) - which is what
+`decimate_mesh`, the next step, needs: it never touches a non-manifold vertex.
+
+  ops.iso_classify    per point the mask of crossing edges that start there, per cell the number of triangles
+  torch plumbing      the two exclusive prefix sums (`torch.cumsum`, int64) and ONE device-to-host read of their totals, which
+                      sizes the outputs
+  ops.iso_vertices    every crossing edge's vertex at its rank: one vertex per edge, in ascending edge id
+  ops.iso_triangles   every cell's triangles at its offset: ordered by cell, tetrahedron, triangle
+  torch plumbing      vertices that no face uses (crossing edges next to non-finite samples) are dropped, order preserved; ONE
+                      more read: the two kernels' flag words with the number of vertices kept
+The arithmetic is written out in include/actionmesh_amd.h (csrc/am_isosurface.hip): fp64 interpolation without fused multiply-adds,
+no atomics, no hash table - the same bits on every run, equal to a numpy restatement of the header (tests/test_isosurface_*).  The
+kernel calls go through one small backend object (`HipBackend`), so the tests can run the same code on CPU tensors with that
+restatement in its place.  No CPU backend is shipped.
+
+`hierarchical_extract_geometry` has the reference call site's name and keywords: a dense grid of 2^dense + 1 points per axis, then for
+every further depth only the 3 x 3 x 3 fine points of the cells the surface passes through (dilated), everything else NaN - "not
+evaluated" - and the extraction at the finest depth.
+
+UNPINNED: parity with `diso` (dual marching cubes: fewer triangles, sharper features) or with skimage is not attempted - neither can
+be installed where this was written; TripoSG's refinement schedule and its `flash_extract_geometry` variant are not reproduced, the
+schedule here is this project's own; the sign convention of the VAE's field is an assumption: positive inside by default,
+`inside="below"` for the other.  What is pinned is the header's contract and the invariants (every edge in two faces, every directed
+edge once, the Euler characteristic, the enclosed volume).
+"""
+from __future__ import annotations
+
+import logging
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+
+logger = logging.getLogger(__name__)
+
+MAX_ITEMS = 2 ** 31 - 1
+DEFAULT_BOUNDS = (-1.005, -1.005, -1.005, 1.005, 1.005, 1.005)
+_POPCOUNT = [bin(i).count("1") for i in range(256)]
+
+
+class HipBackend:
+    """The three kernels (csrc/am_isosurface.hip).  `flag`: the caller's int32 (1,) word, which it reads with its other figures."""
+
+    classify = staticmethod(ops.iso_classify)
+    vertices = staticmethod(ops.iso_vertices)
+    triangles = staticmethod(ops.iso_triangles)
+
+
+def _inside_above(inside) -> bool:
+    if inside not in ("above", "below"):
+        raise ValueError(f"extract_isosurface: inside must be 'above' or 'below', got {inside!r}")
+    return inside == "above"
+
+
+def _frame(shape, bounds, origin, spacing):
+    """(origin, spacing) as two tuples of three floats: given directly, or from bounds (x0, y0, z0, x1, y1, z1) - the first and the
+    last point of every axis -, or the index frame."""
+    if bounds is not None:
+        if origin is not None or spacing is not None:
+            raise ValueError("extract_isosurface: give bounds or origin / spacing, not both")
+        b = [float(x) for x in ((-bounds,) * 3 + (bounds,) * 3 if isinstance(bounds, (int, float)) else bounds)]
+        if len(b) != 6:
+            raise ValueError(f"extract_isosurface: bounds are (x0, y0, z0, x1, y1, z1), got {len(b)} numbers")
+        return tuple(b[:3]), tuple((b[3 + c] - b[c]) / (shape[c] - 1) for c in range(3))
+    origin = (0.0, 0.0, 0.0) if origin is None else tuple(float(x) for x in origin)
+    spacing = (1.0, 1.0, 1.0) if spacing is None else tuple(float(x) for x in spacing)
+    if len(origin) != 3 or len(spacing) != 3:
+        raise ValueError("extract_isosurface: origin and spacing are three numbers each")
+    return origin, spacing
+
+
+def _empty(dev):
+    return torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev)
+
+
+def extract_isosurface(values: torch.Tensor, level: float = 0.0, bounds=None, origin=None, spacing=None, inside: str = "above",
+                       backend=None):
+    """The surface `values == level` of an fp32 grid (X, Y, Z), every axis at least 2, as (vertices (V, 3) fp32, faces (F, 3) int64)
+    on the tensor's device, oriented with the normals from the inside - finite and above the level, or below it with
+    `inside="below"` - to the outside.  A non-finite value means "not evaluated": no triangle touches it.  Positions: point (i, j, k)
+    lies at origin + (i, j, k) * spacing, given directly or through `bounds` (x0, y0, z0, x1, y1, z1), the positions of the first and
+    last points; the index frame without either.  Every returned vertex is used by a face.  A grid the surface does not cross gives
+    (0, 3) and (0, 3).  More than 2^31 - 1 vertices or triangles raise ValueError before anything is extracted.  `backend`: the
+    kernels (tests)."""
+    backend = HipBackend if backend is None else backend
+    if not isinstance(values, torch.Tensor) or values.dim() != 3 or min(values.shape) < 2:
+        raise ValueError(f"extract_isosurface: expected (X, Y, Z) values with every axis at least 2, got {tuple(getattr(values, 'shape', ()))}")
+    if values.dtype != torch.float32:
+        raise TypeError(f"extract_isosurface: expected float32 values, got {values.dtype}")
+    above = _inside_above(inside)
+    level = float(level)
+    if not np.isfinite(level):
+        raise ValueError(f"extract_isosurface: the level must be finite, got {level}")
+    origin, spacing = _frame(values.shape, bounds, origin, spacing)
+    values, dev = values.contiguous(), values.device
+    mask, count = backend.classify(values, level, above)
+    crossings = torch.tensor(_POPCOUNT, dtype=torch.int64, device=dev)[mask.reshape(-1).long()]
+    vertex_end, tri_end = torch.cumsum(crossings, 0), torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
+    n_vertices, n_triangles = torch.stack((vertex_end[-1], tri_end[-1])).tolist()              # the read that sizes the outputs
+    if n_vertices > MAX_ITEMS or n_triangles > MAX_ITEMS:
+        raise ValueError(f"extract_isosurface: {n_vertices} vertices and {n_triangles} triangles; more than 2^31 - 1 of either is "
+                         "not supported")
+    if n_vertices == 0 or n_triangles == 0:
+        return _empty(dev)
+    vertex_offset, tri_offset = (vertex_end - crossings).view(values.shape), (tri_end - count.reshape(-1)).view(values.shape)
+    flags = torch.zeros((2,), dtype=torch.int32, device=dev)
+    vertices = backend.vertices(values, mask, vertex_offset, n_vertices, origin, spacing, level, flag=flags[0:1])
+    faces = backend.triangles(values, mask, count, vertex_offset, tri_offset, n_vertices, n_triangles, level, above, flag=flags[1:2])
+    # a valid face index lies inside [0, n_vertices); where a flag is set a row may be unwritten, so the scatter below is clamped
+    used = torch.zeros((n_vertices,), dtype=torch.bool, device=dev)
+    used[faces.long().reshape(-1).clamp_(0, n_vertices - 1)] = True
+    rank = torch.cumsum(used, 0) - 1
+    f_vertices, f_triangles, n_used = torch.cat((flags.long(), rank[-1:] + 1)).tolist()          # the second and last read
+    if f_vertices | f_triangles:
+        raise ValueError("extract_isosurface: " + ops.iso_flag_message(f_vertices | f_triangles))
+    if n_used == n_vertices:
+        return vertices, faces.long()
+    dest = torch.where(used, rank, torch.full_like(rank, n_used))
+    kept = torch.empty((n_used + 1, 3), dtype=vertices.dtype, device=dev)
+    kept.index_copy_(0, dest, vertices)
+    return kept[:n_used].contiguous(), rank[faces.long()]
+
+
+def border_edge_count(faces: torch.Tensor) -> int:
+    """The number of edges that only one face uses (0 on a closed surface).  One sort; one device-to-host read."""
+    if faces.shape[0] == 0:
+        return 0
+    f = faces.long()
+    a, b = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)
+    key = torch.minimum(a, b) * (int(f.max()) + 1) + torch.maximum(a, b)
+    return int((torch.unique(key, return_counts=True)[1] == 1).sum())
+
+
+def _axis_points(lo: float, hi: float, n: int, dev) -> torch.Tensor:
+    """The n positions of one axis in float32: `np.linspace` in float64 on the host (n is a few hundred), rounded once."""
+    return torch.from_numpy(np.linspace(lo, hi, n).astype(np.float32)).to(dev)
+
+
+def _evaluate(geometric_func, axes, linear: Optional[torch.Tensor], n: int, max_points_per_call: int, dtype) -> torch.Tensor:
+    """The field at the points `linear` (indices into the n^3 grid; all of them when None), in chunks: (B, len) float32."""
+    dev = axes[0].device
+    total = n ** 3 if linear is None else linear.numel()
+    out = []
+    for start in range(0, total, max_points_per_call):
+        idx = torch.arange(start, min(start + max_points_per_call, total), device=dev) if linear is None else linear[start:start + max_points_per_call]
+        pts = torch.stack((axes[0][idx // (n * n)], axes[1][(idx // n) % n], axes[2][idx % n]), dim=-1).to(dtype)
+        val = geometric_func(pts.unsqueeze(0))
+        if val.dim() == 3 and val.shape[-1] == 1:
+            val = val[..., 0]
+        if val.dim() != 2 or val.shape[1] != idx.numel():
+            raise ValueError(f"hierarchical_extract_geometry: geometric_func returned {tuple(val.shape)} for {idx.numel()} points")
+        out.append(val.float())
+    return torch.cat(out, dim=1)
+
+
+def hierarchical_extract_geometry(geometric_func, device, bounds=DEFAULT_BOUNDS, dense_octree_depth: int = 8,
+                                  hierarchical_octree_depth: int = 9, dilation: int = 1, max_points_per_call: int = 1 << 21,
+                                  level: float = 0.0, inside: str = "above", dtype=torch.float32, backend=None):
+    """TripoSG's entry point as the reference calls it (triposg.py:193-199): `geometric_func(points (B, n, 3)) -> (B, n, 1)` is the
+    field, `bounds` the box (one number b means (-b, -b, -b, b, b, b)).  Returns a list with one (vertices np.float32 (V, 3), faces
+    np.int64 (F, 3)) per batch entry of what the function returns.
+
+    The schedule: the grid of 2^dense_octree_depth + 1 points per axis is evaluated whole, `max_points_per_call` points at a time.
+    For every further depth up to hierarchical_octree_depth, the active coarse cells - a non-zero triangle count from
+    `ops.iso_classify`: eight finite corners, not all on one side - of ANY batch entry are dilated by `dilation` cells, the
+    3 x 3 x 3 fine points of each are evaluated, and every other fine point is NaN.  The surface is extracted at the finest depth;
+    when it has border edges - it left the evaluated band, or the box - their number is logged as a warning.  The points handed to
+    `geometric_func` are `dtype` (float32) on `device`: `np.linspace` between the bounds in float64, rounded once."""
+    backend = HipBackend if backend is None else backend
+    above = _inside_above(inside)
+    dense, finest = int(dense_octree_depth), max(int(dense_octree_depth), int(hierarchical_octree_depth))
+    if dense < 1 or finest > 10:
+        raise ValueError(f"hierarchical_extract_geometry: depths {dense} .. {finest} are outside 1 .. 10")
+    if int(dilation) < 0 or int(max_points_per_call) < 1:
+        raise ValueError("hierarchical_extract_geometry: dilation must be >= 0 and max_points_per_call >= 1")
+    b = [float(x) for x in ((-bounds,) * 3 + (bounds,) * 3 if isinstance(bounds, (int, float)) else bounds)]
+    if len(b) != 6:
+        raise ValueError(f"hierarchical_extract_geometry: bounds are (x0, y0, z0, x1, y1, z1), got {len(b)} numbers")
+    dev = torch.device(device)
+    n = 2 ** dense + 1
+    axes = [_axis_points(b[c], b[3 + c], n, dev) for c in range(3)]
+    values = _evaluate(geometric_func, axes, None, n, int(max_points_per_call), dtype)
+    values = values.reshape(values.shape[0], n, n, n)
+    for depth in range(dense + 1, finest + 1):
+        active = torch.zeros((n - 1,) * 3, dtype=torch.bool, device=dev)
+        for grid in values:
+            active |= backend.classify(grid.contiguous(), level, above)[1][:-1, :-1, :-1] != 0
+        if int(dilation):
+            k = 2 * int(dilation) + 1
+            active = torch.nn.functional.max_pool3d(active[None, None].float(), k, stride=1, padding=int(dilation))[0, 0] != 0
+        n = 2 ** depth + 1
+        cells = torch.nonzero(active)                                     # (K, 3); a read: it sizes the evaluation
+        offsets = torch.stack(torch.meshgrid(*(torch.arange(3, device=dev),) * 3, indexing="ij"), dim=-1).reshape(-1, 3)
+        fine = (2 * cells[:, None, :] + offsets[None]).reshape(-1, 3)
+        marked = torch.zeros((n ** 3,), dtype=torch.bool, device=dev)
+        marked[(fine[:, 0] * n + fine[:, 1]) * n + fine[:, 2]] = True
+        linear = torch.nonzero(marked)[:, 0]
+        axes = [_axis_points(b[c], b[3 + c], n, dev) for c in range(3)]
+        next_values = torch.full((values.shape[0], n ** 3), float("nan"), dtype=torch.float32, device=dev)
+        if linear.numel():
+            next_values[:, linear] = _evaluate(geometric_func, axes, linear, n, int(max_points_per_call), dtype)
+        values = next_values.reshape(-1, n, n, n)
+    meshes = []
+    for grid in values:
+        vertices, faces = extract_isosurface(grid, level, bounds=b, inside=inside, backend=backend)
+        borders = border_edge_count(faces)
+        if borders:
+            logger.warning("hierarchical_extract_geometry: the surface has %d border edges: it left the evaluated band or the bounds",
+                           borders)
+        meshes.append((vertices.cpu().numpy(), faces.cpu().numpy()))
+    return meshes
+
+
+# ---- seam S11 --------------------------------------------------------------------------------------------------------------------
+SEAM_NAME = "hierarchical_extract_geometry"
+PIPELINE_MODULE = "triposg.pipelines.pipeline_triposg"
+_MISSING = object()
+
+
+def install_into(module) -> dict:
+    """Give `module` - meant for `actionmesh.external.triposg` - this module's `hierarchical_extract_geometry` under the name it
+    imported from `triposg.inference_utils` (triposg.py:13), which `TripoSGVAE.decode_latents` resolves at call time.  When the
+    `triposg` package is importable, the pipeline module that imported the same name (`TripoSGPipeline.__call__`, reached through
+    `TripoSGPipelinePlus`) gets it too.  Returns what the names held, for `uninstall_from`."""
+    saved = {"module": getattr(module, SEAM_NAME, _MISSING), "pipeline": None}
+    setattr(module, SEAM_NAME, hierarchical_extract_geometry)
+    try:
+        import importlib
+        pipeline = importlib.import_module(PIPELINE_MODULE)
+    except ImportError:
+        pipeline = None
+    if pipeline is not None and hasattr(pipeline, SEAM_NAME):
+        saved["pipeline"] = (pipeline, getattr(pipeline, SEAM_NAME))
+        setattr(pipeline, SEAM_NAME, hierarchical_extract_geometry)
+    return saved
+
+
+def uninstall_from(module, saved: dict) -> None:
+    if saved["module"] is _MISSING:
+        if hasattr(module, SEAM_NAME):
+            delattr(module, SEAM_NAME)
+    else:
+        setattr(module, SEAM_NAME, saved["module"])
+    if saved.get("pipeline"):
+        pipeline, value = saved["pipeline"]
+        setattr(pipeline, SEAM_NAME, value)

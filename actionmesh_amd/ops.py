@@ -1041,6 +1041,101 @@ def decimate_apply(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch
     return dead
 
 
+# ---- iso-surface extraction (csrc/am_isosurface.hip; the contract is the header's, the prefix sums and the sizing are isosurface.py's) ----
+_ISO_MAX = 2 ** 31 - 1
+_ISO_FLAGS = {L.ISO_BAD_VERTEX_OFFSET: "a vertex offset is negative or leads past the vertex count",
+              L.ISO_BAD_TRI_OFFSET: "a triangle offset is negative or leads past the triangle count",
+              L.ISO_BAD_TABLE: "the crossing masks or triangle counts do not belong to these values"}
+
+
+def iso_flag_message(bits: int) -> str:
+    """What the set bits of an am_iso_* flag word say."""
+    return "; ".join(msg for bit, msg in _ISO_FLAGS.items() if bits & bit)
+
+
+def _iso_grid(what: str, a, values: torch.Tensor, level: float):
+    """The checks on (values, level) the three entry points share; they come before the device check, so they hold for any tensor.
+    Sets the grid fields of `a`; returns ((nx, ny, nz), device)."""
+    if not isinstance(values, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor")
+    if values.dim() != 3 or min(values.shape) < 2:
+        raise ValueError(f"{what}: expected (X, Y, Z) values with every axis at least 2, got {tuple(values.shape)}")
+    if values.numel() > _ISO_MAX:
+        raise ValueError(f"{what}: a grid of {tuple(values.shape)} points has more than 2^31 - 1")
+    level = float(level)
+    if level != level or level in (float("inf"), float("-inf")):
+        raise ValueError(f"{what}: the level must be finite, got {level}")
+    _need(values, torch.float32, f"{what}: values")
+    a.values, (a.nx, a.ny, a.nz), a.level = values.data_ptr(), values.shape, level
+    return tuple(values.shape), values.device
+
+
+def iso_classify(values: torch.Tensor, level: float = 0.0, inside_above: bool = True, out_mask: Optional[torch.Tensor] = None,
+                 out_count: Optional[torch.Tensor] = None):
+    """am_iso_classify: for every point of the fp32 grid (X, Y, Z) the 7-bit mask of crossing edges that start there, and for every
+    cell - at the point of its (0, 0, 0) corner - the number of triangles 0 .. 12 of its six tetrahedra.  Both (X, Y, Z) uint8."""
+    what = "iso_classify"
+    a = L.AmIsoClassifyArgs()
+    shape, dev = _iso_grid(what, a, values, level)
+    mask = _mesh_out(f"{what}: out_mask", out_mask, shape, torch.uint8, dev)
+    count = _mesh_out(f"{what}: out_count", out_count, shape, torch.uint8, dev)
+    a.inside_above, a.out_mask, a.out_count = int(bool(inside_above)), mask.data_ptr(), count.data_ptr()
+    _call(values, None, "am_iso_classify", C.byref(a))
+    return mask, count
+
+
+def _iso_tables(what: str, shape, dev, **tables) -> None:
+    for name, (t, dtype) in tables.items():
+        _decimate_rows(f"{what}: {name}", t, dtype, shape, dev)
+
+
+def iso_vertices(values: torch.Tensor, mask: torch.Tensor, vertex_offset: torch.Tensor, n_vertices: int, origin, spacing,
+                 level: float = 0.0, out: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_iso_vertices: the (n_vertices, 3) fp32 positions of the crossing edges, edge (p, m) at vertex_offset[p] + the rank of bit
+    m - 1 in mask[p].  mask (X, Y, Z) uint8 from iso_classify, vertex_offset (X, Y, Z) int64: the exclusive prefix sum of the masks'
+    popcounts.  origin, spacing: three fp64 numbers each.  `flag` as in decimate_quadrics."""
+    what = "iso_vertices"
+    a = L.AmIsoVerticesArgs()
+    shape, dev = _iso_grid(what, a, values, level)
+    _iso_tables(what, shape, dev, mask=(mask, torch.uint8), vertex_offset=(vertex_offset, torch.int64))
+    n_vertices = int(n_vertices)
+    if not 1 <= n_vertices <= _ISO_MAX:
+        raise ValueError(f"{what}: {n_vertices} vertices are outside 1 .. 2^31 - 1")
+    out = _mesh_out(f"{what}: out", out, (n_vertices, 3), torch.float32, dev)
+    flag, own = _decimate_flag(what, flag, dev)
+    a.origin, a.spacing = (C.c_double * 3)(*(float(x) for x in origin)), (C.c_double * 3)(*(float(x) for x in spacing))
+    a.mask, a.vertex_offset, a.n_vertices, a.out_vertices, a.out_flag = mask.data_ptr(), vertex_offset.data_ptr(), n_vertices, out.data_ptr(), flag.data_ptr()
+    _call(values, None, "am_iso_vertices", C.byref(a))
+    if own and int(flag):
+        raise ValueError(f"{what}: " + iso_flag_message(int(flag)))
+    return out
+
+
+def iso_triangles(values: torch.Tensor, mask: torch.Tensor, count: torch.Tensor, vertex_offset: torch.Tensor, tri_offset: torch.Tensor,
+                  n_vertices: int, n_triangles: int, level: float = 0.0, inside_above: bool = True, out: Optional[torch.Tensor] = None,
+                  flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_iso_triangles: the (n_triangles, 3) int32 faces, the triangles of cell p from row tri_offset[p] on.  mask, count (X, Y, Z)
+    uint8 from iso_classify; vertex_offset, tri_offset (X, Y, Z) int64: the exclusive prefix sums of the masks' popcounts and of the
+    counts.  `flag` as in decimate_quadrics."""
+    what = "iso_triangles"
+    a = L.AmIsoTrianglesArgs()
+    shape, dev = _iso_grid(what, a, values, level)
+    _iso_tables(what, shape, dev, mask=(mask, torch.uint8), count=(count, torch.uint8), vertex_offset=(vertex_offset, torch.int64),
+                tri_offset=(tri_offset, torch.int64))
+    n_vertices, n_triangles = int(n_vertices), int(n_triangles)
+    if not 1 <= n_vertices <= _ISO_MAX or not 1 <= n_triangles <= _ISO_MAX:
+        raise ValueError(f"{what}: {n_vertices} vertices and {n_triangles} triangles are outside 1 .. 2^31 - 1")
+    out = _mesh_out(f"{what}: out", out, (n_triangles, 3), torch.int32, dev)
+    flag, own = _decimate_flag(what, flag, dev)
+    a.inside_above, a.mask, a.count = int(bool(inside_above)), mask.data_ptr(), count.data_ptr()
+    a.vertex_offset, a.tri_offset, a.n_vertices, a.n_triangles = vertex_offset.data_ptr(), tri_offset.data_ptr(), n_vertices, n_triangles
+    a.out_faces, a.out_flag = out.data_ptr(), flag.data_ptr()
+    _call(values, None, "am_iso_triangles", C.byref(a))
+    if own and int(flag):
+        raise ValueError(f"{what}: " + iso_flag_message(int(flag)))
+    return out
+
+
 # ---- exact-fp32 path (csrc/am_f32.hip, am_elementwise.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              gelu: bool = False, out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:

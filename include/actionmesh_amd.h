@@ -928,6 +928,108 @@ typedef struct {
 } am_decimate_apply_args;
 int am_decimate_apply(const am_decimate_apply_args* args, void* stream);
 
+/* Iso-surface extraction (INTEGRATION seam S11): marching tetrahedra on a regular grid, the three kernels behind
+ * actionmesh_amd/isosurface.py, which stands in for the `diso` dual marching cubes inside TripoSG's hierarchical_extract_geometry
+ * (actionmesh/external/triposg.py:13, 193-199).  The two prefix sums between the kernels, the sizing of the outputs and the removal
+ * of unused vertices are the caller's.  There are no atomics but the OR into the flag word and no hash table: the result is the same
+ * bits on every run, and a numpy restatement of the lines below reproduces it bit for bit (tests/test_isosurface_*).
+ *
+ * Grid.  `values` is fp32 (nx, ny, nz), contiguous, every axis >= 2 and nx ny nz <= 2^31 - 1.  Point (i, j, k) has the linear index
+ * p = (i ny + j) nz + k and the position origin[c] + idx[c] * spacing[c] per component, fp64, a multiply then an add (no fused
+ * multiply-add).  A point is INSIDE when its value is finite and (double)value > level (inside_above != 0) or (double)value < level
+ * (inside_above == 0).  A non-finite value means "not evaluated".  The surface is oriented with its normals from the inside to the
+ * outside whichever comparison is chosen, so inside_above = 0 gives the reverse winding of inside_above = 1 on the same values - and
+ * on the negated values, with the negated level, the identical mesh.
+ *
+ * Subdivision.  Every cell - eight points p + m, m in {000 .. 111} with bits (di, dj, dk), dk lowest - is cut into the six Kuhn
+ * (Freudenthal) tetrahedra.  Tetrahedron t belongs to the t-th permutation pi of the axes (i, j, k) in lexicographic order; its
+ * corners are c0 = 000, c1 = c0 + e_pi0, c2 = c1 + e_pi1, c3 = 111.  Every edge of a tetrahedron therefore runs from a grid point p to
+ * p + m for one of the seven non-zero offsets m, and face and body diagonals agree between neighbouring cells.
+ *
+ * Vertices.  Edge (p, m) CROSSES when p + m is inside the grid, both ends are finite and exactly one is inside.  It has the id
+ * 7 p + (m - 1); there is one vertex per crossing edge, numbered in ascending id.  With a = p, b = p + m, in fp64:
+ *   t = (level - v_a) / (v_b - v_a);   position[c] = pa[c] + t * (pb[c] - pa[c]),   rounded once to fp32.
+ *
+ * Triangles.  A tetrahedron with a non-finite corner emits nothing.  Otherwise the inside mask of (c0 .. c3), bit q for corner q,
+ * selects one of 14 cases; a polygon vertex is the vertex of the edge between two corners:
+ *   one inside corner a:     the polygon (a, o) over the outside corners o in ascending order;
+ *   three inside corners:    the polygon (i, o) over the inside corners i in ascending order, o the outside one;
+ *   two inside corners:      the quad (i0, o0), (i0, o1), (i1, o1), (i1, o0), split along its first and third vertex into
+ *                            (q0, q1, q2) and (q0, q2, q3).
+ * A polygon is reversed - first vertex kept, the rest in reverse order, BEFORE the split - when its normal
+ * (q1 - q0) x (q2 - q0), taken on the unit tetrahedron with the edge midpoints as crossings, has a negative dot product with
+ * (mean of the outside corners) - (mean of the inside corners).  Triangles are ordered by the linear index of the cell's 000 corner,
+ * then tetrahedron, then triangle; faces are int32.
+ *
+ * am_iso_classify, per point p:  out_mask[p] = bit (m - 1) for every crossing edge (p, m);  out_count[p] = the number of triangles,
+ *   0 .. 12, of the cell whose 000 corner is p, and 0 where no cell starts (i = nx - 1, j = ny - 1 or k = nz - 1).
+ * The caller makes the exclusive prefix sums vertex_offset[p] over popcount(out_mask) and tri_offset[p] over out_count (int64); their
+ * totals are n_vertices and n_triangles, each 1 .. 2^31 - 1 for the two calls below.
+ * am_iso_vertices, per point with a non-zero mask:  the vertex of edge (p, m) goes to row vertex_offset[p] + popcount(mask[p] &
+ *   ((1 << (m - 1)) - 1)) of out_vertices (n_vertices, 3) fp32.
+ * am_iso_triangles, per point with a non-zero count:  the cell's triangles go to rows tri_offset[p] .. of out_faces (n_triangles, 3);
+ *   the vertex of edge (p, m) is vertex_offset[p] + popcount(mask[p] & ((1 << (m - 1)) - 1)).
+ *
+ * out_flag, device int32[1], cleared by each of the two calls; the caller reads it with the result and treats a non-zero value as
+ * failure:
+ *   AM_ISO_BAD_VERTEX_OFFSET  a vertex offset is negative or leads past n_vertices;
+ *   AM_ISO_BAD_TRI_OFFSET     a triangle offset is negative or leads past n_triangles;
+ *   AM_ISO_BAD_TABLE          mask or count do not belong to these values: a mask above 127, a mask bit for an edge that leaves the
+ *                             grid or that a triangle needs and the mask lacks, a count above 12, where no cell starts, or other
+ *                             than the number of triangles the values give.
+ * Every offset and index read from memory is compared with its bound BEFORE it is used as an address; what a bad one would have
+ * written is left out. */
+#define AM_ISO_BAD_VERTEX_OFFSET 1
+#define AM_ISO_BAD_TRI_OFFSET 2
+#define AM_ISO_BAD_TABLE 4
+typedef struct {
+  const float* values;          /* (nx, ny, nz) */
+  int64_t nx;
+  int64_t ny;
+  int64_t nz;
+  double level;                 /* finite */
+  int32_t inside_above;
+  int32_t reserved;
+  uint8_t* out_mask;            /* [nx ny nz] */
+  uint8_t* out_count;           /* [nx ny nz] */
+} am_iso_classify_args;
+int am_iso_classify(const am_iso_classify_args* args, void* stream);
+
+typedef struct {
+  const float* values;
+  int64_t nx;
+  int64_t ny;
+  int64_t nz;
+  double level;
+  double origin[3];
+  double spacing[3];
+  const uint8_t* mask;          /* am_iso_classify's out_mask */
+  const int64_t* vertex_offset; /* [nx ny nz] */
+  int64_t n_vertices;           /* >= 1 */
+  float* out_vertices;          /* (n_vertices, 3) */
+  int32_t* out_flag;
+} am_iso_vertices_args;
+int am_iso_vertices(const am_iso_vertices_args* args, void* stream);
+
+typedef struct {
+  const float* values;
+  int64_t nx;
+  int64_t ny;
+  int64_t nz;
+  double level;
+  int32_t inside_above;
+  int32_t reserved;
+  const uint8_t* mask;
+  const uint8_t* count;         /* am_iso_classify's out_count */
+  const int64_t* vertex_offset;
+  const int64_t* tri_offset;    /* [nx ny nz] */
+  int64_t n_vertices;
+  int64_t n_triangles;          /* >= 1 */
+  int32_t* out_faces;           /* (n_triangles, 3) */
+  int32_t* out_flag;
+} am_iso_triangles_args;
+int am_iso_triangles(const am_iso_triangles_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

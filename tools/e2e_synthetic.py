@@ -21,6 +21,8 @@ BASELINE.json's "end-to-end video->4D wall-clock" restricted to the stages this 
                                                   (duplicated seam vertices, degenerate and duplicate faces, GLB units) that goes through
                                                   merge_and_clean_mesh -> normalize_mesh -> sample_surface(16384) in front of Stage II and
                                                   through denormalize_mesh + expand_to_original behind it (pipeline_with_3d.py:92-104, 229-238)
+    python tools/e2e_synthetic.py --config 3 --face-decimation N --field-grid G     opt-in: the mesh itself comes from an analytic torus field
+                                                  on G^3 points, extracted on the device (extract_isosurface, seam S11), then as below
     python tools/e2e_synthetic.py --config 3 --face-decimation N      opt-in: the dirty torus goes through the reference's Stage-0 post-processing
                                                   instead - process_mesh(face_decimation=N, decimation="hip"): clean-up, then the quadric decimation
                                                   on the device (actionmesh_amd/mesh_decimate.py; MeshPostprocessor.process_mesh, pipeline.py:418) -
@@ -125,7 +127,7 @@ def dirty_mesh(v, f, cols: int, seed: int = 2):
 
 
 def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44, clip: str = None, label: str = None,
-        raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False, face_decimation: int = 0):
+        raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False, face_decimation: int = 0, field_grid: int = 0):
     from actionmesh_amd import LatentBank, generate_3d_latents, generate_vertex_animation
     from actionmesh_amd import mesh_prep as MP
     t_build = time.perf_counter()
@@ -164,9 +166,23 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
     timesteps = torch.arange(frames, dtype=torch.float32)
     anchor_latent = torch.randn((1, n_tokens, 64), generator=g).to(dev)
     clean_v, clean_f, cols = torus_mesh(vertices)
-    t_prep = None
+    t_prep = t_iso = None
     if mesh_prep:          # the {video+3D} front end: dirty mesh -> clean-up -> normalise -> surface samples, all on the device
-        raw_v, raw_f = (torch.from_numpy(x).to(dev) for x in dirty_mesh(clean_v, clean_f, cols))
+        if field_grid:     # Stage 0's last step first: the mesh is extracted on the device from an analytic torus field (seam S11)
+            from actionmesh_amd import isosurface as ISO
+            ax = torch.linspace(-1.0, 1.0, field_grid, dtype=torch.float64, device=dev)
+            gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
+            field = (0.25 - (((gx * gx + gy * gy).sqrt() - 0.6) ** 2 + gz * gz).sqrt()).float()
+            ISO.extract_isosurface(field[:9, :9, :9], bounds=1.0)       # the library's first call, outside the stage
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            raw_v, raw_f = ISO.extract_isosurface(field, bounds=1.0)
+            torch.cuda.synchronize(dev)
+            t_iso = time.perf_counter() - t0
+            assert raw_f.shape[0] > face_decimation, (raw_f.shape, face_decimation)
+            raw_v = raw_v.double() * 3.0 + torch.tensor((5.0, -2.0, 1.0), dtype=torch.float64, device=dev)      # model units
+        else:
+            raw_v, raw_f = (torch.from_numpy(x).to(dev) for x in dirty_mesh(clean_v, clean_f, cols))
         warm_v, warm_f, _, _ = MP.merge_and_clean_mesh(raw_v, raw_f)     # the library's first calls, outside the stage
         MP.sample_surface(MP.normalize_mesh(warm_v)[0], warm_f, 16, seed=0)
         torch.cuda.synchronize(dev)
@@ -250,6 +266,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
                         "model_build_and_upload": round(t_build, 1),
                         **({"preprocess_s": round(t_pre, 4)} if t_pre is not None else {}),
                         **({"mesh_prep": round(t_prep, 4)} if mesh_prep else {}),
+                        **({"isosurface": round(t_iso, 4)} if t_iso is not None else {}),
                         **({"mesh_back_to_original": round(t_back, 4)} if t_back is not None else {}),
                         "output_files_host_side": round(t_out, 3), "chamfer_metrics": round(t_metric, 4)},
             "preview_video_s": round(t_preview, 3),          # grid_normal.* (HipVisualizer), written into the output files above
@@ -257,6 +274,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             "config": {"workload": f"{frames} frames, {n_win} AR window(s) of {window}, {steps} denoise steps, N={n_tokens} tokens, "
                                    f"{vertices} vertices, {'tiny' if tiny else 'shipped'} model shapes, random-init weights"
                                    + (f", frames = the reference's {clip} clip" if clip else ", random frames")
+                                   + (f", mesh extracted from a {field_grid}^3 torus field on the device" if field_grid else "")
                                    + (f", decimated to {faces.shape[0]} faces on the device" if face_decimation else "")},
             **({"baseline_config": label} if label else {}),
             "context_rms": round(float(context.float().pow(2).mean().sqrt()), 4), "latents_rms": round(float(lat[1:].float().pow(2).mean().sqrt()), 4)}
@@ -276,12 +294,17 @@ def main():
     ap.add_argument("--mesh-prep", action="store_true", help="start from a dirty mesh and run the {video+3D} mesh glue around Stage II (implied by --config 3)")
     ap.add_argument("--face-decimation", type=int, default=0,
                     help="with --mesh-prep / --config 3: decimate the cleaned mesh to this many faces on the device (process_mesh(decimation='hip'))")
+    ap.add_argument("--field-grid", type=int, default=0, metavar="N",
+                    help="with --face-decimation: start from an analytic torus field on N^3 points instead of a prepared mesh - "
+                         "extract_isosurface on the device, then the clean-up and the decimation (adds seconds.isosurface)")
     ap.add_argument("--config", type=int, default=None, choices=[1, 3], help="BASELINE.json configs[1] / configs[3] as a plumbing record (see the module docstring)")
     a = ap.parse_args()
     if a.raw_frames and not (a.clip or a.config):
         ap.error("--raw-frames needs --clip (or --config)")
     if a.face_decimation and not (a.mesh_prep or a.config == 3):
         ap.error("--face-decimation needs --mesh-prep (or --config 3)")
+    if a.field_grid and not a.face_decimation:
+        ap.error("--field-grid needs --face-decimation (the extracted mesh has as many faces as the grid gives it)")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     label = None
@@ -294,7 +317,8 @@ def main():
                  "anchor latent's source (Stage 0, reference path), which is seeded noise in both records, and in the mesh glue around Stage II "
                  "(dirty mesh -> merge_and_clean_mesh -> normalize_mesh -> sample_surface; denormalize_mesh + expand_to_original at the end)")
     print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames,
-                         features=a.features, mesh_prep=a.mesh_prep, face_decimation=a.face_decimation)))
+                         features=a.features, mesh_prep=a.mesh_prep, face_decimation=a.face_decimation,
+                         field_grid=a.field_grid)))
 
 
 if __name__ == "__main__":
