@@ -33,9 +33,14 @@ __device__ inline float edge_fn(float px, float py, float ax, float ay, float bx
 }
 
 // PyTorch3D's CheckPixelInsideFace for blur 0 and clipped, perspective-correct barycentrics: true when (px, py) is covered;
-// then b = the clipped barycentrics and z = the interpolated depth (>= 0).
+// then b = the clipped barycentrics and z = the interpolated depth (>= 0).  A centre outside the closed bounding box of the three
+// projected vertices is never covered (PyTorch3D's rule as remembered, unpinned): that is decided here, exactly, so that it does not
+// depend on the loop bounds of pix_range.  Only a face with a vertex behind the camera has barycentrics > 0 outside its box.
 __device__ inline bool cover(const float4& v0, const float4& v1, const float4& v2, float px, float py, float b[3], float& z) {
 #pragma clang fp contract(off)
+  if (px < fminf(fminf(v0.x, v1.x), v2.x) || px > fmaxf(fmaxf(v0.x, v1.x), v2.x) || py < fminf(fminf(v0.y, v1.y), v2.y) ||
+      py > fmaxf(fmaxf(v0.y, v1.y), v2.y))
+    return false;
   const float area = edge_fn(v2.x, v2.y, v0.x, v0.y, v1.x, v1.y) + K_EPS;
   const float w0 = edge_fn(px, py, v1.x, v1.y, v2.x, v2.y) / area;
   const float w1 = edge_fn(px, py, v2.x, v2.y, v0.x, v0.y) / area;
@@ -55,7 +60,8 @@ __device__ inline bool cover(const float4& v0, const float4& v1, const float4& v
 
 __device__ inline float ndc_of(int i, int n) { return 1.f - (float)(2 * i + 1) / (float)n; }
 
-// the sub-pixel range [lo, hi] whose centres can lie in [a_min, a_max] of NDC (conservative by one sub-pixel; NaN / inf -> all)
+// the sub-pixel range [lo, hi] whose centres can lie in [a_min, a_max] of NDC (conservative by one sub-pixel; NaN / inf -> all):
+// a loop bound only - cover() decides with the exact box
 __device__ inline void pix_range(float a_min, float a_max, int n, int& lo, int& hi) {
   const float f_lo = ((1.f - a_max) * (float)n - 1.f) * 0.5f, f_hi = ((1.f - a_min) * (float)n - 1.f) * 0.5f;
   lo = !(f_lo > 1.f) ? 0 : (f_lo >= (float)n ? n : (int)f_lo - 1);

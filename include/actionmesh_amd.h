@@ -432,7 +432,13 @@ int am_nn_search(const am_nn_args* args, void* workspace_dev, size_t workspace_b
  *                   normalised with eps 1e-6 (Meshes.verts_normals_packed; no float atomics: bit-identical run to run);
  *   projection:     view = X @ R + T (row vectors), x_ndc = fx * view.x / view.z + px, y likewise, depth = view.z;
  *   raster:         at 2S x 2S, pixel centre x = 1 - (2 col + 1) / W, y = 1 - (2 row + 1) / H; covered when the three
- *                   perspective-corrected, unclipped barycentrics are all > 0; the nearest face wins, ties -> lowest index;
+ *                   perspective-corrected, unclipped barycentrics are all > 0; the nearest face wins, ties -> lowest index.
+ *                   A face is skipped (1) altogether when all three depths are negative, (2) altogether when the signed area
+ *                   (twice it: the edge function of one projected vertex against the other two) is within 1e-8 of zero, and (3) at every
+ *                   sub-pixel centre outside the closed box [min x, max x] x [min y, max y] of its three projected vertices -
+ *                   which changes nothing for a face in front of the camera (a covered centre lies inside the triangle) and
+ *                   confines a face with a vertex behind the camera, whose barycentrics are all > 0 in the cone beyond that
+ *                   vertex's projection, to the part of the cone inside the box (often none of it);
  *   resolve to S x S: mask = covered sub-pixels / 4; normal of sub-pixel (2i, 2j) through n @ R + T / 2, normalised,
  *                   (n + 1) / 2, clamped; rgba8 = trunc(255 * (normal * mask + 1 - mask)), alpha = trunc(255 * mask).
  * faces_host is the host copy of `faces` (the same (n_faces, 3) array): every index is checked against n_verts on it before

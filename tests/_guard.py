@@ -8,7 +8,9 @@ element, so a read outside the logical operand shows up in the value comparison.
     kernel(..., out=a.view)
     a.assert_untouched("C")
 
-Arena.flat(shape, ...) is the form for contiguous N-D buffers (attention operands, states, statistics): guards in front and behind."""
+Arena.flat(shape, ...) is the form for contiguous N-D buffers (attention operands, states, statistics): guards in front and behind.
+Padded64 is the fp64 form (the sentinel is a value of the caller's choice: NaN around an input, a marker around an output)."""
+import numpy as np
 import torch
 
 SENTINEL = {torch.bfloat16: 0x7FA5, torch.float16: 0x7EA5, torch.float32: 0x7FA5A5A5, torch.int32: 0x5A5A5A5A, torch.uint8: 0xA5}
@@ -16,6 +18,7 @@ _BITS = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32:
 ALIGN = 16                      # bytes: the alignment every kernel entry point may assume of an operand
 GUARD_ROWS = 256                # one edge of the largest tile (the 256x256 GEMM tile, the 256-row query block)
 FLAT_GUARD = 256 * 256          # elements in front of and behind a flat arena
+PAD = 1024                      # doubles in front of and behind a padded fp64 buffer
 
 
 class Arena:
@@ -85,3 +88,22 @@ class Arena:
         count, first = self.violations()
         assert count == 0, (f"{what}: {count} element(s) outside the ({self.rows}, {self.cols}) view (ld {self.ld}) were written; "
                             f"first (row, col) offsets relative to the view: {first}")
+
+
+class Padded64:
+    """A contiguous fp64 tensor of `shape` with PAD doubles of `fill` on each side."""
+
+    def __init__(self, shape, dev, fill, data=None):
+        n = int(np.prod(shape))
+        self.buf = torch.full((n + 2 * PAD,), fill, dtype=torch.float64, device=dev)
+        self.view = self.buf[PAD:PAD + n].view(shape)
+        if data is not None:
+            self.view.copy_(data)
+        self.before = self.buf.clone()
+        self.n = n
+
+    def assert_untouched(self, what, written=False):
+        now, was = self.buf.view(torch.int64), self.before.view(torch.int64)
+        assert torch.equal(now[:PAD], was[:PAD]) and torch.equal(now[PAD + self.n:], was[PAD + self.n:]), f"{what}: a guard changed"
+        if not written:
+            assert torch.equal(now, was), f"{what}: an input changed"

@@ -78,8 +78,9 @@ def test_chamfer_scores_match_reference(gold, dev):
 @pytest.mark.gpu
 @pytest.mark.parametrize("P,Q,B", [(1, 1, 1), (513, 7, 1), (5000, 300, 1), (2049, 1025, 3), (20000, 64, 24), (700, 70000, 1)])
 def test_nn_shapes_splits_and_batches(dev, P, Q, B):
-    """every launch plan (1 or 4 queries per thread, 1..n point splits, batches, a cloud shared by the batch) against a
-    torch fp64 brute force; ties (duplicated points) resolve to the lowest index"""
+    """one query per thread (every shape here is below the 524 288 queries at which nn_plan switches to four: that plan is
+    tests/test_nn_plans_gpu.py's), 1..n point splits, batches, a cloud shared by the batch, against a torch fp64 brute force; ties
+    (duplicated points) resolve to the lowest index"""
     g = torch.Generator().manual_seed(P * 31 + Q)
     pts = torch.randn((B, P, 3), generator=g)
     if P > 10:

@@ -154,6 +154,36 @@ def test_otsu_flt_epsilon_skip():
     assert stats[0].tolist() == [0, 1, 1, 1] and lab[0, 1234, 567] == 1 + 1234 * 2900 + 567
 
 
+CC_HIST_BLOCK_PIXELS, CC_HIST_MAX_BLOCKS = 256 * 16, 64      # csrc/am_components.hip: CC_THREADS * CC_HIST_CHUNK, CC_HIST_MAX_BLOCKS
+
+
+def two_trip_frame():
+    """601 x 499 = 299 899 pixels: uniform noise in the 262 144 pixels the first trip of cc_hist_kernel's loop reads, a two-level
+    distribution in the rest, so the Otsu threshold depends on the second trip; the last chunk holds 11 pixels."""
+    h, w = 601, 499
+    first_trip = CC_HIST_MAX_BLOCKS * CC_HIST_BLOCK_PIXELS
+    # mirrors the launch of cc_hist_kernel in am_mask_refine: min(ceil(hw / 4096), 64) blocks striding by blocks * 4096 pixels
+    assert -(-h * w // CC_HIST_BLOCK_PIXELS) > CC_HIST_MAX_BLOCKS and first_trip == 262_144 < h * w < 2 * first_trip
+    assert (h * w) % 16 == 11
+    rng = np.random.default_rng(0)
+    f = np.empty(h * w, np.uint8)
+    f[:first_trip] = rng.integers(0, 256, first_trip)
+    f[first_trip:] = np.where(rng.random(h * w - first_trip) < 0.7, 235, 180)
+    whole, head = int(MR.otsu_threshold(f.reshape(h, w))), int(MR.otsu_threshold(f[:first_trip].reshape(512, 512)))
+    assert whole != head, (whole, head)                     # a histogram without the second trip gives another threshold
+    return f.reshape(h, w)
+
+
+def test_histogram_second_trip():
+    """more than 64 blocks x 4096 pixels a frame: the grid-stride loop of cc_hist_kernel runs a second, ragged trip - alone and as
+    frame 1 of a batch of two; threshold, labels, mask and stats bit for bit"""
+    frame = two_trip_frame()
+    _, _, stats = _check([frame], 200)
+    assert stats[0, 0] == int(MR.otsu_threshold(frame))
+    _, _, stats2 = _check([soft_blob(601, 499, 5), frame], 200)
+    assert stats2[1].tolist() == stats[0].tolist()
+
+
 def soft_blob(h, w, seed):
     """A soft disc (a sigmoid of the distance to a jittered centre) plus Gaussian noise, uint8: what a matting network's mask looks
     like to the labelling - one large component, a few thousand specks."""

@@ -1,5 +1,5 @@
 """Guard bands of the mesh kernels (am_mesh.hip): fp32 and int32 outputs in arenas of sentinels (tests/_guard.py), fp64 outputs in a
-sentinel-padded buffer built here, every input in a poisoned arena - NaN around the vertices, the prefix sum and the uniforms, an
+sentinel-padded buffer (Padded64), every input in a poisoned arena - NaN around the vertices, the prefix sum and the uniforms, an
 index far outside the mesh around the faces and the CSR - so that a read past the last vertex, face, corner or sample shows up in the
 values or in the entry point's flag.  Values against the restatements of tests/test_mesh_prep_gpu.py at its bounds."""
 import numpy as np
@@ -7,11 +7,10 @@ import pytest
 import torch
 
 import test_mesh_prep_gpu as tg
-from _guard import Arena
+from _guard import Arena, Padded64
 
 pytestmark = pytest.mark.gpu
 
-PAD = 1024                      # doubles in front of and behind a padded fp64 buffer
 OUT_SENTINEL = -7.25e300
 
 
@@ -22,25 +21,6 @@ def dev():
     from actionmesh_amd import _lib
     _lib.lib()
     return torch.device("cuda:0")
-
-
-class Padded64:
-    """A contiguous fp64 tensor of `shape` with PAD doubles of `fill` on each side."""
-
-    def __init__(self, shape, dev, fill, data=None):
-        n = int(np.prod(shape))
-        self.buf = torch.full((n + 2 * PAD,), fill, dtype=torch.float64, device=dev)
-        self.view = self.buf[PAD:PAD + n].view(shape)
-        if data is not None:
-            self.view.copy_(data)
-        self.before = self.buf.clone()
-        self.n = n
-
-    def assert_untouched(self, what, written=False):
-        now, was = self.buf.view(torch.int64), self.before.view(torch.int64)
-        assert torch.equal(now[:PAD], was[:PAD]) and torch.equal(now[PAD + self.n:], was[PAD + self.n:]), f"{what}: a guard changed"
-        if not written:
-            assert torch.equal(now, was), f"{what}: an input changed"
 
 
 def _mesh(V, F, seed):

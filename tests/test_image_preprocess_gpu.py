@@ -21,7 +21,13 @@ RAW = os.path.join(GOLDEN, "frames_raw")
 CLIPS = ["davis_camel", "panda", "kangaroo"]
 # (in width, in height, out width, out height)
 RESIZE_CASES = [(614, 614, 256, 256), (100, 100, 256, 256), (1500, 1500, 256, 256), (300, 200, 384, 256), (523, 524, 256, 256),
-                (257, 255, 256, 258), (37, 1999, 256, 300), (256, 256, 256, 256), (2, 2, 256, 256)]
+                (257, 255, 256, 258), (37, 1999, 256, 300), (256, 256, 256, 256), (2, 2, 256, 256),
+                # tap tables beyond the LDS budget, read from global memory (horizontal, vertical), and the last size that fits
+                (2817, 40, 256, 256), (40, 2817, 256, 256), (2816, 40, 256, 256), (40, 2816, 256, 256)]
+IMAGE_LDS_BYTES = 48 * 1024         # csrc/am_image.hip
+# am_image_alpha_stats sizes its grid for four trips a thread, ceil(npix / (IMAGE_THREADS * 4 * 4)) blocks, and caps it at 256; a trip of
+# image_alpha_stats_kernel covers blocks * IMAGE_THREADS * 4 pixels (four pixels a thread)
+ALPHA_THREADS, ALPHA_PIXELS_PER_THREAD, ALPHA_TRIPS_UNCAPPED, ALPHA_MAX_BLOCKS = 256, 4, 4, 256
 DINO_CONFIG = {"crop_size": {"height": 224, "width": 224}, "do_center_crop": True, "do_convert_rgb": True, "do_normalize": True,
                "do_rescale": True, "do_resize": True, "image_mean": [0.485, 0.456, 0.406], "image_std": [0.229, 0.224, 0.225],
                "image_processor_type": "BitImageProcessor", "resample": 3, "rescale_factor": 0.00392156862745098,
@@ -63,6 +69,38 @@ def pil_processor(frames, settings):
 
 @pytest.mark.parametrize("w,h,ow,oh", RESIZE_CASES)
 def test_resample_against_pil(w, h, ow, oh):
+    images = sample_images(w, h, seed=w * 7919 + h)
+    names = sorted(images)
+    got = IP.resize_rgb(torch.from_numpy(np.stack([images[n] for n in names])).cuda(), oh, ow).cpu().numpy()
+    assert got.shape == (2, oh, ow, 3)
+    for i, n in enumerate(names):
+        want = np.asarray(Image.fromarray(images[n]).resize((ow, oh), Image.BICUBIC))
+        assert int((got[i] != want).sum()) == 0, (n, int((got[i] != want).sum()))
+
+
+def tap_tables_in_lds(w, h, ow, oh):
+    """mirrors use_h / use_v of am_image_resample (csrc/am_image.hip): (horizontal, vertical) table copied to LDS"""
+    ks_h, ks_v = int(IP.pack_taps(w, ow)[2]), int(IP.pack_taps(h, oh)[2])
+    return ow * (2 + ks_h) * 4 <= IMAGE_LDS_BYTES, oh * (2 + ks_v) * 4 <= IMAGE_LDS_BYTES
+
+
+def test_resize_cases_reach_both_tap_table_plans():
+    """the four threshold cases of RESIZE_CASES select what they are there for: if IMAGE_LDS_BYTES or the tap count moves, this fails
+    instead of test_resample_against_pil silently testing the LDS copy four more times"""
+    plans = {c: tap_tables_in_lds(*c) for c in RESIZE_CASES}
+    assert plans[(2817, 40, 256, 256)] == (False, True) and plans[(40, 2817, 256, 256)] == (True, False)
+    assert plans[(2816, 40, 256, 256)] == (True, True) and plans[(40, 2816, 256, 256)] == (True, True)
+    assert int(IP.pack_taps(2816, 256)[2]) == 45 and 256 * (2 + 45) * 4 == 48128              # the last size in LDS ...
+    assert int(IP.pack_taps(2817, 256)[2]) == 47 and 256 * (2 + 47) * 4 == 50176              # ... and the first one beyond
+    assert all(p == (True, True) for c, p in plans.items() if max(c[:2]) < 2816)
+
+
+def test_resample_both_tables_in_global_memory_and_a_ragged_width():
+    """2817 x 2817 -> 255 x 255: both passes read their taps from global memory, and the output width is no multiple of four, so the
+    vertical pass stores byte by byte; against PIL, zero differing bytes"""
+    w = h = 2817
+    ow = oh = 255
+    assert tap_tables_in_lds(w, h, ow, oh) == (False, False) and ow % 4 != 0
     images = sample_images(w, h, seed=w * 7919 + h)
     names = sorted(images)
     got = IP.resize_rgb(torch.from_numpy(np.stack([images[n] for n in names])).cuda(), oh, ow).cpu().numpy()
@@ -114,6 +152,41 @@ def test_alpha_stats_against_numpy():
             assert list(got[t]) == [int((a > 127).sum()), xs.min(), ys.min(), xs.max(), ys.max(), 0, 0, 0]
     empty = np.zeros((1, 16, 16, 4), dtype=np.uint8)
     assert list(ops.image_alpha_stats(torch.from_numpy(empty).cuda()).cpu().numpy()[0][:5]) == [0, 2 ** 31 - 1, 2 ** 31 - 1, -1, -1]
+
+
+@pytest.mark.parametrize("H,W", [(1024, 1025), (1023, 1027)], ids=["vector-loads", "scalar-loads"])
+def test_alpha_stats_fifth_trip_on_the_capped_grid(H, W):
+    """The grid of am_image_alpha_stats is sized so that a thread of image_alpha_stats_kernel makes up to four trips of its
+    grid-stride loop, until the cap of 256 blocks binds: beyond 256 x 4096 = 1 048 576 pixels a frame the loop runs a fifth trip,
+    which no smaller frame does (512 x 512 is 64 blocks and four trips).  Frame 0 is random; every alpha > 0 of frame 1 lies beyond
+    pixel 1 048 576, that is in the fifth trip alone, one of them in the very last column of the last row, so a dropped or
+    misindexed fifth trip changes the count and all four bounds"""
+    npix = H * W
+    # mirrors the launch of am_image_alpha_stats: min(ceil(npix / (IMAGE_THREADS * 4 * 4)), 256) blocks ...
+    blocks = min(-(-npix // (ALPHA_THREADS * ALPHA_PIXELS_PER_THREAD * ALPHA_TRIPS_UNCAPPED)), ALPHA_MAX_BLOCKS)
+    # ... and the loop of image_alpha_stats_kernel: step = gridDim.x * IMAGE_THREADS * 4 pixels
+    step = blocks * ALPHA_THREADS * ALPHA_PIXELS_PER_THREAD
+    four_trips = ALPHA_TRIPS_UNCAPPED * step                # the pixels that the first four trips cover
+    assert blocks == ALPHA_MAX_BLOCKS and step == 262_144 and four_trips == 1_048_576
+    assert -(-npix // step) == 5 > ALPHA_TRIPS_UNCAPPED
+    assert (npix % 4 == 0) == (W == 1025)                   # vector loads need a multiple of four pixels a frame
+    rng = np.random.default_rng(H)
+    rgba = rng.integers(0, 256, (2, H, W, 4), dtype=np.uint8)
+    rgba[0, ..., 3] = np.where(rng.random((H, W)) < 0.6, 0, rgba[0, ..., 3])
+    rgba[0, :5] = 0
+    rgba[0, :, :7] = 0
+    a1 = np.where(rng.random(npix) < 0.5, 0, rgba[1, ..., 3].reshape(-1))
+    a1[:four_trips] = 0                                     # nothing in trips one to four: what is left is the last rows only
+    a1[four_trips] = 90                                     # the first pixel of the fifth trip ...
+    a1[-1] = 200                                            # ... and the last column of the last row
+    rgba[1, ..., 3] = a1.reshape(H, W)
+    assert (np.nonzero(a1)[0] >= four_trips).all() and np.count_nonzero(a1) > 400
+    got = ops.image_alpha_stats(torch.from_numpy(rgba).cuda()).cpu().numpy()
+    for t in range(2):
+        a = rgba[t, ..., 3]
+        ys, xs = np.nonzero(a > 0)
+        assert list(got[t]) == [int((a > 127).sum()), xs.min(), ys.min(), xs.max(), ys.max(), 0, 0, 0], t
+    assert got[1][3] == W - 1 and got[1][4] == H - 1 and got[1][2] == four_trips // W
 
 
 def test_invalid_alpha_raises_on_the_device_path():

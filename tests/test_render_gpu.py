@@ -69,9 +69,11 @@ def vertex_normals(V, F):
 
 
 def restate(V, F, camd, S, tol=1e-5):
-    """Every sub-pixel of the 2S x 2S raster against every face, in fp64.  Returns the face index, the clipped barycentrics, a
-    `stable` flag (centre more than `tol` NDC from the boundary of every face that covers or nearly covers it, and the two nearest
-    depths more than `tol` apart), and the S x S mask / normal / rgba8 of the resolve."""
+    """Every sub-pixel of the 2S x 2S raster against every face, in fp64, with the three rejections of the header: all depths
+    negative, |area| <= 1e-8, centre outside the closed box of the projected vertices.  Returns the face index, the clipped
+    barycentrics, a `stable` flag (centre more than `tol` NDC from the boundary of every face that covers or nearly covers it - for a
+    face with a vertex behind the camera: from the lines through its edges and from its box - and the two nearest depths more than
+    `tol` apart), and the S x S mask / normal / rgba8 of the resolve."""
     W = 2 * S
     Rm, T = camd["R"].double().numpy(), camd["T"].double().numpy()
     f, p = camd["focal_length"].double().numpy(), camd["principal_point"].double().numpy()
@@ -89,15 +91,14 @@ def restate(V, F, camd, S, tol=1e-5):
         v0, v1, v2 = P[i0], P[i1], P[i2]
         if max(v0[2], v1[2], v2[2]) < 0 or abs(edge(v0[0], v0[1], v1, v2)) <= 1e-8:
             continue
-        # the window of centres the face can reach (all of them when a vertex is behind the camera)
-        if min(v0[2], v1[2], v2[2]) > 0:
-            lo, hi = np.minimum(np.minimum(v0, v1), v2)[:2] - 4.0 / W, np.maximum(np.maximum(v0, v1), v2)[:2] + 4.0 / W
-            cs, rs = np.nonzero((xs >= lo[0]) & (xs <= hi[0]))[0], np.nonzero((xs >= lo[1]) & (xs <= hi[1]))[0]
-            if len(cs) == 0 or len(rs) == 0:
-                continue
-            win = (slice(rs[0], rs[-1] + 1), slice(cs[0], cs[-1] + 1))
-        else:
-            win = (slice(0, W), slice(0, W))
+        # no centre outside the closed box of the three projected vertices is covered; the window adds a margin for `stable`
+        lo, hi = np.minimum(np.minimum(v0, v1), v2)[:2], np.maximum(np.maximum(v0, v1), v2)[:2]
+        cs = np.nonzero((xs >= lo[0] - 4.0 / W) & (xs <= hi[0] + 4.0 / W))[0]
+        rs = np.nonzero((xs >= lo[1] - 4.0 / W) & (xs <= hi[1] + 4.0 / W))[0]
+        if len(cs) == 0 or len(rs) == 0:
+            continue
+        win = (slice(rs[0], rs[-1] + 1), slice(cs[0], cs[-1] + 1))
+        front = min(v0[2], v1[2], v2[2]) > 0
         X, Y = Xa[win], Ya[win]
         area = edge(v2[0], v2[1], v0, v1)
         w = np.stack([edge(X, Y, v1, v2), edge(X, Y, v2, v0), edge(X, Y, v0, v1)], -1) / area
@@ -107,13 +108,18 @@ def restate(V, F, camd, S, tol=1e-5):
         cb = np.maximum(pb, 0)
         cb = cb / np.maximum(cb.sum(-1, keepdims=True), 1e-5)
         z = cb @ np.array([v0[2], v1[2], v2[2]])
-        cov = inside & (z >= 0)
-        # distance of every centre to the triangle's boundary (segments)
+        cov = inside & (z >= 0) & (X >= lo[0]) & (X <= hi[0]) & (Y >= lo[1]) & (Y <= hi[1])
+        # distance of every centre to the triangle's boundary: its segments for a face in front of the camera; for a face with a
+        # vertex behind it the barycentrics change sign on the whole LINES through the edges, and the box decides as well
         d = np.full(X.shape, np.inf)
         for a, b in ((v0, v1), (v1, v2), (v2, v0)):
             ab = b[:2] - a[:2]
-            s = np.clip(((X - a[0]) * ab[0] + (Y - a[1]) * ab[1]) / max(ab @ ab, 1e-300), 0, 1)
+            s = ((X - a[0]) * ab[0] + (Y - a[1]) * ab[1]) / max(ab @ ab, 1e-300)
+            s = np.clip(s, 0, 1) if front else s
             d = np.minimum(d, np.hypot(X - a[0] - s * ab[0], Y - a[1] - s * ab[1]))
+        if not front:
+            for k, A in enumerate((X, Y)):
+                d = np.minimum(d, np.minimum(np.abs(A - lo[k]), np.abs(A - hi[k])))
         stable[win] &= d > tol
         b_, s_ = best[win], second[win]
         closer = cov & (z < b_)
@@ -134,8 +140,8 @@ def restate(V, F, camd, S, tol=1e-5):
     return dict(face=face, bary=bary, stable=stable, mask=mask, normal=u, rgba8=np.floor(rgba * 255).astype(np.int64))
 
 
-def check_against_restatement(V, F, cams, S):
-    got = render(V, F, cams, S)
+def check_against_restatement(V, F, cams, S, got=None):
+    got = render(V, F, cams, S) if got is None else got
     compared = 0
     for c, camd in enumerate(cams):
         ref = restate(V, F, camd, S)
@@ -166,6 +172,35 @@ def test_icosphere_matches_restatement():
     V = V + np.array([0.1, -0.05, 0.07])
     cams = [R.uniform_cameras(distance=3.0)[t] for t in R.VISUALIZER_CAMERAS]
     assert check_against_restatement(V, F, cams, 128) > 3 * 128 * 128 * 0.8
+
+
+SCAN_CHUNK = 1024                   # csrc/am_raster.hip: adj_scan_kernel scans the per-vertex face counts 1024 at a time with a carry
+
+
+def test_vertex_table_scan_carries_across_chunks():
+    """2562 used vertices scattered by a permutation over 3072 rows (the other 510 are on no face): three full chunks of
+    adj_scan_kernel, non-trivial counts on both sides of every chunk border and zero counts inside.  A wrong carry gives a vertex
+    the face list of another one, which moves its normal; the unused rows' normals must never show."""
+    V0, F0 = icosphere(4, 0.8)
+    rng = np.random.default_rng(7)
+    V0 = V0 * rng.uniform(0.9, 1.1, size=(len(V0), 1))
+    n = 3072
+    # mirrors the loop of adj_scan_kernel: ceil(V / 1024) trips of one block, the carry crossing every border between them
+    assert len(V0) == 2562 and n % SCAN_CHUNK == 0 and n // SCAN_CHUNK == 3 and len(V0) > 2 * SCAN_CHUNK
+    rows = rng.permutation(n)[: len(V0)]
+    V = rng.normal(0, 0.3, size=(n, 3))
+    V[rows] = V0
+    F = rows[F0]
+    valence = np.bincount(F.reshape(-1), minlength=n)
+    assert (valence == 0).sum() == n - len(V0)
+    for border in (SCAN_CHUNK, 2 * SCAN_CHUNK):
+        assert valence[:border].sum() > 0 and valence[border - 8: border + 8].max() > 0 and valence[border:].sum() > 0
+        assert (valence[border - 64: border + 64] == 0).any()
+    cams = [R.uniform_cameras(distance=3.0)[t] for t in R.VISUALIZER_CAMERAS]
+    got = render(V, F, cams, 48)
+    assert check_against_restatement(V, F, cams, 48, got) > 3 * 48 * 48 * 0.8
+    pf = got["pix_to_face"]
+    assert pf.min() == -1 and pf.max() < len(F) and (pf >= 0).sum() > 3 * 2000       # only real faces are named
 
 
 def test_analytic_sphere():
@@ -256,6 +291,38 @@ def test_frame_filling_quad_behind_camera_and_half_plane():
     vals = set(np.unique(got["mask"]).tolist())
     assert vals <= {0.0, 0.25, 0.5, 0.75, 1.0} and {0.0, 1.0} <= vals and len(vals) > 2
     assert set(np.unique(got["rgba"][..., 3]).tolist()) <= {0, 63, 127, 191, 255}
+
+
+def test_faces_straddling_the_camera_plane():
+    """A face with a vertex behind the camera has barycentrics > 0 in the cone beyond the vertex on the other side of the camera
+    plane.  For the two triangles here that vertex's projection is extreme in y, so the whole cone lies OUTSIDE the box of the
+    projected vertices, and the box rule of include/actionmesh_amd.h skips every centre outside the box: these faces cover nothing,
+    whatever the resolution.  (Not every such face: where that vertex projects extreme on neither axis, part of the cone lies inside
+    the box and stays covered.)  pix_to_face is compared with the restatement on every sub-pixel more than 1e-5 from a box edge or
+    an edge's line (restate() counts both for such a face), not on a subset chosen by hand."""
+    two_behind = np.array([(-0.5, -0.5, -3.0), (0.6, -0.4, -3.0), (0.0, 0.3, 0.0)])      # view z = -1, -1, 2 with cam()
+    one_behind = np.array([(-0.5, -0.5, 0.0), (0.6, -0.4, 0.0), (0.0, 0.3, -3.0)])       # view z = 2, 2, -1
+    tri = np.array([[0, 1, 2]])
+    for S in (32, 45):
+        for V in (two_behind, one_behind):
+            got = render(V, tri, [cam()], S)
+            ref = restate(V, tri, cam(), S)
+            assert (ref["face"] == -1).all() and ref["stable"].mean() > 0.9
+            st = ref["stable"]
+            assert np.array_equal(got["pix_to_face"][0, 0][st], ref["face"][st])
+            assert (got["pix_to_face"] == -1).all() and (got["bary"] == -1).all(), int((got["pix_to_face"] >= 0).sum())
+            assert (got["mask"] == 0).all() and (got["rgba"][..., :3] == 255).all() and (got["rgba"][..., 3] == 0).all()
+    # the first triangle in front of a frame-filling quad (the one of the test below, at view z = 2.5): the quad shows everywhere
+    S = 32
+    quad = np.array([(-3.0, -3.05, 0.5), (3.0, -3.05, 0.5), (3.0, 2.95, 0.5), (-3.0, 2.95, 0.5)])
+    V = np.concatenate([quad, two_behind])
+    F = np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6]])
+    got = render(V, F, [cam()], S)
+    ref = restate(V, F, cam(), S)
+    st = ref["stable"]
+    assert st.mean() > 0.9 and set(np.unique(ref["face"])) == {0, 1}
+    assert np.array_equal(got["pix_to_face"][0, 0][st], ref["face"][st])
+    assert set(np.unique(got["pix_to_face"])) == {0, 1} and (got["mask"] == 1.0).all() and (got["rgba"][..., 3] == 255).all()
 
 
 def test_deterministic_and_batch_independent():
