@@ -202,7 +202,8 @@ class AmSurfaceSampleArgs(C.Structure):        # am_surface_sample_args
 
 
 DECIMATE_NO_KEY = 2 ** 63 - 1               # AM_DECIMATE_NO_KEY
-DECIMATE_BAD_FACE, DECIMATE_BAD_CSR, DECIMATE_BAD_EDGE, DECIMATE_BAD_KEPT = 1, 2, 4, 8      # am_decimate_*'s out_flag bits
+MESH_BAD_FACE, MESH_BAD_CSR = 1, 2          # the out_flag bits of am_vertex_normals / am_face_areas / am_surface_sample
+DECIMATE_BAD_FACE, DECIMATE_BAD_CSR, DECIMATE_BAD_EDGE, DECIMATE_BAD_KEPT = MESH_BAD_FACE, MESH_BAD_CSR, 4, 8      # am_decimate_*'s out_flag bits
 
 
 class AmDecimateQuadricsArgs(C.Structure):     # am_decimate_quadrics_args

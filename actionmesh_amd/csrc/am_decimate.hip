@@ -11,30 +11,11 @@
 //   am_decimate_apply      one thread per kept edge: moves u, adds the quadrics, rewrites v -> u in v's corners, marks the two faces
 // No floating-point atomics anywhere (the only atomic is the OR into the flag word).  No index read from memory is ever used as an
 // address before it has been compared with its bound; loops over corners run between CSR offsets that were validated first.
-#include "am_common.h"
-
-#pragma clang fp contract(off)      // the helpers below too, whatever flags the file is built with
+#include "am_geometry.h"
 
 namespace {
 
-constexpr int DEC_THREADS = 256;
-constexpr int64_t DEC_MAX = (((int64_t)1 << 31) - 1) / 3;       // 3 * n fits an int32 corner id
 constexpr int64_t NO_KEY = AM_DECIMATE_NO_KEY;
-
-struct vec3 {
-  double x, y, z;
-};
-
-__device__ __forceinline__ vec3 load3(const double* p, int v) {
-  const int64_t o = (int64_t)v * 3;
-  return {p[o], p[o + 1], p[o + 2]};
-}
-__device__ __forceinline__ vec3 sub3(vec3 a, vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot3(vec3 a, vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ vec3 cross3(vec3 a, vec3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ bool in_range(int i, int64_t n) { return i >= 0 && (int64_t)i < n; }
 
 __device__ __forceinline__ uint32_t mix32(uint32_t h) {
   h ^= h >> 16;
@@ -43,51 +24,6 @@ __device__ __forceinline__ uint32_t mix32(uint32_t h) {
   h *= 0xc2b2ae35u;
   h ^= h >> 16;
   return h;
-}
-
-// what every kernel knows of the mesh
-struct mesh_view {
-  int64_t n_vertices, n_faces, n_edges;
-  const int32_t* faces;
-  const int32_t* offsets;
-  const int32_t* corners;
-  const int32_t* edges;
-  const int32_t* he2e;
-  int32_t* flag;
-};
-
-// the validated corner range of vertex v (v already inside [0, n_vertices)); an invalid one is empty and raises the flag
-__device__ __forceinline__ bool csr_range(const mesh_view& m, int v, int& begin, int& end) {
-  begin = m.offsets[v];
-  end = m.offsets[v + 1];
-  if (begin < 0 || end < begin || (int64_t)end > 3 * m.n_faces) {
-    atomicOr(m.flag, AM_DECIMATE_BAD_CSR);
-    begin = end = 0;
-    return false;
-  }
-  return true;
-}
-
-// corner j of the range of vertex v: the corner id, or -1 (flag raised) when it is outside [0, 3 n_faces) or names another vertex
-__device__ __forceinline__ int corner_at(const mesh_view& m, int j, int v) {
-  const int c = m.corners[j];
-  if (c < 0 || (int64_t)c >= 3 * m.n_faces || m.faces[c] != v) {
-    atomicOr(m.flag, AM_DECIMATE_BAD_CSR);
-    return -1;
-  }
-  return c;
-}
-
-// the other two vertices of the face of corner c, in face order behind the corner; false (flag raised) when one is out of range
-__device__ __forceinline__ bool corner_others(const mesh_view& m, int c, int& w1, int& w2) {
-  const int f3 = c - c % 3, k = c % 3;
-  w1 = m.faces[f3 + (k + 1) % 3];
-  w2 = m.faces[f3 + (k + 2) % 3];
-  if (!in_range(w1, m.n_vertices) || !in_range(w2, m.n_vertices)) {
-    atomicOr(m.flag, AM_DECIMATE_BAD_FACE);
-    return false;
-  }
-  return true;
 }
 
 // the edge index of half-edge h, which runs between vertices a and b; -1 (flag raised) when the table does not say so
@@ -113,10 +49,10 @@ __device__ bool adjacent(const mesh_view& m, int v, int begin, int end, int w) {
   return found;
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void decimate_quadrics_kernel(mesh_view m, const double* __restrict__ positions,
-                                                                        double* __restrict__ out_quadrics) {
+__global__ __launch_bounds__(MESH_THREADS) void decimate_quadrics_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                         double* __restrict__ out_quadrics) {
 #pragma clang fp contract(off)
-  const int64_t v = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= m.n_vertices) return;
   double q[10];
   for (int i = 0; i < 10; ++i) q[i] = 0.0;
@@ -125,17 +61,13 @@ __global__ __launch_bounds__(DEC_THREADS) void decimate_quadrics_kernel(mesh_vie
   for (int j = begin; j < end; ++j) {
     const int c = corner_at(m, j, (int)v);
     if (c < 0) continue;
-    const int f3 = c - c % 3;
-    const int i0 = m.faces[f3], i1 = m.faces[f3 + 1], i2 = m.faces[f3 + 2];
-    if (!in_range(i0, m.n_vertices) || !in_range(i1, m.n_vertices) || !in_range(i2, m.n_vertices)) {
-      atomicOr(m.flag, AM_DECIMATE_BAD_FACE);
-      continue;
-    }
+    int i0, i1, i2;
+    if (!face_indices(m.faces + (c - c % 3), m.n_vertices, m.flag, i0, i1, i2)) continue;
     const vec3 p0 = load3(positions, i0), p1 = load3(positions, i1), p2 = load3(positions, i2);
     const vec3 cr = cross3(sub3(p1, p0), sub3(p2, p0));
-    const double len = sqrt(dot3(cr, cr));
+    const double len = norm3(cr);
     if (!(len > AM_MESH_ZERO)) continue;
-    const vec3 n = {cr.x / len, cr.y / len, cr.z / len};
+    const vec3 n = div3(cr, len);
     const double d = -dot3(n, p0);
     const double w = len / 2.0;
     const double p[4] = {n.x, n.y, n.z, d};
@@ -216,13 +148,13 @@ __device__ bool walk_flips(const mesh_view& m, const double* __restrict__ positi
   return ok;
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void decimate_edges_kernel(mesh_view m, const double* __restrict__ positions,
-                                                                     const double* __restrict__ quadrics,
-                                                                     const int32_t* __restrict__ edge_count,
-                                                                     double* __restrict__ out_positions, double* __restrict__ out_cost,
-                                                                     int64_t* __restrict__ out_key) {
+__global__ __launch_bounds__(MESH_THREADS) void decimate_edges_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                      const double* __restrict__ quadrics,
+                                                                      const int32_t* __restrict__ edge_count,
+                                                                      double* __restrict__ out_positions, double* __restrict__ out_cost,
+                                                                      int64_t* __restrict__ out_key) {
 #pragma clang fp contract(off)
-  const int64_t e = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (e >= m.n_edges) return;
   const int u = m.edges[2 * e], v = m.edges[2 * e + 1];
   vec3 x = {0.0, 0.0, 0.0};
@@ -302,9 +234,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decimate_edges_kernel(mesh_view m
 }
 
 // pass 0: m1[v] = min key of v's edges;  pass 1: m2[v] = min of m1 over v and its neighbours
-__global__ __launch_bounds__(DEC_THREADS) void decimate_min_kernel(mesh_view m, int pass, const int64_t* __restrict__ in,
-                                                                   int64_t* __restrict__ out) {
-  const int64_t v = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void decimate_min_kernel(mesh_view m, int pass, const int64_t* __restrict__ in,
+                                                                    int64_t* __restrict__ out) {
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= m.n_vertices) return;
   int64_t best = pass == 0 ? NO_KEY : in[v];
   int begin, end;
@@ -330,9 +262,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decimate_min_kernel(mesh_view m, 
   out[v] = best;
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void decimate_pick_kernel(mesh_view m, const int64_t* __restrict__ keys,
-                                                                    const int64_t* __restrict__ m2, uint8_t* __restrict__ out_selected) {
-  const int64_t e = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void decimate_pick_kernel(mesh_view m, const int64_t* __restrict__ keys,
+                                                                     const int64_t* __restrict__ m2, uint8_t* __restrict__ out_selected) {
+  const int64_t e = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (e >= m.n_edges) return;
   const int u = m.edges[2 * e], v = m.edges[2 * e + 1];
   uint8_t sel = 0;
@@ -345,12 +277,12 @@ __global__ __launch_bounds__(DEC_THREADS) void decimate_pick_kernel(mesh_view m,
   out_selected[e] = sel;
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void decimate_apply_kernel(mesh_view m, int64_t n_kept, const int32_t* __restrict__ kept,
-                                                                     const double* __restrict__ candidates, double* positions,
-                                                                     double* quadrics, int32_t* faces, int32_t* __restrict__ vertex_map,
-                                                                     uint8_t* __restrict__ out_face_dead) {
+__global__ __launch_bounds__(MESH_THREADS) void decimate_apply_kernel(mesh_view m, int64_t n_kept, const int32_t* __restrict__ kept,
+                                                                      const double* __restrict__ candidates, double* positions,
+                                                                      double* quadrics, int32_t* faces, int32_t* __restrict__ vertex_map,
+                                                                      uint8_t* __restrict__ out_face_dead) {
 #pragma clang fp contract(off)
-  const int64_t i = (int64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (i >= n_kept) return;
   const int e = kept[i];
   if (!in_range(e, m.n_edges)) {
@@ -378,14 +310,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decimate_apply_kernel(mesh_view m
   vertex_map[v] = u;
 }
 
-unsigned dec_blocks(int64_t n) { return (unsigned)((n + DEC_THREADS - 1) / DEC_THREADS); }
-
-int check_mesh(const char* who, int64_t n_vertices, int64_t n_faces) {
-  AM_CHECK(n_vertices >= 1 && n_vertices <= DEC_MAX, "%s: %lld vertices outside 1 .. (2^31 - 1) / 3", who, (long long)n_vertices);
-  AM_CHECK(n_faces >= 1 && n_faces <= DEC_MAX, "%s: %lld faces outside 1 .. (2^31 - 1) / 3", who, (long long)n_faces);
-  return AM_OK;
-}
-
 int check_edges(const char* who, int64_t n_edges) {
   AM_CHECK(n_edges >= 1 && n_edges <= (((int64_t)1 << 31) - 1), "%s: %lld edges outside 1 .. 2^31 - 1", who, (long long)n_edges);
   return AM_OK;
@@ -400,7 +324,7 @@ extern "C" int am_decimate_quadrics(const am_decimate_quadrics_args* a, void* st
   hipStream_t st = (hipStream_t)stream;
   const mesh_view m = {a->n_vertices, a->n_faces, 0, a->faces, a->offsets, a->corners, nullptr, nullptr, a->out_flag};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(decimate_quadrics_kernel, dim3(dec_blocks(a->n_vertices)), dim3(DEC_THREADS), 0, st, m, a->positions, a->out_quadrics);
+  hipLaunchKernelGGL(decimate_quadrics_kernel, dim3(mesh_blocks(a->n_vertices)), dim3(MESH_THREADS), 0, st, m, a->positions, a->out_quadrics);
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
@@ -415,7 +339,7 @@ extern "C" int am_decimate_edges(const am_decimate_edges_args* a, void* stream) 
   hipStream_t st = (hipStream_t)stream;
   const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(decimate_edges_kernel, dim3(dec_blocks(a->n_edges)), dim3(DEC_THREADS), 0, st, m, a->positions, a->quadrics,
+  hipLaunchKernelGGL(decimate_edges_kernel, dim3(mesh_blocks(a->n_edges)), dim3(MESH_THREADS), 0, st, m, a->positions, a->quadrics,
                      a->edge_count, a->out_positions, a->out_cost, a->out_key);
   AM_HIP(hipGetLastError());
   return AM_OK;
@@ -431,10 +355,10 @@ extern "C" int am_decimate_select(const am_decimate_select_args* a, void* stream
   hipStream_t st = (hipStream_t)stream;
   const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(decimate_min_kernel, dim3(dec_blocks(a->n_vertices)), dim3(DEC_THREADS), 0, st, m, 0, a->keys, a->out_m1);
-  hipLaunchKernelGGL(decimate_min_kernel, dim3(dec_blocks(a->n_vertices)), dim3(DEC_THREADS), 0, st, m, 1, (const int64_t*)a->out_m1,
+  hipLaunchKernelGGL(decimate_min_kernel, dim3(mesh_blocks(a->n_vertices)), dim3(MESH_THREADS), 0, st, m, 0, a->keys, a->out_m1);
+  hipLaunchKernelGGL(decimate_min_kernel, dim3(mesh_blocks(a->n_vertices)), dim3(MESH_THREADS), 0, st, m, 1, (const int64_t*)a->out_m1,
                      a->out_m2);
-  hipLaunchKernelGGL(decimate_pick_kernel, dim3(dec_blocks(a->n_edges)), dim3(DEC_THREADS), 0, st, m, a->keys, (const int64_t*)a->out_m2,
+  hipLaunchKernelGGL(decimate_pick_kernel, dim3(mesh_blocks(a->n_edges)), dim3(MESH_THREADS), 0, st, m, a->keys, (const int64_t*)a->out_m2,
                      a->out_selected);
   AM_HIP(hipGetLastError());
   return AM_OK;
@@ -453,7 +377,7 @@ extern "C" int am_decimate_apply(const am_decimate_apply_args* a, void* stream) 
   const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, nullptr, a->out_flag};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
   AM_HIP(hipMemsetAsync(a->out_face_dead, 0, (size_t)a->n_faces, st));
-  hipLaunchKernelGGL(decimate_apply_kernel, dim3(dec_blocks(a->n_kept)), dim3(DEC_THREADS), 0, st, m, a->n_kept, a->kept, a->candidates,
+  hipLaunchKernelGGL(decimate_apply_kernel, dim3(mesh_blocks(a->n_kept)), dim3(MESH_THREADS), 0, st, m, a->n_kept, a->kept, a->candidates,
                      a->positions, a->quadrics, a->faces, a->vertex_map, a->out_face_dead);
   AM_HIP(hipGetLastError());
   return AM_OK;

@@ -12,36 +12,13 @@
 //              A gather: no floating-point atomics, so the bits do not depend on scheduling.
 //   am_face_areas and am_surface_sample: one launch each, one thread per face / per sample.
 // No index read from memory is ever used as an address before it has been compared with its bound.
-#include "am_common.h"
-
-#pragma clang fp contract(off)      // the helpers below too, whatever flags the file is built with
+#include "am_geometry.h"
 
 namespace {
 
-constexpr int MESH_THREADS = 256;
 constexpr double MESH_PI = 3.14159265358979323846;
 
-__device__ __forceinline__ double mesh_load(const void* p, int64_t i, int f64) {
-  return f64 ? reinterpret_cast<const double*>(p)[i] : (double)reinterpret_cast<const float*>(p)[i];
-}
-
-struct vec3 {
-  double x, y, z;
-};
-
-__device__ __forceinline__ vec3 mesh_vertex(const void* verts, int64_t base, int v, int f64) {
-  const int64_t o = base + (int64_t)v * 3;
-  return {mesh_load(verts, o, f64), mesh_load(verts, o + 1, f64), mesh_load(verts, o + 2, f64)};
-}
-__device__ __forceinline__ vec3 sub3(vec3 a, vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot3(vec3 a, vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ double norm3(vec3 a) { return sqrt(dot3(a, a)); }
-__device__ __forceinline__ vec3 div3(vec3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ vec3 cross3(vec3 a, vec3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
 __device__ __forceinline__ double clip1(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
-__device__ __forceinline__ bool in_range(int i, int64_t n) { return i >= 0 && (int64_t)i < n; }
 
 // c = e1 x e2 and |c|; the unit normal is c / |c|, or zero when |c| <= AM_MESH_ZERO
 __device__ __forceinline__ vec3 unit_normal(vec3 c, double len) {
@@ -58,10 +35,10 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_face_kernel(const void* __r
   const int64_t f = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (f >= n_faces) return;
   const int t = blockIdx.y;
-  const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
   vec3 n = {0.0, 0.0, 0.0};
   double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-  if (in_range(i0, n_vertices) && in_range(i1, n_vertices) && in_range(i2, n_vertices)) {
+  int i0, i1, i2;
+  if (face_indices(faces + 3 * f, n_vertices, flag, i0, i1, i2)) {
     const int64_t base = (int64_t)t * frame_stride;
     const vec3 v0 = mesh_vertex(verts, base, i0, f64), v1 = mesh_vertex(verts, base, i1, f64), v2 = mesh_vertex(verts, base, i2, f64);
     const vec3 e1 = sub3(v1, v0), e2 = sub3(v2, v0), e3 = sub3(v2, v1);
@@ -74,8 +51,6 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_face_kernel(const void* __r
       a1 = acos(clip1(-dot3(u, w)));
       a2 = (MESH_PI - a0) - a1;
     }
-  } else {
-    atomicOr(flag, 1);
   }
   double* s = staged + ((int64_t)t * n_faces + f) * 6;
   s[0] = n.x;
@@ -93,29 +68,20 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_face_kernel(const void* __r
 }
 
 // grid (vertex blocks, n_frames)
-__global__ __launch_bounds__(MESH_THREADS) void mesh_vertex_kernel(const void* __restrict__ verts, int f64, int64_t frame_stride,
-                                                                   int64_t n_vertices, int64_t n_faces, const int32_t* __restrict__ faces,
-                                                                   const int32_t* __restrict__ offsets, const int32_t* __restrict__ corners,
-                                                                   const double* __restrict__ staged, float* __restrict__ out_features,
-                                                                   float* __restrict__ out_normals, int32_t* __restrict__ flag) {
+__global__ __launch_bounds__(MESH_THREADS) void mesh_vertex_kernel(mesh_view m, const void* __restrict__ verts, int f64,
+                                                                   int64_t frame_stride, const double* __restrict__ staged,
+                                                                   float* __restrict__ out_features, float* __restrict__ out_normals) {
 #pragma clang fp contract(off)
   const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
-  if (v >= n_vertices) return;
+  if (v >= m.n_vertices) return;
   const int t = blockIdx.y;
-  const int64_t n_corners = 3 * n_faces;
-  int begin = offsets[v], end = offsets[v + 1];
-  if (begin < 0 || end < begin || (int64_t)end > n_corners) {
-    atomicOr(flag, 2);
-    begin = end = 0;
-  }
-  const double* st = staged + (int64_t)t * n_faces * 6;
+  int begin, end;
+  csr_range(m, (int)v, begin, end);
+  const double* st = staged + (int64_t)t * m.n_faces * 6;
   double sx = 0.0, sy = 0.0, sz = 0.0;
   for (int j = begin; j < end; ++j) {
-    const int c = corners[j];
-    if (c < 0 || (int64_t)c >= n_corners || (int64_t)faces[c] != v) {       // faces[c]: c = 3 * face + k, checked just before
-      atomicOr(flag, 2);
-      continue;
-    }
+    const int c = corner_at(m, j, (int)v);
+    if (c < 0) continue;
     const double* s = st + (int64_t)(c / 3) * 6;
     const double a = s[3 + c % 3];
     sx = sx + a * s[0];
@@ -135,7 +101,7 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertex_kernel(const void* _
   nx = nx / l32;
   ny = ny / l32;
   nz = nz / l32;
-  const int64_t row = (int64_t)t * n_vertices + v;
+  const int64_t row = (int64_t)t * m.n_vertices + v;
   if (out_features) {
     const int64_t src = (int64_t)t * frame_stride + v * 3;
     float* o = out_features + row * 6;
@@ -160,13 +126,11 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_area_kernel(const void* __r
 #pragma clang fp contract(off)
   const int64_t f = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (f >= n_faces) return;
-  const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
   double area = 0.0;
-  if (in_range(i0, n_vertices) && in_range(i1, n_vertices) && in_range(i2, n_vertices)) {
+  int i0, i1, i2;
+  if (face_indices(faces + 3 * f, n_vertices, flag, i0, i1, i2)) {
     const vec3 v0 = mesh_vertex(verts, 0, i0, f64), v1 = mesh_vertex(verts, 0, i1, f64), v2 = mesh_vertex(verts, 0, i2, f64);
     area = norm3(cross3(sub3(v1, v0), sub3(v2, v0))) / 2.0;
-  } else {
-    atomicOr(flag, 1);
   }
   out_areas[f] = area;
 }
@@ -200,9 +164,9 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_sample_kernel(const void* _
   }
   r0 = fabs(r0);
   r1 = fabs(r1);
-  const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
   vec3 p = {0.0, 0.0, 0.0}, n = {0.0, 0.0, 0.0};
-  if (in_range(i0, n_vertices) && in_range(i1, n_vertices) && in_range(i2, n_vertices)) {
+  int i0, i1, i2;
+  if (face_indices(faces + 3 * f, n_vertices, flag, i0, i1, i2)) {
     const vec3 v0 = mesh_vertex(verts, 0, i0, f64), v1 = mesh_vertex(verts, 0, i1, f64), v2 = mesh_vertex(verts, 0, i2, f64);
     const vec3 e1 = sub3(v1, v0), e2 = sub3(v2, v0);
     p.x = (v0.x + e1.x * r0) + e2.x * r1;
@@ -212,8 +176,6 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_sample_kernel(const void* _
       const vec3 c = cross3(e1, e2);
       n = unit_normal(c, norm3(c));
     }
-  } else {
-    atomicOr(flag, 1);
   }
   out_points[3 * i] = p.x;
   out_points[3 * i + 1] = p.y;
@@ -224,10 +186,6 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_sample_kernel(const void* _
     out_normals[3 * i + 2] = n.z;
   }
 }
-
-constexpr int64_t MESH_MAX = (((int64_t)1 << 31) - 1) / 3;      // 3 * n fits an int32 corner id / element offset of one frame
-
-unsigned mesh_blocks(int64_t n) { return (unsigned)((n + MESH_THREADS - 1) / MESH_THREADS); }
 
 }  // namespace
 
@@ -240,9 +198,7 @@ extern "C" size_t am_vertex_normals_workspace_bytes(int n_frames, int64_t n_face
 extern "C" int am_vertex_normals(const am_vertex_normals_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_vertex_normals: null arguments");
   AM_CHECK(a->n_frames >= 1 && a->n_frames <= 65535, "am_vertex_normals: %d frames outside 1 .. 65535", a->n_frames);
-  AM_CHECK(a->n_vertices >= 1 && a->n_vertices <= MESH_MAX, "am_vertex_normals: %lld vertices outside 1 .. (2^31 - 1) / 3",
-           (long long)a->n_vertices);
-  AM_CHECK(a->n_faces >= 0 && a->n_faces <= MESH_MAX, "am_vertex_normals: %lld faces outside 0 .. (2^31 - 1) / 3", (long long)a->n_faces);
+  AM_TRY(check_mesh("am_vertex_normals", a->n_vertices, a->n_faces, 0));
   AM_CHECK(a->vertices_f64 == 0 || a->vertices_f64 == 1, "am_vertex_normals: vertices_f64 must be 0 or 1, got %d", a->vertices_f64);
   AM_CHECK(a->frame_stride >= 3 * a->n_vertices || a->n_frames == 1, "am_vertex_normals: frame stride %lld below 3 * %lld vertices",
            (long long)a->frame_stride, (long long)a->n_vertices);
@@ -259,19 +215,18 @@ extern "C" int am_vertex_normals(const am_vertex_normals_args* a, void* stream) 
   if (a->n_faces > 0)
     hipLaunchKernelGGL(mesh_face_kernel, dim3(mesh_blocks(a->n_faces), a->n_frames), dim3(MESH_THREADS), 0, st, a->vertices,
                        (int)a->vertices_f64, stride, a->n_vertices, a->n_faces, a->faces, staged, a->out_face_normals, a->out_flag);
-  if (a->out_features || a->out_normals)
-    hipLaunchKernelGGL(mesh_vertex_kernel, dim3(mesh_blocks(a->n_vertices), a->n_frames), dim3(MESH_THREADS), 0, st, a->vertices,
-                       (int)a->vertices_f64, stride, a->n_vertices, a->n_faces, a->faces, a->offsets, a->corners, staged, a->out_features,
-                       a->out_normals, a->out_flag);
+  if (a->out_features || a->out_normals) {
+    const mesh_view m = {a->n_vertices, a->n_faces, 0, a->faces, a->offsets, a->corners, nullptr, nullptr, a->out_flag};
+    hipLaunchKernelGGL(mesh_vertex_kernel, dim3(mesh_blocks(a->n_vertices), a->n_frames), dim3(MESH_THREADS), 0, st, m, a->vertices,
+                       (int)a->vertices_f64, stride, staged, a->out_features, a->out_normals);
+  }
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
 
 extern "C" int am_face_areas(const am_face_areas_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_face_areas: null arguments");
-  AM_CHECK(a->n_vertices >= 1 && a->n_vertices <= MESH_MAX, "am_face_areas: %lld vertices outside 1 .. (2^31 - 1) / 3",
-           (long long)a->n_vertices);
-  AM_CHECK(a->n_faces >= 1 && a->n_faces <= MESH_MAX, "am_face_areas: %lld faces outside 1 .. (2^31 - 1) / 3", (long long)a->n_faces);
+  AM_TRY(check_mesh("am_face_areas", a->n_vertices, a->n_faces));
   AM_CHECK(a->vertices_f64 == 0 || a->vertices_f64 == 1, "am_face_areas: vertices_f64 must be 0 or 1, got %d", a->vertices_f64);
   AM_CHECK(a->vertices && a->faces && a->out_areas && a->out_flag, "am_face_areas: null pointer");
   hipStream_t st = (hipStream_t)stream;
@@ -284,9 +239,7 @@ extern "C" int am_face_areas(const am_face_areas_args* a, void* stream) {
 
 extern "C" int am_surface_sample(const am_surface_sample_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_surface_sample: null arguments");
-  AM_CHECK(a->n_vertices >= 1 && a->n_vertices <= MESH_MAX, "am_surface_sample: %lld vertices outside 1 .. (2^31 - 1) / 3",
-           (long long)a->n_vertices);
-  AM_CHECK(a->n_faces >= 1 && a->n_faces <= MESH_MAX, "am_surface_sample: %lld faces outside 1 .. (2^31 - 1) / 3", (long long)a->n_faces);
+  AM_TRY(check_mesh("am_surface_sample", a->n_vertices, a->n_faces));
   AM_CHECK(a->n_samples >= 1 && a->n_samples <= MESH_MAX, "am_surface_sample: %lld samples outside 1 .. (2^31 - 1) / 3",
            (long long)a->n_samples);
   AM_CHECK(a->vertices_f64 == 0 || a->vertices_f64 == 1, "am_surface_sample: vertices_f64 must be 0 or 1, got %d", a->vertices_f64);

@@ -36,6 +36,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .mesh_topology import EdgeTables, compact_rows, referenced_vertices
 
 logger = logging.getLogger(__name__)
 
@@ -113,28 +114,20 @@ def extract_isosurface(values: torch.Tensor, level: float = 0.0, bounds=None, or
     vertices = backend.vertices(values, mask, vertex_offset, n_vertices, origin, spacing, level, flag=flags[0:1])
     faces = backend.triangles(values, mask, count, vertex_offset, tri_offset, n_vertices, n_triangles, level, above, flag=flags[1:2])
     # a valid face index lies inside [0, n_vertices); where a flag is set a row may be unwritten, so the scatter below is clamped
-    used = torch.zeros((n_vertices,), dtype=torch.bool, device=dev)
-    used[faces.long().reshape(-1).clamp_(0, n_vertices - 1)] = True
-    rank = torch.cumsum(used, 0) - 1
+    used, rank = referenced_vertices(faces.long().clamp_(0, n_vertices - 1), n_vertices)
     f_vertices, f_triangles, n_used = torch.cat((flags.long(), rank[-1:] + 1)).tolist()          # the second and last read
     if f_vertices | f_triangles:
         raise ValueError("extract_isosurface: " + ops.iso_flag_message(f_vertices | f_triangles))
     if n_used == n_vertices:
         return vertices, faces.long()
-    dest = torch.where(used, rank, torch.full_like(rank, n_used))
-    kept = torch.empty((n_used + 1, 3), dtype=vertices.dtype, device=dev)
-    kept.index_copy_(0, dest, vertices)
-    return kept[:n_used].contiguous(), rank[faces.long()]
+    return compact_rows(vertices, used, n_used), rank[faces.long()]
 
 
 def border_edge_count(faces: torch.Tensor) -> int:
     """The number of edges that only one face uses (0 on a closed surface).  One sort; one device-to-host read."""
     if faces.shape[0] == 0:
         return 0
-    f = faces.long()
-    a, b = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)
-    key = torch.minimum(a, b) * (int(f.max()) + 1) + torch.maximum(a, b)
-    return int((torch.unique(key, return_counts=True)[1] == 1).sum())
+    return int((EdgeTables(faces, None).edge_count == 1).sum())
 
 
 def _axis_points(lo: float, hi: float, n: int, dev) -> torch.Tensor:

@@ -12,13 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-
-
-def _check_faces(faces: torch.Tensor, what: str) -> None:
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{what}: expected (F, 3) faces, got {tuple(getattr(faces, 'shape', ()))}")
-    if faces.is_floating_point() or faces.dtype == torch.bool:
-        raise TypeError(f"{what}: faces must hold integers, got {faces.dtype}")
+from .mesh_topology import EdgeTables, check_faces, referenced_vertices
 
 
 def face_adjacency(faces: torch.Tensor) -> torch.Tensor:
@@ -27,23 +21,17 @@ def face_adjacency(faces: torch.Tensor) -> torch.Tensor:
     Contract (a recollection of trimesh's `face_adjacency`, UNPINNED): an edge contributes a pair only when EXACTLY two faces use
     it.  A boundary edge (one face) contributes none, and neither does an edge used by three or more faces - so three faces that
     meet in one edge are NOT joined through it."""
-    _check_faces(faces, "face_adjacency")
-    F = faces.shape[0]
-    f = faces.long()
-    ends = torch.stack((f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]), dim=1).reshape(-1, 2)        # edge 3 * face + k
-    key = (ends.min(dim=1).values << 32) | ends.max(dim=1).values
-    key, order = torch.sort(key, stable=True)
-    owner = torch.arange(F, device=faces.device).repeat_interleave(3)[order]
-    _, counts = torch.unique_consecutive(key, return_counts=True)
-    first = torch.cumsum(counts, 0) - counts
-    first = first[counts == 2]
-    return torch.stack((owner[first], owner[first + 1]), dim=1)
+    check_faces(faces, "face_adjacency")
+    tables = EdgeTables(faces, None, with_order=True)   # no vertex count here, and no read to get one
+    counts = tables.edge_count.long()
+    first = (torch.cumsum(counts, 0) - counts)[counts == 2]
+    return torch.stack((tables.order[first] // 3, tables.order[first + 1] // 3), dim=1)        # half-edge 3 * face + k
 
 
 def face_components(faces: torch.Tensor):
     """(label, size), int32 (F,) each: the smallest face index of the face's component, and the number of faces in it.  Components
     are those of the `face_adjacency` graph."""
-    _check_faces(faces, "face_components")
+    check_faces(faces, "face_components")
     adj = face_adjacency(faces).to(torch.int32).contiguous()
     return ops.graph_components(faces.shape[0], adj, return_size=True)
 
@@ -57,7 +45,7 @@ def remove_floaters(vertices: torch.Tensor, faces: torch.Tensor, threshold: floa
     re-indexed - a permutation of what `trimesh.util.concatenate` yields (component after component; UNPINNED), which nothing
     downstream depends on.  Vertices no kept face references are dropped, as `mesh.split` drops them.
     Returns (vertices, faces), and with `return_index` also (kept vertex indices, kept face indices), int64."""
-    _check_faces(faces, "remove_floaters")
+    check_faces(faces, "remove_floaters")
     if vertices.dim() not in (2, 3) or vertices.shape[-1] != 3:
         raise ValueError(f"remove_floaters: expected (V, 3) or (T, V, 3) vertices, got {tuple(vertices.shape)}")
     V, F = vertices.shape[-2], faces.shape[0]
@@ -81,10 +69,8 @@ def remove_floaters(vertices: torch.Tensor, faces: torch.Tensor, threshold: floa
         return unchanged()
     face_index = torch.nonzero(keep).reshape(-1)
     kept = faces[face_index].long()
-    used = torch.zeros(V, dtype=torch.bool, device=dev)
-    used[kept.reshape(-1)] = True
+    used, remap = referenced_vertices(kept, V)
     vertex_index = torch.nonzero(used).reshape(-1)
-    remap = torch.cumsum(used, 0) - 1
     new_faces = remap[kept].to(faces.dtype)
     new_vertices = vertices.index_select(vertices.dim() - 2, vertex_index.to(vertices.device))
     if return_index:

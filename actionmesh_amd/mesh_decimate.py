@@ -5,8 +5,8 @@ round here evaluates every edge at once, picks a set of edges whose closed stars
 
   per mesh   quadrics: every vertex sums the area-weighted plane quadrics of its faces                       ops.decimate_quadrics
   per round  1. torch plumbing on the mesh's device (it also runs on CPU tensors): the vertex -> corner CSR of the live faces
-                (`mesh_prep.MeshTopology`) and their unique undirected edges - one `torch.unique` of the 3 F half-edge keys, with
-                the inverse (half-edge -> edge) and the use count of every edge;
+                (`mesh_topology.MeshTopology`) and their unique undirected edges (`mesh_topology.EdgeTables`) - one `torch.unique`
+                (a sort) of the 3 F half-edge keys, with the inverse (half-edge -> edge) and the use count of every edge;
              2. every edge gets a candidate position, a cost and a 64-bit key (cost as fp32 bits, then a bijective hash of the
                 edge index), or "not a candidate" when an endpoint is on a border or a non-manifold edge, the link condition
                 fails, or a face of either star would flip or degenerate                                      ops.decimate_edges
@@ -40,8 +40,8 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from . import mesh_cleanup, ops
-from .mesh_prep import MeshTopology
+from . import ops
+from .mesh_topology import EdgeTables, MeshTopology, check_mesh, compact_rows, referenced_vertices
 
 logger = logging.getLogger(__name__)
 
@@ -57,32 +57,6 @@ class HipBackend:
     edges = staticmethod(ops.decimate_edges)
     select = staticmethod(ops.decimate_select)
     apply = staticmethod(ops.decimate_apply)
-
-
-class EdgeTables:
-    """The unique undirected edges of a face array: `edges` (E, 2) int32 with u < v in ascending (u, v), `half_edge_to_edge` (3 F,)
-    int32 - half-edge 3 f + k runs from faces[f][k] to faces[f][(k + 1) % 3] - and `edge_count` (E,) int32, the number of half-edges
-    of every edge.  One `torch.unique` (a sort) of the 3 F keys u * n_vertices + v."""
-
-    def __init__(self, faces: torch.Tensor, n_vertices: int):
-        f = faces.long()
-        a, b = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)
-        key = torch.minimum(a, b) * int(n_vertices) + torch.maximum(a, b)
-        uniq, inverse, counts = torch.unique(key, return_inverse=True, return_counts=True)
-        self.edges = torch.stack((uniq // int(n_vertices), uniq % int(n_vertices)), dim=1).to(torch.int32).contiguous()
-        self.half_edge_to_edge = inverse.to(torch.int32).contiguous()
-        self.edge_count = counts.to(torch.int32).contiguous()
-
-
-def _compact_faces(faces: torch.Tensor, dead: torch.Tensor, n_live: int) -> torch.Tensor:
-    """The faces with dead == 0, in order, as a fresh (n_live, 3) tensor, without reading the device: every face is written to its
-    rank among the live ones, a dead one (or one beyond n_live) to a spare row that is cut off."""
-    live = dead == 0
-    rank = torch.cumsum(live, 0) - 1
-    dest = torch.where(live & (rank < n_live), rank, torch.full_like(rank, n_live))
-    out = torch.empty((n_live + 1, 3), dtype=faces.dtype, device=faces.device)
-    out.index_copy_(0, dest, faces)
-    return out[:n_live].contiguous()
 
 
 def decimate_rounds(positions: torch.Tensor, faces: torch.Tensor, target_faces: int, backend=None, observer=None):
@@ -120,7 +94,7 @@ def decimate_rounds(positions: torch.Tensor, faces: torch.Tensor, target_faces: 
         round_map = torch.arange(V, device=dev, dtype=torch.int32)
         dead = backend.apply(positions, quadrics, faces, topology, tables.edges, cand, kept, round_map, flag=flags[2:3])
         merged = round_map.long()[merged]
-        faces = _compact_faces(faces, dead, F - 2 * n_kept)
+        faces = compact_rows(faces, dead == 0, F - 2 * n_kept)
         rounds += 1
     bits = int(flags[2])
     if bits:
@@ -139,12 +113,7 @@ def decimate_mesh(vertices: torch.Tensor, faces: torch.Tensor, target_faces: int
     in the ORIGINAL numbering from every vertex to the surviving vertex it was merged into (survivors map to themselves:
     `map[map] == map`, and `vertices'` are the final positions of the referenced fixed points, in order); with `return_rounds` the
     number of rounds run.  A face index outside [0, V) raises ValueError.  `backend`: the kernels (tests)."""
-    mesh_cleanup._check_faces(faces, "decimate_mesh")
-    if (not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1
-            or not vertices.is_floating_point()):
-        raise ValueError(f"decimate_mesh: expected non-empty floating-point (V, 3) vertices, got {tuple(getattr(vertices, 'shape', ()))}")
-    if faces.device != vertices.device:
-        raise ValueError(f"decimate_mesh: vertices on {vertices.device}, faces on {faces.device}")
+    check_mesh(vertices, faces, "decimate_mesh")
     target_faces = int(target_faces)
     if target_faces < 0:
         raise ValueError(f"decimate_mesh: target_faces {target_faces} is negative")
@@ -156,9 +125,7 @@ def decimate_mesh(vertices: torch.Tensor, faces: torch.Tensor, target_faces: int
     else:
         positions, live, merged, rounds = decimate_rounds(vertices.double().contiguous(), faces.to(torch.int32).contiguous(), target_faces,
                                                           backend=backend)
-        used = torch.zeros(V, dtype=torch.bool, device=dev)
-        used[live.long().reshape(-1)] = True
-        remap = torch.cumsum(used, 0) - 1
+        used, remap = referenced_vertices(live, V)
         out = (positions[used].to(vertices.dtype), remap[live.long()].to(faces.dtype))
     if return_map:
         out = out + (merged,)

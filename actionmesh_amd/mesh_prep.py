@@ -27,40 +27,13 @@ import numpy as np
 import torch
 
 from . import mesh_cleanup, ops
+from .mesh_topology import MeshTopology, check_faces, check_mesh, referenced_vertices
 
 MERGE_DIGITS = 8                # trimesh's tol.merge = 1e-8 as decimal digits
 DEGENERATE_HEIGHT = 1e-8        # trimesh's nondegenerate_faces(height=tol.merge)
 
 NO_IMAGE_MESSAGE = ("Some pre-merge vertices have no close match in the merged mesh ({count} of {total}). "
                     "merge_vertices() may have altered positions.")
-
-
-def _check_mesh(vertices: torch.Tensor, faces: torch.Tensor, what: str) -> None:
-    mesh_cleanup._check_faces(faces, what)
-    if (not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1
-            or not vertices.is_floating_point()):
-        raise ValueError(f"{what}: expected non-empty floating-point (V, 3) vertices, got {tuple(getattr(vertices, 'shape', ()))}")
-    if faces.device != vertices.device:
-        raise ValueError(f"{what}: vertices on {vertices.device}, faces on {faces.device}")
-
-
-class MeshTopology:
-    """The vertex -> corner CSR of a face array, in the order am_vertex_normals sums in (include/actionmesh_amd.h): corner id
-    3 * face + k names vertex faces[face][k]; `corners[offsets[v] : offsets[v + 1]]` are the corners of vertex v in ascending corner
-    id.  One stable sort of the flattened faces.  The faces of an animation never change, so one object serves every frame and
-    every window.  Indices outside [0, n_vertices) are left out of every vertex's list (the kernel reports them), so building never
-    reads the device back."""
-
-    def __init__(self, faces: torch.Tensor, n_vertices: int):
-        mesh_cleanup._check_faces(faces, "MeshTopology")
-        self.n_vertices, self.n_faces = int(n_vertices), int(faces.shape[0])
-        if self.n_vertices < 1:
-            raise ValueError(f"MeshTopology: n_vertices {n_vertices} is not positive")
-        self.faces = faces.to(torch.int32).contiguous()
-        flat, order = torch.sort(self.faces.reshape(-1), stable=True)
-        bounds = torch.arange(self.n_vertices + 1, device=faces.device, dtype=torch.int32)
-        self.offsets = torch.searchsorted(flat, bounds, out_int32=True).contiguous()
-        self.corners = order.to(torch.int32).contiguous()
 
 
 def get_mesh_features(vertices: torch.Tensor, faces: torch.Tensor, with_normals: bool, topology: Optional[MeshTopology] = None) -> torch.Tensor:
@@ -78,7 +51,7 @@ class VertexFeatures:
     topology is built on first use and kept."""
 
     def __init__(self, faces: torch.Tensor):
-        mesh_cleanup._check_faces(faces, "VertexFeatures")
+        check_faces(faces, "VertexFeatures")
         self.faces = faces
         self.topology: Optional[MeshTopology] = None
 
@@ -135,9 +108,8 @@ def _clean(vertices: torch.Tensor, faces: torch.Tensor):
         is_first = _first_index(finv, sets.shape[0])[finv] == torch.arange(f.shape[0], device=dev)
         face_index, f = face_index[is_first], f[is_first]
     # 4. unreferenced vertices
-    used = torch.zeros(n_groups, dtype=torch.bool, device=dev)
-    used[f.reshape(-1)] = True
-    remap = torch.where(used, torch.cumsum(used, 0) - 1, torch.full((n_groups,), -1, dtype=torch.int64, device=dev))
+    used, rank = referenced_vertices(f, n_groups)
+    remap = torch.where(used, rank, torch.full_like(rank, -1))
     return merged[used], remap[f].to(faces.dtype), remap[merged_of], face_index
 
 
@@ -154,7 +126,7 @@ def merge_and_clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, return_ind
     of the kept faces.  The map comes straight from the merge and the re-index (the reference recovers it with a cKDTree because
     trimesh hides it).  An original vertex without a surviving image - one that no kept face reaches - raises AssertionError, as the
     reference's distance assertion does (one device-to-host read for that check)."""
-    _check_mesh(vertices, faces, "merge_and_clean_mesh")
+    check_mesh(vertices, faces, "merge_and_clean_mesh")
     new_vertices, new_faces, merge_map, face_index = _clean(vertices, faces)
     missing = int((merge_map < 0).sum())
     if missing:
@@ -172,7 +144,7 @@ def process_mesh(vertices: torch.Tensor, faces: torch.Tensor, face_decimation: i
     `face_decimation` other than -1 below the mesh's face count then raises NotImplementedError (at or above it the reference skips
     the decimation too); "hip": `mesh_decimate.decimate_mesh`, rounds of parallel edge collapses on the mesh's device (not the
     reference's `fast_simplification` schedule: mesh_decimate.py)."""
-    _check_mesh(vertices, faces, "process_mesh")
+    check_mesh(vertices, faces, "process_mesh")
     if decimation not in (None, "hip"):
         raise ValueError(f"process_mesh: decimation must be None or 'hip', got {decimation!r}")
     vertices, faces, _, _ = _clean(vertices, faces)
@@ -258,7 +230,7 @@ def sample_surface(vertices: torch.Tensor, faces: torch.Tensor, n_points: int, s
     of the area prefix sum) and the points are HIP (am_face_areas, am_surface_sample); the prefix sum is torch.cumsum in fp64; the
     3 n uniforms are `draw_uniforms(n_points, seed)`, uploaded once.  With `return_face_index` also (face indices (n,) int32, the
     prefix sum (F,) fp64)."""
-    _check_mesh(vertices, faces, "sample_surface")
+    check_mesh(vertices, faces, "sample_surface")
     faces32 = faces.to(torch.int32).contiguous()
     vertices = vertices.contiguous()
     cdf = torch.cumsum(ops.face_areas(vertices, faces32), 0)

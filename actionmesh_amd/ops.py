@@ -12,6 +12,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from .mesh_topology import MeshTopology
 
 HEAD_DIM = 128
 
@@ -727,7 +728,53 @@ def graph_components(n_nodes: int, edges: torch.Tensor, return_size: bool = Fals
 
 # ---- anchor-mesh preparation (csrc/am_mesh.hip; the contract is the header's, the tensor interface is mesh_prep.py's) ----------------
 _MESH_MAX = (2 ** 31 - 1) // 3
-_MESH_FLAGS = {1: "a face names a vertex outside [0, {V})", 2: "the vertex -> corner CSR does not belong to these faces"}
+_MESH_FLAGS = {L.MESH_BAD_FACE: "a face names a vertex outside [0, {V})",
+               L.MESH_BAD_CSR: "the vertex -> corner CSR does not belong to these faces"}
+
+
+# What this section, the decimator's and the iso-surface's share: the operand checks and the one path a flag word takes.
+def _shaped(what: str, t: torch.Tensor, dtype, shape, dev) -> torch.Tensor:
+    """A contiguous tensor of this dtype, shape and device."""
+    _need(t, dtype, what)
+    if tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError(f"{what}: {tuple(t.shape)} on {t.device}, expected {tuple(shape)} on {dev}")
+    return t
+
+
+def _out(what: str, out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    """A fresh contiguous output, or the caller's of the same shape and dtype."""
+    return torch.empty(shape, dtype=dtype, device=device) if out is None else _shaped(what, out, dtype, shape, device)
+
+
+def _positions(what: str, positions: torch.Tensor):
+    """Non-empty contiguous (V, 3) fp64 positions.  Returns (V, device)."""
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
+        raise ValueError(f"{what}: expected non-empty (V, 3) positions, got {tuple(getattr(positions, 'shape', ()))}")
+    _need(positions, torch.float64, f"{what}: positions")
+    return positions.shape[0], positions.device
+
+
+def _flag_message(table: dict, bits: int, **values) -> str:
+    """What the set bits of a flag word say, by the bit -> message table of its entry points."""
+    return "; ".join(msg.format(**values) for bit, msg in table.items() if bits & bit)
+
+
+def _flag_word(what: str, flag: Optional[torch.Tensor], dev) -> Tuple[torch.Tensor, bool]:
+    """The flag word of one call: the caller's int32 (1,) tensor - who then reads it, together with whatever else it needs from the
+    device - or a fresh one that the wrapper reads itself (`_raise_own_flag`)."""
+    if flag is None:
+        return torch.empty((1,), dtype=torch.int32, device=dev), True
+    _need(flag, torch.int32, f"{what}: flag")
+    if flag.numel() != 1 or flag.device != dev:
+        raise ValueError(f"{what}: the flag must be one int32 on {dev}")
+    return flag, False
+
+
+def _raise_own_flag(what: str, flag: torch.Tensor, own: bool, table: dict, **values) -> None:
+    """Behind the launch, for a flag word the wrapper made itself: ONE device-to-host read, and a set bit is a ValueError."""
+    bits = int(flag) if own else 0
+    if bits:
+        raise ValueError(f"{what}: " + _flag_message(table, bits, **values))
 
 
 def _mesh_operands(what: str, vertices: torch.Tensor, faces: torch.Tensor, frames: bool):
@@ -759,35 +806,17 @@ def _mesh_operands(what: str, vertices: torch.Tensor, faces: torch.Tensor, frame
     return T, V, F, (stride[0] if vertices.dim() == 3 and T > 1 else 3 * V)
 
 
-def _mesh_flag(what: str, flag: torch.Tensor, V: int) -> None:
-    """ONE device-to-host read behind the launch: a set bit of the entry point's flag is a ValueError."""
-    bits = int(flag)
-    if bits:
-        raise ValueError(f"{what}: " + "; ".join(msg.format(V=V) for bit, msg in _MESH_FLAGS.items() if bits & bit))
-
-
-def _mesh_out(what: str, out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
-    """A fresh contiguous output, or the caller's of the same shape and dtype."""
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    _need(out, dtype, what)
-    if tuple(out.shape) != tuple(shape) or out.device != device:
-        raise ValueError(f"{what}: {tuple(out.shape)} on {out.device}, expected {tuple(shape)} on {device}")
-    return out
-
-
 def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, topology=None, features: bool = False, return_face_normals: bool = False,
                    out: Optional[torch.Tensor] = None, out_face_normals: Optional[torch.Tensor] = None):
     """am_vertex_normals: trimesh's angle-weighted vertex normals followed by the reference's fp32 F.normalize (the contract is the
     header's).  vertices (V, 3) or (T, V, 3), fp32 or fp64, frames that share `faces` (F, 3) int32; a frame stride above 3 V is passed
     as it is (no copy).  `topology`: the vertex -> corner CSR of the faces, an object with int32 device tensors `.offsets` (V + 1)
-    and `.corners` (3 F) - a `mesh_prep.MeshTopology`, built here when None; a caller that keeps its faces keeps it too.
+    and `.corners` (3 F) - a `mesh_topology.MeshTopology`, built here when None; a caller that keeps its faces keeps it too.
     Returns fp32 normals (..., V, 3), or with `features` (..., V, 6) = position rounded to fp32 | normal; with `return_face_normals`
     also the fp64 unit face normals (..., F, 3).  Faces and CSR are validated on the device: ONE device-to-host read behind the
     launch (the flag) turns a vertex index outside [0, V) into a ValueError.  `out` / `out_face_normals`: the caller's buffers."""
     T, V, F, stride = _mesh_operands("vertex_normals", vertices, faces, frames=True)
     if topology is None:
-        from .mesh_prep import MeshTopology
         topology = MeshTopology(faces, V)
     offsets = _need(topology.offsets, torch.int32, "vertex_normals: topology.offsets")
     corners = _need(topology.corners, torch.int32, "vertex_normals: topology.corners")
@@ -796,11 +825,11 @@ def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, topology=None, f
                          f"has {V} and {F}")
     dev = vertices.device
     lead = tuple(vertices.shape[:-2])
-    out = _mesh_out("vertex_normals: out", out, lead + (V, 6 if features else 3), torch.float32, dev)
+    out = _out("vertex_normals: out", out, lead + (V, 6 if features else 3), torch.float32, dev)
     face_normals = None
     if return_face_normals:
-        face_normals = _mesh_out("vertex_normals: out_face_normals", out_face_normals, lead + (F, 3), torch.float64, dev)
-    flag = torch.empty((1,), dtype=torch.int32, device=dev)
+        face_normals = _out("vertex_normals: out_face_normals", out_face_normals, lead + (F, 3), torch.float64, dev)
+    flag, own = _flag_word("vertex_normals", None, dev)
     ws, need = _workspace(dev, "am_vertex_normals_workspace_bytes", T, F)
     a = L.AmVertexNormalsArgs()
     a.vertices, a.vertices_f64, a.n_frames = vertices.data_ptr(), int(vertices.dtype == torch.float64), T
@@ -810,7 +839,7 @@ def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, topology=None, f
     a.out_face_normals, a.out_flag = _p(face_normals), flag.data_ptr()
     a.workspace, a.workspace_bytes = _p(ws), need
     _call(vertices, None, "am_vertex_normals", C.byref(a))
-    _mesh_flag("vertex_normals", flag, V)
+    _raise_own_flag("vertex_normals", flag, own, _MESH_FLAGS, V=V)
     return (out, face_normals) if return_face_normals else out
 
 
@@ -820,13 +849,13 @@ def face_areas(vertices: torch.Tensor, faces: torch.Tensor, out: Optional[torch.
     _, V, F, _ = _mesh_operands("face_areas", vertices, faces, frames=False)
     if F < 1:
         raise ValueError("face_areas: the mesh has no faces")
-    out = _mesh_out("face_areas: out", out, (F,), torch.float64, vertices.device)
-    flag = torch.empty((1,), dtype=torch.int32, device=vertices.device)
+    out = _out("face_areas: out", out, (F,), torch.float64, vertices.device)
+    flag, own = _flag_word("face_areas", None, vertices.device)
     a = L.AmFaceAreasArgs()
     a.vertices, a.vertices_f64, a.n_vertices, a.n_faces = vertices.data_ptr(), int(vertices.dtype == torch.float64), V, F
     a.faces, a.out_areas, a.out_flag = faces.data_ptr(), out.data_ptr(), flag.data_ptr()
     _call(vertices, None, "am_face_areas", C.byref(a))
-    _mesh_flag("face_areas", flag, V)
+    _raise_own_flag("face_areas", flag, own, _MESH_FLAGS, V=V)
     return out
 
 
@@ -848,44 +877,33 @@ def surface_sample(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tenso
         raise ValueError(f"surface_sample: cdf {tuple(cdf.shape)}, u_face {tuple(u_face.shape)}, u_bary {tuple(u_bary.shape)} "
                          f"do not fit {F} faces and (n,), (n, 2) uniforms")
     dev = vertices.device
-    points = _mesh_out("surface_sample: out_points", out_points, (n, 3), torch.float64, dev)
-    normals = _mesh_out("surface_sample: out_normals", out_normals, (n, 3), torch.float64, dev) if with_normals else None
-    idx = _mesh_out("surface_sample: out_face_index", out_face_index, (n,), torch.int32, dev)
-    flag = torch.empty((1,), dtype=torch.int32, device=dev)
+    points = _out("surface_sample: out_points", out_points, (n, 3), torch.float64, dev)
+    normals = _out("surface_sample: out_normals", out_normals, (n, 3), torch.float64, dev) if with_normals else None
+    idx = _out("surface_sample: out_face_index", out_face_index, (n,), torch.int32, dev)
+    flag, own = _flag_word("surface_sample", None, dev)
     a = L.AmSurfaceSampleArgs()
     a.vertices, a.vertices_f64, a.n_vertices, a.n_faces, a.n_samples = vertices.data_ptr(), int(vertices.dtype == torch.float64), V, F, n
     a.faces, a.cdf, a.u_face, a.u_bary = faces.data_ptr(), cdf.data_ptr(), u_face.data_ptr(), u_bary.data_ptr()
     a.out_points, a.out_face_index, a.out_normals, a.out_flag = points.data_ptr(), idx.data_ptr(), _p(normals), flag.data_ptr()
     _call(vertices, None, "am_surface_sample", C.byref(a))
-    _mesh_flag("surface_sample", flag, V)
+    _raise_own_flag("surface_sample", flag, own, _MESH_FLAGS, V=V)
     return points, idx, normals
 
 
 # ---- mesh decimation (csrc/am_decimate.hip; the contract is the header's, the round loop is mesh_decimate.py's) ----------------------
-_DECIMATE_FLAGS = {L.DECIMATE_BAD_FACE: "a face names a vertex outside [0, {V})",
-                   L.DECIMATE_BAD_CSR: "the vertex -> corner CSR does not belong to these faces",
+_DECIMATE_FLAGS = {**_MESH_FLAGS,           # L.DECIMATE_BAD_FACE, L.DECIMATE_BAD_CSR: the same two bits, the same two messages
                    L.DECIMATE_BAD_EDGE: "the edge tables do not belong to these faces",
                    L.DECIMATE_BAD_KEPT: "a kept edge index is outside the edge list"}
 
 
 def decimate_flag_message(bits: int, V: int) -> str:
     """What the set bits of an am_decimate_* flag word say."""
-    return "; ".join(msg.format(V=V) for bit, msg in _DECIMATE_FLAGS.items() if bits & bit)
+    return _flag_message(_DECIMATE_FLAGS, bits, V=V)
 
 
-def _decimate_flag(what: str, flag: Optional[torch.Tensor], dev) -> Tuple[torch.Tensor, bool]:
-    """The flag word of one call: the caller's int32 (1,) tensor - who then reads it, together with whatever else it needs from the
-    device - or a fresh one that the wrapper reads itself."""
-    if flag is None:
-        return torch.empty((1,), dtype=torch.int32, device=dev), True
-    _need(flag, torch.int32, f"{what}: flag")
-    if flag.numel() != 1 or flag.device != dev:
-        raise ValueError(f"{what}: the flag must be one int32 on {dev}")
-    return flag, False
-
-
-def _decimate_mesh(what: str, faces: torch.Tensor, topology, V: int) -> int:
-    """The checks on (faces, CSR) the four entry points share.  Returns F."""
+def _decimate_mesh(what: str, faces: torch.Tensor, topology, V: int, dev=None) -> int:
+    """The checks on (faces, CSR) the four entry points share; `dev`: the positions' device, where the call has positions.
+    Returns F."""
     if not isinstance(faces, torch.Tensor):
         raise TypeError(f"{what}: expected torch tensors")
     _need(faces, torch.int32, f"{what}: faces")
@@ -901,14 +919,9 @@ def _decimate_mesh(what: str, faces: torch.Tensor, topology, V: int) -> int:
                          f"{V} and {F}")
     if offsets.device != faces.device or corners.device != faces.device:
         raise ValueError(f"{what}: the topology is not on {faces.device}")
+    if dev is not None and faces.device != dev:
+        raise ValueError(f"{what}: positions on {dev}, faces on {faces.device}")
     return F
-
-
-def _decimate_rows(what: str, t: torch.Tensor, dtype, shape, dev) -> torch.Tensor:
-    _need(t, dtype, what)
-    if tuple(t.shape) != tuple(shape) or t.device != dev:
-        raise ValueError(f"{what}: {tuple(t.shape)} on {t.device}, expected {tuple(shape)} on {dev}")
-    return t
 
 
 def _decimate_edge_tables(what: str, a, edges: torch.Tensor, half_edge_to_edge: Optional[torch.Tensor], F: int, dev) -> int:
@@ -916,35 +929,29 @@ def _decimate_edge_tables(what: str, a, edges: torch.Tensor, half_edge_to_edge: 
     if not isinstance(edges, torch.Tensor) or edges.dim() != 2 or edges.shape[1] != 2 or edges.shape[0] < 1:
         raise ValueError(f"{what}: expected non-empty (E, 2) edges, got {tuple(getattr(edges, 'shape', ()))}")
     E = edges.shape[0]
-    _decimate_rows(f"{what}: edges", edges, torch.int32, (E, 2), dev)
+    _shaped(f"{what}: edges", edges, torch.int32, (E, 2), dev)
     a.n_edges, a.edges = E, edges.data_ptr()
     if half_edge_to_edge is not None:
-        a.half_edge_to_edge = _decimate_rows(f"{what}: half_edge_to_edge", half_edge_to_edge, torch.int32, (3 * F,), dev).data_ptr()
+        a.half_edge_to_edge = _shaped(f"{what}: half_edge_to_edge", half_edge_to_edge, torch.int32, (3 * F,), dev).data_ptr()
     return E
 
 
 def decimate_quadrics(positions: torch.Tensor, faces: torch.Tensor, topology, out: Optional[torch.Tensor] = None,
                       flag: Optional[torch.Tensor] = None) -> torch.Tensor:
     """am_decimate_quadrics: the area-weighted plane quadrics (V, 10) fp64 of every vertex, summed over its faces in the CSR order
-    of `topology` (a `mesh_prep.MeshTopology` of `faces`).  positions (V, 3) fp64, faces (F, 3) int32.  Without `flag`, ONE
+    of `topology` (a `mesh_topology.MeshTopology` of `faces`).  positions (V, 3) fp64, faces (F, 3) int32.  Without `flag`, ONE
     device-to-host read behind the launch turns a bad face index or CSR into a ValueError; with the caller's int32 (1,) `flag`
     nothing is read here."""
     what = "decimate_quadrics"
-    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
-        raise ValueError(f"{what}: expected non-empty (V, 3) positions, got {tuple(getattr(positions, 'shape', ()))}")
-    V, dev = positions.shape[0], positions.device
-    _need(positions, torch.float64, f"{what}: positions")
-    F = _decimate_mesh(what, faces, topology, V)
-    if faces.device != dev:
-        raise ValueError(f"{what}: positions on {dev}, faces on {faces.device}")
-    out = _mesh_out(f"{what}: out", out, (V, 10), torch.float64, dev)
-    flag, own = _decimate_flag(what, flag, dev)
+    V, dev = _positions(what, positions)
+    F = _decimate_mesh(what, faces, topology, V, dev)
+    out = _out(f"{what}: out", out, (V, 10), torch.float64, dev)
+    flag, own = _flag_word(what, flag, dev)
     a = L.AmDecimateQuadricsArgs()
     a.positions, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), V, F, faces.data_ptr()
     a.offsets, a.corners, a.out_quadrics, a.out_flag = topology.offsets.data_ptr(), topology.corners.data_ptr(), out.data_ptr(), flag.data_ptr()
     _call(positions, None, "am_decimate_quadrics", C.byref(a))
-    if own and int(flag):
-        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
     return out
 
 
@@ -956,27 +963,21 @@ def decimate_edges(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch
     surviving vertex (E, 3) fp64, its quadric cost (E,) fp64, and the int64 key (E,) - `_lib.DECIMATE_NO_KEY` where the edge is not a
     candidate (the tests are the header's).  half_edge_to_edge (3 F,) and edge_count (E,) int32.  `flag` as in decimate_quadrics."""
     what = "decimate_edges"
-    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
-        raise ValueError(f"{what}: expected non-empty (V, 3) positions, got {tuple(getattr(positions, 'shape', ()))}")
-    V, dev = positions.shape[0], positions.device
-    _need(positions, torch.float64, f"{what}: positions")
-    _decimate_rows(f"{what}: quadrics", quadrics, torch.float64, (V, 10), dev)
-    F = _decimate_mesh(what, faces, topology, V)
-    if faces.device != dev:
-        raise ValueError(f"{what}: positions on {dev}, faces on {faces.device}")
+    V, dev = _positions(what, positions)
+    _shaped(f"{what}: quadrics", quadrics, torch.float64, (V, 10), dev)
+    F = _decimate_mesh(what, faces, topology, V, dev)
     a = L.AmDecimateEdgesArgs()
     E = _decimate_edge_tables(what, a, edges, half_edge_to_edge, F, dev)
-    a.edge_count = _decimate_rows(f"{what}: edge_count", edge_count, torch.int32, (E,), dev).data_ptr()
-    cand = _mesh_out(f"{what}: out_positions", out_positions, (E, 3), torch.float64, dev)
-    cost = _mesh_out(f"{what}: out_cost", out_cost, (E,), torch.float64, dev)
-    key = _mesh_out(f"{what}: out_key", out_key, (E,), torch.int64, dev)
-    flag, own = _decimate_flag(what, flag, dev)
+    a.edge_count = _shaped(f"{what}: edge_count", edge_count, torch.int32, (E,), dev).data_ptr()
+    cand = _out(f"{what}: out_positions", out_positions, (E, 3), torch.float64, dev)
+    cost = _out(f"{what}: out_cost", out_cost, (E,), torch.float64, dev)
+    key = _out(f"{what}: out_key", out_key, (E,), torch.int64, dev)
+    flag, own = _flag_word(what, flag, dev)
     a.positions, a.quadrics, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), quadrics.data_ptr(), V, F, faces.data_ptr()
     a.offsets, a.corners = topology.offsets.data_ptr(), topology.corners.data_ptr()
     a.out_positions, a.out_cost, a.out_key, a.out_flag = cand.data_ptr(), cost.data_ptr(), key.data_ptr(), flag.data_ptr()
     _call(positions, None, "am_decimate_edges", C.byref(a))
-    if own and int(flag):
-        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
     return cand, cost, key
 
 
@@ -992,16 +993,15 @@ def decimate_select(n_vertices: int, faces: torch.Tensor, topology, edges: torch
     dev = faces.device
     a = L.AmDecimateSelectArgs()
     E = _decimate_edge_tables(what, a, edges, half_edge_to_edge, F, dev)
-    _decimate_rows(f"{what}: keys", keys, torch.int64, (E,), dev)
-    m1 = _mesh_out(f"{what}: out_m1", out_m1, (V,), torch.int64, dev)
-    m2 = _mesh_out(f"{what}: out_m2", out_m2, (V,), torch.int64, dev)
-    sel = _mesh_out(f"{what}: out_selected", out_selected, (E,), torch.uint8, dev)
-    flag, own = _decimate_flag(what, flag, dev)
+    _shaped(f"{what}: keys", keys, torch.int64, (E,), dev)
+    m1 = _out(f"{what}: out_m1", out_m1, (V,), torch.int64, dev)
+    m2 = _out(f"{what}: out_m2", out_m2, (V,), torch.int64, dev)
+    sel = _out(f"{what}: out_selected", out_selected, (E,), torch.uint8, dev)
+    flag, own = _flag_word(what, flag, dev)
     a.n_vertices, a.n_faces, a.faces, a.offsets, a.corners = V, F, faces.data_ptr(), topology.offsets.data_ptr(), topology.corners.data_ptr()
     a.keys, a.out_m1, a.out_m2, a.out_selected, a.out_flag = keys.data_ptr(), m1.data_ptr(), m2.data_ptr(), sel.data_ptr(), flag.data_ptr()
     _call(faces, None, "am_decimate_select", C.byref(a))
-    if own and int(flag):
-        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
     return m1, m2, sel
 
 
@@ -1013,31 +1013,25 @@ def decimate_apply(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch
     int32).  `topology` is the CSR of the faces BEFORE the call.  Returns face_dead (F,) uint8: 1 on the two faces of every collapsed
     edge, which the caller drops.  `flag` as in decimate_quadrics."""
     what = "decimate_apply"
-    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
-        raise ValueError(f"{what}: expected non-empty (V, 3) positions, got {tuple(getattr(positions, 'shape', ()))}")
-    V, dev = positions.shape[0], positions.device
-    _need(positions, torch.float64, f"{what}: positions")
-    _decimate_rows(f"{what}: quadrics", quadrics, torch.float64, (V, 10), dev)
-    F = _decimate_mesh(what, faces, topology, V)
-    if faces.device != dev:
-        raise ValueError(f"{what}: positions on {dev}, faces on {faces.device}")
+    V, dev = _positions(what, positions)
+    _shaped(f"{what}: quadrics", quadrics, torch.float64, (V, 10), dev)
+    F = _decimate_mesh(what, faces, topology, V, dev)
     a = L.AmDecimateApplyArgs()
     E = _decimate_edge_tables(what, a, edges, None, F, dev)
-    _decimate_rows(f"{what}: candidates", candidates, torch.float64, (E, 3), dev)
+    _shaped(f"{what}: candidates", candidates, torch.float64, (E, 3), dev)
     if not isinstance(kept, torch.Tensor) or kept.dim() != 1 or not 1 <= kept.numel() <= E:
         raise ValueError(f"{what}: expected 1 .. {E} kept edge indices, got {tuple(getattr(kept, 'shape', ()))}")
     K = kept.numel()
-    _decimate_rows(f"{what}: kept", kept, torch.int32, (K,), dev)
-    _decimate_rows(f"{what}: vertex_map", vertex_map, torch.int32, (V,), dev)
-    dead = _mesh_out(f"{what}: out_face_dead", out_face_dead, (F,), torch.uint8, dev)
-    flag, own = _decimate_flag(what, flag, dev)
+    _shaped(f"{what}: kept", kept, torch.int32, (K,), dev)
+    _shaped(f"{what}: vertex_map", vertex_map, torch.int32, (V,), dev)
+    dead = _out(f"{what}: out_face_dead", out_face_dead, (F,), torch.uint8, dev)
+    flag, own = _flag_word(what, flag, dev)
     a.n_vertices, a.n_faces, a.n_kept, a.kept, a.candidates = V, F, K, kept.data_ptr(), candidates.data_ptr()
     a.offsets, a.corners = topology.offsets.data_ptr(), topology.corners.data_ptr()
     a.positions, a.quadrics, a.faces, a.vertex_map = positions.data_ptr(), quadrics.data_ptr(), faces.data_ptr(), vertex_map.data_ptr()
     a.out_face_dead, a.out_flag = dead.data_ptr(), flag.data_ptr()
     _call(positions, None, "am_decimate_apply", C.byref(a))
-    if own and int(flag):
-        raise ValueError(f"{what}: " + decimate_flag_message(int(flag), V))
+    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
     return dead
 
 
@@ -1050,7 +1044,7 @@ _ISO_FLAGS = {L.ISO_BAD_VERTEX_OFFSET: "a vertex offset is negative or leads pas
 
 def iso_flag_message(bits: int) -> str:
     """What the set bits of an am_iso_* flag word say."""
-    return "; ".join(msg for bit, msg in _ISO_FLAGS.items() if bits & bit)
+    return _flag_message(_ISO_FLAGS, bits)
 
 
 def _iso_grid(what: str, a, values: torch.Tensor, level: float):
@@ -1077,16 +1071,11 @@ def iso_classify(values: torch.Tensor, level: float = 0.0, inside_above: bool = 
     what = "iso_classify"
     a = L.AmIsoClassifyArgs()
     shape, dev = _iso_grid(what, a, values, level)
-    mask = _mesh_out(f"{what}: out_mask", out_mask, shape, torch.uint8, dev)
-    count = _mesh_out(f"{what}: out_count", out_count, shape, torch.uint8, dev)
+    mask = _out(f"{what}: out_mask", out_mask, shape, torch.uint8, dev)
+    count = _out(f"{what}: out_count", out_count, shape, torch.uint8, dev)
     a.inside_above, a.out_mask, a.out_count = int(bool(inside_above)), mask.data_ptr(), count.data_ptr()
     _call(values, None, "am_iso_classify", C.byref(a))
     return mask, count
-
-
-def _iso_tables(what: str, shape, dev, **tables) -> None:
-    for name, (t, dtype) in tables.items():
-        _decimate_rows(f"{what}: {name}", t, dtype, shape, dev)
 
 
 def iso_vertices(values: torch.Tensor, mask: torch.Tensor, vertex_offset: torch.Tensor, n_vertices: int, origin, spacing,
@@ -1097,17 +1086,17 @@ def iso_vertices(values: torch.Tensor, mask: torch.Tensor, vertex_offset: torch.
     what = "iso_vertices"
     a = L.AmIsoVerticesArgs()
     shape, dev = _iso_grid(what, a, values, level)
-    _iso_tables(what, shape, dev, mask=(mask, torch.uint8), vertex_offset=(vertex_offset, torch.int64))
+    _shaped(f"{what}: mask", mask, torch.uint8, shape, dev)
+    _shaped(f"{what}: vertex_offset", vertex_offset, torch.int64, shape, dev)
     n_vertices = int(n_vertices)
     if not 1 <= n_vertices <= _ISO_MAX:
         raise ValueError(f"{what}: {n_vertices} vertices are outside 1 .. 2^31 - 1")
-    out = _mesh_out(f"{what}: out", out, (n_vertices, 3), torch.float32, dev)
-    flag, own = _decimate_flag(what, flag, dev)
+    out = _out(f"{what}: out", out, (n_vertices, 3), torch.float32, dev)
+    flag, own = _flag_word(what, flag, dev)
     a.origin, a.spacing = (C.c_double * 3)(*(float(x) for x in origin)), (C.c_double * 3)(*(float(x) for x in spacing))
     a.mask, a.vertex_offset, a.n_vertices, a.out_vertices, a.out_flag = mask.data_ptr(), vertex_offset.data_ptr(), n_vertices, out.data_ptr(), flag.data_ptr()
     _call(values, None, "am_iso_vertices", C.byref(a))
-    if own and int(flag):
-        raise ValueError(f"{what}: " + iso_flag_message(int(flag)))
+    _raise_own_flag(what, flag, own, _ISO_FLAGS)
     return out
 
 
@@ -1120,19 +1109,19 @@ def iso_triangles(values: torch.Tensor, mask: torch.Tensor, count: torch.Tensor,
     what = "iso_triangles"
     a = L.AmIsoTrianglesArgs()
     shape, dev = _iso_grid(what, a, values, level)
-    _iso_tables(what, shape, dev, mask=(mask, torch.uint8), count=(count, torch.uint8), vertex_offset=(vertex_offset, torch.int64),
-                tri_offset=(tri_offset, torch.int64))
+    for name, t, dtype in (("mask", mask, torch.uint8), ("count", count, torch.uint8), ("vertex_offset", vertex_offset, torch.int64),
+                           ("tri_offset", tri_offset, torch.int64)):
+        _shaped(f"{what}: {name}", t, dtype, shape, dev)
     n_vertices, n_triangles = int(n_vertices), int(n_triangles)
     if not 1 <= n_vertices <= _ISO_MAX or not 1 <= n_triangles <= _ISO_MAX:
         raise ValueError(f"{what}: {n_vertices} vertices and {n_triangles} triangles are outside 1 .. 2^31 - 1")
-    out = _mesh_out(f"{what}: out", out, (n_triangles, 3), torch.int32, dev)
-    flag, own = _decimate_flag(what, flag, dev)
+    out = _out(f"{what}: out", out, (n_triangles, 3), torch.int32, dev)
+    flag, own = _flag_word(what, flag, dev)
     a.inside_above, a.mask, a.count = int(bool(inside_above)), mask.data_ptr(), count.data_ptr()
     a.vertex_offset, a.tri_offset, a.n_vertices, a.n_triangles = vertex_offset.data_ptr(), tri_offset.data_ptr(), n_vertices, n_triangles
     a.out_faces, a.out_flag = out.data_ptr(), flag.data_ptr()
     _call(values, None, "am_iso_triangles", C.byref(a))
-    if own and int(flag):
-        raise ValueError(f"{what}: " + iso_flag_message(int(flag)))
+    _raise_own_flag(what, flag, own, _ISO_FLAGS)
     return out
 
 

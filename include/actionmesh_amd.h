@@ -714,14 +714,14 @@ int am_graph_components(const am_graph_args* args, void* stream);
  *   out_features      optional device fp32 (n_frames, n_vertices, 6) = position rounded to fp32 | normal;
  *   out_normals       optional device fp32 (n_frames, n_vertices, 3);
  *   out_face_normals  optional device fp64 (n_frames, n_faces, 3): the unit face normals;       at least one output is required
- *   out_flag          device int32[1]: 0, or bit 0 when a face names a vertex outside [0, n_vertices), bit 1 when the CSR is not
- *                     one of these faces (offsets not ascending inside [0, 3 n_faces], a corner outside [0, 3 n_faces) or one that
- *                     does not name the vertex it is listed under).  Every index is compared with its bound BEFORE it is used as
- *                     an address: a bad face contributes zeros, a bad corner nothing, and the caller, who reads the flag together
- *                     with the result, treats the call as failed;
+ *   out_flag          device int32[1]: 0, or AM_MESH_BAD_FACE when a face names a vertex outside [0, n_vertices), AM_MESH_BAD_CSR
+ *                     when the CSR is not one of these faces (offsets not ascending inside [0, 3 n_faces], a corner outside
+ *                     [0, 3 n_faces) or one that does not name the vertex it is listed under).  Every index is compared with its
+ *                     bound BEFORE it is used as an address: a bad face contributes zeros, a bad corner nothing, and the caller,
+ *                     who reads the flag together with the result, treats the call as failed;
  *   workspace         16-byte aligned device scratch of am_vertex_normals_workspace_bytes(n_frames, n_faces) bytes.
  *
- * Face areas (am_face_areas): out_areas[f] = |c| / 2 as fp64; out_flag as above (bit 0; such a face gets area 0).
+ * Face areas (am_face_areas): out_areas[f] = |c| / 2 as fp64; out_flag as above (AM_MESH_BAD_FACE; such a face gets area 0).
  *
  * Surface samples (am_surface_sample): trimesh.sample.sample_surface with the random draws supplied by the caller.
  *   cdf       device fp64[n_faces]: the inclusive prefix sum of the face areas (the caller's: any non-decreasing weights do);
@@ -732,11 +732,13 @@ int am_graph_components(const am_graph_args* args, void* stream);
  *   point = (v0 + (v1 - v0) * r0) + (v2 - v0) * r1                                           per component
  *   out_points      device fp64 (n_samples, 3);   out_face_index: device int32[n_samples];
  *   out_normals     optional device fp64 (n_samples, 3): the unit face normal of the picked face as defined above;
- *   out_flag        as above (bit 0): the sample of a face with a bad index is (0, 0, 0).
+ *   out_flag        as above (AM_MESH_BAD_FACE): the sample of a face with a bad index is (0, 0, 0).
  * A face of zero area has cdf[face] == cdf[face - 1] and is never picked (face 0 is picked by pick == 0 whatever its area).
  * That trimesh draws and combines its uniforms this way is a recollection, UNPINNED; the tests hold the device to a numpy
  * restatement of the lines above: points and face indices exactly, the normals to the rounding of sqrt and acos. */
 #define AM_MESH_ZERO 1e-13
+#define AM_MESH_BAD_FACE 1
+#define AM_MESH_BAD_CSR 2
 typedef struct {
   const void* vertices;
   int32_t vertices_f64;         /* 0: fp32, 1: fp64 */
@@ -863,8 +865,8 @@ int am_surface_sample(const am_surface_sample_args* args, void* stream);
 #define AM_DECIMATE_REACH 4.0
 #define AM_DECIMATE_FLIP 0.2
 #define AM_DECIMATE_NO_KEY INT64_MAX
-#define AM_DECIMATE_BAD_FACE 1
-#define AM_DECIMATE_BAD_CSR 2
+#define AM_DECIMATE_BAD_FACE AM_MESH_BAD_FACE      /* the same two conditions, found by the same device code */
+#define AM_DECIMATE_BAD_CSR AM_MESH_BAD_CSR
 #define AM_DECIMATE_BAD_EDGE 4
 #define AM_DECIMATE_BAD_KEPT 8
 typedef struct {

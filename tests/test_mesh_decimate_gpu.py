@@ -254,3 +254,22 @@ def test_process_mesh_decimates_on_the_device(dev):
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
     with pytest.raises(NotImplementedError, match="face_decimation"):
         MP.process_mesh(tv, tf, face_decimation=300)
+
+
+@pytest.mark.parametrize("name", ["random-7x300", "icosphere3"])
+def test_edge_tables_on_the_device_equal_the_cpu_tables(dev, name):
+    """`mesh_topology.EdgeTables` is torch plumbing that runs wherever its faces are: `torch.unique`, or with `with_order` a stable
+    sort, `unique_consecutive` and a scatter.  The device must give the CPU's tables in every field, both ways - for a 300-face array
+    over 7 vertices (every edge many times, repeated indices within a face) and a small closed mesh (every edge twice)."""
+    from actionmesh_amd.mesh_topology import EdgeTables
+    if name == "random-7x300":
+        faces, V = np.random.default_rng(11).integers(0, 7, (300, 3)), 7
+    else:
+        v, faces = R.icosphere(3)
+        V = len(v)
+    faces = torch.from_numpy(np.ascontiguousarray(faces))
+    for n_vertices, with_order in ((V, False), (V, True), (None, True)):
+        want, got = EdgeTables(faces, n_vertices, with_order), EdgeTables(faces.to(dev), n_vertices, with_order)
+        for field in ("edges", "half_edge_to_edge", "edge_count") + (("order",) if with_order else ()):
+            a, b = getattr(want, field), getattr(got, field)
+            assert b.device.type == "cuda" and a.dtype == b.dtype and torch.equal(a, b.cpu()), (field, n_vertices, with_order)
