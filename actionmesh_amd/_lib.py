@@ -266,6 +266,40 @@ class AmIsoTrianglesArgs(C.Structure):         # am_iso_triangles_args
     ]
 
 
+DMC_BAD_VERTEX_OFFSET, DMC_BAD_TRI_OFFSET, DMC_BAD_CODE = 1, 2, 4      # am_dmc_vertices' / am_dmc_triangles' out_flag bits
+
+
+class AmDmcCellsArgs(C.Structure):             # am_dmc_cells_args
+    _fields_ = [
+        ("values", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("level", C.c_double),
+        ("inside_above", C.c_int32), ("reserved", C.c_int32), ("out_config", C.c_void_p), ("out_double", C.c_void_p),
+    ]
+
+
+class AmDmcClassifyArgs(C.Structure):          # am_dmc_classify_args
+    _fields_ = [
+        ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("config", C.c_void_p), ("double_faces", C.c_void_p),
+        ("out_code", C.c_void_p), ("out_count", C.c_void_p), ("out_edge_mask", C.c_void_p),
+    ]
+
+
+class AmDmcVerticesArgs(C.Structure):          # am_dmc_vertices_args
+    _fields_ = [
+        ("values", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("level", C.c_double),
+        ("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("inside_above", C.c_int32), ("reserved", C.c_int32),
+        ("code", C.c_void_p), ("vertex_offset", C.c_void_p), ("n_vertices", C.c_int64), ("out_vertices", C.c_void_p),
+        ("out_flag", C.c_void_p),
+    ]
+
+
+class AmDmcTrianglesArgs(C.Structure):         # am_dmc_triangles_args
+    _fields_ = [
+        ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("code", C.c_void_p), ("edge_mask", C.c_void_p),
+        ("vertex_offset", C.c_void_p), ("tri_offset", C.c_void_p), ("vertices", C.c_void_p), ("n_vertices", C.c_int64),
+        ("n_triangles", C.c_int64), ("out_faces", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
 PEER_MAX_RANKS = 16
 
 
@@ -291,6 +325,8 @@ STRUCTS = {
     "am_decimate_quadrics_args": AmDecimateQuadricsArgs, "am_decimate_edges_args": AmDecimateEdgesArgs,
     "am_decimate_select_args": AmDecimateSelectArgs, "am_decimate_apply_args": AmDecimateApplyArgs,
     "am_iso_classify_args": AmIsoClassifyArgs, "am_iso_vertices_args": AmIsoVerticesArgs, "am_iso_triangles_args": AmIsoTrianglesArgs,
+    "am_dmc_cells_args": AmDmcCellsArgs, "am_dmc_classify_args": AmDmcClassifyArgs, "am_dmc_vertices_args": AmDmcVerticesArgs,
+    "am_dmc_triangles_args": AmDmcTrianglesArgs,
     "am_peer_ring": AmPeerRing,
 }
 
@@ -344,6 +380,10 @@ SYMBOLS = {
     "am_iso_classify": (C.c_int, [C.POINTER(AmIsoClassifyArgs), _P]),
     "am_iso_vertices": (C.c_int, [C.POINTER(AmIsoVerticesArgs), _P]),
     "am_iso_triangles": (C.c_int, [C.POINTER(AmIsoTrianglesArgs), _P]),
+    "am_dmc_cells": (C.c_int, [C.POINTER(AmDmcCellsArgs), _P]),
+    "am_dmc_classify": (C.c_int, [C.POINTER(AmDmcClassifyArgs), _P]),
+    "am_dmc_vertices": (C.c_int, [C.POINTER(AmDmcVerticesArgs), _P]),
+    "am_dmc_triangles": (C.c_int, [C.POINTER(AmDmcTrianglesArgs), _P]),
     "am_layer_pre_attn": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_attn_local": (C.c_int, [_P, C.c_int, _P]),
     "am_layer_post_attn": (C.c_int, [_P, C.c_int, _P]),

@@ -1,6 +1,6 @@
 """`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage2-hip [--stage2-cross-fp32]]
                                  [--render {auto,hip,off}] [--pointcloud {hip,off}] [--preprocess {hip,off}]
-                                 [--mask-refine {hip,off}] [--isosurface {hip,off}] [--script NAME] [--reference-root DIR] -- <the reference CLI's own arguments>`
+                                 [--mask-refine {hip,off}] [--isosurface {hip,hip-dual,off}] [--script NAME] [--reference-root DIR] -- <the reference CLI's own arguments>`
 
 Runs the reference's UNMODIFIED command-line script (inference/video_to_animated_mesh.py:120-248, or
 inference/video_and_3d_to_animated_mesh.py with `--script video_and_3d_to_animated_mesh`) with its own argument parser and
@@ -57,9 +57,10 @@ def split_args(argv: List[str]) -> Tuple[argparse.Namespace, List[str]]:
     ap.add_argument("--mask-refine", choices=["hip", "off"], default="off",
                     help="with --backend hip: hip = the background remover's refine_mask (Otsu threshold, connected components, removal of "
                          "the small ones) on the HIP labelling kernels, without cv2 / skimage arithmetic; off (default) = leave it alone")
-    ap.add_argument("--isosurface", choices=["hip", "off"], default="off",
+    ap.add_argument("--isosurface", choices=["hip", "hip-dual", "off"], default="off",
                     help="with --backend hip: hip = TripoSG's hierarchical_extract_geometry behind the Stage-0 VAE on the HIP marching "
-                         "tetrahedra, without the diso wheel; off (default) = leave it alone")
+                         "tetrahedra, without the diso wheel; hip-dual = the same on the HIP dual marching cubes (about a third of the "
+                         "triangles); off (default) = leave it alone")
     ap.add_argument("--script", choices=SCRIPTS, default=SCRIPTS[0])
     ap.add_argument("--reference-root", default=None)
     ap.add_argument("--amd-help", action="store_true", help="this wrapper's options (plain --help shows the reference CLI's)")
@@ -90,8 +91,8 @@ def main(argv: Optional[List[str]] = None) -> None:
             dropin.install_preprocess()
         if ours.mask_refine == "hip":
             dropin.install_mask_refine()
-        if ours.isosurface == "hip":
-            dropin.install_isosurface()
+        if ours.isosurface != "off":
+            dropin.install_isosurface(method="dual" if ours.isosurface == "hip-dual" else "tetrahedra")
     old_argv = sys.argv
     sys.argv = [script] + rest
     try:

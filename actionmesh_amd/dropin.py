@@ -26,7 +26,8 @@ The reference builds its Stage-I objects in three places, none of which takes a 
     rebound to the HIP labelling (actionmesh_amd/mask_refine.py, seam S9);
   * optionally (`install_isosurface()` after `install()`) the iso-surface extraction behind the Stage-0 VAE:
     `hierarchical_extract_geometry`, a name `TripoSGVAE.decode_latents` resolves in `actionmesh.external.triposg`'s globals
-    (triposg.py:13, 193), is rebound to the HIP marching tetrahedra (actionmesh_amd/isosurface.py, seam S11).
+    (triposg.py:13, 193), is rebound to the HIP marching tetrahedra, or with method="dual" to the HIP dual marching cubes
+    (actionmesh_amd/isosurface.py, seam S11).
 
 `uninstall()` restores every name.  Nothing here imports the reference at module import time: `install()` imports
 `actionmesh.pipeline` (the caller's environment must be able to - that is the environment the reference runs in).
@@ -227,19 +228,21 @@ def install_mask_refine() -> None:
     B.refine_mask = refine_mask
 
 
-def install_isosurface() -> None:
+def install_isosurface(method: str = "tetrahedra") -> None:
     """On top of `install()` (called with its defaults first if nothing is installed; idempotent): `hierarchical_extract_geometry`
     in `actionmesh.external.triposg` - and, with it, in the `triposg` pipeline module that imported the same name - becomes
     `actionmesh_amd.isosurface.hierarchical_extract_geometry`: the call site's name and keywords, marching tetrahedra on the HIP
-    kernels instead of the `diso` wheel.  `uninstall()` - and therefore a later `install()` - takes it back.  A call of its own, like
-    `install_preprocess()`: `install()` keeps its parameter list."""
+    kernels instead of the `diso` wheel - or, with method="dual", that function with the HIP dual marching cubes as its extraction
+    (about a third of the triangles; the same manifold guarantee).  `uninstall()` - and therefore a later `install()` - takes it
+    back.  A call of its own, like `install_preprocess()`: `install()` keeps its parameter list."""
+    from . import isosurface as I
+    I._method("install_isosurface", method)
     if not _state.get("installed"):
         install()
     if _state.get("isosurface"):
         return
     import actionmesh.external.triposg as T      # the reference's module (needs the triposg package, as its anchor path does)
-    from . import isosurface as I
-    _state["isosurface"] = (T, I.install_into(T))
+    _state["isosurface"] = (T, I.install_into(T, method))
 
 
 def uninstall() -> None:

@@ -17,12 +17,28 @@ no atomics, no hash table - the same bits on every run, equal to a numpy restate
 kernel calls go through one small backend object (`HipBackend`), so the tests can run the same code on CPU tensors with that
 restatement in its place.  No CPU backend is shipped.
 
+`method="dual"` (opt-in; the default stays "tetrahedra") is the second extraction: dual marching cubes with a manifold rule, over
+csrc/am_dualcubes.hip - one vertex per patch of every active cell, one quad per crossing grid edge, about a third of the triangles,
+with the same guarantees (a closed, oriented 2-manifold wherever the surface stays inside the evaluated points; the same bits on every
+run) and the same shape of the call:
+  ops.dmc_cells       per cell its configuration (the 8-bit inside mask; 0 unless all eight corners are finite and not on one side)
+                      and which of its faces is "double"
+  ops.dmc_classify    per cell its code - configuration, + 256 when its double face is double in the neighbour too and therefore
+                      flipped, which is what keeps the mesh a manifold -, its number of patches, and per point the mask of the axis
+                      edges that emit a quad
+  torch plumbing      the two prefix sums and the ONE sizing read, as above
+  ops.dmc_vertices    every patch's vertex - the mean of its edges' crossings, fp64, rounded once - at its cell's offset + patch
+  ops.dmc_triangles   every emitting edge's quad, split along its shorter diagonal, at its offset
+  torch plumbing      unused vertices (next to non-finite samples or the grid border) dropped; the second and last read
+Its kernels go through a second backend object (`HipDualBackend`, keyword `dual_backend`).
+
 `hierarchical_extract_geometry` has the reference call site's name and keywords: a dense grid of 2^dense + 1 points per axis, then for
 every further depth only the 3 x 3 x 3 fine points of the cells the surface passes through (dilated), everything else NaN - "not
 evaluated" - and the extraction at the finest depth.
 
-UNPINNED: parity with `diso` (dual marching cubes: fewer triangles, sharper features) or with skimage is not attempted - neither can
-be installed where this was written; TripoSG's refinement schedule and its `flash_extract_geometry` variant are not reproduced, the
+UNPINNED: parity with `diso` (its vertex placement, its diagonal rule, its tables) or with skimage is not attempted, by either
+method - neither can be installed where this was written; sharp-feature (QEF) vertex placement is not attempted: a dual vertex is the
+mean of its patch's crossings; TripoSG's refinement schedule and its `flash_extract_geometry` variant are not reproduced, the
 schedule here is this project's own; the sign convention of the VAE's field is an assumption: positive inside by default,
 `inside="below"` for the other.  What is pinned is the header's contract and the invariants (every edge in two faces, every directed
 edge once, the Euler characteristic, the enclosed volume).
@@ -53,6 +69,24 @@ class HipBackend:
     triangles = staticmethod(ops.iso_triangles)
 
 
+class HipDualBackend:
+    """The four kernels of method="dual" (csrc/am_dualcubes.hip).  `flag` as in HipBackend."""
+
+    cells = staticmethod(ops.dmc_cells)
+    classify = staticmethod(ops.dmc_classify)
+    vertices = staticmethod(ops.dmc_vertices)
+    triangles = staticmethod(ops.dmc_triangles)
+
+
+METHODS = ("tetrahedra", "dual")
+
+
+def _method(who: str, method) -> str:
+    if method not in METHODS:
+        raise ValueError(f"{who}: method must be 'tetrahedra' or 'dual', got {method!r}")
+    return method
+
+
 def _inside_above(inside) -> bool:
     if inside not in ("above", "below"):
         raise ValueError(f"extract_isosurface: inside must be 'above' or 'below', got {inside!r}")
@@ -80,16 +114,32 @@ def _empty(dev):
     return torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev)
 
 
+def _used_vertices_only(vertices, faces, flags, n_vertices: int, flag_message):
+    """The end of both methods: the vertices that no face uses dropped, order preserved, with the second and last device-to-host
+    read - the two kernels' flag words and the number of vertices kept; a set flag bit raises."""
+    # a valid face index lies inside [0, n_vertices); where a flag is set a row may be unwritten, so the scatter below is clamped
+    used, rank = referenced_vertices(faces.long().clamp_(0, n_vertices - 1), n_vertices)
+    f_vertices, f_triangles, n_used = torch.cat((flags.long(), rank[-1:] + 1)).tolist()
+    if f_vertices | f_triangles:
+        raise ValueError("extract_isosurface: " + flag_message(f_vertices | f_triangles))
+    if n_used == n_vertices:
+        return vertices, faces.long()
+    return compact_rows(vertices, used, n_used), rank[faces.long()]
+
+
 def extract_isosurface(values: torch.Tensor, level: float = 0.0, bounds=None, origin=None, spacing=None, inside: str = "above",
-                       backend=None):
+                       backend=None, method: str = "tetrahedra", dual_backend=None):
     """The surface `values == level` of an fp32 grid (X, Y, Z), every axis at least 2, as (vertices (V, 3) fp32, faces (F, 3) int64)
     on the tensor's device, oriented with the normals from the inside - finite and above the level, or below it with
     `inside="below"` - to the outside.  A non-finite value means "not evaluated": no triangle touches it.  Positions: point (i, j, k)
     lies at origin + (i, j, k) * spacing, given directly or through `bounds` (x0, y0, z0, x1, y1, z1), the positions of the first and
     last points; the index frame without either.  Every returned vertex is used by a face.  A grid the surface does not cross gives
-    (0, 3) and (0, 3).  More than 2^31 - 1 vertices or triangles raise ValueError before anything is extracted.  `backend`: the
-    kernels (tests)."""
+    (0, 3) and (0, 3).  More than 2^31 - 1 vertices or triangles raise ValueError before anything is extracted.  `method`:
+    "tetrahedra" (marching tetrahedra) or "dual" (dual marching cubes: about a third of the triangles, the same guarantees).
+    `backend`, `dual_backend`: the kernels of the two methods (tests)."""
+    method = _method("extract_isosurface", method)
     backend = HipBackend if backend is None else backend
+    dual_backend = HipDualBackend if dual_backend is None else dual_backend
     if not isinstance(values, torch.Tensor) or values.dim() != 3 or min(values.shape) < 2:
         raise ValueError(f"extract_isosurface: expected (X, Y, Z) values with every axis at least 2, got {tuple(getattr(values, 'shape', ()))}")
     if values.dtype != torch.float32:
@@ -100,6 +150,8 @@ def extract_isosurface(values: torch.Tensor, level: float = 0.0, bounds=None, or
         raise ValueError(f"extract_isosurface: the level must be finite, got {level}")
     origin, spacing = _frame(values.shape, bounds, origin, spacing)
     values, dev = values.contiguous(), values.device
+    if method == "dual":
+        return _extract_dual(values, level, above, origin, spacing, dual_backend)
     mask, count = backend.classify(values, level, above)
     crossings = torch.tensor(_POPCOUNT, dtype=torch.int64, device=dev)[mask.reshape(-1).long()]
     vertex_end, tri_end = torch.cumsum(crossings, 0), torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
@@ -113,14 +165,27 @@ def extract_isosurface(values: torch.Tensor, level: float = 0.0, bounds=None, or
     flags = torch.zeros((2,), dtype=torch.int32, device=dev)
     vertices = backend.vertices(values, mask, vertex_offset, n_vertices, origin, spacing, level, flag=flags[0:1])
     faces = backend.triangles(values, mask, count, vertex_offset, tri_offset, n_vertices, n_triangles, level, above, flag=flags[1:2])
-    # a valid face index lies inside [0, n_vertices); where a flag is set a row may be unwritten, so the scatter below is clamped
-    used, rank = referenced_vertices(faces.long().clamp_(0, n_vertices - 1), n_vertices)
-    f_vertices, f_triangles, n_used = torch.cat((flags.long(), rank[-1:] + 1)).tolist()          # the second and last read
-    if f_vertices | f_triangles:
-        raise ValueError("extract_isosurface: " + ops.iso_flag_message(f_vertices | f_triangles))
-    if n_used == n_vertices:
-        return vertices, faces.long()
-    return compact_rows(vertices, used, n_used), rank[faces.long()]
+    return _used_vertices_only(vertices, faces, flags, n_vertices, ops.iso_flag_message)
+
+
+def _extract_dual(values: torch.Tensor, level: float, above: bool, origin, spacing, backend):
+    """extract_isosurface's method="dual" behind its argument checks: the same two reads, the same limits, the same empty result."""
+    dev = values.device
+    config, double = backend.cells(values, level, above)
+    code, count, edge_mask = backend.classify(config, double)
+    triangles = 2 * torch.tensor(_POPCOUNT[:8], dtype=torch.int64, device=dev)[edge_mask.reshape(-1).long().clamp_(max=7)]
+    vertex_end, tri_end = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64), torch.cumsum(triangles, 0)
+    n_vertices, n_triangles = torch.stack((vertex_end[-1], tri_end[-1])).tolist()              # the read that sizes the outputs
+    if n_vertices > MAX_ITEMS or n_triangles > MAX_ITEMS:
+        raise ValueError(f"extract_isosurface: {n_vertices} vertices and {n_triangles} triangles; more than 2^31 - 1 of either is "
+                         "not supported")
+    if n_vertices == 0 or n_triangles == 0:
+        return _empty(dev)
+    vertex_offset, tri_offset = (vertex_end - count.reshape(-1)).view(values.shape), (tri_end - triangles).view(values.shape)
+    flags = torch.zeros((2,), dtype=torch.int32, device=dev)
+    vertices = backend.vertices(values, code, vertex_offset, n_vertices, origin, spacing, level, above, flag=flags[0:1])
+    faces = backend.triangles(code, edge_mask, vertex_offset, tri_offset, vertices, n_vertices, n_triangles, flag=flags[1:2])
+    return _used_vertices_only(vertices, faces, flags, n_vertices, ops.dmc_flag_message)
 
 
 def border_edge_count(faces: torch.Tensor) -> int:
@@ -154,7 +219,8 @@ def _evaluate(geometric_func, axes, linear: Optional[torch.Tensor], n: int, max_
 
 def hierarchical_extract_geometry(geometric_func, device, bounds=DEFAULT_BOUNDS, dense_octree_depth: int = 8,
                                   hierarchical_octree_depth: int = 9, dilation: int = 1, max_points_per_call: int = 1 << 21,
-                                  level: float = 0.0, inside: str = "above", dtype=torch.float32, backend=None):
+                                  level: float = 0.0, inside: str = "above", dtype=torch.float32, backend=None,
+                                  method: str = "tetrahedra", dual_backend=None):
     """TripoSG's entry point as the reference calls it (triposg.py:193-199): `geometric_func(points (B, n, 3)) -> (B, n, 1)` is the
     field, `bounds` the box (one number b means (-b, -b, -b, b, b, b)).  Returns a list with one (vertices np.float32 (V, 3), faces
     np.int64 (F, 3)) per batch entry of what the function returns.
@@ -162,9 +228,11 @@ def hierarchical_extract_geometry(geometric_func, device, bounds=DEFAULT_BOUNDS,
     The schedule: the grid of 2^dense_octree_depth + 1 points per axis is evaluated whole, `max_points_per_call` points at a time.
     For every further depth up to hierarchical_octree_depth, the active coarse cells - a non-zero triangle count from
     `ops.iso_classify`: eight finite corners, not all on one side - of ANY batch entry are dilated by `dilation` cells, the
-    3 x 3 x 3 fine points of each are evaluated, and every other fine point is NaN.  The surface is extracted at the finest depth;
+    3 x 3 x 3 fine points of each are evaluated, and every other fine point is NaN.  That test is also the ACTIVE of method="dual",
+    so the schedule is the same for both methods; `method` chooses the extraction at the finest depth (`extract_isosurface`);
     when it has border edges - it left the evaluated band, or the box - their number is logged as a warning.  The points handed to
     `geometric_func` are `dtype` (float32) on `device`: `np.linspace` between the bounds in float64, rounded once."""
+    method = _method("hierarchical_extract_geometry", method)
     backend = HipBackend if backend is None else backend
     above = _inside_above(inside)
     dense, finest = int(dense_octree_depth), max(int(dense_octree_depth), int(hierarchical_octree_depth))
@@ -201,7 +269,7 @@ def hierarchical_extract_geometry(geometric_func, device, bounds=DEFAULT_BOUNDS,
         values = next_values.reshape(-1, n, n, n)
     meshes = []
     for grid in values:
-        vertices, faces = extract_isosurface(grid, level, bounds=b, inside=inside, backend=backend)
+        vertices, faces = extract_isosurface(grid, level, bounds=b, inside=inside, backend=backend, method=method, dual_backend=dual_backend)
         borders = border_edge_count(faces)
         if borders:
             logger.warning("hierarchical_extract_geometry: the surface has %d border edges: it left the evaluated band or the bounds",
@@ -216,13 +284,21 @@ PIPELINE_MODULE = "triposg.pipelines.pipeline_triposg"
 _MISSING = object()
 
 
-def install_into(module) -> dict:
-    """Give `module` - meant for `actionmesh.external.triposg` - this module's `hierarchical_extract_geometry` under the name it
+def hierarchical_extract_geometry_dual(*args, **kwargs):
+    """`hierarchical_extract_geometry` with method="dual" as its default: what `install_into(module, method="dual")` installs."""
+    kwargs.setdefault("method", "dual")
+    return hierarchical_extract_geometry(*args, **kwargs)
+
+
+def install_into(module, method: str = "tetrahedra") -> dict:
+    """Give `module` - meant for `actionmesh.external.triposg` - this module's `hierarchical_extract_geometry` (with
+    method="dual": `hierarchical_extract_geometry_dual`, the same function with that method as its default) under the name it
     imported from `triposg.inference_utils` (triposg.py:13), which `TripoSGVAE.decode_latents` resolves at call time.  When the
     `triposg` package is importable, the pipeline module that imported the same name (`TripoSGPipeline.__call__`, reached through
     `TripoSGPipelinePlus`) gets it too.  Returns what the names held, for `uninstall_from`."""
+    ours = hierarchical_extract_geometry_dual if _method("install_into", method) == "dual" else hierarchical_extract_geometry
     saved = {"module": getattr(module, SEAM_NAME, _MISSING), "pipeline": None}
-    setattr(module, SEAM_NAME, hierarchical_extract_geometry)
+    setattr(module, SEAM_NAME, ours)
     try:
         import importlib
         pipeline = importlib.import_module(PIPELINE_MODULE)
@@ -230,7 +306,7 @@ def install_into(module) -> dict:
         pipeline = None
     if pipeline is not None and hasattr(pipeline, SEAM_NAME):
         saved["pipeline"] = (pipeline, getattr(pipeline, SEAM_NAME))
-        setattr(pipeline, SEAM_NAME, hierarchical_extract_geometry)
+        setattr(pipeline, SEAM_NAME, ours)
     return saved
 
 

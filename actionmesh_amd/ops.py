@@ -1125,6 +1125,115 @@ def iso_triangles(values: torch.Tensor, mask: torch.Tensor, count: torch.Tensor,
     return out
 
 
+# ---- dual marching cubes (csrc/am_dualcubes.hip; the contract is the header's, the prefix sums and the sizing are isosurface.py's) ----
+_DMC_FLAGS = {L.DMC_BAD_VERTEX_OFFSET: "a vertex offset is negative or leads past the vertex count",
+              L.DMC_BAD_TRI_OFFSET: "a triangle offset is negative or leads past the triangle count",
+              L.DMC_BAD_CODE: "the cell codes or edge masks do not belong to these values"}
+
+
+def dmc_flag_message(bits: int) -> str:
+    """What the set bits of an am_dmc_* flag word say."""
+    return _flag_message(_DMC_FLAGS, bits)
+
+
+def _dmc_tables(what: str, a, first: torch.Tensor, first_name: str, first_dtype, others):
+    """The grid of the two entry points that take no values: `first` (X, Y, Z) of `first_dtype` sets it, `others` ((name, tensor,
+    dtype), ...) have its shape and device.  Sets nx, ny, nz of `a`; returns ((nx, ny, nz), device)."""
+    if not isinstance(first, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor")
+    if first.dim() != 3 or min(first.shape) < 2:
+        raise ValueError(f"{what}: expected an (X, Y, Z) {first_name} with every axis at least 2, got {tuple(first.shape)}")
+    if first.numel() > _ISO_MAX:
+        raise ValueError(f"{what}: a grid of {tuple(first.shape)} points has more than 2^31 - 1")
+    _need(first, first_dtype, f"{what}: {first_name}")
+    shape, dev = tuple(first.shape), first.device
+    for name, t, dtype in others:
+        _shaped(f"{what}: {name}", t, dtype, shape, dev)
+    a.nx, a.ny, a.nz = shape
+    return shape, dev
+
+
+def dmc_cells(values: torch.Tensor, level: float = 0.0, inside_above: bool = True, out_config: Optional[torch.Tensor] = None,
+              out_double: Optional[torch.Tensor] = None):
+    """am_dmc_cells: for every cell of the fp32 grid (X, Y, Z) - at the point of its (0, 0, 0) corner - its configuration, the 8-bit
+    inside mask of an active cell (eight finite corners, not all on one side; 0 otherwise), and the 6-bit mask of that
+    configuration's double faces.  Both (X, Y, Z) uint8."""
+    what = "dmc_cells"
+    a = L.AmDmcCellsArgs()
+    shape, dev = _iso_grid(what, a, values, level)
+    config = _out(f"{what}: out_config", out_config, shape, torch.uint8, dev)
+    double = _out(f"{what}: out_double", out_double, shape, torch.uint8, dev)
+    a.inside_above, a.out_config, a.out_double = int(bool(inside_above)), config.data_ptr(), double.data_ptr()
+    _call(values, None, "am_dmc_cells", C.byref(a))
+    return config, double
+
+
+def dmc_classify(config: torch.Tensor, double: torch.Tensor, out_code: Optional[torch.Tensor] = None,
+                 out_count: Optional[torch.Tensor] = None, out_edge_mask: Optional[torch.Tensor] = None):
+    """am_dmc_classify: from dmc_cells' two results, per point the cell's code (X, Y, Z) int16 - its configuration, + 256 when its
+    double face is double in the neighbour too and so flipped -, its number of patches 0 .. 4 under that code and the 3-bit mask of
+    the axis edges from the point that emit a quad (both (X, Y, Z) uint8)."""
+    what = "dmc_classify"
+    a = L.AmDmcClassifyArgs()
+    shape, dev = _dmc_tables(what, a, config, "config", torch.uint8, (("double", double, torch.uint8),))
+    code = _out(f"{what}: out_code", out_code, shape, torch.int16, dev)
+    count = _out(f"{what}: out_count", out_count, shape, torch.uint8, dev)
+    mask = _out(f"{what}: out_edge_mask", out_edge_mask, shape, torch.uint8, dev)
+    a.config, a.double_faces, a.out_code, a.out_count, a.out_edge_mask = (config.data_ptr(), double.data_ptr(), code.data_ptr(),
+                                                                          count.data_ptr(), mask.data_ptr())
+    _call(config, None, "am_dmc_classify", C.byref(a))
+    return code, count, mask
+
+
+def dmc_vertices(values: torch.Tensor, code: torch.Tensor, vertex_offset: torch.Tensor, n_vertices: int, origin, spacing,
+                 level: float = 0.0, inside_above: bool = True, out: Optional[torch.Tensor] = None,
+                 flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_dmc_vertices: the (n_vertices, 3) fp32 dual vertices, patch q of cell p - the mean of its edges' crossings - at
+    vertex_offset[p] + q.  code (X, Y, Z) int16 from dmc_classify, vertex_offset (X, Y, Z) int64: the exclusive prefix sum of its
+    patch counts.  origin, spacing: three fp64 numbers each.  `flag` as in decimate_quadrics."""
+    what = "dmc_vertices"
+    a = L.AmDmcVerticesArgs()
+    shape, dev = _iso_grid(what, a, values, level)
+    _shaped(f"{what}: code", code, torch.int16, shape, dev)
+    _shaped(f"{what}: vertex_offset", vertex_offset, torch.int64, shape, dev)
+    n_vertices = int(n_vertices)
+    if not 1 <= n_vertices <= _ISO_MAX:
+        raise ValueError(f"{what}: {n_vertices} vertices are outside 1 .. 2^31 - 1")
+    out = _out(f"{what}: out", out, (n_vertices, 3), torch.float32, dev)
+    flag, own = _flag_word(what, flag, dev)
+    a.origin, a.spacing = (C.c_double * 3)(*(float(x) for x in origin)), (C.c_double * 3)(*(float(x) for x in spacing))
+    a.inside_above, a.code, a.vertex_offset, a.n_vertices = int(bool(inside_above)), code.data_ptr(), vertex_offset.data_ptr(), n_vertices
+    a.out_vertices, a.out_flag = out.data_ptr(), flag.data_ptr()
+    _call(values, None, "am_dmc_vertices", C.byref(a))
+    _raise_own_flag(what, flag, own, _DMC_FLAGS)
+    return out
+
+
+def dmc_triangles(code: torch.Tensor, edge_mask: torch.Tensor, vertex_offset: torch.Tensor, tri_offset: torch.Tensor,
+                  vertices: torch.Tensor, n_vertices: int, n_triangles: int, out: Optional[torch.Tensor] = None,
+                  flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_dmc_triangles: the (n_triangles, 3) int32 faces, two per emitting edge - its quad over the four cells around it, split
+    along the shorter diagonal - from row tri_offset[p] on.  code (X, Y, Z) int16 and edge_mask (X, Y, Z) uint8 from dmc_classify;
+    vertex_offset, tri_offset (X, Y, Z) int64: the exclusive prefix sums of the patch counts and of twice the masks' popcounts;
+    vertices (n_vertices, 3) fp32 from dmc_vertices.  `flag` as in decimate_quadrics."""
+    what = "dmc_triangles"
+    a = L.AmDmcTrianglesArgs()
+    shape, dev = _dmc_tables(what, a, code, "code", torch.int16, (("edge_mask", edge_mask, torch.uint8),
+                                                                  ("vertex_offset", vertex_offset, torch.int64),
+                                                                  ("tri_offset", tri_offset, torch.int64)))
+    n_vertices, n_triangles = int(n_vertices), int(n_triangles)
+    if not 1 <= n_vertices <= _ISO_MAX or not 1 <= n_triangles <= _ISO_MAX:
+        raise ValueError(f"{what}: {n_vertices} vertices and {n_triangles} triangles are outside 1 .. 2^31 - 1")
+    _shaped(f"{what}: vertices", vertices, torch.float32, (n_vertices, 3), dev)
+    out = _out(f"{what}: out", out, (n_triangles, 3), torch.int32, dev)
+    flag, own = _flag_word(what, flag, dev)
+    a.code, a.edge_mask, a.vertex_offset, a.tri_offset = code.data_ptr(), edge_mask.data_ptr(), vertex_offset.data_ptr(), tri_offset.data_ptr()
+    a.vertices, a.n_vertices, a.n_triangles, a.out_faces, a.out_flag = vertices.data_ptr(), n_vertices, n_triangles, out.data_ptr(), flag.data_ptr()
+    _call(code, None, "am_dmc_triangles", C.byref(a))
+    _raise_own_flag(what, flag, own, _DMC_FLAGS)
+    return out
+
+
 # ---- exact-fp32 path (csrc/am_f32.hip, am_elementwise.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              gelu: bool = False, out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:

@@ -1038,6 +1038,136 @@ typedef struct {
 } am_iso_triangles_args;
 int am_iso_triangles(const am_iso_triangles_args* args, void* stream);
 
+/* Iso-surface extraction, the second method (isosurface.py, method="dual"): dual marching cubes with a manifold rule - one vertex per
+ * patch of every active cell, one quad per crossing grid edge, about a third of the triangles of am_iso_*.  The four kernels below;
+ * the two prefix sums between them, the sizing of the outputs and the removal of unused vertices are the caller's, as for am_iso_*.
+ * There are no atomics but the OR into the flag word and no hash table: the result is the same bits on every run, and a numpy
+ * restatement of the lines below, which DERIVES the tables the kernels carry as constants, reproduces it bit for bit
+ * (tests/test_dualcubes_*).  UNPINNED: parity with `diso` - its vertex placement, its diagonal rule, its tables - and sharp-feature
+ * (QEF) placement.
+ *
+ * Grid.  As for am_iso_*: `values` is fp32 (nx, ny, nz), contiguous, every axis >= 2 and nx ny nz <= 2^31 - 1; point (i, j, k) has the
+ * linear index p = (i ny + j) nz + k and the position origin[c] + idx[c] * spacing[c] per component, fp64, a multiply then an add (no
+ * fused multiply-add); a point is INSIDE when its value is finite and (double)value > level (inside_above != 0) or (double)value <
+ * level (inside_above == 0); a non-finite value means "not evaluated"; the normals point from the inside to the outside whichever
+ * comparison is chosen, so the negated values with the negated level and the other comparison give the identical mesh.
+ *
+ * Cell.  The cell p has the eight points p + m, m in {000 .. 111} with bits (di, dj, dk), dk lowest; it exists when i < nx - 1,
+ * j < ny - 1 and k < nz - 1.  It is ACTIVE when all eight values are finite and they are not all on one side.  Its CONFIGURATION is
+ * the 8-bit inside mask, bit m for corner m (1 .. 254 on an active cell).  The twelve cell edges are the corner pairs (a, b), a < b,
+ * that differ in one bit, numbered 0 .. 11 in ascending (a, b): (0,1) (0,2) (0,4) (1,3) (1,5) (2,3) (2,6) (3,7) (4,5) (4,6) (5,7)
+ * (6,7).  A cell edge CROSSES when exactly one of its corners is inside.  Face 2 axis + side (axis 0, 1, 2 = i, j, k) holds the four
+ * corners whose bit of that axis equals `side`.
+ *
+ * Patches.  On each of the six faces, two crossing edges are joined by one segment; a face with four crossing edges (AMBIGUOUS: its
+ * diagonal corners are inside) gets two segments, each joining the two face edges at one INSIDE corner of the face (cutting that
+ * corner off) - the default rule.  Every crossing edge lies on two faces, so the segments form cycles over the crossing edges; each
+ * cycle is a PATCH.  Patches are numbered by their smallest edge id, ascending.  The 256 configurations have 0 / 1 / 2 / 3 / 4
+ * patches in 2 / 162 / 82 / 8 / 2 cases.
+ *
+ * Flip (what makes the mesh a manifold).  An ambiguous face of a cell is DOUBLE when the default rule puts both of its segments on the
+ * same patch.  A face shared by two ACTIVE cells is FLIPPED when it is double in both; on a flipped face the two segments cut off the
+ * OUTSIDE corners instead, in both cells.  A face on the grid border, or towards a cell that is not active, never flips.  Exactly 36
+ * configurations have a double face and each of them has exactly one ambiguous face, so a cell has at most one flipped face, and its
+ * state - its CODE - is its configuration, + 256 when that face is flipped (int16; 0 where no active cell starts).
+ *
+ * Dual vertices.  One per patch of every active cell, numbered by the linear index of the cell's 000 corner, then by patch.  Its
+ * position: the crossing positions of the patch's edges (a, b), each with t = (level - v_a) / (v_b - v_a) and, per component,
+ * pa[c] + t * (pb[c] - pa[c]) in fp64 as in am_iso_vertices but NOT rounded to fp32, are added in ascending edge id to a sum that
+ * starts at +0, the sum is divided by their number, and the quotient is rounded once to fp32.
+ *
+ * Quads and triangles.  The grid edge (p, axis) from p to p + e_axis EMITS when the four cells around it - p, p - e_u, p - e_u - e_v,
+ * p - e_v with u = (axis + 1) mod 3, v = (axis + 2) mod 3 - all exist and are ACTIVE, and it crosses.  Its quad (q0, q1, q2, q3) has,
+ * in that order of the cells, the vertex of the patch that holds this edge in each cell; when p is not inside (the far end is), q1 and
+ * q3 change places, so that the normal points from the inside to the outside.  The quad is split along its shorter diagonal: with
+ * d02 = |q0 - q2|^2 and d13 = |q1 - q3|^2 - each ((x x + y y) + z z) in fp64 on the differences of the STORED fp32 positions - the
+ * triangles are (q0, q1, q3), (q1, q2, q3) when d13 < d02 and (q0, q1, q2), (q0, q2, q3) otherwise (a tie goes to first - third).
+ * Triangles are ordered by 3 p + axis, two per quad; faces are int32.
+ *
+ * am_dmc_cells, per point p:  out_config[p] = the configuration of the cell p when it is ACTIVE, 0 otherwise and where no cell starts;
+ *   out_double[p] = the 6-bit mask of that configuration's double faces, bit 2 axis + side (0 or one bit).
+ * am_dmc_classify, per point p, from the two results above:  out_code[p];  out_count[p] = the cell's number of patches, 0 .. 4, under
+ *   that code;  out_edge_mask[p] = bit `axis` for every emitting edge (p, axis).
+ * The caller makes the exclusive prefix sums vertex_offset[p] over out_count and tri_offset[p] over 2 popcount(out_edge_mask) (int64);
+ * their totals are n_vertices and n_triangles, each 1 .. 2^31 - 1 for the two calls below.
+ * am_dmc_vertices, per point with a non-zero code:  the vertex of patch q goes to row vertex_offset[p] + q of out_vertices.
+ * am_dmc_triangles, per point with a non-zero edge mask:  the two triangles of edge (p, axis) go to rows tri_offset[p] +
+ *   2 popcount(edge_mask[p] & ((1 << axis) - 1)) and the next of out_faces; the vertex of patch q of cell c is vertex_offset[c] + q;
+ *   `vertices` is am_dmc_vertices' output (the diagonals).  Dual vertices that no quad uses - next to non-finite samples or to the grid
+ *   border - stay in out_vertices; the caller drops them, order preserved.
+ *
+ * out_flag, device int32[1], cleared by each of the last two calls; the caller reads it with the result and treats a non-zero value
+ * as failure:
+ *   AM_DMC_BAD_VERTEX_OFFSET  a vertex offset is negative or leads past n_vertices;
+ *   AM_DMC_BAD_TRI_OFFSET     a triangle offset is negative or leads past n_triangles;
+ *   AM_DMC_BAD_CODE           code or edge mask do not belong to these values: a code outside 0 .. 511, with the configuration 0 or
+ *                             255, with + 256 on a configuration without a double face, where no cell starts, or (am_dmc_vertices)
+ *                             with another configuration than the values give; an edge mask above 7, a mask bit where one of the
+ *                             four cells does not exist or has the code 0, or for an edge that does not cross under the cell's code.
+ * Every offset, code and index read from memory is compared with its bound BEFORE it is used as an address; what a bad one would have
+ * written is left out. */
+#define AM_DMC_BAD_VERTEX_OFFSET 1
+#define AM_DMC_BAD_TRI_OFFSET 2
+#define AM_DMC_BAD_CODE 4
+typedef struct {
+  const float* values;          /* (nx, ny, nz) */
+  int64_t nx;
+  int64_t ny;
+  int64_t nz;
+  double level;                 /* finite */
+  int32_t inside_above;
+  int32_t reserved;
+  uint8_t* out_config;          /* [nx ny nz] */
+  uint8_t* out_double;          /* [nx ny nz] */
+} am_dmc_cells_args;
+int am_dmc_cells(const am_dmc_cells_args* args, void* stream);
+
+typedef struct {
+  int64_t nx;
+  int64_t ny;
+  int64_t nz;
+  const uint8_t* config;        /* am_dmc_cells' out_config */
+  const uint8_t* double_faces;  /* am_dmc_cells' out_double */
+  int16_t* out_code;            /* [nx ny nz] */
+  uint8_t* out_count;           /* [nx ny nz] */
+  uint8_t* out_edge_mask;       /* [nx ny nz] */
+} am_dmc_classify_args;
+int am_dmc_classify(const am_dmc_classify_args* args, void* stream);
+
+typedef struct {
+  const float* values;
+  int64_t nx;
+  int64_t ny;
+  int64_t nz;
+  double level;
+  double origin[3];
+  double spacing[3];
+  int32_t inside_above;
+  int32_t reserved;
+  const int16_t* code;          /* am_dmc_classify's out_code */
+  const int64_t* vertex_offset; /* [nx ny nz] */
+  int64_t n_vertices;           /* >= 1 */
+  float* out_vertices;          /* (n_vertices, 3) */
+  int32_t* out_flag;
+} am_dmc_vertices_args;
+int am_dmc_vertices(const am_dmc_vertices_args* args, void* stream);
+
+typedef struct {
+  int64_t nx;
+  int64_t ny;
+  int64_t nz;
+  const int16_t* code;
+  const uint8_t* edge_mask;     /* am_dmc_classify's out_edge_mask */
+  const int64_t* vertex_offset;
+  const int64_t* tri_offset;    /* [nx ny nz] */
+  const float* vertices;        /* am_dmc_vertices' out_vertices */
+  int64_t n_vertices;
+  int64_t n_triangles;          /* >= 1 */
+  int32_t* out_faces;           /* (n_triangles, 3) */
+  int32_t* out_flag;
+} am_dmc_triangles_args;
+int am_dmc_triangles(const am_dmc_triangles_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

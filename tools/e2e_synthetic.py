@@ -127,7 +127,8 @@ def dirty_mesh(v, f, cols: int, seed: int = 2):
 
 
 def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44, clip: str = None, label: str = None,
-        raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False, face_decimation: int = 0, field_grid: int = 0):
+        raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False, face_decimation: int = 0, field_grid: int = 0,
+        iso_method: str = "tetrahedra"):
     from actionmesh_amd import LatentBank, generate_3d_latents, generate_vertex_animation
     from actionmesh_amd import mesh_prep as MP
     t_build = time.perf_counter()
@@ -173,10 +174,10 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             ax = torch.linspace(-1.0, 1.0, field_grid, dtype=torch.float64, device=dev)
             gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
             field = (0.25 - (((gx * gx + gy * gy).sqrt() - 0.6) ** 2 + gz * gz).sqrt()).float()
-            ISO.extract_isosurface(field[:9, :9, :9], bounds=1.0)       # the library's first call, outside the stage
+            ISO.extract_isosurface(field[:9, :9, :9], bounds=1.0, method=iso_method)       # the library's first call, outside the stage
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
-            raw_v, raw_f = ISO.extract_isosurface(field, bounds=1.0)
+            raw_v, raw_f = ISO.extract_isosurface(field, bounds=1.0, method=iso_method)
             torch.cuda.synchronize(dev)
             t_iso = time.perf_counter() - t0
             assert raw_f.shape[0] > face_decimation, (raw_f.shape, face_decimation)
@@ -274,7 +275,7 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             "config": {"workload": f"{frames} frames, {n_win} AR window(s) of {window}, {steps} denoise steps, N={n_tokens} tokens, "
                                    f"{vertices} vertices, {'tiny' if tiny else 'shipped'} model shapes, random-init weights"
                                    + (f", frames = the reference's {clip} clip" if clip else ", random frames")
-                                   + (f", mesh extracted from a {field_grid}^3 torus field on the device" if field_grid else "")
+                                   + (f", mesh extracted from a {field_grid}^3 torus field on the device ({iso_method})" if field_grid else "")
                                    + (f", decimated to {faces.shape[0]} faces on the device" if face_decimation else "")},
             **({"baseline_config": label} if label else {}),
             "context_rms": round(float(context.float().pow(2).mean().sqrt()), 4), "latents_rms": round(float(lat[1:].float().pow(2).mean().sqrt()), 4)}
@@ -297,6 +298,9 @@ def main():
     ap.add_argument("--field-grid", type=int, default=0, metavar="N",
                     help="with --face-decimation: start from an analytic torus field on N^3 points instead of a prepared mesh - "
                          "extract_isosurface on the device, then the clean-up and the decimation (adds seconds.isosurface)")
+    ap.add_argument("--iso-method", default="tetrahedra", choices=["tetrahedra", "dual"],
+                    help="with --field-grid: the extraction - marching tetrahedra (default) or dual marching cubes (about a third of the "
+                         "triangles in front of the decimation)")
     ap.add_argument("--config", type=int, default=None, choices=[1, 3], help="BASELINE.json configs[1] / configs[3] as a plumbing record (see the module docstring)")
     a = ap.parse_args()
     if a.raw_frames and not (a.clip or a.config):
@@ -318,7 +322,7 @@ def main():
                  "(dirty mesh -> merge_and_clean_mesh -> normalize_mesh -> sample_surface; denormalize_mesh + expand_to_original at the end)")
     print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames,
                          features=a.features, mesh_prep=a.mesh_prep, face_decimation=a.face_decimation,
-                         field_grid=a.field_grid)))
+                         field_grid=a.field_grid, iso_method=a.iso_method)))
 
 
 if __name__ == "__main__":

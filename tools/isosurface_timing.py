@@ -16,7 +16,12 @@ implementation anyone would ship, and labelled as that in the output.
 
 Writes profiles/isosurface.json; no test asserts a time.
 
-    python tools/isosurface_timing.py [--out profiles/isosurface.json] [--grids 257 513]
+`--method dual` measures the second extraction (dual marching cubes, csrc/am_dualcubes.hip) against the first IN ONE PROCESS: per field
+and grid the four am_dmc_* kernels by HIP events, then the whole `extract_isosurface` call of both methods, alternating call by call
+(wall clock around a device synchronisation), and - what the method is for - `merge_and_clean_mesh` + `decimate_mesh` of the 257^3
+sphere mesh of either method to 40 000 faces: rounds and milliseconds, alternating too.  Writes profiles/isosurface_dual.json.
+
+    python tools/isosurface_timing.py [--method tetrahedra|dual] [--out profiles/isosurface.json] [--grids 257 513]
 """
 import argparse
 import json
@@ -82,12 +87,95 @@ def by_clock(fn, repeats, warmup, dev):
     return summary(times)
 
 
+def alternating(fns, repeats, warmup, dev):
+    """by_clock for several callables, one call of each per round, so that drift of the clocks or of the box hits all alike."""
+    times = {name: [] for name in fns}
+    for k in range(warmup + repeats):
+        for name, fn in fns.items():
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            if k >= warmup:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+    return {name: summary(t) for name, t in times.items()}
+
+
+def main_dual(a):
+    from actionmesh_amd import isosurface as ISO
+    from actionmesh_amd import mesh_decimate, mesh_prep, ops
+    dev = torch.device("cuda:0")
+    rows = []
+    for name, fn in (("sphere", sphere_of), ("gyroid", gyroid_of)):
+        for n in a.grids:
+            values = grid_field(fn, n, dev)
+            config, double = ops.dmc_cells(values)
+            code, count, edge_mask = ops.dmc_classify(config, double)
+            triangles = 2 * torch.tensor(ISO._POPCOUNT[:8], dtype=torch.int64, device=dev)[edge_mask.reshape(-1).long()]
+            vertex_end, tri_end = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64), torch.cumsum(triangles, 0)
+            V, F = int(vertex_end[-1]), int(tri_end[-1])
+            voff, toff = (vertex_end - count.reshape(-1)).view(values.shape), (tri_end - triangles).view(values.shape)
+            flipped = int((code >> 8).sum()) // 2
+            del triangles, vertex_end, tri_end
+            vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+            faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+            flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+            origin, spacing = BOUNDS[:3], ((BOUNDS[3] - BOUNDS[0]) / (n - 1),) * 3
+            t_cells = by_events(lambda: ops.dmc_cells(values, out_config=config, out_double=double), 20, 3, dev)
+            t_classify = by_events(lambda: ops.dmc_classify(config, double, out_code=code, out_count=count, out_edge_mask=edge_mask), 20, 3, dev)
+            t_vertices = by_events(lambda: ops.dmc_vertices(values, code, voff, V, origin, spacing, out=vertices, flag=flag), 20, 3, dev)
+            bad = int(flag)
+            t_triangles = by_events(lambda: ops.dmc_triangles(code, edge_mask, voff, toff, vertices, V, F, out=faces, flag=flag), 20, 3, dev)
+            assert bad == 0 and int(flag) == 0
+            del voff, toff, vertices, faces, config, double, code, count, edge_mask
+            whole = alternating({"tetrahedra": lambda: ISO.extract_isosurface(values, bounds=BOUNDS),
+                                 "dual": lambda: ISO.extract_isosurface(values, bounds=BOUNDS, method="dual")}, 20, 3, dev)
+            tet_faces = int(ISO.extract_isosurface(values, bounds=BOUNDS)[1].shape[0])
+            rows.append({"field": name, "grid": n, "points": n ** 3, "dual_vertices_before_compaction": V, "dual_triangles": F,
+                         "flipped_faces": flipped, "tetrahedra_triangles": tet_faces, "triangle_ratio": round(F / tet_faces, 4),
+                         "am_dmc_cells": t_cells, "am_dmc_cells_GBps_at_6_bytes_per_point": round(6 * n ** 3 / t_cells["median_ms"] / 1e6, 1),
+                         "am_dmc_classify": t_classify, "am_dmc_vertices": t_vertices, "am_dmc_triangles": t_triangles,
+                         "extract_isosurface": whole})
+            print(json.dumps(rows[-1]), flush=True)
+            del values
+    values = grid_field(sphere_of, a.decimate_grid, dev)
+    meshes, rounds = {}, {}
+    for method in ISO.METHODS:
+        v, f = ISO.extract_isosurface(values, bounds=BOUNDS, method=method)
+        meshes[method] = mesh_prep.merge_and_clean_mesh(v, f)[:2]
+
+    def decimate(method):
+        dv, df, rounds[method] = mesh_decimate.decimate_mesh(*meshes[method], a.decimate_faces, return_rounds=True)
+        assert df.shape[0] == a.decimate_faces
+
+    t_decimate = alternating({m: (lambda m=m: decimate(m)) for m in ISO.METHODS}, 5, 1, dev)
+    decimation = {"field": "sphere", "grid": a.decimate_grid, "target_faces": a.decimate_faces,
+                  **{m: {"faces_in": int(meshes[m][1].shape[0]), "rounds": rounds[m], "decimate_mesh": t_decimate[m]} for m in ISO.METHODS}}
+    print(json.dumps(decimation), flush=True)
+    out = {"what": "iso-surface extraction by dual marching cubes against marching tetrahedra on one MI355X, one process: kernels by HIP "
+                   "events (medians of 20 after 3 warm-up launches), whole calls by wall clock around a device synchronisation, the two "
+                   "methods alternating call by call (medians of 20 after 3; the decimation: 5 after 1)",
+           "comparison": "none with diso or skimage (not installable offline)",
+           "device": torch.cuda.get_device_name(dev), "rows": rows, "decimation": decimation}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "isosurface.json"))
+    ap.add_argument("--method", choices=["tetrahedra", "dual"], default="tetrahedra")
+    ap.add_argument("--out", default=None, help="default: profiles/isosurface.json, or profiles/isosurface_dual.json with --method dual")
+    ap.add_argument("--decimate-grid", type=int, default=257)
+    ap.add_argument("--decimate-faces", type=int, default=40_000)
     ap.add_argument("--grids", type=int, nargs="+", default=[257, 513])
     ap.add_argument("--hierarchy", type=int, nargs=2, default=[8, 9], metavar=("DENSE", "FINEST"))
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "isosurface_dual.json" if a.method == "dual" else "isosurface.json")
+    if a.method == "dual":
+        return main_dual(a)
     from actionmesh_amd import isosurface as ISO
     from actionmesh_amd import ops
     import _isosurface_ref as R
