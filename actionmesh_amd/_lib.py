@@ -79,6 +79,32 @@ class AmNnArgs(C.Structure):
     ]
 
 
+NN_GRID_MAX_CELLS = 128                    # AM_NN_GRID_MAX_CELLS
+NN_GRID_BAD_ORDER, NN_GRID_BAD_CELL_START, NN_GRID_BAD_INDEX, NN_GRID_BAD_QUERY_ORDER = 1, 2, 4, 8     # the AM_NN_GRID_BAD_* flag bits
+
+
+class AmNnGrid(C.Structure):               # am_nn_grid
+    _fields_ = [
+        ("n_points", C.c_int64), ("batch", C.c_int32), ("cells", C.c_int32),
+        ("frame", C.c_void_p), ("slabs", C.c_void_p), ("cell_start", C.c_void_p), ("order", C.c_void_p), ("sorted", C.c_void_p),
+    ]
+
+
+class AmNnGridBuildArgs(C.Structure):      # am_nn_grid_build_args
+    _fields_ = [
+        ("points", C.c_void_p), ("points_bstride", C.c_int64), ("grid", AmNnGrid), ("out_cell", C.c_void_p), ("out_flag", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AmNnGridSearchArgs(C.Structure):     # am_nn_grid_search_args
+    _fields_ = [
+        ("grid", AmNnGrid), ("queries", C.c_void_p), ("n_queries", C.c_int64), ("queries_bstride", C.c_int64),
+        ("batch", C.c_int32), ("precise", C.c_int32), ("query_order", C.c_void_p), ("query_order_bstride", C.c_int64),
+        ("out_index", C.c_void_p), ("out_d2", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
 class AmAttnArgs(C.Structure):
     _fields_ = [
         ("Q", C.c_void_p), ("K", C.c_void_p), ("Vt", C.c_void_p), ("O", C.c_void_p),
@@ -317,7 +343,8 @@ class AmPeerRing(C.Structure):          # include/actionmesh_amd_sharded.h
 # every size and field offset with what a C compiler makes of them)
 STRUCTS = {
     "am_config": AmConfig, "am_gemm_args": AmGemmArgs, "am_headpost_args": AmHeadPostArgs, "am_attn_args": AmAttnArgs,
-    "am_attn_f32_args": AmAttnF32Args, "am_nn_args": AmNnArgs, "am_render_camera": AmRenderCamera, "am_render_args": AmRenderArgs,
+    "am_attn_f32_args": AmAttnF32Args, "am_nn_args": AmNnArgs, "am_nn_grid": AmNnGrid, "am_nn_grid_build_args": AmNnGridBuildArgs,
+    "am_nn_grid_search_args": AmNnGridSearchArgs, "am_render_camera": AmRenderCamera, "am_render_args": AmRenderArgs,
     "am_fps_args": AmFpsArgs, "am_image_frame": AmImageFrame, "am_image_alpha_stats_args": AmImageAlphaStatsArgs,
     "am_image_resample_args": AmImageResampleArgs, "am_image_materialize_args": AmImageMaterializeArgs,
     "am_mask_refine_args": AmMaskRefineArgs, "am_graph_args": AmGraphArgs, "am_vertex_normals_args": AmVertexNormalsArgs,
@@ -357,6 +384,11 @@ SYMBOLS = {
     "am_displacement_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P]),
     "am_nn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "am_nn_search": (C.c_int, [C.POINTER(AmNnArgs), _P, C.c_size_t, _P]),
+    "am_nn_grid_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "am_nn_grid_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "am_nn_grid_cells": (C.c_int, [C.POINTER(AmNnGridBuildArgs), _P]),
+    "am_nn_grid_build": (C.c_int, [C.POINTER(AmNnGridBuildArgs), _P]),
+    "am_nn_grid_search": (C.c_int, [C.POINTER(AmNnGridSearchArgs), _P]),
     "am_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "am_render_normals": (C.c_int, [C.POINTER(AmRenderArgs), _P, C.c_size_t, _P]),
     "am_fps_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),

@@ -513,6 +513,158 @@ def nn_indices_valid(*indices: torch.Tensor) -> None:
         raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
 
 
+class NnGrid:
+    """The uniform grid of one cloud or of a batch of clouds (am_nn_grid of include/actionmesh_amd.h): ONE device allocation of
+    am_nn_grid_bytes carved into frame (B, 8) fp32, slabs (B, 2, 3, G) fp32, cell_start (B, G^3 + 2) int32, order (B, P) int32 and
+    sorted (B, P, 4) fp32.  `shared`: built from a 2-D cloud - a search of any batch uses the one grid.  `order` is the cloud's own
+    cell order: the `query_order` to pass when this cloud is the QUERY of another grid.  `buffer`: the caller's allocation of exactly
+    am_nn_grid_bytes to carve instead of a fresh one."""
+
+    def __init__(self, n_points: int, batch: int, cells: int, shared: bool, device, buffer: Optional[torch.Tensor] = None):
+        self.n_points, self.batch, self.cells, self.shared, self.device = n_points, batch, cells, shared, device
+        nbytes = _entry(None, "am_nn_grid_bytes")[1](n_points, batch, cells)
+        if nbytes == 0:
+            raise ValueError(f"nn_grid_build: no grid of {cells} cells per axis over {batch} x {n_points} points (cells 1 .. {L.NN_GRID_MAX_CELLS})")
+        if buffer is not None and (buffer.dtype != torch.uint8 or buffer.numel() != nbytes or not buffer.is_contiguous() or buffer.data_ptr() % 16):
+            raise ValueError(f"NnGrid: the buffer must be {nbytes} contiguous, 16-byte aligned uint8 elements")
+        self.buffer = torch.empty((nbytes,), dtype=torch.uint8, device=device) if buffer is None else buffer
+        off = 0
+
+        def carve(shape, dtype):
+            nonlocal off
+            n = 4
+            for s in shape:
+                n *= s
+            t = self.buffer[off:off + n].view(dtype).view(shape)
+            off += round_up(n, 16)
+            return t
+
+        self.frame = carve((batch, 8), torch.float32)
+        self.slabs = carve((batch, 2, 3, cells), torch.float32)
+        self.cell_start = carve((batch, cells ** 3 + 2), torch.int32)
+        self.order = carve((batch, n_points), torch.int32)
+        self.sorted = carve((batch, n_points, 4), torch.float32)
+        assert off == nbytes
+        self.flags = torch.zeros((1,), dtype=torch.int32, device=device)      # every flag a check=False search has raised since valid()
+
+    def struct(self) -> "L.AmNnGrid":
+        g = L.AmNnGrid()
+        g.n_points, g.batch, g.cells = self.n_points, self.batch, self.cells
+        g.frame, g.slabs, g.cell_start = self.frame.data_ptr(), self.slabs.data_ptr(), self.cell_start.data_ptr()
+        g.order, g.sorted = self.order.data_ptr(), self.sorted.data_ptr()
+        return g
+
+
+_NN_GRID_FLAGS = {L.NN_GRID_BAD_ORDER: "an order entry outside the points", L.NN_GRID_BAD_CELL_START: "cell_start not ascending inside the points",
+                  L.NN_GRID_BAD_INDEX: "a sorted record with an index outside the points", L.NN_GRID_BAD_QUERY_ORDER: "a query_order entry outside the queries"}
+
+
+def _nn_grid_raise(flag: int, who: str) -> None:
+    if flag:
+        raise ValueError(f"{who}: bad grid ({', '.join(t for b, t in _NN_GRID_FLAGS.items() if flag & b)})")
+
+
+def nn_grid_default_cells(n_points: int) -> int:
+    """G = clamp(ceil(cbrt(2 P)), 1, 128): about half a point per cell (tools/nn_grid_timing.py sweeps it)."""
+    g = max(1, int(round((2.0 * n_points) ** (1.0 / 3.0))))
+    while g ** 3 < 2 * n_points:
+        g += 1
+    while g > 1 and (g - 1) ** 3 >= 2 * n_points:
+        g -= 1
+    return min(max(g, 1), L.NN_GRID_MAX_CELLS)
+
+
+def nn_grid_build(points: torch.Tensor, cells: Optional[int] = None) -> NnGrid:
+    """am_nn_grid_cells + a stable torch sort + am_nn_grid_build: the grid of points (P, 3) - one shared grid - or (B, P, 3) fp32."""
+    _need(points, torch.float32, "points")
+    if points.shape[-1] != 3 or points.dim() not in (2, 3):
+        raise ValueError(f"nn_grid_build: expected (P, 3) or (B, P, 3) points, got {tuple(points.shape)}")
+    P = points.shape[-2]
+    if P == 0:
+        raise ValueError("nn_grid_build: empty point cloud")
+    batch = points.shape[0] if points.dim() == 3 else 1
+    G = nn_grid_default_cells(P) if cells is None else int(cells)
+    if not 1 <= G <= L.NN_GRID_MAX_CELLS:
+        raise ValueError(f"nn_grid_build: cells {G} outside 1 .. {L.NN_GRID_MAX_CELLS}")
+    grid = NnGrid(P, batch, G, points.dim() == 2, points.device)
+    ws, need = _workspace(points.device, "am_nn_grid_workspace_bytes", P, batch, G)
+    cell = torch.empty((batch, P), dtype=torch.int32, device=points.device)
+    flag = torch.empty((1,), dtype=torch.int32, device=points.device)
+    a = L.AmNnGridBuildArgs()
+    a.points, a.points_bstride, a.grid = points.data_ptr(), (P * 3 if points.dim() == 3 else 0), grid.struct()
+    a.out_cell, a.out_flag, a.workspace, a.workspace_bytes = cell.data_ptr(), flag.data_ptr(), ws.data_ptr(), need
+    _call(points, None, "am_nn_grid_cells", C.byref(a))
+    grid.order.copy_(torch.sort(cell, dim=1, stable=True).indices)          # plumbing: (cell, index) order
+    _call(points, None, "am_nn_grid_build", C.byref(a))
+    return grid
+
+
+def nn_grid_search(grid: NnGrid, queries: torch.Tensor, precise: bool = True, query_order: Optional[torch.Tensor] = None,
+                   check: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """am_nn_grid_search: nearest_neighbors' (index int32, squared distance) bit for bit, through `grid`.  queries (Q, 3) or (B, Q, 3)
+    fp32; a batched grid needs the same B (2-D queries are then shared).  `query_order`: int32 (Q,) or (B, Q), a permutation of the
+    queries - the order in which lanes pick them (the query cloud's own NnGrid.order makes a wave share cells); results stay at the
+    query's own position.  `check` as in nearest_neighbors; with check=False the kernel's flag is kept in grid.flags for nn_grid_valid."""
+    _need(queries, torch.float32, "queries")
+    if queries.shape[-1] != 3 or queries.dim() not in (2, 3):
+        raise ValueError(f"nn_grid_search: expected (Q, 3) or (B, Q, 3) queries, got {tuple(queries.shape)}")
+    if queries.device != grid.device:
+        raise ValueError("nn_grid_search: the queries and the grid are on different devices")
+    Q = queries.shape[-2]
+    if Q == 0:
+        raise ValueError("nn_grid_search: empty point cloud")
+    batch = max(1 if grid.shared else grid.batch, queries.shape[0] if queries.dim() == 3 else 1)
+    if (not grid.shared and grid.batch != batch) or (queries.dim() == 3 and queries.shape[0] != batch):
+        raise ValueError(f"nn_grid_search: grid batch {grid.batch} / queries {tuple(queries.shape)} do not make a batch of {batch}")
+    out_shape = (batch, Q) if (not grid.shared or queries.dim() == 3) else (Q,)
+    idx = torch.empty(out_shape, dtype=torch.int32, device=queries.device)
+    d2 = torch.empty(out_shape, dtype=torch.float64 if precise else torch.float32, device=queries.device)
+    flag = torch.empty((1,), dtype=torch.int32, device=queries.device)
+    a = L.AmNnGridSearchArgs()
+    a.grid = grid.struct()
+    a.queries, a.n_queries, a.queries_bstride = queries.data_ptr(), Q, (Q * 3 if queries.dim() == 3 else 0)
+    a.batch, a.precise = batch, 1 if precise else 0
+    if query_order is not None:
+        _need(query_order, torch.int32, "query_order")
+        if tuple(query_order.shape) not in ((Q,), (1, Q), (batch, Q)):
+            raise ValueError(f"nn_grid_search: query_order {tuple(query_order.shape)} is neither ({Q},) nor ({batch}, {Q})")
+        a.query_order, a.query_order_bstride = query_order.data_ptr(), (Q if query_order.dim() == 2 and query_order.shape[0] == batch and batch > 1 else 0)
+    a.out_index, a.out_d2, a.out_flag = idx.data_ptr(), d2.data_ptr(), flag.data_ptr()
+    _call(queries, None, "am_nn_grid_search", C.byref(a))
+    if check:
+        bad = torch.stack(((idx < 0).any().to(torch.int32), flag[0])).tolist()
+        _nn_grid_raise(bad[1], "nn_grid_search")
+        if bad[0]:
+            raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
+    else:
+        grid.flags |= flag
+    return idx, d2
+
+
+def nn_grid_valid(grids: Sequence[NnGrid], *indices: torch.Tensor) -> None:
+    """The deferred check of check=False grid searches: ONE device-to-host read for the flags of `grids` and any number of index tensors."""
+    words = [g.flags[0] for g in grids] + [(i < 0).any().to(torch.int32) for i in indices]
+    got = torch.stack(words).tolist()
+    for g, f in zip(grids, got):
+        g.flags.zero_()
+        _nn_grid_raise(f, "nn_grid_search")
+    if any(got[len(grids):]):
+        raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
+
+
+def nearest_neighbors_grid(points: torch.Tensor, queries: torch.Tensor, precise: bool = True,
+                           check: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """nearest_neighbors through a grid built for the call (default cells): the same operands, return types, bits and errors."""
+    _need(points, torch.float32, "points"); _need(queries, torch.float32, "queries")
+    if points.shape[-1] != 3 or queries.shape[-1] != 3 or points.dim() not in (2, 3) or queries.dim() not in (2, 3):
+        raise ValueError(f"nearest_neighbors: expected (..., n, 3) operands, got {tuple(points.shape)} / {tuple(queries.shape)}")
+    if points.dim() == 3 and queries.dim() == 3 and points.shape[0] != queries.shape[0]:
+        raise ValueError(f"nearest_neighbors: points batch {points.shape[0]} != {queries.shape[0]}")
+    if points.shape[-2] == 0 or queries.shape[-2] == 0:
+        raise ValueError("nearest_neighbors: empty point cloud")
+    return nn_grid_search(nn_grid_build(points), queries, precise=precise, check=check)
+
+
 _FPS_DTYPES = {torch.float32: L.FPS_F32, torch.float16: L.FPS_F16, torch.bfloat16: L.FPS_BF16}
 
 

@@ -425,6 +425,100 @@ typedef struct {
 size_t am_nn_workspace_bytes(int64_t n_points, int64_t n_queries, int batch, int precise);
 int am_nn_search(const am_nn_args* args, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The same search through a uniform grid (csrc/am_nn_grid.hip): out_index and out_d2 are am_nn_search's BIT FOR BIT - the same
+ * d2 = ((dx*dx) + (dy*dy)) + dz*dz in fp32 or fp64 without contraction, the minimum over all points, ties to the lowest index,
+ * index -1 with d2 = +inf when no distance is finite - while only the points of a growing cube of cells are evaluated.  General
+ * purpose and exact; what it buys depends on how close the clouds lie (profiles/nn_grid.json).
+ *
+ * THE GRID of one cloud of n_points (batch entries are independent), G = cells per axis, 1 .. 128.  All arithmetic is fp32, each
+ * operation rounded on its own, fl() below:
+ *   frame       float[8] = { lo_x, lo_y, lo_z, 0, inv_x, inv_y, inv_z, 0 }.  lo_k / hi_k: the minimum / maximum of coordinate k
+ *               over the points whose three coordinates are all finite, in the total order of the IEEE bit patterns (-0 below +0);
+ *               no such point: lo = 0, inv = 0.  inv_k = fl(G / fl(hi_k - lo_k)); when the extent is 0 or that quotient is not
+ *               finite, inv_k = 0.
+ *   cell of p   c_k = 0 when inv_k == 0 (the product is not formed), else c_k = min(G - 1, (int)floorf(fl(fl(p_k - lo_k) * inv_k)));
+ *               cell = (c_z * G + c_y) * G + c_x.  A point with a non-finite coordinate goes to the extra cell G^3 and never matches.
+ *   order       int32[n_points]: the point indices sorted by (cell, index) - ties inside a cell in ascending index, so every array
+ *               here is defined bit for bit.
+ *   cell_start  int32[G^3 + 2]: cell_start[c] = number of points in cells below c; [G^3] starts the extra cell, [G^3 + 1] = n_points.
+ *   sorted      float[n_points][4] = { x, y, z, index bits } of the points in `order` (16-byte records).
+ *   slabs       float[2][3][G]: [0][k][j] = the smallest coordinate k over the finite points with c_k >= j (suffix minimum, +inf when
+ *               there is none), [1][k][j] = the largest coordinate k over those with c_k <= j (prefix maximum, -inf when none).
+ * am_nn_grid_bytes(n_points, batch, cells) is the size of ONE allocation that holds frame, slabs, cell_start, order and sorted of
+ * `batch` grids in that order, each array padded to a multiple of 16 bytes; every pointer must be 16-byte aligned.
+ *
+ * BUILDING takes two calls around a sort that is the caller's (any stable sort of out_cell; the Python binding uses torch's):
+ *   am_nn_grid_cells  writes grid.frame and out_cell (batch, n_points) = the cell of every point;
+ *   [caller]          grid.order = the stable argsort of out_cell along the points;
+ *   am_nn_grid_build  reads grid.frame and grid.order, writes grid.sorted, grid.cell_start and grid.slabs.
+ * Both need am_nn_grid_workspace_bytes(n_points, batch, cells) bytes of 16-byte aligned device scratch, whose content on entry is
+ * irrelevant.  No float atomics: extrema go through integer atomics on the order-preserving map of the bit patterns.
+ *
+ * THE SEARCH of a query q (one lane per query; `query_order`, optional, an int32 permutation of the queries (batch stride
+ * query_order_bstride elements, 0 = shared) that says in which order lanes pick queries - pass the cell order of the query cloud and
+ * a wave shares cells; results are always written at the query's own position):
+ *   1. a query with a non-finite coordinate has no finite distance: index -1, d2 = +inf.
+ *   2. its cell is the clamped one: per axis 0 when inv_k == 0 or t = fl(fl(q_k - lo_k) * inv_k) is not >= 0, G - 1 when t >= G,
+ *      else (int)floorf(t).  c_k(.) is monotone (non-decreasing) in the coordinate: it composes monotone roundings.
+ *   3. rings r = 0, 1, ... : all cells at Chebyshev distance r from that cell, inside the grid; every point of them is evaluated with
+ *      the arithmetic above (T = float or double, operands converted first) and the best (d2, index) is kept lexicographically.
+ *   4. after ring r, per axis k and side: high side g = fl_T(slabs[0][k][c_k + r + 1] - q_k), low side g = fl_T(q_k -
+ *      slabs[1][k][c_k - r - 1]); a side whose slab index leaves 0 .. G - 1 is exhausted (g = +inf).
+ *   5. stop when every side is exhausted, or when best < fl_T(g_min * g_min), g_min the smallest of the six; at most G rings.
+ * WHY THIS IS EXACT.  A point p outside the cube of rings 0 .. r has, on some axis k, c_k(p) >= c_k(q) + r + 1 or <= c_k(q) - r - 1.
+ * High side: c_k is monotone and c_k(p) > c_k(q), so p_k > q_k for every such p, hence the slab minimum m satisfies p_k >= m >= q_k;
+ * rounding is monotone, so |fl(q_k - p_k)| = fl(p_k - q_k) >= fl(m - q_k) = g >= 0, then fl(dx dx) >= fl(g g), and a rounded sum of
+ * non-negative terms is no smaller than either term: d2(p) >= fl(g g) >= fl(g_min g_min) > best.  The low side mirrors it.  So no
+ * point outside the cube beats OR TIES the best; nothing rests on where a cell's edge falls after rounding.  Points of the extra
+ * cell have no finite distance and are never the answer of am_nn_search either.
+ *
+ * Every cell_start value, every index of `sorted`, every `order` and `query_order` entry is compared with its bound before it is used
+ * as an address or written as a result; a violation sets a bit of out_flag (device int32[1], zeroed by the call) and the element
+ * concerned is written as "no neighbour" (index -1, d2 +inf; a bad `order` entry as a NaN record in the extra cell; a bad
+ * `query_order` entry names no position and is skipped): a bad grid reports an error and nothing outside the outputs is written.  The status is AM_OK; the caller reads the flag. */
+#define AM_NN_GRID_MAX_CELLS 128
+#define AM_NN_GRID_BAD_ORDER 1         /* am_nn_grid_build: an `order` entry outside [0, n_points) */
+#define AM_NN_GRID_BAD_CELL_START 2    /* am_nn_grid_search: cell_start not ascending inside [0, n_points] */
+#define AM_NN_GRID_BAD_INDEX 4         /* am_nn_grid_search: an index of `sorted` outside [0, n_points) */
+#define AM_NN_GRID_BAD_QUERY_ORDER 8   /* am_nn_grid_search: a `query_order` entry outside [0, n_queries) */
+typedef struct {
+  int64_t n_points;
+  int32_t batch;      /* number of grids; a search of more batch entries than 1 may share ONE grid (batch == 1) */
+  int32_t cells;      /* G */
+  float* frame;
+  float* slabs;
+  int32_t* cell_start;
+  int32_t* order;
+  float* sorted;
+} am_nn_grid;
+typedef struct {
+  const float* points;      /* (batch, n_points, 3) fp32 */
+  int64_t points_bstride;   /* elements; 0 = one cloud for every grid */
+  am_nn_grid grid;
+  int32_t* out_cell;        /* am_nn_grid_cells only: (batch, n_points) */
+  int32_t* out_flag;        /* am_nn_grid_build only */
+  void* workspace;
+  size_t workspace_bytes;
+} am_nn_grid_build_args;
+typedef struct {
+  am_nn_grid grid;
+  const float* queries;     /* (batch, n_queries, 3) fp32 */
+  int64_t n_queries;
+  int64_t queries_bstride;  /* elements; 0 = shared */
+  int32_t batch;
+  int32_t precise;
+  const int32_t* query_order;
+  int64_t query_order_bstride;
+  int32_t* out_index;       /* (batch, n_queries) */
+  void* out_d2;             /* (batch, n_queries) double when precise != 0, else float */
+  int32_t* out_flag;
+} am_nn_grid_search_args;
+size_t am_nn_grid_bytes(int64_t n_points, int batch, int cells);
+size_t am_nn_grid_workspace_bytes(int64_t n_points, int batch, int cells);
+int am_nn_grid_cells(const am_nn_grid_build_args* args, void* stream);
+int am_nn_grid_build(const am_nn_grid_build_args* args, void* stream);
+int am_nn_grid_search(const am_nn_grid_search_args* args, void* stream);
+
 /* Preview rendering (INTEGRATION seam S6; reference actionmesh/render/{renderer,visualizer}.py, PyTorch3D's
  * MeshRasterizer + soft_normal_shading): normal maps of ONE animated mesh - n_frames vertex sets on one topology - seen by
  * n_cameras PerspectiveCameras, every (frame, camera) image of the call in a fixed number of launches.
