@@ -4,8 +4,7 @@
 // fp64, every operation rounded on its own (the file is built with -ffp-contract=off), so codes, counts, vertices and faces are
 // compared bit for bit with a numpy restatement that derives the tables below from the header's rule.
 //
-//   am_dmc_cells       one block per 8 x 8 x 64 tile of points, the tile and its one-point halo on the high sides through LDS as one
-//                      state byte per point (the launch plan of am_iso_classify): per cell its configuration and its double faces
+//   am_dmc_cells       one block per 8 x 8 x 64 tile of points (am_grid.h's tile_walk): per cell its configuration and its double faces
 //   am_dmc_classify    one thread per point: the cell's code (configuration + flip bit) from its own and its six neighbours' double
 //                      faces, its number of patches, and the mask of the axis edges from the point that emit a quad
 //   am_dmc_vertices    one thread per point: an active cell writes the centroids of its patches at vertex_offset[p] + patch
@@ -14,17 +13,13 @@
 // recompute from a two-sided halo of values.  No atomics but the OR into the flag word, no hash table: the order of vertices and
 // faces is fixed by the two prefix sums the caller makes.  No offset, code or index read from memory is used as an address before
 // it has been compared with its bound.
+// From am_grid.h, shared with am_isosurface.hip: the grid and point_state, the tile walk, the index arithmetic of a point and of a
+// cell's corners, the crossing interpolation, the launch arithmetic and the host checks.  From am_geometry.h: vec3 and mesh_vertex.
 #include "am_geometry.h"
-
-#pragma clang fp contract(off)      // the helpers below too, whatever flags the file is built with
+#include "am_grid.h"
 
 namespace {
 
-constexpr int DMC_THREADS = 256;
-constexpr int TILE_I = 8, TILE_J = 8, TILE_K = 64;                         // points of an am_dmc_cells tile; k is the contiguous axis
-constexpr int HALO_I = TILE_I + 1, HALO_J = TILE_J + 1, HALO_K = TILE_K + 1;
-constexpr int HALO_POINTS = HALO_I * HALO_J * HALO_K;
-constexpr int64_t DMC_MAX = ((int64_t)1 << 31) - 1;
 constexpr uint32_t NO_PATCH = 15u;
 
 // [flipped][configuration]: nibble e = the patch of cell edge e (15: the edge does not cross), nibble 12 = the number of patches.
@@ -138,20 +133,6 @@ __device__ const uint8_t DMC_EDGE_ID[8][3] = {{2, 1, 0}, {4, 3, 255}, {6, 255, 5
 // the two corners of cell edge e, a < b, in ascending (a, b)
 __device__ const uint8_t DMC_EDGE[12][2] = {{0, 1}, {0, 2}, {0, 4}, {1, 3}, {1, 5}, {2, 3}, {2, 6}, {3, 7}, {4, 5}, {4, 6}, {5, 7}, {6, 7}};
 
-struct grid_view {
-  int64_t nx, ny, nz;
-  double level;
-  int inside_above;
-};
-
-// bit 0: the value is finite; bit 1: it is finite and inside (am_isosurface.hip's)
-__device__ __forceinline__ uint32_t point_state(float v, double level, int inside_above) {
-  if (!(fabsf(v) <= 3.402823466e+38f)) return 0u;                 // NaN and both infinities fail the comparison
-  const double d = (double)v;
-  const bool in = inside_above ? d > level : d < level;
-  return in ? 3u : 1u;
-}
-
 // the configuration of a cell from the states of its corners: 0 unless the cell is ACTIVE
 __device__ __forceinline__ uint32_t cell_config(const uint32_t (&s)[8]) {
   uint32_t finite = 1u, cfg = 0u;
@@ -169,54 +150,36 @@ __device__ __forceinline__ bool code_valid(uint32_t code) {
   return code <= 511u && cfg != 0u && cfg != 255u && (code < 256u || DMC_DOUBLE[cfg] != 0);
 }
 
-__global__ __launch_bounds__(DMC_THREADS) void dmc_cells_kernel(grid_view g, const float* __restrict__ values,
-                                                                uint8_t* __restrict__ out_config, uint8_t* __restrict__ out_double) {
-  __shared__ uint8_t state[HALO_POINTS];
-  const int64_t i0 = (int64_t)blockIdx.z * TILE_I, j0 = (int64_t)blockIdx.y * TILE_J, k0 = (int64_t)blockIdx.x * TILE_K;
-  for (int e = threadIdx.x; e < HALO_POINTS; e += DMC_THREADS) {
-    const int li = e / (HALO_J * HALO_K), r = e - li * (HALO_J * HALO_K), lj = r / HALO_K, lk = r - lj * HALO_K;
-    const int64_t i = i0 + li, j = j0 + lj, k = k0 + lk;
-    uint32_t s = 0u;                                              // a point outside the grid is "not evaluated": no cell there
-    if (i < g.nx && j < g.ny && k < g.nz) s = point_state(values[(i * g.ny + j) * g.nz + k], g.level, g.inside_above);
-    state[e] = (uint8_t)s;
-  }
-  __syncthreads();
-  const int lk = threadIdx.x % TILE_K, plane = threadIdx.x / TILE_K;
-  const int64_t k = k0 + lk;
-  if (k >= g.nz) return;
-  for (int ij = plane; ij < TILE_I * TILE_J; ij += DMC_THREADS / TILE_K) {
-    const int li = ij / TILE_J, lj = ij - li * TILE_J;
-    const int64_t i = i0 + li, j = j0 + lj;
-    if (i >= g.nx || j >= g.ny) continue;
-    uint32_t s[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) s[m] = state[((li + (m >> 2)) * HALO_J + (lj + ((m >> 1) & 1))) * HALO_K + (lk + (m & 1))];
-    const uint32_t cfg = cell_config(s);
-    const int64_t p = (i * g.ny + j) * g.nz + k;
+__global__ __launch_bounds__(GRID_THREADS) void dmc_cells_kernel(grid_view g, const float* __restrict__ values,
+                                                                 uint8_t* __restrict__ out_config, uint8_t* __restrict__ out_double) {
+  tile_walk(g, values, [=](int64_t p, cell_states c) {
+    const uint32_t cfg = cell_config(c.s);
     out_config[p] = (uint8_t)cfg;
     out_double[p] = DMC_DOUBLE[cfg];
-  }
+  });
 }
 
-__global__ __launch_bounds__(DMC_THREADS) void dmc_classify_kernel(int64_t nx, int64_t ny, int64_t nz, const uint8_t* __restrict__ config,
-                                                                   const uint8_t* __restrict__ dbl, int16_t* __restrict__ out_code,
-                                                                   uint8_t* __restrict__ out_count, uint8_t* __restrict__ out_mask) {
-  const int64_t p = (int64_t)blockIdx.x * DMC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GRID_THREADS) void dmc_classify_kernel(int64_t nx, int64_t ny, int64_t nz, const uint8_t* __restrict__ config,
+                                                                    const uint8_t* __restrict__ dbl, int16_t* __restrict__ out_code,
+                                                                    uint8_t* __restrict__ out_count, uint8_t* __restrict__ out_mask) {
+  const int64_t p = (int64_t)blockIdx.x * GRID_THREADS + threadIdx.x;
   if (p >= nx * ny * nz) return;
   const uint32_t cfg = config[p];
   uint32_t flip = 0u, mask = 0u;
   if (cfg != 0u) {
-    const int64_t idx[3] = {p / (ny * nz), p / nz % ny, p % nz}, n[3] = {nx, ny, nz}, step[3] = {ny * nz, nz, 1};
+    const grid_point at = point_at(p, ny, nz);
+    const grid_steps step = steps_of(ny, nz);
+    const int64_t idx[3] = {at.i, at.j, at.k}, n[3] = {nx, ny, nz};
     const uint32_t d = dbl[p];
     for (int axis = 0; axis < 3 && d != 0u; ++axis) {             // a face is flipped when it is double on both of its sides
-      if ((d >> (2 * axis) & 1u) && idx[axis] >= 1 && (dbl[p - step[axis]] >> (2 * axis + 1) & 1u)) flip = 1u;
-      if ((d >> (2 * axis + 1) & 1u) && idx[axis] + 1 < n[axis] && (dbl[p + step[axis]] >> (2 * axis) & 1u)) flip = 1u;
+      if ((d >> (2 * axis) & 1u) && idx[axis] >= 1 && (dbl[p - step.s[axis]] >> (2 * axis + 1) & 1u)) flip = 1u;
+      if ((d >> (2 * axis + 1) & 1u) && idx[axis] + 1 < n[axis] && (dbl[p + step.s[axis]] >> (2 * axis) & 1u)) flip = 1u;
     }
     for (int axis = 0; axis < 3; ++axis) {
       const int u = (axis + 1) % 3, v = (axis + 2) % 3;
       if (idx[u] < 1 || idx[v] < 1) continue;                     // one of the four cells around the edge does not exist
       if (((cfg ^ (cfg >> (4 >> axis))) & 1u) == 0u) continue;    // corner 000 and the corner along the axis on one side
-      if (config[p - step[u]] != 0 && config[p - step[u] - step[v]] != 0 && config[p - step[v]] != 0) mask |= 1u << axis;
+      if (config[p - step.s[u]] != 0 && config[p - step.s[u] - step.s[v]] != 0 && config[p - step.s[v]] != 0) mask |= 1u << axis;
     }
   }
   out_code[p] = (int16_t)(cfg | flip << 8);
@@ -224,27 +187,27 @@ __global__ __launch_bounds__(DMC_THREADS) void dmc_classify_kernel(int64_t nx, i
   out_mask[p] = (uint8_t)mask;
 }
 
-__global__ __launch_bounds__(DMC_THREADS) void dmc_vertices_kernel(grid_view g, const float* __restrict__ values,
-                                                                   const int16_t* __restrict__ code,
-                                                                   const int64_t* __restrict__ vertex_offset, int64_t n_vertices,
-                                                                   double ox, double oy, double oz, double sx, double sy, double sz,
-                                                                   float* __restrict__ out_vertices, int32_t* flag) {
+__global__ __launch_bounds__(GRID_THREADS) void dmc_vertices_kernel(grid_view g, const float* __restrict__ values,
+                                                                    const int16_t* __restrict__ code,
+                                                                    const int64_t* __restrict__ vertex_offset, int64_t n_vertices,
+                                                                    double ox, double oy, double oz, double sx, double sy, double sz,
+                                                                    float* __restrict__ out_vertices, int32_t* flag) {
 #pragma clang fp contract(off)
-  const int64_t p = (int64_t)blockIdx.x * DMC_THREADS + threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * GRID_THREADS + threadIdx.x;
   if (p >= g.nx * g.ny * g.nz) return;
   const uint32_t c = (uint16_t)code[p];
   if (c == 0u) return;
-  const int64_t k = p % g.nz, ij = p / g.nz, j = ij % g.ny, i = ij / g.ny;
-  if (!code_valid(c) || i + 1 >= g.nx || j + 1 >= g.ny || k + 1 >= g.nz) {   // no such code, or a code where no cell starts
+  const grid_point at = point_at(p, g.ny, g.nz);
+  if (!code_valid(c) || at.i + 1 >= g.nx || at.j + 1 >= g.ny || at.k + 1 >= g.nz) {   // no such code, or a code where no cell starts
     atomicOr(flag, AM_DMC_BAD_CODE);
     return;
   }
-  const int64_t step[3] = {g.ny * g.nz, g.nz, 1};
+  const grid_steps step = steps_of(g.ny, g.nz);
   double value[8];
   uint32_t s[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
-    const float v = values[p + (m >> 2) * step[0] + ((m >> 1) & 1) * step[1] + (m & 1) * step[2]];
+    const float v = values[cell_corner(p, step, m)];
     value[m] = (double)v;
     s[m] = point_state(v, g.level, g.inside_above);
   }
@@ -260,7 +223,7 @@ __global__ __launch_bounds__(DMC_THREADS) void dmc_vertices_kernel(grid_view g, 
     return;
   }
   const double org[3] = {ox, oy, oz}, sp[3] = {sx, sy, sz};
-  const int64_t idx[3] = {i, j, k};
+  const int64_t idx[3] = {at.i, at.j, at.k};
   for (int64_t q = 0; q < patches; ++q) {
     double sum[3] = {0.0, 0.0, 0.0};
     int number = 0;
@@ -268,14 +231,10 @@ __global__ __launch_bounds__(DMC_THREADS) void dmc_vertices_kernel(grid_view g, 
     for (int e = 0; e < 12; ++e) {                                // ascending edge id: the order of the sum
       if ((int64_t)(table >> (4 * e) & 15u) != q) continue;
       const int a = DMC_EDGE[e][0], b = DMC_EDGE[e][1];
-      const double t = (g.level - value[a]) / (value[b] - value[a]);
       for (int x = 0; x < 3; ++x) {
         const double pa = org[x] + (double)(idx[x] + (a >> (2 - x) & 1)) * sp[x];
         const double pb = org[x] + (double)(idx[x] + (b >> (2 - x) & 1)) * sp[x];
-        const double d = pb - pa;
-        const double td = t * d;
-        const double crossing = pa + td;
-        sum[x] = sum[x] + crossing;
+        sum[x] = sum[x] + crossing(g.level, value[a], value[b], pa, pb);
       }
       ++number;
     }
@@ -283,18 +242,20 @@ __global__ __launch_bounds__(DMC_THREADS) void dmc_vertices_kernel(grid_view g, 
   }
 }
 
-__global__ __launch_bounds__(DMC_THREADS) void dmc_triangles_kernel(int64_t nx, int64_t ny, int64_t nz, const int16_t* __restrict__ code,
-                                                                    const uint8_t* __restrict__ edge_mask,
-                                                                    const int64_t* __restrict__ vertex_offset,
-                                                                    const int64_t* __restrict__ tri_offset,
-                                                                    const float* __restrict__ vertices, int64_t n_vertices,
-                                                                    int64_t n_triangles, int32_t* __restrict__ out_faces, int32_t* flag) {
+__global__ __launch_bounds__(GRID_THREADS) void dmc_triangles_kernel(int64_t nx, int64_t ny, int64_t nz, const int16_t* __restrict__ code,
+                                                                     const uint8_t* __restrict__ edge_mask,
+                                                                     const int64_t* __restrict__ vertex_offset,
+                                                                     const int64_t* __restrict__ tri_offset,
+                                                                     const float* __restrict__ vertices, int64_t n_vertices,
+                                                                     int64_t n_triangles, int32_t* __restrict__ out_faces, int32_t* flag) {
 #pragma clang fp contract(off)
-  const int64_t p = (int64_t)blockIdx.x * DMC_THREADS + threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * GRID_THREADS + threadIdx.x;
   if (p >= nx * ny * nz) return;
   const uint32_t mk = edge_mask[p];
   if (mk == 0u) return;
-  const int64_t idx[3] = {p / (ny * nz), p / nz % ny, p % nz}, step[3] = {ny * nz, nz, 1};
+  const grid_point at = point_at(p, ny, nz);
+  const grid_steps step = steps_of(ny, nz);
+  const int64_t idx[3] = {at.i, at.j, at.k};
   if (mk > 7u || idx[0] + 1 >= nx || idx[1] + 1 >= ny || idx[2] + 1 >= nz) {   // no such mask, or a mask where no cell starts
     atomicOr(flag, AM_DMC_BAD_CODE);
     return;
@@ -317,7 +278,7 @@ __global__ __launch_bounds__(DMC_THREADS) void dmc_triangles_kernel(int64_t nx, 
     bool ok = true, lower_inside = false;
     for (int r = 0; r < 4; ++r) {                                 // around the edge: p, p - e_u, p - e_u - e_v, p - e_v
       const int du = r == 1 || r == 2, dv = r >= 2;
-      const int64_t cell = p - du * step[u] - dv * step[v];
+      const int64_t cell = p - du * step.s[u] - dv * step.s[v];
       const uint32_t c = (uint16_t)code[cell];
       if (!code_valid(c)) {
         atomicOr(flag, AM_DMC_BAD_CODE);
@@ -356,21 +317,6 @@ __global__ __launch_bounds__(DMC_THREADS) void dmc_triangles_kernel(int64_t nx, 
   }
 }
 
-unsigned dmc_blocks(int64_t n) { return (unsigned)((n + DMC_THREADS - 1) / DMC_THREADS); }
-
-int check_grid(const char* who, int64_t nx, int64_t ny, int64_t nz) {
-  AM_CHECK(nx >= 2 && ny >= 2 && nz >= 2, "%s: a grid of %lld x %lld x %lld points; every axis needs at least 2", who, (long long)nx,
-           (long long)ny, (long long)nz);
-  AM_CHECK(nx <= DMC_MAX && ny <= DMC_MAX && nz <= DMC_MAX && nx * ny <= DMC_MAX && nx * ny * nz <= DMC_MAX,
-           "%s: a grid of %lld x %lld x %lld points has more than 2^31 - 1", who, (long long)nx, (long long)ny, (long long)nz);
-  return AM_OK;
-}
-
-int check_level(const char* who, double level) {
-  AM_CHECK(level == level && level - level == 0.0, "%s: the level is not finite", who);
-  return AM_OK;
-}
-
 }  // namespace
 
 extern "C" int am_dmc_cells(const am_dmc_cells_args* a, void* stream) {
@@ -378,11 +324,10 @@ extern "C" int am_dmc_cells(const am_dmc_cells_args* a, void* stream) {
   AM_TRY(check_grid("am_dmc_cells", a->nx, a->ny, a->nz));
   AM_TRY(check_level("am_dmc_cells", a->level));
   AM_CHECK(a->values && a->out_config && a->out_double, "am_dmc_cells: null pointer");
-  const int64_t bi = (a->nx + TILE_I - 1) / TILE_I, bj = (a->ny + TILE_J - 1) / TILE_J, bk = (a->nz + TILE_K - 1) / TILE_K;
-  AM_CHECK(bi <= 65535 && bj <= 65535, "am_dmc_cells: more than 65535 tiles along an axis");
+  dim3 blocks;
+  AM_TRY(tile_blocks("am_dmc_cells", a->nx, a->ny, a->nz, blocks));
   const grid_view g = {a->nx, a->ny, a->nz, a->level, a->inside_above != 0};
-  hipLaunchKernelGGL(dmc_cells_kernel, dim3((unsigned)bk, (unsigned)bj, (unsigned)bi), dim3(DMC_THREADS), 0, (hipStream_t)stream, g,
-                     a->values, a->out_config, a->out_double);
+  hipLaunchKernelGGL(dmc_cells_kernel, blocks, dim3(GRID_THREADS), 0, (hipStream_t)stream, g, a->values, a->out_config, a->out_double);
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
@@ -391,7 +336,7 @@ extern "C" int am_dmc_classify(const am_dmc_classify_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_dmc_classify: null arguments");
   AM_TRY(check_grid("am_dmc_classify", a->nx, a->ny, a->nz));
   AM_CHECK(a->config && a->double_faces && a->out_code && a->out_count && a->out_edge_mask, "am_dmc_classify: null pointer");
-  hipLaunchKernelGGL(dmc_classify_kernel, dim3(dmc_blocks(a->nx * a->ny * a->nz)), dim3(DMC_THREADS), 0, (hipStream_t)stream, a->nx,
+  hipLaunchKernelGGL(dmc_classify_kernel, dim3(grid_blocks(a->nx * a->ny * a->nz)), dim3(GRID_THREADS), 0, (hipStream_t)stream, a->nx,
                      a->ny, a->nz, a->config, a->double_faces, a->out_code, a->out_count, a->out_edge_mask);
   AM_HIP(hipGetLastError());
   return AM_OK;
@@ -401,12 +346,12 @@ extern "C" int am_dmc_vertices(const am_dmc_vertices_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_dmc_vertices: null arguments");
   AM_TRY(check_grid("am_dmc_vertices", a->nx, a->ny, a->nz));
   AM_TRY(check_level("am_dmc_vertices", a->level));
-  AM_CHECK(a->n_vertices >= 1 && a->n_vertices <= DMC_MAX, "am_dmc_vertices: %lld vertices outside 1 .. 2^31 - 1", (long long)a->n_vertices);
+  AM_TRY(check_count("am_dmc_vertices", "vertices", a->n_vertices));
   AM_CHECK(a->values && a->code && a->vertex_offset && a->out_vertices && a->out_flag, "am_dmc_vertices: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const grid_view g = {a->nx, a->ny, a->nz, a->level, a->inside_above != 0};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(dmc_vertices_kernel, dim3(dmc_blocks(a->nx * a->ny * a->nz)), dim3(DMC_THREADS), 0, st, g, a->values, a->code,
+  hipLaunchKernelGGL(dmc_vertices_kernel, dim3(grid_blocks(a->nx * a->ny * a->nz)), dim3(GRID_THREADS), 0, st, g, a->values, a->code,
                      a->vertex_offset, a->n_vertices, a->origin[0], a->origin[1], a->origin[2], a->spacing[0], a->spacing[1],
                      a->spacing[2], a->out_vertices, a->out_flag);
   AM_HIP(hipGetLastError());
@@ -416,14 +361,13 @@ extern "C" int am_dmc_vertices(const am_dmc_vertices_args* a, void* stream) {
 extern "C" int am_dmc_triangles(const am_dmc_triangles_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_dmc_triangles: null arguments");
   AM_TRY(check_grid("am_dmc_triangles", a->nx, a->ny, a->nz));
-  AM_CHECK(a->n_vertices >= 1 && a->n_vertices <= DMC_MAX, "am_dmc_triangles: %lld vertices outside 1 .. 2^31 - 1", (long long)a->n_vertices);
-  AM_CHECK(a->n_triangles >= 1 && a->n_triangles <= DMC_MAX, "am_dmc_triangles: %lld triangles outside 1 .. 2^31 - 1",
-           (long long)a->n_triangles);
+  AM_TRY(check_count("am_dmc_triangles", "vertices", a->n_vertices));
+  AM_TRY(check_count("am_dmc_triangles", "triangles", a->n_triangles));
   AM_CHECK(a->code && a->edge_mask && a->vertex_offset && a->tri_offset && a->vertices && a->out_faces && a->out_flag,
            "am_dmc_triangles: null pointer");
   hipStream_t st = (hipStream_t)stream;
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(dmc_triangles_kernel, dim3(dmc_blocks(a->nx * a->ny * a->nz)), dim3(DMC_THREADS), 0, st, a->nx, a->ny, a->nz, a->code,
+  hipLaunchKernelGGL(dmc_triangles_kernel, dim3(grid_blocks(a->nx * a->ny * a->nz)), dim3(GRID_THREADS), 0, st, a->nx, a->ny, a->nz, a->code,
                      a->edge_mask, a->vertex_offset, a->tri_offset, a->vertices, a->n_vertices, a->n_triangles, a->out_faces, a->out_flag);
   AM_HIP(hipGetLastError());
   return AM_OK;

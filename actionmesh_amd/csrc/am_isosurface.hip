@@ -3,25 +3,17 @@
 // include/actionmesh_amd.h's; the interpolation is fp64, every operation rounded on its own (the file is built with
 // -ffp-contract=off), so masks, counts, vertices and faces are compared bit for bit with a numpy restatement.
 //
-//   am_iso_classify    one block per 8 x 8 x 64 tile of points: the tile and its one-point halo on the high sides go through LDS as
-//                      one state byte per point (finite, inside), so every value is fetched about once (9 * 9 * 65 / 4096 = 1.29
-//                      with the halo, most of which the L2 serves); per point the mask of crossing edges that start there, per cell
-//                      the number of triangles
+//   am_iso_classify    one block per 8 x 8 x 64 tile of points (am_grid.h's tile_walk): per point the mask of crossing edges that
+//                      start there, per cell the number of triangles
 //   am_iso_vertices    one thread per point: a point with a non-zero mask writes its vertices at vertex_offset[p] + rank of the bit
 //   am_iso_triangles   one thread per point: a cell with a non-zero count writes its faces at tri_offset[p]
 // No atomics but the OR into the flag word, no hash table: the order of vertices and faces is fixed by the two prefix sums the caller
 // makes.  No offset or index read from memory is used as an address before it has been compared with its bound.
-#include "am_common.h"
-
-#pragma clang fp contract(off)      // the helpers below too, whatever flags the file is built with
+// From am_grid.h, shared with am_dualcubes.hip: the grid and point_state, the tile walk, the index arithmetic of a point and of a
+// cell's corners, the crossing interpolation, the launch arithmetic and the host checks.
+#include "am_grid.h"
 
 namespace {
-
-constexpr int ISO_THREADS = 256;
-constexpr int TILE_I = 8, TILE_J = 8, TILE_K = 64;                         // points of a classify tile; k is the contiguous axis
-constexpr int HALO_I = TILE_I + 1, HALO_J = TILE_J + 1, HALO_K = TILE_K + 1;
-constexpr int HALO_POINTS = HALO_I * HALO_J * HALO_K;
-constexpr int64_t ISO_MAX = ((int64_t)1 << 31) - 1;
 
 // the corners c0 .. c3 of Kuhn tetrahedron t as offset codes (di << 2 | dj << 1 | dk): c0 = 000, c1 = c0 + e_pi0, c2 = c1 + e_pi1,
 // c3 = 111, for the t-th permutation pi of the axes (i, j, k) in lexicographic order
@@ -42,20 +34,6 @@ __constant__ uint8_t ISO_CASE[2][16][6] = {
      {3, 7, 11, 255, 255, 255},      {1, 7, 11, 1, 11, 2},     {1, 6, 11, 1, 11, 3},     {2, 6, 11, 255, 255, 255},
      {2, 3, 7, 2, 7, 6},             {1, 7, 6, 255, 255, 255}, {1, 2, 3, 255, 255, 255}, {255, 255, 255, 255, 255, 255}}};
 
-struct grid_view {
-  int64_t nx, ny, nz;
-  double level;
-  int inside_above;
-};
-
-// bit 0: the value is finite; bit 1: it is finite and inside
-__device__ __forceinline__ uint32_t point_state(float v, double level, int inside_above) {
-  if (!(fabsf(v) <= 3.402823466e+38f)) return 0u;                 // NaN and both infinities fail the comparison
-  const double d = (double)v;
-  const bool in = inside_above ? d > level : d < level;
-  return in ? 3u : 1u;
-}
-
 // the triangles of one tetrahedron from the states of its corners: 0 with a non-finite corner
 __device__ __forceinline__ uint32_t tet_case(const uint32_t (&s)[8], int t, bool& finite) {
   const uint32_t a = s[0], b = s[ISO_CORNER[t][1]], c = s[ISO_CORNER[t][2]], d = s[7];
@@ -67,52 +45,32 @@ __device__ __forceinline__ uint32_t case_triangles(uint32_t cs) {
   return n == 0 || n == 4 ? 0u : (n == 2 ? 2u : 1u);
 }
 
-__global__ __launch_bounds__(ISO_THREADS) void iso_classify_kernel(grid_view g, const float* __restrict__ values,
-                                                                   uint8_t* __restrict__ out_mask, uint8_t* __restrict__ out_count) {
-  __shared__ uint8_t state[HALO_POINTS];
-  const int64_t i0 = (int64_t)blockIdx.z * TILE_I, j0 = (int64_t)blockIdx.y * TILE_J, k0 = (int64_t)blockIdx.x * TILE_K;
-  for (int e = threadIdx.x; e < HALO_POINTS; e += ISO_THREADS) {
-    const int li = e / (HALO_J * HALO_K), r = e - li * (HALO_J * HALO_K), lj = r / HALO_K, lk = r - lj * HALO_K;
-    const int64_t i = i0 + li, j = j0 + lj, k = k0 + lk;
-    uint32_t s = 0u;                                              // a point outside the grid is "not evaluated"
-    if (i < g.nx && j < g.ny && k < g.nz) s = point_state(values[(i * g.ny + j) * g.nz + k], g.level, g.inside_above);
-    state[e] = (uint8_t)s;
-  }
-  __syncthreads();
-  const int lk = threadIdx.x % TILE_K, plane = threadIdx.x / TILE_K;
-  const int64_t k = k0 + lk;
-  if (k >= g.nz) return;
-  for (int ij = plane; ij < TILE_I * TILE_J; ij += ISO_THREADS / TILE_K) {
-    const int li = ij / TILE_J, lj = ij - li * TILE_J;
-    const int64_t i = i0 + li, j = j0 + lj;
-    if (i >= g.nx || j >= g.ny) continue;
-    uint32_t s[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) s[m] = state[((li + (m >> 2)) * HALO_J + (lj + ((m >> 1) & 1))) * HALO_K + (lk + (m & 1))];
+__global__ __launch_bounds__(GRID_THREADS) void iso_classify_kernel(grid_view g, const float* __restrict__ values,
+                                                                    uint8_t* __restrict__ out_mask, uint8_t* __restrict__ out_count) {
+  tile_walk(g, values, [=](int64_t p, cell_states c) {
     uint32_t mask = 0u;
 #pragma unroll
     for (int m = 1; m < 8; ++m)
-      if ((s[0] & s[m] & 1u) && ((s[0] ^ s[m]) & 2u)) mask |= 1u << (m - 1);
+      if ((c.s[0] & c.s[m] & 1u) && ((c.s[0] ^ c.s[m]) & 2u)) mask |= 1u << (m - 1);
     uint32_t count = 0u;
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
       bool finite;
-      const uint32_t cs = tet_case(s, t, finite);
+      const uint32_t cs = tet_case(c.s, t, finite);
       if (finite) count += case_triangles(cs);
     }
-    const int64_t p = (i * g.ny + j) * g.nz + k;
     out_mask[p] = (uint8_t)mask;
     out_count[p] = (uint8_t)count;
-  }
+  });
 }
 
-__global__ __launch_bounds__(ISO_THREADS) void iso_vertices_kernel(grid_view g, const float* __restrict__ values,
-                                                                   const uint8_t* __restrict__ mask,
-                                                                   const int64_t* __restrict__ vertex_offset, int64_t n_vertices,
-                                                                   double ox, double oy, double oz, double sx, double sy, double sz,
-                                                                   float* __restrict__ out_vertices, int32_t* flag) {
+__global__ __launch_bounds__(GRID_THREADS) void iso_vertices_kernel(grid_view g, const float* __restrict__ values,
+                                                                    const uint8_t* __restrict__ mask,
+                                                                    const int64_t* __restrict__ vertex_offset, int64_t n_vertices,
+                                                                    double ox, double oy, double oz, double sx, double sy, double sz,
+                                                                    float* __restrict__ out_vertices, int32_t* flag) {
 #pragma clang fp contract(off)
-  const int64_t p = (int64_t)blockIdx.x * ISO_THREADS + threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * GRID_THREADS + threadIdx.x;
   if (p >= g.nx * g.ny * g.nz) return;
   const uint32_t mk = mask[p];
   if (mk == 0u) return;
@@ -121,40 +79,35 @@ __global__ __launch_bounds__(ISO_THREADS) void iso_vertices_kernel(grid_view g, 
     atomicOr(flag, mk > 127u ? AM_ISO_BAD_TABLE : AM_ISO_BAD_VERTEX_OFFSET);
     return;
   }
-  const int64_t k = p % g.nz, ij = p / g.nz, j = ij % g.ny, i = ij / g.ny;
+  const grid_point at = point_at(p, g.ny, g.nz);
   const double va = (double)values[p];
-  const double pa[3] = {ox + (double)i * sx, oy + (double)j * sy, oz + (double)k * sz};
+  const double pa[3] = {ox + (double)at.i * sx, oy + (double)at.j * sy, oz + (double)at.k * sz};
   int rank = 0;
   for (int m = 1; m < 8; ++m) {
     if (!(mk >> (m - 1) & 1u)) continue;
     const int64_t slot = base + rank++;
-    const int64_t bi = i + (m >> 2), bj = j + ((m >> 1) & 1), bk = k + (m & 1);
+    const int64_t bi = at.i + (m >> 2), bj = at.j + ((m >> 1) & 1), bk = at.k + (m & 1);
     if (bi >= g.nx || bj >= g.ny || bk >= g.nz) {               // the mask names an edge that leaves the grid
       atomicOr(flag, AM_ISO_BAD_TABLE);
       continue;
     }
     const double vb = (double)values[(bi * g.ny + bj) * g.nz + bk];
-    const double t = (g.level - va) / (vb - va);
     const double pb[3] = {ox + (double)bi * sx, oy + (double)bj * sy, oz + (double)bk * sz};
-    for (int c = 0; c < 3; ++c) {
-      const double d = pb[c] - pa[c];
-      const double td = t * d;
-      out_vertices[slot * 3 + c] = (float)(pa[c] + td);
-    }
+    for (int c = 0; c < 3; ++c) out_vertices[slot * 3 + c] = (float)crossing(g.level, va, vb, pa[c], pb[c]);
   }
 }
 
-__global__ __launch_bounds__(ISO_THREADS) void iso_triangles_kernel(grid_view g, const float* __restrict__ values,
-                                                                    const uint8_t* __restrict__ mask, const uint8_t* __restrict__ count,
-                                                                    const int64_t* __restrict__ vertex_offset,
-                                                                    const int64_t* __restrict__ tri_offset, int64_t n_vertices,
-                                                                    int64_t n_triangles, int32_t* __restrict__ out_faces, int32_t* flag) {
-  const int64_t p = (int64_t)blockIdx.x * ISO_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GRID_THREADS) void iso_triangles_kernel(grid_view g, const float* __restrict__ values,
+                                                                     const uint8_t* __restrict__ mask, const uint8_t* __restrict__ count,
+                                                                     const int64_t* __restrict__ vertex_offset,
+                                                                     const int64_t* __restrict__ tri_offset, int64_t n_vertices,
+                                                                     int64_t n_triangles, int32_t* __restrict__ out_faces, int32_t* flag) {
+  const int64_t p = (int64_t)blockIdx.x * GRID_THREADS + threadIdx.x;
   if (p >= g.nx * g.ny * g.nz) return;
   const int64_t want = count[p];
   if (want == 0) return;
-  const int64_t k = p % g.nz, ij = p / g.nz, j = ij % g.ny, i = ij / g.ny;
-  if (want > 12 || i + 1 >= g.nx || j + 1 >= g.ny || k + 1 >= g.nz) {      // a count where no cell starts
+  const grid_point at = point_at(p, g.ny, g.nz);
+  if (want > 12 || at.i + 1 >= g.nx || at.j + 1 >= g.ny || at.k + 1 >= g.nz) {      // a count where no cell starts
     atomicOr(flag, AM_ISO_BAD_TABLE);
     return;
   }
@@ -163,12 +116,12 @@ __global__ __launch_bounds__(ISO_THREADS) void iso_triangles_kernel(grid_view g,
     atomicOr(flag, AM_ISO_BAD_TRI_OFFSET);
     return;
   }
-  const int64_t step[3] = {g.ny * g.nz, g.nz, 1};
+  const grid_steps step = steps_of(g.ny, g.nz);
   uint32_t s[8];
   int64_t corner[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
-    corner[m] = p + (m >> 2) * step[0] + ((m >> 1) & 1) * step[1] + (m & 1) * step[2];
+    corner[m] = cell_corner(p, step, m);
     s[m] = point_state(values[corner[m]], g.level, g.inside_above);
   }
   int64_t written = 0;
@@ -213,21 +166,6 @@ __global__ __launch_bounds__(ISO_THREADS) void iso_triangles_kernel(grid_view g,
   if (bad_table || written != want) atomicOr(flag, AM_ISO_BAD_TABLE);
 }
 
-unsigned iso_blocks(int64_t n) { return (unsigned)((n + ISO_THREADS - 1) / ISO_THREADS); }
-
-int check_grid(const char* who, int64_t nx, int64_t ny, int64_t nz) {
-  AM_CHECK(nx >= 2 && ny >= 2 && nz >= 2, "%s: a grid of %lld x %lld x %lld points; every axis needs at least 2", who, (long long)nx,
-           (long long)ny, (long long)nz);
-  AM_CHECK(nx <= ISO_MAX && ny <= ISO_MAX && nz <= ISO_MAX && nx * ny <= ISO_MAX && nx * ny * nz <= ISO_MAX,
-           "%s: a grid of %lld x %lld x %lld points has more than 2^31 - 1", who, (long long)nx, (long long)ny, (long long)nz);
-  return AM_OK;
-}
-
-int check_level(const char* who, double level) {
-  AM_CHECK(level == level && level - level == 0.0, "%s: the level is not finite", who);
-  return AM_OK;
-}
-
 }  // namespace
 
 extern "C" int am_iso_classify(const am_iso_classify_args* a, void* stream) {
@@ -235,11 +173,10 @@ extern "C" int am_iso_classify(const am_iso_classify_args* a, void* stream) {
   AM_TRY(check_grid("am_iso_classify", a->nx, a->ny, a->nz));
   AM_TRY(check_level("am_iso_classify", a->level));
   AM_CHECK(a->values && a->out_mask && a->out_count, "am_iso_classify: null pointer");
-  const int64_t bi = (a->nx + TILE_I - 1) / TILE_I, bj = (a->ny + TILE_J - 1) / TILE_J, bk = (a->nz + TILE_K - 1) / TILE_K;
-  AM_CHECK(bi <= 65535 && bj <= 65535, "am_iso_classify: more than 65535 tiles along an axis");
+  dim3 blocks;
+  AM_TRY(tile_blocks("am_iso_classify", a->nx, a->ny, a->nz, blocks));
   const grid_view g = {a->nx, a->ny, a->nz, a->level, a->inside_above != 0};
-  hipLaunchKernelGGL(iso_classify_kernel, dim3((unsigned)bk, (unsigned)bj, (unsigned)bi), dim3(ISO_THREADS), 0, (hipStream_t)stream, g,
-                     a->values, a->out_mask, a->out_count);
+  hipLaunchKernelGGL(iso_classify_kernel, blocks, dim3(GRID_THREADS), 0, (hipStream_t)stream, g, a->values, a->out_mask, a->out_count);
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
@@ -248,12 +185,12 @@ extern "C" int am_iso_vertices(const am_iso_vertices_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_iso_vertices: null arguments");
   AM_TRY(check_grid("am_iso_vertices", a->nx, a->ny, a->nz));
   AM_TRY(check_level("am_iso_vertices", a->level));
-  AM_CHECK(a->n_vertices >= 1 && a->n_vertices <= ISO_MAX, "am_iso_vertices: %lld vertices outside 1 .. 2^31 - 1", (long long)a->n_vertices);
+  AM_TRY(check_count("am_iso_vertices", "vertices", a->n_vertices));
   AM_CHECK(a->values && a->mask && a->vertex_offset && a->out_vertices && a->out_flag, "am_iso_vertices: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const grid_view g = {a->nx, a->ny, a->nz, a->level, 1};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(iso_vertices_kernel, dim3(iso_blocks(a->nx * a->ny * a->nz)), dim3(ISO_THREADS), 0, st, g, a->values, a->mask,
+  hipLaunchKernelGGL(iso_vertices_kernel, dim3(grid_blocks(a->nx * a->ny * a->nz)), dim3(GRID_THREADS), 0, st, g, a->values, a->mask,
                      a->vertex_offset, a->n_vertices, a->origin[0], a->origin[1], a->origin[2], a->spacing[0], a->spacing[1],
                      a->spacing[2], a->out_vertices, a->out_flag);
   AM_HIP(hipGetLastError());
@@ -264,15 +201,14 @@ extern "C" int am_iso_triangles(const am_iso_triangles_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_iso_triangles: null arguments");
   AM_TRY(check_grid("am_iso_triangles", a->nx, a->ny, a->nz));
   AM_TRY(check_level("am_iso_triangles", a->level));
-  AM_CHECK(a->n_vertices >= 1 && a->n_vertices <= ISO_MAX, "am_iso_triangles: %lld vertices outside 1 .. 2^31 - 1", (long long)a->n_vertices);
-  AM_CHECK(a->n_triangles >= 1 && a->n_triangles <= ISO_MAX, "am_iso_triangles: %lld triangles outside 1 .. 2^31 - 1",
-           (long long)a->n_triangles);
+  AM_TRY(check_count("am_iso_triangles", "vertices", a->n_vertices));
+  AM_TRY(check_count("am_iso_triangles", "triangles", a->n_triangles));
   AM_CHECK(a->values && a->mask && a->count && a->vertex_offset && a->tri_offset && a->out_faces && a->out_flag,
            "am_iso_triangles: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const grid_view g = {a->nx, a->ny, a->nz, a->level, a->inside_above != 0};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(iso_triangles_kernel, dim3(iso_blocks(a->nx * a->ny * a->nz)), dim3(ISO_THREADS), 0, st, g, a->values, a->mask,
+  hipLaunchKernelGGL(iso_triangles_kernel, dim3(grid_blocks(a->nx * a->ny * a->nz)), dim3(GRID_THREADS), 0, st, g, a->values, a->mask,
                      a->count, a->vertex_offset, a->tri_offset, a->n_vertices, a->n_triangles, a->out_faces, a->out_flag);
   AM_HIP(hipGetLastError());
   return AM_OK;

@@ -93,15 +93,21 @@ def _inside_above(inside) -> bool:
     return inside == "above"
 
 
+def _bounds(who: str, bounds) -> list:
+    """The box (x0, y0, z0, x1, y1, z1) as six floats; one number b means (-b, -b, -b, b, b, b)."""
+    b = [float(x) for x in ((-bounds,) * 3 + (bounds,) * 3 if isinstance(bounds, (int, float)) else bounds)]
+    if len(b) != 6:
+        raise ValueError(f"{who}: bounds are (x0, y0, z0, x1, y1, z1), got {len(b)} numbers")
+    return b
+
+
 def _frame(shape, bounds, origin, spacing):
     """(origin, spacing) as two tuples of three floats: given directly, or from bounds (x0, y0, z0, x1, y1, z1) - the first and the
     last point of every axis -, or the index frame."""
     if bounds is not None:
         if origin is not None or spacing is not None:
             raise ValueError("extract_isosurface: give bounds or origin / spacing, not both")
-        b = [float(x) for x in ((-bounds,) * 3 + (bounds,) * 3 if isinstance(bounds, (int, float)) else bounds)]
-        if len(b) != 6:
-            raise ValueError(f"extract_isosurface: bounds are (x0, y0, z0, x1, y1, z1), got {len(b)} numbers")
+        b = _bounds("extract_isosurface", bounds)
         return tuple(b[:3]), tuple((b[3 + c] - b[c]) / (shape[c] - 1) for c in range(3))
     origin = (0.0, 0.0, 0.0) if origin is None else tuple(float(x) for x in origin)
     spacing = (1.0, 1.0, 1.0) if spacing is None else tuple(float(x) for x in spacing)
@@ -112,6 +118,21 @@ def _frame(shape, bounds, origin, spacing):
 
 def _empty(dev):
     return torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev)
+
+
+def _sized(vertex_counts: torch.Tensor, tri_counts: torch.Tensor, shape):
+    """The middle of both methods, from the flat per-point numbers of vertices and of triangles (integers; summed in int64): the two
+    prefix sums and the ONE read of their totals; more than MAX_ITEMS of either raises.  None where the surface does not cross the grid,
+    else (n_vertices, n_triangles, the two exclusive offsets as int64 `shape`, the (2,) int32 flag words of the kernels that follow)."""
+    vertex_end, tri_end = torch.cumsum(vertex_counts, 0, dtype=torch.int64), torch.cumsum(tri_counts, 0, dtype=torch.int64)
+    n_vertices, n_triangles = torch.stack((vertex_end[-1], tri_end[-1])).tolist()              # the read that sizes the outputs
+    if n_vertices > MAX_ITEMS or n_triangles > MAX_ITEMS:
+        raise ValueError(f"extract_isosurface: {n_vertices} vertices and {n_triangles} triangles; more than 2^31 - 1 of either is "
+                         "not supported")
+    if n_vertices == 0 or n_triangles == 0:
+        return None
+    flags = torch.zeros((2,), dtype=torch.int32, device=vertex_counts.device)
+    return n_vertices, n_triangles, (vertex_end - vertex_counts).view(shape), (tri_end - tri_counts).view(shape), flags
 
 
 def _used_vertices_only(vertices, faces, flags, n_vertices: int, flag_message):
@@ -154,15 +175,10 @@ def extract_isosurface(values: torch.Tensor, level: float = 0.0, bounds=None, or
         return _extract_dual(values, level, above, origin, spacing, dual_backend)
     mask, count = backend.classify(values, level, above)
     crossings = torch.tensor(_POPCOUNT, dtype=torch.int64, device=dev)[mask.reshape(-1).long()]
-    vertex_end, tri_end = torch.cumsum(crossings, 0), torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
-    n_vertices, n_triangles = torch.stack((vertex_end[-1], tri_end[-1])).tolist()              # the read that sizes the outputs
-    if n_vertices > MAX_ITEMS or n_triangles > MAX_ITEMS:
-        raise ValueError(f"extract_isosurface: {n_vertices} vertices and {n_triangles} triangles; more than 2^31 - 1 of either is "
-                         "not supported")
-    if n_vertices == 0 or n_triangles == 0:
+    sized = _sized(crossings, count.reshape(-1), values.shape)
+    if sized is None:
         return _empty(dev)
-    vertex_offset, tri_offset = (vertex_end - crossings).view(values.shape), (tri_end - count.reshape(-1)).view(values.shape)
-    flags = torch.zeros((2,), dtype=torch.int32, device=dev)
+    n_vertices, n_triangles, vertex_offset, tri_offset, flags = sized
     vertices = backend.vertices(values, mask, vertex_offset, n_vertices, origin, spacing, level, flag=flags[0:1])
     faces = backend.triangles(values, mask, count, vertex_offset, tri_offset, n_vertices, n_triangles, level, above, flag=flags[1:2])
     return _used_vertices_only(vertices, faces, flags, n_vertices, ops.iso_flag_message)
@@ -174,15 +190,10 @@ def _extract_dual(values: torch.Tensor, level: float, above: bool, origin, spaci
     config, double = backend.cells(values, level, above)
     code, count, edge_mask = backend.classify(config, double)
     triangles = 2 * torch.tensor(_POPCOUNT[:8], dtype=torch.int64, device=dev)[edge_mask.reshape(-1).long().clamp_(max=7)]
-    vertex_end, tri_end = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64), torch.cumsum(triangles, 0)
-    n_vertices, n_triangles = torch.stack((vertex_end[-1], tri_end[-1])).tolist()              # the read that sizes the outputs
-    if n_vertices > MAX_ITEMS or n_triangles > MAX_ITEMS:
-        raise ValueError(f"extract_isosurface: {n_vertices} vertices and {n_triangles} triangles; more than 2^31 - 1 of either is "
-                         "not supported")
-    if n_vertices == 0 or n_triangles == 0:
+    sized = _sized(count.reshape(-1), triangles, values.shape)
+    if sized is None:
         return _empty(dev)
-    vertex_offset, tri_offset = (vertex_end - count.reshape(-1)).view(values.shape), (tri_end - triangles).view(values.shape)
-    flags = torch.zeros((2,), dtype=torch.int32, device=dev)
+    n_vertices, n_triangles, vertex_offset, tri_offset, flags = sized
     vertices = backend.vertices(values, code, vertex_offset, n_vertices, origin, spacing, level, above, flag=flags[0:1])
     faces = backend.triangles(code, edge_mask, vertex_offset, tri_offset, vertices, n_vertices, n_triangles, flag=flags[1:2])
     return _used_vertices_only(vertices, faces, flags, n_vertices, ops.dmc_flag_message)
@@ -240,9 +251,7 @@ def hierarchical_extract_geometry(geometric_func, device, bounds=DEFAULT_BOUNDS,
         raise ValueError(f"hierarchical_extract_geometry: depths {dense} .. {finest} are outside 1 .. 10")
     if int(dilation) < 0 or int(max_points_per_call) < 1:
         raise ValueError("hierarchical_extract_geometry: dilation must be >= 0 and max_points_per_call >= 1")
-    b = [float(x) for x in ((-bounds,) * 3 + (bounds,) * 3 if isinstance(bounds, (int, float)) else bounds)]
-    if len(b) != 6:
-        raise ValueError(f"hierarchical_extract_geometry: bounds are (x0, y0, z0, x1, y1, z1), got {len(b)} numbers")
+    b = _bounds("hierarchical_extract_geometry", bounds)
     dev = torch.device(device)
     n = 2 ** dense + 1
     axes = [_axis_points(b[c], b[3 + c], n, dev) for c in range(3)]

@@ -1188,7 +1188,7 @@ def decimate_apply(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch
 
 
 # ---- iso-surface extraction (csrc/am_isosurface.hip; the contract is the header's, the prefix sums and the sizing are isosurface.py's) ----
-_ISO_MAX = 2 ** 31 - 1
+_GRID_MAX = 2 ** 31 - 1
 _ISO_FLAGS = {L.ISO_BAD_VERTEX_OFFSET: "a vertex offset is negative or leads past the vertex count",
               L.ISO_BAD_TRI_OFFSET: "a triangle offset is negative or leads past the triangle count",
               L.ISO_BAD_TABLE: "the crossing masks or triangle counts do not belong to these values"}
@@ -1199,21 +1199,41 @@ def iso_flag_message(bits: int) -> str:
     return _flag_message(_ISO_FLAGS, bits)
 
 
-def _iso_grid(what: str, a, values: torch.Tensor, level: float):
-    """The checks on (values, level) the three entry points share; they come before the device check, so they hold for any tensor.
-    Sets the grid fields of `a`; returns ((nx, ny, nz), device)."""
-    if not isinstance(values, torch.Tensor):
+# The grid, count and frame helpers are the dual marching cubes' too.
+def _grid(what: str, a, first: torch.Tensor, name: str, dtype, level: Optional[float] = None, others=()):
+    """The grid checks the am_iso_* and am_dmc_* entry points share; they come before the device check, so they hold for any tensor.
+    `first` (X, Y, Z) of `dtype` sets the grid - the values, where a `level` comes with it -, `others` ((name, tensor, dtype), ...)
+    have its shape and device.  Sets nx, ny, nz of `a`, and values and level where given; returns ((nx, ny, nz), device)."""
+    if not isinstance(first, torch.Tensor):
         raise TypeError(f"{what}: expected a torch tensor")
-    if values.dim() != 3 or min(values.shape) < 2:
-        raise ValueError(f"{what}: expected (X, Y, Z) values with every axis at least 2, got {tuple(values.shape)}")
-    if values.numel() > _ISO_MAX:
-        raise ValueError(f"{what}: a grid of {tuple(values.shape)} points has more than 2^31 - 1")
-    level = float(level)
-    if level != level or level in (float("inf"), float("-inf")):
-        raise ValueError(f"{what}: the level must be finite, got {level}")
-    _need(values, torch.float32, f"{what}: values")
-    a.values, (a.nx, a.ny, a.nz), a.level = values.data_ptr(), values.shape, level
-    return tuple(values.shape), values.device
+    if first.dim() != 3 or min(first.shape) < 2:
+        raise ValueError(f"{what}: expected {'' if level is not None else 'an '}(X, Y, Z) {name} with every axis at least 2, got {tuple(first.shape)}")
+    if first.numel() > _GRID_MAX:
+        raise ValueError(f"{what}: a grid of {tuple(first.shape)} points has more than 2^31 - 1")
+    if level is not None:
+        level = float(level)
+        if level != level or level in (float("inf"), float("-inf")):
+            raise ValueError(f"{what}: the level must be finite, got {level}")
+    _need(first, dtype, f"{what}: {name}")
+    shape, dev = tuple(first.shape), first.device
+    for other, t, other_dtype in others:
+        _shaped(f"{what}: {other}", t, other_dtype, shape, dev)
+    a.nx, a.ny, a.nz = shape
+    if level is not None:
+        a.values, a.level = first.data_ptr(), level
+    return shape, dev
+
+
+def _grid_counts(what: str, **counts) -> Tuple[int, ...]:
+    """n_vertices, or n_vertices and n_triangles (`vertices=`, `triangles=`), as ints inside 1 .. 2^31 - 1."""
+    counts = {unit: int(n) for unit, n in counts.items()}
+    if not all(1 <= n <= _GRID_MAX for n in counts.values()):
+        raise ValueError(f"{what}: " + " and ".join(f"{n} {unit}" for unit, n in counts.items()) + " are outside 1 .. 2^31 - 1")
+    return tuple(counts.values())
+
+
+def _grid_frame(a, origin, spacing) -> None:
+    a.origin, a.spacing = ((C.c_double * 3)(*(float(x) for x in three)) for three in (origin, spacing))
 
 
 def iso_classify(values: torch.Tensor, level: float = 0.0, inside_above: bool = True, out_mask: Optional[torch.Tensor] = None,
@@ -1222,7 +1242,7 @@ def iso_classify(values: torch.Tensor, level: float = 0.0, inside_above: bool = 
     cell - at the point of its (0, 0, 0) corner - the number of triangles 0 .. 12 of its six tetrahedra.  Both (X, Y, Z) uint8."""
     what = "iso_classify"
     a = L.AmIsoClassifyArgs()
-    shape, dev = _iso_grid(what, a, values, level)
+    shape, dev = _grid(what, a, values, "values", torch.float32, level)
     mask = _out(f"{what}: out_mask", out_mask, shape, torch.uint8, dev)
     count = _out(f"{what}: out_count", out_count, shape, torch.uint8, dev)
     a.inside_above, a.out_mask, a.out_count = int(bool(inside_above)), mask.data_ptr(), count.data_ptr()
@@ -1237,15 +1257,11 @@ def iso_vertices(values: torch.Tensor, mask: torch.Tensor, vertex_offset: torch.
     popcounts.  origin, spacing: three fp64 numbers each.  `flag` as in decimate_quadrics."""
     what = "iso_vertices"
     a = L.AmIsoVerticesArgs()
-    shape, dev = _iso_grid(what, a, values, level)
-    _shaped(f"{what}: mask", mask, torch.uint8, shape, dev)
-    _shaped(f"{what}: vertex_offset", vertex_offset, torch.int64, shape, dev)
-    n_vertices = int(n_vertices)
-    if not 1 <= n_vertices <= _ISO_MAX:
-        raise ValueError(f"{what}: {n_vertices} vertices are outside 1 .. 2^31 - 1")
+    shape, dev = _grid(what, a, values, "values", torch.float32, level, (("mask", mask, torch.uint8), ("vertex_offset", vertex_offset, torch.int64)))
+    n_vertices, = _grid_counts(what, vertices=n_vertices)
     out = _out(f"{what}: out", out, (n_vertices, 3), torch.float32, dev)
     flag, own = _flag_word(what, flag, dev)
-    a.origin, a.spacing = (C.c_double * 3)(*(float(x) for x in origin)), (C.c_double * 3)(*(float(x) for x in spacing))
+    _grid_frame(a, origin, spacing)
     a.mask, a.vertex_offset, a.n_vertices, a.out_vertices, a.out_flag = mask.data_ptr(), vertex_offset.data_ptr(), n_vertices, out.data_ptr(), flag.data_ptr()
     _call(values, None, "am_iso_vertices", C.byref(a))
     _raise_own_flag(what, flag, own, _ISO_FLAGS)
@@ -1260,13 +1276,10 @@ def iso_triangles(values: torch.Tensor, mask: torch.Tensor, count: torch.Tensor,
     counts.  `flag` as in decimate_quadrics."""
     what = "iso_triangles"
     a = L.AmIsoTrianglesArgs()
-    shape, dev = _iso_grid(what, a, values, level)
-    for name, t, dtype in (("mask", mask, torch.uint8), ("count", count, torch.uint8), ("vertex_offset", vertex_offset, torch.int64),
-                           ("tri_offset", tri_offset, torch.int64)):
-        _shaped(f"{what}: {name}", t, dtype, shape, dev)
-    n_vertices, n_triangles = int(n_vertices), int(n_triangles)
-    if not 1 <= n_vertices <= _ISO_MAX or not 1 <= n_triangles <= _ISO_MAX:
-        raise ValueError(f"{what}: {n_vertices} vertices and {n_triangles} triangles are outside 1 .. 2^31 - 1")
+    shape, dev = _grid(what, a, values, "values", torch.float32, level,
+                       (("mask", mask, torch.uint8), ("count", count, torch.uint8), ("vertex_offset", vertex_offset, torch.int64),
+                        ("tri_offset", tri_offset, torch.int64)))
+    n_vertices, n_triangles = _grid_counts(what, vertices=n_vertices, triangles=n_triangles)
     out = _out(f"{what}: out", out, (n_triangles, 3), torch.int32, dev)
     flag, own = _flag_word(what, flag, dev)
     a.inside_above, a.mask, a.count = int(bool(inside_above)), mask.data_ptr(), count.data_ptr()
@@ -1278,31 +1291,13 @@ def iso_triangles(values: torch.Tensor, mask: torch.Tensor, count: torch.Tensor,
 
 
 # ---- dual marching cubes (csrc/am_dualcubes.hip; the contract is the header's, the prefix sums and the sizing are isosurface.py's) ----
-_DMC_FLAGS = {L.DMC_BAD_VERTEX_OFFSET: "a vertex offset is negative or leads past the vertex count",
-              L.DMC_BAD_TRI_OFFSET: "a triangle offset is negative or leads past the triangle count",
+_DMC_FLAGS = {L.DMC_BAD_VERTEX_OFFSET: _ISO_FLAGS[L.ISO_BAD_VERTEX_OFFSET], L.DMC_BAD_TRI_OFFSET: _ISO_FLAGS[L.ISO_BAD_TRI_OFFSET],
               L.DMC_BAD_CODE: "the cell codes or edge masks do not belong to these values"}
 
 
 def dmc_flag_message(bits: int) -> str:
     """What the set bits of an am_dmc_* flag word say."""
     return _flag_message(_DMC_FLAGS, bits)
-
-
-def _dmc_tables(what: str, a, first: torch.Tensor, first_name: str, first_dtype, others):
-    """The grid of the two entry points that take no values: `first` (X, Y, Z) of `first_dtype` sets it, `others` ((name, tensor,
-    dtype), ...) have its shape and device.  Sets nx, ny, nz of `a`; returns ((nx, ny, nz), device)."""
-    if not isinstance(first, torch.Tensor):
-        raise TypeError(f"{what}: expected a torch tensor")
-    if first.dim() != 3 or min(first.shape) < 2:
-        raise ValueError(f"{what}: expected an (X, Y, Z) {first_name} with every axis at least 2, got {tuple(first.shape)}")
-    if first.numel() > _ISO_MAX:
-        raise ValueError(f"{what}: a grid of {tuple(first.shape)} points has more than 2^31 - 1")
-    _need(first, first_dtype, f"{what}: {first_name}")
-    shape, dev = tuple(first.shape), first.device
-    for name, t, dtype in others:
-        _shaped(f"{what}: {name}", t, dtype, shape, dev)
-    a.nx, a.ny, a.nz = shape
-    return shape, dev
 
 
 def dmc_cells(values: torch.Tensor, level: float = 0.0, inside_above: bool = True, out_config: Optional[torch.Tensor] = None,
@@ -1312,7 +1307,7 @@ def dmc_cells(values: torch.Tensor, level: float = 0.0, inside_above: bool = Tru
     configuration's double faces.  Both (X, Y, Z) uint8."""
     what = "dmc_cells"
     a = L.AmDmcCellsArgs()
-    shape, dev = _iso_grid(what, a, values, level)
+    shape, dev = _grid(what, a, values, "values", torch.float32, level)
     config = _out(f"{what}: out_config", out_config, shape, torch.uint8, dev)
     double = _out(f"{what}: out_double", out_double, shape, torch.uint8, dev)
     a.inside_above, a.out_config, a.out_double = int(bool(inside_above)), config.data_ptr(), double.data_ptr()
@@ -1327,7 +1322,7 @@ def dmc_classify(config: torch.Tensor, double: torch.Tensor, out_code: Optional[
     the axis edges from the point that emit a quad (both (X, Y, Z) uint8)."""
     what = "dmc_classify"
     a = L.AmDmcClassifyArgs()
-    shape, dev = _dmc_tables(what, a, config, "config", torch.uint8, (("double", double, torch.uint8),))
+    shape, dev = _grid(what, a, config, "config", torch.uint8, others=(("double", double, torch.uint8),))
     code = _out(f"{what}: out_code", out_code, shape, torch.int16, dev)
     count = _out(f"{what}: out_count", out_count, shape, torch.uint8, dev)
     mask = _out(f"{what}: out_edge_mask", out_edge_mask, shape, torch.uint8, dev)
@@ -1345,15 +1340,11 @@ def dmc_vertices(values: torch.Tensor, code: torch.Tensor, vertex_offset: torch.
     patch counts.  origin, spacing: three fp64 numbers each.  `flag` as in decimate_quadrics."""
     what = "dmc_vertices"
     a = L.AmDmcVerticesArgs()
-    shape, dev = _iso_grid(what, a, values, level)
-    _shaped(f"{what}: code", code, torch.int16, shape, dev)
-    _shaped(f"{what}: vertex_offset", vertex_offset, torch.int64, shape, dev)
-    n_vertices = int(n_vertices)
-    if not 1 <= n_vertices <= _ISO_MAX:
-        raise ValueError(f"{what}: {n_vertices} vertices are outside 1 .. 2^31 - 1")
+    shape, dev = _grid(what, a, values, "values", torch.float32, level, (("code", code, torch.int16), ("vertex_offset", vertex_offset, torch.int64)))
+    n_vertices, = _grid_counts(what, vertices=n_vertices)
     out = _out(f"{what}: out", out, (n_vertices, 3), torch.float32, dev)
     flag, own = _flag_word(what, flag, dev)
-    a.origin, a.spacing = (C.c_double * 3)(*(float(x) for x in origin)), (C.c_double * 3)(*(float(x) for x in spacing))
+    _grid_frame(a, origin, spacing)
     a.inside_above, a.code, a.vertex_offset, a.n_vertices = int(bool(inside_above)), code.data_ptr(), vertex_offset.data_ptr(), n_vertices
     a.out_vertices, a.out_flag = out.data_ptr(), flag.data_ptr()
     _call(values, None, "am_dmc_vertices", C.byref(a))
@@ -1370,12 +1361,9 @@ def dmc_triangles(code: torch.Tensor, edge_mask: torch.Tensor, vertex_offset: to
     vertices (n_vertices, 3) fp32 from dmc_vertices.  `flag` as in decimate_quadrics."""
     what = "dmc_triangles"
     a = L.AmDmcTrianglesArgs()
-    shape, dev = _dmc_tables(what, a, code, "code", torch.int16, (("edge_mask", edge_mask, torch.uint8),
-                                                                  ("vertex_offset", vertex_offset, torch.int64),
-                                                                  ("tri_offset", tri_offset, torch.int64)))
-    n_vertices, n_triangles = int(n_vertices), int(n_triangles)
-    if not 1 <= n_vertices <= _ISO_MAX or not 1 <= n_triangles <= _ISO_MAX:
-        raise ValueError(f"{what}: {n_vertices} vertices and {n_triangles} triangles are outside 1 .. 2^31 - 1")
+    shape, dev = _grid(what, a, code, "code", torch.int16, others=(("edge_mask", edge_mask, torch.uint8), ("vertex_offset", vertex_offset, torch.int64),
+                                                                   ("tri_offset", tri_offset, torch.int64)))
+    n_vertices, n_triangles = _grid_counts(what, vertices=n_vertices, triangles=n_triangles)
     _shaped(f"{what}: vertices", vertices, torch.float32, (n_vertices, 3), dev)
     out = _out(f"{what}: out", out, (n_triangles, 3), torch.int32, dev)
     flag, own = _flag_word(what, flag, dev)
