@@ -190,6 +190,20 @@ extern std::atomic<uint64_t> g_am_scratch_generation;
 // Diagnostic trace (am_debug_trace_begin / _end, am_elementwise.hip): while a trace is open, am_trace() appends a position-weighted
 // integer checksum of a device buffer to the caller's device log, in stream order (one tiny kernel; integer adds, so the value does
 // not depend on the order the words are visited in).  A no-op otherwise.  tag = stage * 100 + layer (am_debug_trace_stage_name).
+// The stages, in tag order (a stage's number is its position here; the numbers are part of recorded traces): identifier, name.
+#define AM_TRACE_STAGES(X)                                                                                                       \
+  X(TR_NONE, "?") X(TR_SKIP_LINEAR, "skip linear (z)") X(TR_SKIP_NORM, "skip LayerNorm (h)") X(TR_NORM_S, "norm_s_attn (z)")       \
+  X(TR_QKV, "qkv GEMM") X(TR_HP_Q, "head_post Q") X(TR_HP_KV, "head_post local K|V^T chunk")                                       \
+  X(TR_ATTN_LOCAL_STATE, "attn local pass: state") X(TR_KV_CHUNKS, "K|V^T all chunks before attention")                            \
+  X(TR_Q_BEFORE_ATTN, "Q before attention") X(TR_ATTN_RESUME, "self-attn O after resume pass")                                     \
+  X(TR_ATTN_LAST_BLOCK, "self-attn O after last-block pass") X(TR_ATTN_ONE_PASS, "self-attn O (one pass)")                         \
+  X(TR_TO_OUT, "to_out + residual (h)") X(TR_NORM_X, "norm_x_attn (z)") X(TR_XQ, "cross to_q GEMM")                                \
+  X(TR_X_HP_Q, "cross head_post Q") X(TR_X_ATTN, "cross-attn O") X(TR_X_TO_OUT, "cross to_out + residual (h)")                     \
+  X(TR_X_BIAS_ONLY, "bias-only cross branch (h)") X(TR_NORM_FF, "norm_ff (z)") X(TR_FF1, "ff1 + GELU")                             \
+  X(TR_FF2, "ff2 + residual (h)") X(TR_PROJ_IN, "proj_in + time token (h)") X(TR_NORM_OUT, "norm_out (z)")                         \
+  X(TR_PROJ_OUT, "proj_out (v)") X(TR_STATE_BEFORE_RESUME, "attn state before resume")
+#define AM_TRACE_STAGE_ID(id, name) id,
+enum am_trace_stage { AM_TRACE_STAGES(AM_TRACE_STAGE_ID) };
 void am_trace(int tag, const void* dev_ptr, size_t bytes, void* stream);
 bool am_trace_on();
 

@@ -297,10 +297,7 @@ extern "C" int am_debug_trace_end(int32_t* tags_host, int capacity, int* n_entri
   return AM_OK;
 }
 extern "C" const char* am_debug_trace_stage_name(int stage) {
-  static const char* names[] = {"?", "skip linear (z)", "skip LayerNorm (h)", "norm_s_attn (z)", "qkv GEMM", "head_post Q", "head_post local K|V^T chunk",
-                                "attn local pass: state", "K|V^T all chunks before attention", "Q before attention", "self-attn O after resume pass",
-                                "self-attn O after last-block pass", "self-attn O (one pass)", "to_out + residual (h)", "norm_x_attn (z)", "cross to_q GEMM",
-                                "cross head_post Q", "cross-attn O", "cross to_out + residual (h)", "bias-only cross branch (h)", "norm_ff (z)",
-                                "ff1 + GELU", "ff2 + residual (h)", "proj_in + time token (h)", "norm_out (z)", "proj_out (v)", "attn state before resume"};
+#define AM_TRACE_STAGE_NAME(id, name) name,
+  static const char* names[] = {AM_TRACE_STAGES(AM_TRACE_STAGE_NAME)};
   return stage >= 0 && stage < (int)(sizeof(names) / sizeof(names[0])) ? names[stage] : "?";
 }

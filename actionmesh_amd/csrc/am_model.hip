@@ -5,11 +5,9 @@
 // stream.  Mirrors ActionMeshDenoiser.forward (temporal_denoiser.py:151-249)
 // and FlowMatchingBlock.forward (block.py:110-154); the cross-attention K/V of
 // the step-invariant context are cached per window (am_set_context).
-#include <map>
-#include <set>
-#include <string>
 #include <vector>
 
+#include <stdlib.h>
 #include <string.h>
 
 #include "am_common.h"
@@ -21,33 +19,42 @@ int am_add_bias_rows_stats(bf16_t* h, const float* bias, int64_t rows, int C, fl
 #define TR(stage, layer, ptr, bytes) do { if (am_trace_on()) am_trace((stage) * 100 + (layer), (ptr), (size_t)(bytes), (void*)st); } while (0)
 
 namespace {
-constexpr int HD = 128;
+constexpr int HD = 128;                                 // head dimension
+constexpr int STATE_ROW = 132;                          // floats per query row of the two-pass attention state (am_attn_args.state)
+constexpr float LN_EPS = 1e-5f, QK_EPS = 1e-6f;         // LayerNorm / qk-RMSNorm
+constexpr float SOFTMAX_SCALE = 0.08838834764831845f;   // 1/sqrt(128)
+constexpr int FP8_FAST_PROBS = 5400;                    // am_attn_args.defer_log2 code: the exponent-field form of the probabilities (am_attention_fp8)
 inline int pad_to(int64_t x, int m) { return (int)round_up(x, m); }
 }  // namespace
 
+// A linear [N][C] that sits behind a LayerNorm (block.py:138 norm_s_attn -> to_q|k|v, :146 norm_x_attn -> to_q, :152 norm_ff -> ff.net.0,
+// temporal_denoiser.py:239-242 norm_out -> proj_out): the loaded operands, and the norm folded in (am_ln_fold_weight): wf = W (.) gamma,
+// its column sums cs, and d = W beta + bias
+struct am_folded {
+  bf16_t* w = nullptr;
+  float *bias = nullptr, *ln_w = nullptr, *ln_b = nullptr;
+  bf16_t* wf = nullptr;
+  float *cs = nullptr, *d = nullptr;
+  int N = 0;
+};
+
 struct am_layer {
-  bf16_t *w_qkv = nullptr, *w_so = nullptr, *w_xq = nullptr, *w_xkv = nullptr, *w_xo = nullptr;
-  bf16_t *w_ff1 = nullptr, *w_ff2 = nullptr, *w_skip = nullptr;
-  float *b_so = nullptr, *b_xo = nullptr, *b_ff1 = nullptr, *b_ff2 = nullptr, *b_skip = nullptr;
-  float *ln_s_w = nullptr, *ln_s_b = nullptr, *ln_x_w = nullptr, *ln_x_b = nullptr;
-  float *ln_f_w = nullptr, *ln_f_b = nullptr, *ln_k_w = nullptr, *ln_k_b = nullptr;
+  am_folded qkv, xq, ff1;
+  bf16_t *w_so = nullptr, *w_xkv = nullptr, *w_xo = nullptr, *w_ff2 = nullptr, *w_skip = nullptr;
+  float *b_so = nullptr, *b_xo = nullptr, *b_ff2 = nullptr, *b_skip = nullptr, *ln_k_w = nullptr, *ln_k_b = nullptr;
   float *s_nq = nullptr, *s_nk = nullptr, *x_nq = nullptr, *x_nk = nullptr;
   bf16_t *kx = nullptr, *vtx = nullptr;   // cross-attention K / V^T cache
-  // the three linears that sit behind a LayerNorm (block.py:138 norm_s_attn -> to_q|k|v, :146 norm_x_attn -> to_q, :152 norm_ff ->
-  // ff.net.0) with the norm folded in (am_ln_fold_weight): W (.) gamma, its column sums, and W beta + bias
-  bf16_t *wf_qkv = nullptr, *wf_xq = nullptr, *wf_ff1 = nullptr;
-  float *cs_qkv = nullptr, *d_qkv = nullptr, *cs_xq = nullptr, *d_xq = nullptr, *cs_ff1 = nullptr, *d_ff1 = nullptr;
 };
 
 struct am_model {
   am_config cfg;
   int C, H, F, Dc, Din, NL, P, rank;
   std::vector<am_layer> layers;
-  bf16_t *w_t1 = nullptr, *w_t2 = nullptr, *w_in = nullptr, *w_out = nullptr;
-  float *b_t1 = nullptr, *b_t2 = nullptr, *b_in = nullptr, *b_out = nullptr, *ln_o_w = nullptr, *ln_o_b = nullptr;
-  bf16_t* wf_out = nullptr;                     // proj_out with norm_out folded in (round 6; temporal_denoiser.py:239-242)
-  float *cs_out = nullptr, *d_out = nullptr;
-  std::set<std::string> expected, loaded;
+  bf16_t *w_t1 = nullptr, *w_t2 = nullptr, *w_in = nullptr;
+  float *b_t1 = nullptr, *b_t2 = nullptr, *b_in = nullptr;
+  am_folded out;
+  std::vector<uint8_t> loaded;                  // per (layer + 1, row of the weight table): the key has been loaded
+  int n_expected = 0;                           // keys of the weight table that exist for this configuration
   std::vector<void*> allocs;
   float* stage_f32 = nullptr;
   size_t stage_elems = 0;
@@ -147,105 +154,134 @@ int dev_alloc_t(am_model* m, T** p, size_t elems, bool zero = true) {
   return dev_alloc(m, reinterpret_cast<void**>(p), elems * sizeof(T), zero);
 }
 
-enum WKind { W_MAT, W_BIAS, W_NORM };
-struct WSlot { void* dst; WKind kind; size_t numel; size_t dst_off; };
+// ---- the weight table: every reference state-dict key, once.  Used by am_create / am_load_weight only. ----------
+enum WKind { W_MAT, W_BIAS, W_NORM };      // bf16 matrix | fp32 vector rounded through bf16 (autocast casts the bias with the weight) | fp32 vector
+enum WScope { S_TOP, S_LAYER, S_SKIP };    // the key as it stands | "blocks.<i>." + key for every layer | for the layers with a skip only
+struct WDef {
+  const char* key;
+  WKind kind;
+  WScope scope;
+  void** (*dst)(am_model& m, am_layer* l);                    // where the device pointer lives
+  size_t (*numel)(size_t C, size_t F, size_t Dc, size_t Din); // elements of the key
+  int slot = 0, nslots = 1;                                   // a destination that concatenates several keys: this key's place in it
+};
+#define TOP(f) S_TOP, [](am_model& m, am_layer*) -> void** { return reinterpret_cast<void**>(&m.f); }
+#define LAYER(f) S_LAYER, [](am_model&, am_layer* l) -> void** { return reinterpret_cast<void**>(&l->f); }
+#define SKIP(f) S_SKIP, [](am_model&, am_layer* l) -> void** { return reinterpret_cast<void**>(&l->f); }
+#define N_(expr) [](size_t C, size_t F, size_t Dc, size_t Din) -> size_t { return expr; }
+const WDef kWeights[] = {
+    {"time_proj.linear_1.weight", W_MAT, TOP(w_t1), N_(4 * C * C)},
+    {"time_proj.linear_1.bias", W_BIAS, TOP(b_t1), N_(4 * C)},
+    {"time_proj.linear_2.weight", W_MAT, TOP(w_t2), N_(4 * C * C)},
+    {"time_proj.linear_2.bias", W_BIAS, TOP(b_t2), N_(C)},
+    {"proj_in.weight", W_MAT, TOP(w_in), N_(C * Din)},
+    {"proj_in.bias", W_BIAS, TOP(b_in), N_(C)},
+    {"proj_out.weight", W_MAT, TOP(out.w), N_(Din * C)},
+    {"proj_out.bias", W_BIAS, TOP(out.bias), N_(Din)},
+    {"norm_out.weight", W_NORM, TOP(out.ln_w), N_(C)},
+    {"norm_out.bias", W_NORM, TOP(out.ln_b), N_(C)},
+    // attention_processor.py:106-110: head h reads columns [384h, 384h+384) of cat(q,k,v) => the fused weight is the plain
+    // row-concatenation [Wq; Wk; Wv]
+    {"s_attn.to_q.weight", W_MAT, LAYER(qkv.w), N_(C * C), 0, 3},
+    {"s_attn.to_k.weight", W_MAT, LAYER(qkv.w), N_(C * C), 1, 3},
+    {"s_attn.to_v.weight", W_MAT, LAYER(qkv.w), N_(C * C), 2, 3},
+    {"s_attn.to_out.0.weight", W_MAT, LAYER(w_so), N_(C * C)},
+    {"s_attn.to_out.0.bias", W_BIAS, LAYER(b_so), N_(C)},
+    {"x_attn.to_q.weight", W_MAT, LAYER(xq.w), N_(C * C)},
+    {"x_attn.to_k.weight", W_MAT, LAYER(w_xkv), N_(C * Dc), 0, 2},          // :111-115 cat(k, v)
+    {"x_attn.to_v.weight", W_MAT, LAYER(w_xkv), N_(C * Dc), 1, 2},
+    {"x_attn.to_out.0.weight", W_MAT, LAYER(w_xo), N_(C * C)},
+    {"x_attn.to_out.0.bias", W_BIAS, LAYER(b_xo), N_(C)},
+    {"ff.net.0.proj.weight", W_MAT, LAYER(ff1.w), N_(F * C)},
+    {"ff.net.0.proj.bias", W_BIAS, LAYER(ff1.bias), N_(F)},
+    {"ff.net.2.weight", W_MAT, LAYER(w_ff2), N_(C * F)},
+    {"ff.net.2.bias", W_BIAS, LAYER(b_ff2), N_(C)},
+    {"norm_s_attn.weight", W_NORM, LAYER(qkv.ln_w), N_(C)},
+    {"norm_s_attn.bias", W_NORM, LAYER(qkv.ln_b), N_(C)},
+    {"norm_x_attn.weight", W_NORM, LAYER(xq.ln_w), N_(C)},
+    {"norm_x_attn.bias", W_NORM, LAYER(xq.ln_b), N_(C)},
+    {"norm_ff.weight", W_NORM, LAYER(ff1.ln_w), N_(C)},
+    {"norm_ff.bias", W_NORM, LAYER(ff1.ln_b), N_(C)},
+    {"s_attn.norm_q.weight", W_NORM, LAYER(s_nq), N_(HD)},
+    {"s_attn.norm_k.weight", W_NORM, LAYER(s_nk), N_(HD)},
+    {"x_attn.norm_q.weight", W_NORM, LAYER(x_nq), N_(HD)},
+    {"x_attn.norm_k.weight", W_NORM, LAYER(x_nk), N_(HD)},
+    {"linear_skip.weight", W_MAT, SKIP(w_skip), N_(2 * C * C)},
+    {"linear_skip.bias", W_BIAS, SKIP(b_skip), N_(C)},
+    {"norm_skip.weight", W_NORM, SKIP(ln_k_w), N_(C)},
+    {"norm_skip.bias", W_NORM, SKIP(ln_k_b), N_(C)},
+};
+#undef TOP
+#undef LAYER
+#undef SKIP
+#undef N_
+constexpr size_t NW = sizeof(kWeights) / sizeof(kWeights[0]);
+inline size_t w_numel(const am_model* m, const WDef& w) { return w.numel(m->C, m->F, m->Dc, m->Din); }
+inline bool w_exists(const am_model* m, const WDef& w, int layer) { return w.scope != S_SKIP || m->has_skip(layer); }
 
-// Reference state-dict key -> destination in our fused layout.
-bool resolve(am_model* m, const std::string& name, WSlot* s) {
-  const size_t C = m->C, F = m->F, Dc = m->Dc, Din = m->Din;
-  auto mat = [&](bf16_t* d, size_t n, size_t off = 0) { *s = {d, W_MAT, n, off}; return true; };
-  auto bias = [&](float* d, size_t n) { *s = {d, W_BIAS, n, 0}; return true; };
-  auto norm = [&](float* d, size_t n) { *s = {d, W_NORM, n, 0}; return true; };
-  if (name == "time_proj.linear_1.weight") return mat(m->w_t1, 4 * C * C);
-  if (name == "time_proj.linear_1.bias") return bias(m->b_t1, 4 * C);
-  if (name == "time_proj.linear_2.weight") return mat(m->w_t2, 4 * C * C);
-  if (name == "time_proj.linear_2.bias") return bias(m->b_t2, C);
-  if (name == "proj_in.weight") return mat(m->w_in, C * Din);
-  if (name == "proj_in.bias") return bias(m->b_in, C);
-  if (name == "norm_out.weight") return norm(m->ln_o_w, C);
-  if (name == "norm_out.bias") return norm(m->ln_o_b, C);
-  if (name == "proj_out.weight") return mat(m->w_out, Din * C);
-  if (name == "proj_out.bias") return bias(m->b_out, Din);
-  if (name.rfind("blocks.", 0) != 0) return false;
-  const size_t dot = name.find('.', 7);
-  if (dot == std::string::npos) return false;
-  int li = -1;
-  try { li = std::stoi(name.substr(7, dot - 7)); } catch (...) { return false; }
-  if (li < 0 || li >= m->NL) return false;
-  am_layer& l = m->layers[li];
-  const std::string r = name.substr(dot + 1);
-  if (r == "norm_s_attn.weight") return norm(l.ln_s_w, C);
-  if (r == "norm_s_attn.bias") return norm(l.ln_s_b, C);
-  if (r == "s_attn.norm_q.weight") return norm(l.s_nq, HD);
-  if (r == "s_attn.norm_k.weight") return norm(l.s_nk, HD);
-  // attention_processor.py:106-110: head h reads columns [384h, 384h+384) of cat(q,k,v)
-  // => the fused weight is the plain row-concatenation [Wq; Wk; Wv].
-  if (r == "s_attn.to_q.weight") return mat(l.w_qkv, C * C, 0);
-  if (r == "s_attn.to_k.weight") return mat(l.w_qkv, C * C, C * C);
-  if (r == "s_attn.to_v.weight") return mat(l.w_qkv, C * C, 2 * C * C);
-  if (r == "s_attn.to_out.0.weight") return mat(l.w_so, C * C);
-  if (r == "s_attn.to_out.0.bias") return bias(l.b_so, C);
-  if (r == "norm_x_attn.weight") return norm(l.ln_x_w, C);
-  if (r == "norm_x_attn.bias") return norm(l.ln_x_b, C);
-  if (r == "x_attn.norm_q.weight") return norm(l.x_nq, HD);
-  if (r == "x_attn.norm_k.weight") return norm(l.x_nk, HD);
-  if (r == "x_attn.to_q.weight") return mat(l.w_xq, C * C);
-  if (r == "x_attn.to_k.weight") return mat(l.w_xkv, C * Dc, 0);          // :111-115 cat(k, v)
-  if (r == "x_attn.to_v.weight") return mat(l.w_xkv, C * Dc, C * Dc);
-  if (r == "x_attn.to_out.0.weight") return mat(l.w_xo, C * C);
-  if (r == "x_attn.to_out.0.bias") return bias(l.b_xo, C);
-  if (r == "norm_ff.weight") return norm(l.ln_f_w, C);
-  if (r == "norm_ff.bias") return norm(l.ln_f_b, C);
-  if (r == "ff.net.0.proj.weight") return mat(l.w_ff1, F * C);
-  if (r == "ff.net.0.proj.bias") return bias(l.b_ff1, F);
-  if (r == "ff.net.2.weight") return mat(l.w_ff2, C * F);
-  if (r == "ff.net.2.bias") return bias(l.b_ff2, C);
-  if (m->has_skip(li)) {
-    if (r == "norm_skip.weight") return norm(l.ln_k_w, C);
-    if (r == "norm_skip.bias") return norm(l.ln_k_b, C);
-    if (r == "linear_skip.weight") return mat(l.w_skip, 2 * C * C);
-    if (r == "linear_skip.bias") return bias(l.b_skip, C);
+// The model's own keys (layer < 0) or those of one layer, in table order: one allocation per destination (slot count x element
+// count) for every key the configuration has; counts those keys.
+int alloc_weights(am_model* m, int layer) {
+  for (const WDef& w : kWeights) {
+    if ((w.scope == S_TOP) != (layer < 0) || !w_exists(m, w, layer)) continue;
+    ++m->n_expected;
+    if (w.slot == 0)
+      AM_TRY(dev_alloc(m, w.dst(*m, layer < 0 ? nullptr : &m->layers[layer]),
+                       w.nslots * w_numel(m, w) * (w.kind == W_MAT ? sizeof(bf16_t) : sizeof(float))));
+  }
+  return AM_OK;
+}
+// the products of am_ln_fold_weight for a linear of N outputs
+int alloc_folded(am_model* m, am_folded& f, int N) {
+  f.N = N;
+  AM_TRY(dev_alloc_t(m, &f.wf, (size_t)N * m->C));
+  AM_TRY(dev_alloc_t(m, &f.cs, (size_t)N));
+  return dev_alloc_t(m, &f.d, (size_t)N);
+}
+
+struct WSlot { void* dst; WKind kind; size_t numel; size_t dst_off; size_t id; };
+// state-dict key -> its destination in our fused layout; false for a key the table (or this configuration) does not have
+bool resolve(am_model* m, const char* name, WSlot* s) {
+  long li = -1;
+  if (strncmp(name, "blocks.", 7) == 0) {
+    char* end = nullptr;
+    li = strtol(name + 7, &end, 10);
+    if (end == name + 7 || *end != '.' || li < 0 || li >= m->NL) return false;
+    name = end + 1;
+  }
+  for (size_t k = 0; k < NW; ++k) {
+    const WDef& w = kWeights[k];
+    if ((w.scope == S_TOP) != (li < 0) || strcmp(name, w.key) != 0) continue;
+    if (!w_exists(m, w, (int)li)) return false;
+    const size_t n = w_numel(m, w);
+    *s = {*w.dst(*m, li < 0 ? nullptr : &m->layers[li]), w.kind, n, w.slot * n, (size_t)(li + 1) * NW + k};
+    return true;
   }
   return false;
 }
 
-void build_expected(am_model* m) {
-  auto& e = m->expected;
-  for (const char* n : {"time_proj.linear_1.weight", "time_proj.linear_1.bias", "time_proj.linear_2.weight",
-                        "time_proj.linear_2.bias", "proj_in.weight", "proj_in.bias", "norm_out.weight",
-                        "norm_out.bias", "proj_out.weight", "proj_out.bias"})
-    e.insert(n);
-  for (int i = 0; i < m->NL; ++i) {
-    const std::string p = "blocks." + std::to_string(i) + ".";
-    for (const char* n :
-         {"norm_s_attn.weight", "norm_s_attn.bias", "s_attn.norm_q.weight", "s_attn.norm_k.weight",
-          "s_attn.to_q.weight", "s_attn.to_k.weight", "s_attn.to_v.weight", "s_attn.to_out.0.weight",
-          "s_attn.to_out.0.bias", "norm_x_attn.weight", "norm_x_attn.bias", "x_attn.norm_q.weight",
-          "x_attn.norm_k.weight", "x_attn.to_q.weight", "x_attn.to_k.weight", "x_attn.to_v.weight",
-          "x_attn.to_out.0.weight", "x_attn.to_out.0.bias", "norm_ff.weight", "norm_ff.bias",
-          "ff.net.0.proj.weight", "ff.net.0.proj.bias", "ff.net.2.weight", "ff.net.2.bias"})
-      e.insert(p + n);
-    if (m->has_skip(i))
-      for (const char* n : {"norm_skip.weight", "norm_skip.bias", "linear_skip.weight", "linear_skip.bias"})
-        e.insert(p + n);
+// C [M][N] = A [M][K] W [N][K]^T + bias, every operand dense; the setters add what a call site needs beyond that (am_gemm_args)
+struct Gemm : am_gemm_args {
+  Gemm() : am_gemm_args{} {}
+  Gemm(const bf16_t* A, const bf16_t* Wp, const float* b, bf16_t* Cp, int ldc_, int64_t M_, int N_, int K_) : am_gemm_args{} {
+    A1 = A; lda1 = K1 = ldw = K = K_; W = Wp; bias = b; C = Cp; ldc = ldc_; M = (int)M_; N = N_;
   }
-}
+  Gemm& gelu() { act = AM_GEMM_ACT_GELU; return *this; }
+  Gemm& add(const bf16_t* res) { residual = res; return *this; }
+  Gemm& split_a(const bf16_t* A2_, int K1_) { A2 = A2_; lda1 = K1 = K1_; lda2 = K - K1_; return *this; }   // A = [A1 | A2] by columns
+  Gemm& a_rows(int G, int gs, int off) { a_G = G; a_gs = gs; a_off = off; return *this; }                  // row maps: am_gemm_args
+  Gemm& c_rows(int G, int gs, int off) { c_G = G; c_gs = gs; c_off = off; return *this; }
+  int run(hipStream_t st) const { return am_gemm_bf16(this, st); }
+};
 
-int gemm(hipStream_t st, const bf16_t* A, int lda, const bf16_t* W, int ldw, const float* bias, const bf16_t* res,
-         bf16_t* Cp, int ldc, int64_t M, int N, int K, int act, const bf16_t* A2 = nullptr, int lda2 = 0, int K1 = 0,
-         int aG = 0, int ags = 0, int aoff = 0, int cG = 0, int cgs = 0, int coff = 0) {
-  am_gemm_args g = {};
-  g.A1 = A; g.lda1 = lda; g.K1 = A2 ? K1 : K;
-  g.A2 = A2; g.lda2 = lda2;
-  g.W = W; g.ldw = ldw; g.bias = bias; g.residual = res; g.C = Cp; g.ldc = ldc;
-  g.M = (int)M; g.N = N; g.K = K; g.act = act;
-  g.a_G = aG; g.a_gs = ags; g.a_off = aoff;
-  g.c_G = cG; g.c_gs = cgs; g.c_off = coff;
-  return am_gemm_bf16(&g, st);
+template <class Fn>
+int for_each_folded(am_model* m, Fn fn) {
+  for (am_layer& l : m->layers)
+    for (am_folded* f : {&l.qkv, &l.xq, &l.ff1}) AM_TRY(fn(*f));
+  return fn(m->out);
 }
 
 int prepare_folds(am_model* m, hipStream_t st) {
-  const int C = m->C, F = m->F;
   {   // the synchronisation below is illegal inside a stream capture (it would invalidate it): a caller that captures the split API
       // must run one eager forward after am_load_weights first (am_denoise_forward_graph does) - say so instead
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -254,12 +290,7 @@ int prepare_folds(am_model* m, hipStream_t st) {
                                   "run one forward eagerly before capturing this stream");
     (void)hipGetLastError();
   }
-  for (am_layer& l : m->layers) {
-    AM_TRY(am_ln_fold_weight(l.w_qkv, l.ln_s_w, l.ln_s_b, nullptr, l.wf_qkv, l.cs_qkv, l.d_qkv, 3 * C, C, st));
-    AM_TRY(am_ln_fold_weight(l.w_xq, l.ln_x_w, l.ln_x_b, nullptr, l.wf_xq, l.cs_xq, l.d_xq, C, C, st));
-    AM_TRY(am_ln_fold_weight(l.w_ff1, l.ln_f_w, l.ln_f_b, l.b_ff1, l.wf_ff1, l.cs_ff1, l.d_ff1, F, C, st));
-  }
-  AM_TRY(am_ln_fold_weight(m->w_out, m->ln_o_w, m->ln_o_b, m->b_out, m->wf_out, m->cs_out, m->d_out, m->Din, C, st));
+  AM_TRY(for_each_folded(m, [&](am_folded& f) { return am_ln_fold_weight(f.w, f.ln_w, f.ln_b, f.bias, f.wf, f.cs, f.d, f.N, m->C, st); }));
   // once per weight load, never inside a capture: the folded weights are read by every later forward on WHATEVER stream it is
   // launched on (an eager forward on another torch stream, the graph stream after an eager call) - make them visible to all of
   // them before the flag says so (they used to be ordered only with the stream of the first forward)
@@ -268,13 +299,68 @@ int prepare_folds(am_model* m, hipStream_t st) {
   return AM_OK;
 }
 
-// (mean, rstd) of rows [r0, r0 + nr) of the residual stream from the slices a producer GEMM left in ln_part
-// (x = the buffer the rows live in; ACTIONMESH_AMD_LN_STATS=recompute reads them back instead - same bits by construction
-// (canonical statistics, am_common.h), which tests/test_denoiser_gpu.py asserts on whole forwards)
-int finalize_stats(am_model* h, const bf16_t* x, int64_t r0, int64_t nr, hipStream_t st) {
-  if (h->ln_recompute) return am_row_stats_bf16(x + r0 * h->C, h->ln_stats + 2 * r0, nr, h->C, 1e-5f, st);
-  const int np = ceil_div(h->C, 256);
-  return am_row_stats_finalize(h->ln_part + 2 * r0 * np, np, h->C, h->ln_stats + 2 * r0, nr, 1e-5f, st);
+// *g = the linear `f` of LayerNorm(x) into out [rows][f.N], x = `rows` rows of the residual stream whose statistics are at `stats`.
+// Folded: the un-normalised rows, their statistics and W (.) gamma.  ln_fold off: the LayerNorm kernel into h->z (trace point
+// `stage`) and the plain linear.  The call site adds what differs (activation, row map, fused head split) and launches.
+int ln_linear(am_model* h, const am_folded& f, const bf16_t* x, int64_t rows, const float* stats, bf16_t* out, am_trace_stage stage,
+              int layer, hipStream_t st, Gemm* g) {
+  if (h->ln_fold) {
+    *g = Gemm(x, f.wf, f.d, out, f.N, rows, f.N, h->C);
+    g->ln_stats = stats; g->ln_colsum = f.cs;
+    return AM_OK;
+  }
+  AM_TRY(am_layernorm_bf16(x, h->z, f.ln_w, f.ln_b, rows, h->C, LN_EPS, st));
+  TR(stage, layer, h->z, (size_t)rows * h->C * 2);
+  *g = Gemm(h->z, f.w, f.bias, out, f.N, rows, f.N, h->C);
+  return AM_OK;
+}
+
+// rows [r0, r0 + nr) of dst = A [nr][K] W^T + bias + the same rows of res (res, dst: residual-stream buffers, C columns).  With
+// `want` (the next reader of these rows is a folded LayerNorm) the store loop leaves the slices of their statistics in ln_part, merged
+// into ln_stats behind it.  ACTIONMESH_AMD_LN_STATS=recompute reads the rows back instead - same bits by construction (canonical
+// statistics, am_common.h), which tests/test_denoiser_gpu.py asserts on whole forwards.
+int residual_linear(am_model* h, const bf16_t* A, const bf16_t* W, const float* bias, int K, const bf16_t* res, bf16_t* dst, int64_t r0,
+                    int64_t nr, bool want, hipStream_t st) {
+  const int C = h->C, np = ceil_div(C, 256);
+  const size_t off = (size_t)r0 * C;
+  float *part = h->ln_part + 2 * r0 * np, *stats = h->ln_stats + 2 * r0;
+  Gemm g(A, W, bias, dst + off, C, nr, C, K);
+  g.add(res + off);
+  if (h->ln_fold && want) g.ln_part = part;
+  AM_TRY(g.run(st));
+  if (!(h->ln_fold && want)) return AM_OK;
+  if (h->ln_recompute) return am_row_stats_bf16(dst + off, stats, nr, C, LN_EPS, st);
+  return am_row_stats_finalize(part, np, C, stats, nr, LN_EPS, st);
+}
+
+// The two attention geometries: `nseq` sequences of `sq` queries (Q in h->Qb, O to h->ao) against `nchunks` chunks of `sk` keys each.
+am_attn_args attn_args(am_model* h, const bf16_t* K, const bf16_t* Vt, int nseq, int sq, int sk, int nchunks, size_t chunk_stride) {
+  am_attn_args at = {};
+  at.Q = h->Qb; at.K = K; at.Vt = Vt; at.O = h->ao;
+  at.heads = h->H; at.ldo = h->C; at.scale = SOFTMAX_SCALE; at.defer_log2 = h->cfg.attn_defer_log2;
+  at.nseq = nseq; at.sq = sq; at.sq_pad = pad_to(sq, 256);
+  at.sk = sk; at.sk_pad = pad_to(sk, 64);
+  at.nchunks = nchunks; at.chunk_stride = (int64_t)chunk_stride;
+  return at;
+}
+// inflated self-attention: one sequence of T * L tokens per batch row, keys in P rank chunks (one-pass and two-pass form alike)
+am_attn_args self_attn_args(am_model* h) { return attn_args(h, h->Kg, h->Vtg, h->B, h->T * h->L, h->T * h->L, h->P, h->chunk_stride); }
+// per-frame self-attention and cross-attention: every frame's L queries against one chunk of its own `sk` keys
+am_attn_args frame_attn_args(am_model* h, const bf16_t* K, const bf16_t* Vt, int nseq, int sk) { return attn_args(h, K, Vt, nseq, h->L, sk, 1, 0); }
+// The one attention launch.  The inflated layers of an fp8 handle read the quantised operands (never a silent bf16 pass there);
+// am_attention_counters counts an inflated layer once: at its one-pass launch or at the first of its two passes.
+int attend(am_model* h, am_attn_args at, bool inflated, hipStream_t st) {
+  const bool counted = inflated && at.state_mode != 2 && at.rows != 2;
+  if (inflated && h->cfg.attn_fp8) {
+    at.chunk_stride = (int64_t)h->chunk_stride8;
+    if (h->cfg.attn_fp8 == 2) at.defer_log2 = FP8_FAST_PROBS;
+    AM_TRY(am_attention_fp8(&at, h->Q8, h->K8, h->Vt8, st));
+    h->n_attn_fp8 += counted;
+  } else {
+    AM_TRY(am_attention_bf16(&at, st));
+    h->n_attn_bf16 += counted;
+  }
+  return AM_OK;
 }
 
 }  // namespace
@@ -303,16 +389,11 @@ extern "C" int am_create(const am_config* cfg, am_handle* out) {
   m->C = cfg->width; m->H = cfg->num_heads; m->F = cfg->ff_inner; m->Dc = cfg->cross_dim;
   m->Din = cfg->in_channels; m->NL = cfg->num_layers; m->P = cfg->world_size; m->rank = cfg->rank;
   m->layers.resize(m->NL);
-  build_expected(m);
+  m->loaded.assign((size_t)(m->NL + 1) * NW, 0);
   const size_t C = m->C, F = m->F, Dc = m->Dc, Din = m->Din;
   int st = AM_OK;
 #define A_(call) do { if (st == AM_OK) st = (call); } while (0)
-  A_(dev_alloc_t(m, &m->w_t1, 4 * C * C)); A_(dev_alloc_t(m, &m->b_t1, 4 * C));
-  A_(dev_alloc_t(m, &m->w_t2, 4 * C * C)); A_(dev_alloc_t(m, &m->b_t2, C));
-  A_(dev_alloc_t(m, &m->w_in, C * Din)); A_(dev_alloc_t(m, &m->b_in, C));
-  A_(dev_alloc_t(m, &m->w_out, Din * C)); A_(dev_alloc_t(m, &m->b_out, Din));
-  A_(dev_alloc_t(m, &m->ln_o_w, C)); A_(dev_alloc_t(m, &m->ln_o_b, C));
-  A_(dev_alloc_t(m, &m->wf_out, Din * C)); A_(dev_alloc_t(m, &m->cs_out, Din)); A_(dev_alloc_t(m, &m->d_out, Din));
+  A_(alloc_weights(m, -1)); A_(alloc_folded(m, m->out, m->Din));
 
   // workspace bounds
   m->maxB = cfg->max_batch; m->maxT = cfg->max_frames_local; m->maxN = cfg->max_tokens; m->maxS = cfg->max_ctx_tokens;
@@ -322,23 +403,8 @@ extern "C" int am_create(const am_config* cfg, am_handle* out) {
   const int Spad = pad_to(m->maxS, 64);
   for (int i = 0; i < m->NL && st == AM_OK; ++i) {
     am_layer& l = m->layers[i];
-    A_(dev_alloc_t(m, &l.w_qkv, 3 * C * C)); A_(dev_alloc_t(m, &l.w_so, C * C)); A_(dev_alloc_t(m, &l.b_so, C));
-    A_(dev_alloc_t(m, &l.w_xq, C * C)); A_(dev_alloc_t(m, &l.w_xkv, 2 * C * Dc));
-    A_(dev_alloc_t(m, &l.w_xo, C * C)); A_(dev_alloc_t(m, &l.b_xo, C));
-    A_(dev_alloc_t(m, &l.w_ff1, F * C)); A_(dev_alloc_t(m, &l.b_ff1, F));
-    A_(dev_alloc_t(m, &l.w_ff2, C * F)); A_(dev_alloc_t(m, &l.b_ff2, C));
-    A_(dev_alloc_t(m, &l.ln_s_w, C)); A_(dev_alloc_t(m, &l.ln_s_b, C));
-    A_(dev_alloc_t(m, &l.ln_x_w, C)); A_(dev_alloc_t(m, &l.ln_x_b, C));
-    A_(dev_alloc_t(m, &l.ln_f_w, C)); A_(dev_alloc_t(m, &l.ln_f_b, C));
-    A_(dev_alloc_t(m, &l.s_nq, (size_t)HD)); A_(dev_alloc_t(m, &l.s_nk, (size_t)HD));
-    A_(dev_alloc_t(m, &l.x_nq, (size_t)HD)); A_(dev_alloc_t(m, &l.x_nk, (size_t)HD));
-    if (m->has_skip(i)) {
-      A_(dev_alloc_t(m, &l.w_skip, 2 * C * C)); A_(dev_alloc_t(m, &l.b_skip, C));
-      A_(dev_alloc_t(m, &l.ln_k_w, C)); A_(dev_alloc_t(m, &l.ln_k_b, C));
-    }
-    A_(dev_alloc_t(m, &l.wf_qkv, 3 * C * C)); A_(dev_alloc_t(m, &l.cs_qkv, 3 * C)); A_(dev_alloc_t(m, &l.d_qkv, 3 * C));
-    A_(dev_alloc_t(m, &l.wf_xq, C * C)); A_(dev_alloc_t(m, &l.cs_xq, C)); A_(dev_alloc_t(m, &l.d_xq, C));
-    A_(dev_alloc_t(m, &l.wf_ff1, F * C)); A_(dev_alloc_t(m, &l.cs_ff1, F)); A_(dev_alloc_t(m, &l.d_ff1, F));
+    A_(alloc_weights(m, i));
+    A_(alloc_folded(m, l.qkv, 3 * m->C)); A_(alloc_folded(m, l.xq, m->C)); A_(alloc_folded(m, l.ff1, m->F));
     A_(dev_alloc_t(m, &l.kx, (size_t)BT * m->H * Spad * HD));
     A_(dev_alloc_t(m, &l.vtx, (size_t)BT * m->H * HD * Spad));
   }
@@ -412,16 +478,15 @@ extern "C" int am_load_weight(am_handle h, const char* name, const float* host, 
       for (auto& v : tmp) v = bf2f(f2bf(v));
     AM_HIP(hipMemcpy(s.dst, tmp.data(), numel * sizeof(float), hipMemcpyHostToDevice));
   }
-  h->loaded.insert(name);
-  h->folds_ready = false;         // the folded linears (am_layer.wf_*) are rebuilt by the next forward's entry point, never inside a capture
+  h->loaded[s.id] = 1;
+  h->folds_ready = false;         // the folded linears (am_folded.wf, cs, d) are rebuilt by the next forward's entry point, never inside a capture
   return AM_OK;
 }
 
 extern "C" int am_weights_missing(am_handle h) {
   if (!h) return -1;
-  int missing = 0;
-  for (const auto& n : h->expected)
-    if (!h->loaded.count(n)) ++missing;
+  int missing = h->n_expected;
+  for (uint8_t done : h->loaded) missing -= done;
   return missing;
 }
 
@@ -494,11 +559,11 @@ extern "C" int am_set_context(am_handle h, const float* ctx_dev, int B, int T, i
   const int Spad = pad_to(S, 64);
   for (int i = 0; i < h->NL; ++i) {
     am_layer& l = h->layers[i];
-    AM_TRY(gemm(st, h->ctxb, h->Dc, l.w_xkv, h->Dc, nullptr, nullptr, h->kvtmp, 2 * h->C, BT * S, 2 * h->C, h->Dc, 0));
+    AM_TRY(Gemm(h->ctxb, l.w_xkv, nullptr, h->kvtmp, 2 * h->C, BT * S, 2 * h->C, h->Dc).run(st));
     am_headpost_args hp = {};
     hp.X = h->kvtmp; hp.ldx = 2 * h->C; hp.rows = BT * S; hp.seq_len = S; hp.rows_per_frame = S;
     hp.heads = h->H; hp.nparts = 2; hp.kinds[0] = 1; hp.kinds[1] = 2;
-    hp.w_q = nullptr; hp.w_k = l.x_nk; hp.eps = 1e-6f;
+    hp.w_q = nullptr; hp.w_k = l.x_nk; hp.eps = QK_EPS;
     hp.out_k = l.kx; hp.out_vt = l.vtx; hp.sk_pad = Spad;
     AM_TRY(am_head_post(&hp, st));
   }
@@ -544,15 +609,13 @@ static int forward_begin_body(am_model* h, const float* x_dev, int B, int T, int
   const int64_t BT = (int64_t)B * T;
   // proj_in (temporal_denoiser.py:205-206) written behind each frame's time token (:217)
   AM_TRY(am_f32_to_bf16(x_dev, h->xb, (size_t)BT * N * Din, st));
-  AM_TRY(gemm(st, h->xb, Din, h->w_in, Din, h->b_in, nullptr, h->hwork, C, BT * N, C, Din, 0, nullptr, 0, 0, 0, 0, 0,
-              /*cG*/ N, /*cgs*/ h->L, /*coff*/ 1));
+  AM_TRY(Gemm(h->xb, h->w_in, h->b_in, h->hwork, C, BT * N, C, Din).c_rows(N, h->L, 1).run(st));
   // time token (:213-217): sinusoid -> Linear -> GELU -> Linear -> row 0 of each frame
   AM_TRY(am_timestep_sinusoid(h->tdev, h->te0, (int)BT, C, st));
-  AM_TRY(gemm(st, h->te0, C, h->w_t1, C, h->b_t1, nullptr, h->te1, 4 * C, BT, 4 * C, C, 1));
-  AM_TRY(gemm(st, h->te1, 4 * C, h->w_t2, 4 * C, h->b_t2, nullptr, h->hwork, C, BT, C, 4 * C, 0, nullptr, 0, 0, 0, 0, 0,
-              /*cG*/ 1, /*cgs*/ h->L, /*coff*/ 0));
-  TR(23, 0, h->hwork, (size_t)h->R * C * 2);
-  if (h->ln_fold) AM_TRY(am_row_stats_bf16(h->hwork, h->ln_stats, h->R, C, 1e-5f, st));
+  AM_TRY(Gemm(h->te0, h->w_t1, h->b_t1, h->te1, 4 * C, BT, 4 * C, C).gelu().run(st));
+  AM_TRY(Gemm(h->te1, h->w_t2, h->b_t2, h->hwork, C, BT, C, 4 * C).c_rows(1, h->L, 0).run(st));
+  TR(TR_PROJ_IN, 0, h->hwork, (size_t)h->R * C * 2);
+  if (h->ln_fold) AM_TRY(am_row_stats_bf16(h->hwork, h->ln_stats, h->R, C, LN_EPS, st));
   h->hsrc = h->hwork;
   h->skip_top = 0;
   h->next_layer = 0;
@@ -561,7 +624,14 @@ static int forward_begin_body(am_model* h, const float* x_dev, int B, int T, int
   return AM_OK;
 }
 
-static void self_attn_args(am_model* h, am_attn_args* at);
+// A bias-free projection fused with its head split (am_gemm_headpost_bf16); trace runs keep the two launches apart so that the
+// linear's output can be checksummed
+static int linear_head_split(const Gemm& g, const am_headpost_args& hp, am_trace_stage stage, int layer, hipStream_t st) {
+  if (!am_trace_on()) return am_gemm_headpost_bf16(&g, &hp, st);
+  AM_TRY(g.run(st));
+  TR(stage, layer, hp.X, (size_t)hp.rows * hp.ldx * 2);
+  return am_head_post(&hp, st);
+}
 
 extern "C" int am_layer_pre_attn(am_handle h, int i, void* stream) {
   AM_CHECK(h, "am_layer_pre_attn: null handle");
@@ -574,79 +644,45 @@ extern "C" int am_layer_pre_attn(am_handle h, int i, void* stream) {
   if (h->has_skip(i)) {   // block.py:131-133
     AM_CHECK(h->skip_top > 0, "am_layer_pre_attn: skip stack empty at layer %d", i);
     const bf16_t* sk = h->skip[--h->skip_top];
-    AM_TRY(gemm(st, sk, C, l.w_skip, 2 * C, l.b_skip, nullptr, h->z, C, R, C, 2 * C, 0, h->hsrc, C, C));
-    TR(1, i, h->z, (size_t)R * C * 2);
-    if (h->ln_fold) AM_TRY(am_layernorm_stats_bf16(h->z, h->hwork, l.ln_k_w, l.ln_k_b, R, C, 1e-5f, h->ln_stats, st));
-    else AM_TRY(am_layernorm_bf16(h->z, h->hwork, l.ln_k_w, l.ln_k_b, R, C, 1e-5f, st));
-    TR(2, i, h->hwork, (size_t)R * C * 2);
+    AM_TRY(Gemm(sk, l.w_skip, l.b_skip, h->z, C, R, C, 2 * C).split_a(h->hsrc, C).run(st));
+    TR(TR_SKIP_LINEAR, i, h->z, (size_t)R * C * 2);
+    if (h->ln_fold) AM_TRY(am_layernorm_stats_bf16(h->z, h->hwork, l.ln_k_w, l.ln_k_b, R, C, LN_EPS, h->ln_stats, st));
+    else AM_TRY(am_layernorm_bf16(h->z, h->hwork, l.ln_k_w, l.ln_k_b, R, C, LN_EPS, st));
+    TR(TR_SKIP_NORM, i, h->hwork, (size_t)R * C * 2);
     h->hsrc = h->hwork;
   }
   // exact shortcut (am_set_branch_hints): until the first cross-attention every batch row is the same tensor - layer 0's
   // self-attention branch runs on row 0 only and am_layer_post_attn copies its result to the other rows
   const bool shared = i == 0 && h->shared_prefix && !h->has_skip(0);
   const int64_t Rs = shared ? R / h->B : R;
-  am_gemm_args gq = {};      // the q | k | v projection (:92-103), fused with the head split below (am_gemm_headpost_bf16)
-  if (h->ln_fold) {          // norm_s_attn (block.py:138) inside the projection: rows of h, their statistics, W (.) gamma
-    gq.A1 = h->hsrc; gq.W = l.wf_qkv; gq.bias = l.d_qkv; gq.ln_stats = h->ln_stats; gq.ln_colsum = l.cs_qkv;
-  } else {
-    AM_TRY(am_layernorm_bf16(h->hsrc, h->z, l.ln_s_w, l.ln_s_b, Rs, C, 1e-5f, st));      // block.py:138
-    TR(3, i, h->z, (size_t)Rs * C * 2);
-    gq.A1 = h->z; gq.W = l.w_qkv;
-  }
-  gq.lda1 = C; gq.K1 = C; gq.ldw = C; gq.C = h->qkv; gq.ldc = 3 * C;
-  gq.M = (int)Rs; gq.N = 3 * C; gq.K = C;
+  // norm_s_attn (block.py:138) -> the q | k | v projection (:92-103) -> head split, qk-norm, RoPE into the attention operand layouts
+  const bool inflated = h->inflated(i), fp8_sharded = h->cfg.attn_fp8 && h->P > 1;
+  const am_attn_args at = inflated ? self_attn_args(h) : frame_attn_args(h, h->Kg, h->Vtg, h->B * h->T, L);
+  Gemm gq;
+  AM_TRY(ln_linear(h, l.qkv, h->hsrc, Rs, h->ln_stats, h->qkv, TR_NORM_S, i, st, &gq));
   am_headpost_args hp = {};
-  hp.X = h->qkv; hp.ldx = 3 * C; hp.rows = Rs; hp.rows_per_frame = L;
+  hp.X = h->qkv; hp.ldx = 3 * C; hp.rows = Rs; hp.seq_len = at.sq; hp.rows_per_frame = L;
   hp.heads = h->H; hp.nparts = 3; hp.kinds[0] = 0; hp.kinds[1] = 1; hp.kinds[2] = 2;
-  hp.w_q = l.s_nq; hp.w_k = l.s_nk; hp.eps = 1e-6f;
+  hp.w_q = l.s_nq; hp.w_k = l.s_nk; hp.eps = QK_EPS;
   hp.rope_cos = h->rope_cos; hp.rope_sin = h->rope_sin;
-  hp.out_q = h->Qb;
-  const bool fp8_layer = h->cfg.attn_fp8 && h->inflated(i);
-  const bool fp8_sharded = h->cfg.attn_fp8 && h->P > 1;
-  if (h->inflated(i)) {
-    hp.seq_len = h->T * L;
-    hp.sq_pad = pad_to(hp.seq_len, 256); hp.sk_pad = pad_to(hp.seq_len, 64);
-    hp.out_k = fp8_sharded ? h->Kg : h->Kg + (size_t)h->rank * h->chunk_stride;
-    hp.out_vt = fp8_sharded ? h->Vtg : h->Vtg + (size_t)h->rank * h->chunk_stride;
-  } else {
-    hp.seq_len = L;
-    hp.sq_pad = pad_to(L, 256); hp.sk_pad = pad_to(L, 64);
-    hp.out_k = h->Kg; hp.out_vt = h->Vtg;
-  }
-  if (am_trace_on()) {       // trace runs keep the two launches apart so that the linear's output can be checksummed
-    AM_TRY(am_gemm_bf16(&gq, st));
-    TR(4, i, h->qkv, (size_t)Rs * 3 * C * 2);
-    AM_TRY(am_head_post(&hp, st));
-  } else {
-    AM_TRY(am_gemm_headpost_bf16(&gq, &hp, st));
-  }
-  if (am_trace_on()) {
-    const size_t nseq = h->inflated(i) ? (size_t)h->B : (size_t)h->B * h->T;
-    TR(5, i, h->Qb, nseq * h->H * hp.sq_pad * HD * 2);
-    TR(6, i, hp.out_k, h->chunk_elems * 2);
-    TR(6, i, hp.out_vt, h->chunk_elems * 2);
-  }
-  if (fp8_layer) {
+  hp.out_q = h->Qb; hp.sq_pad = at.sq_pad; hp.sk_pad = at.sk_pad;
+  // an inflated layer writes this rank's chunk of the gather buffers (fp8 + sharding: Kg / Vtg hold the local shard only - ensure_kv)
+  const size_t own = inflated && !fp8_sharded ? (size_t)h->rank * h->chunk_stride : 0;
+  hp.out_k = h->Kg + own; hp.out_vt = h->Vtg + own;
+  AM_TRY(linear_head_split(gq, hp, TR_QKV, i, st));
+  TR(TR_HP_Q, i, h->Qb, (size_t)at.nseq * h->H * hp.sq_pad * HD * 2);
+  TR(TR_HP_KV, i, hp.out_k, h->chunk_elems * 2);
+  TR(TR_HP_KV, i, hp.out_vt, h->chunk_elems * 2);
+  if (inflated && h->cfg.attn_fp8) {
     // fp8 variant: Q and THIS rank's K / V^T shard are quantised here, so that with world_size > 1 the shards that travel are the
     // fp8 ones (half the bytes on the links, and every rank quantises 1 / P of the keys instead of all of them after the gather)
-    am_attn_args qa = {};
-    self_attn_args(h, &qa);
+    am_attn_args qa = at;
     if (shared) qa.nseq /= h->B;
     qa.K = hp.out_k; qa.Vt = hp.out_vt; qa.nchunks = 1; qa.chunk_stride = 0;
     AM_TRY(am_attention_quantize_fp8(&qa, h->Q8, h->K8 + (size_t)h->rank * h->chunk_stride8, h->Vt8 + (size_t)h->rank * h->chunk_stride8, st));
   }
   h->pre_done = true;
   return AM_OK;
-}
-
-// Shared by the one-pass and the two-pass self-attention of an inflated layer.
-static void self_attn_args(am_model* h, am_attn_args* at) {
-  const int L = h->L;
-  at->Q = h->Qb; at->K = h->Kg; at->Vt = h->Vtg; at->O = h->ao;
-  at->heads = h->H; at->ldo = h->C; at->scale = 0.08838834764831845f; at->defer_log2 = h->cfg.attn_defer_log2;
-  at->nseq = h->B; at->sq = h->T * L; at->sq_pad = pad_to(at->sq, 256);
-  at->sk = h->T * L; at->sk_pad = pad_to(at->sk, 64);
-  at->nchunks = h->P; at->chunk_stride = (int64_t)h->chunk_stride;
 }
 
 // Multi-GPU overlap: between am_layer_pre_attn and am_layer_post_attn of an inflated layer, while the all-gather of
@@ -657,29 +693,18 @@ extern "C" int am_layer_attn_local(am_handle h, int i, void* stream) {
   AM_CHECK(h, "am_layer_attn_local: null handle");
   if (!h->in_forward || i != h->next_layer || !h->pre_done)
     AM_FAIL(AM_ERR_STATE, "am_layer_attn_local: layer %d out of order (next=%d)", i, h->next_layer);
+  hipStream_t st = (hipStream_t)stream;
   h->local_done = false;
   const int tiles = (h->T * h->L + 63) / 64;
   const bool product = h->cfg.attn_defer_log2 == 0 || h->cfg.attn_defer_log2 == 8;
   if (h->P < 2 || !h->inflated(i) || tiles < 16 || !product) return AM_OK;
-  am_attn_args at = {};
-  self_attn_args(h, &at);
+  am_attn_args at = self_attn_args(h);
   if (!h->attn_state)
-    AM_TRY(dev_alloc_t(h, &h->attn_state, (size_t)h->maxB * h->H * pad_to((int64_t)h->maxT * h->maxL, 256) * 132));
+    AM_TRY(dev_alloc_t(h, &h->attn_state, (size_t)h->maxB * h->H * pad_to((int64_t)h->maxT * h->maxL, 256) * STATE_ROW));
   at.rows = 1; at.state_mode = 1; at.state = h->attn_state;
   at.nchunks = 1; at.chunk_first = h->rank; at.chunk_total = h->P;
-  if (h->cfg.attn_fp8) {                       // never a silent bf16 pass on an fp8 handle
-    at.chunk_stride = (int64_t)h->chunk_stride8;
-    if (h->cfg.attn_fp8 == 2) at.defer_log2 = 5400;      /* the exponent-field form of the probabilities (am_attention_fp8) */
-    AM_TRY(am_attention_fp8(&at, h->Q8, h->K8, h->Vt8, stream));
-    ++h->n_attn_fp8;
-  } else {
-    AM_TRY(am_attention_bf16(&at, stream));
-    ++h->n_attn_bf16;
-  }
-  {
-    hipStream_t st = (hipStream_t)stream;
-    TR(7, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * 132 * 4);
-  }
+  AM_TRY(attend(h, at, true, st));
+  TR(TR_ATTN_LOCAL_STATE, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * STATE_ROW * 4);
   h->local_done = true;
   return AM_OK;
 }
@@ -692,80 +717,47 @@ extern "C" int am_layer_post_attn(am_handle h, int i, void* stream) {
   am_layer& l = h->layers[i];
   const int C = h->C, L = h->L, F = h->F;
   const int64_t R = h->R;
-  const float scale = 0.08838834764831845f;   // 1/sqrt(128)
+  const bool inflated = h->inflated(i);
   const bool shared = i == 0 && h->shared_prefix && !h->has_skip(0);
   const int64_t Rs = shared ? R / h->B : R;
   // ---- self-attention (attention_processor.py:133-166) ------------------------
-  am_attn_args at = {};
-  at.Q = h->Qb; at.K = h->Kg; at.Vt = h->Vtg; at.O = h->ao;
-  at.heads = h->H; at.ldo = C; at.scale = scale; at.defer_log2 = h->cfg.attn_defer_log2;
-  if (h->inflated(i) && h->local_done) {
+  if (inflated && h->local_done) {
     // second pass: the full blocks resume from the saved state over the P-1 remote shards (rank+1 .. rank-1, wrapping);
     // the short last block runs one pass over all shards
-    self_attn_args(h, &at);
-    am_attn_args rest = at;
+    am_attn_args rest = self_attn_args(h), at = rest;
     at.rows = 1; at.state_mode = 2; at.state = h->attn_state;
     at.nchunks = h->P - 1; at.chunk_first = (h->rank + 1) % h->P; at.chunk_total = h->P;
     if (am_trace_on()) {
       // the shards the attention really reads: an fp8 handle with P > 1 gathers QUANTISED shards in K8 / Vt8 (Kg / Vtg then hold one
-      // chunk only - ensure_kv - so walking P chunks of them would read out of bounds; ADVICE r03)
+      // chunk only - ensure_kv - so walking P chunks of them would read out of bounds)
       const bool fp8_sharded = h->cfg.attn_fp8 && h->P > 1;
       for (int c = 0; c < h->P; ++c) {
         if (fp8_sharded) {
-          TR(8, i, h->K8 + (size_t)c * h->chunk_stride8, h->chunk_elems);
-          TR(8, i, h->Vt8 + (size_t)c * h->chunk_stride8, h->chunk_elems);
+          TR(TR_KV_CHUNKS, i, h->K8 + (size_t)c * h->chunk_stride8, h->chunk_elems);
+          TR(TR_KV_CHUNKS, i, h->Vt8 + (size_t)c * h->chunk_stride8, h->chunk_elems);
         } else {
-          TR(8, i, h->Kg + (size_t)c * h->chunk_stride, h->chunk_elems * 2);
-          TR(8, i, h->Vtg + (size_t)c * h->chunk_stride, h->chunk_elems * 2);
+          TR(TR_KV_CHUNKS, i, h->Kg + (size_t)c * h->chunk_stride, h->chunk_elems * 2);
+          TR(TR_KV_CHUNKS, i, h->Vtg + (size_t)c * h->chunk_stride, h->chunk_elems * 2);
         }
       }
-      TR(9, i, h->Qb, (size_t)at.nseq * at.heads * at.sq_pad * HD * 2);
-      TR(26, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * 132 * 4);
+      TR(TR_Q_BEFORE_ATTN, i, h->Qb, (size_t)at.nseq * at.heads * at.sq_pad * HD * 2);
+      TR(TR_STATE_BEFORE_RESUME, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * STATE_ROW * 4);
     }
-    if (h->cfg.attn_fp8) {
-      at.chunk_stride = rest.chunk_stride = (int64_t)h->chunk_stride8;
-      if (h->cfg.attn_fp8 == 2) at.defer_log2 = 5400;      /* the exponent-field form of the probabilities (am_attention_fp8) */
-      AM_TRY(am_attention_fp8(&at, h->Q8, h->K8, h->Vt8, st));
-      TR(10, i, h->ao, (size_t)Rs * C * 2);
-      rest.rows = 2;
-      if (h->cfg.attn_fp8 == 2) rest.defer_log2 = 5400;      /* the exponent-field form of the probabilities (am_attention_fp8) */
-      AM_TRY(am_attention_fp8(&rest, h->Q8, h->K8, h->Vt8, st));
-    } else {
-      AM_TRY(am_attention_bf16(&at, st));
-      TR(10, i, h->ao, (size_t)Rs * C * 2);
-      rest.rows = 2;
-      AM_TRY(am_attention_bf16(&rest, st));
-    }
-    TR(11, i, h->ao, (size_t)Rs * C * 2);
+    AM_TRY(attend(h, at, true, st));
+    TR(TR_ATTN_RESUME, i, h->ao, (size_t)Rs * C * 2);
+    rest.rows = 2;
+    AM_TRY(attend(h, rest, true, st));
+    TR(TR_ATTN_LAST_BLOCK, i, h->ao, (size_t)Rs * C * 2);
     h->local_done = false;
   } else {
-    if (h->inflated(i)) {
-      self_attn_args(h, &at);
-    } else {
-      at.nseq = h->B * h->T; at.sq = L; at.sq_pad = pad_to(L, 256);
-      at.sk = L; at.sk_pad = pad_to(L, 64); at.nchunks = 1; at.chunk_stride = 0;
-    }
+    am_attn_args at = inflated ? self_attn_args(h) : frame_attn_args(h, h->Kg, h->Vtg, h->B * h->T, L);
     if (shared) at.nseq /= h->B;                           // row 0's sequences only (they come first in every layout)
-    if (h->cfg.attn_fp8 && h->inflated(i)) {       // fp8 variant of the long-key-stream attention (configs[4]); operands quantised in pre
-      at.chunk_stride = (int64_t)h->chunk_stride8;
-      if (h->cfg.attn_fp8 == 2) at.defer_log2 = 5400;      /* the exponent-field form of the probabilities (am_attention_fp8) */
-      AM_TRY(am_attention_fp8(&at, h->Q8, h->K8, h->Vt8, st));
-      ++h->n_attn_fp8;
-    } else {
-      AM_TRY(am_attention_bf16(&at, st));
-      if (h->inflated(i)) ++h->n_attn_bf16;
-    }
-    TR(12, i, h->ao, (size_t)Rs * C * 2);
+    AM_TRY(attend(h, at, inflated, st));
+    TR(TR_ATTN_ONE_PASS, i, h->ao, (size_t)Rs * C * 2);
   }
-  {   // to_out + residual (block.py:137); with the norms folded, its store loop leaves the row statistics of the new h
-    am_gemm_args go = {};
-    go.A1 = h->ao; go.lda1 = C; go.K1 = C; go.W = l.w_so; go.ldw = C; go.bias = l.b_so; go.residual = h->hsrc;
-    go.C = h->hwork; go.ldc = C; go.M = (int)Rs; go.N = C; go.K = C;
-    if (h->ln_fold) go.ln_part = h->ln_part;
-    AM_TRY(am_gemm_bf16(&go, st));
-    if (h->ln_fold) AM_TRY(finalize_stats(h, h->hwork, 0, Rs, st));
-  }
-  TR(13, i, h->hwork, (size_t)Rs * C * 2);
+  // to_out + residual (block.py:137)
+  AM_TRY(residual_linear(h, h->ao, l.w_so, l.b_so, C, h->hsrc, h->hwork, 0, Rs, true, st));
+  TR(TR_TO_OUT, i, h->hwork, (size_t)Rs * C * 2);
   if (shared)
     for (int b = 1; b < h->B; ++b) {
       AM_HIP(hipMemcpyAsync(h->hwork + (size_t)b * Rs * C, h->hwork, (size_t)Rs * C * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
@@ -776,92 +768,44 @@ extern "C" int am_layer_post_attn(am_handle h, int i, void* stream) {
   // ---- cross-attention to the frame's own context tokens (block.py:146-149) ----
   // Batch rows whose context is identically zero (am_set_branch_hints: the unconditional guidance branch) get the exact
   // result of the branch - h += to_out bias - instead of the branch; the others run it, one contiguous run of rows at a time.
-  {
-    const int64_t R1 = R / h->B;                       // rows of one batch row
-    for (int b0 = 0; b0 < h->B;) {
-      const bool zero = !h->ctx_zero.empty() && h->ctx_zero[b0];
-      int b1 = b0 + 1;
-      while (b1 < h->B && (!h->ctx_zero.empty() && h->ctx_zero[b1]) == zero) ++b1;
-      const int64_t r0 = (int64_t)b0 * R1, nr = (int64_t)(b1 - b0) * R1;
-      bf16_t* hrun = h->hwork + (size_t)r0 * C;
-      if (zero) {
-        if (h->ln_fold) AM_TRY(am_add_bias_rows_stats(hrun, l.b_xo, nr, C, 1e-5f, h->ln_stats + 2 * r0, st));
-        else AM_TRY(am_add_bias_rows(hrun, l.b_xo, nr, C, st));
-        TR(19, i, hrun, (size_t)nr * C * 2);
-      } else {
-        am_gemm_args gx = {};      // cross-attention to_q, fused with its head split
-        if (h->ln_fold) {          // norm_x_attn (block.py:146) inside to_q
-          gx.A1 = hrun; gx.W = l.wf_xq; gx.bias = l.d_xq; gx.ln_stats = h->ln_stats + 2 * r0; gx.ln_colsum = l.cs_xq;
-        } else {
-          AM_TRY(am_layernorm_bf16(hrun, h->z, l.ln_x_w, l.ln_x_b, nr, C, 1e-5f, st));
-          TR(14, i, h->z, (size_t)nr * C * 2);
-          gx.A1 = h->z; gx.W = l.w_xq;
-        }
-        gx.lda1 = C; gx.K1 = C; gx.ldw = C; gx.C = h->qkv; gx.ldc = C;
-        gx.M = (int)nr; gx.N = C; gx.K = C;
-        am_headpost_args hp = {};
-        hp.X = h->qkv; hp.ldx = C; hp.rows = nr; hp.seq_len = L; hp.rows_per_frame = L;
-        hp.heads = h->H; hp.nparts = 1; hp.kinds[0] = 0;
-        hp.w_q = l.x_nq; hp.eps = 1e-6f;
-        hp.out_q = h->Qb; hp.sq_pad = pad_to(L, 256);
-        if (am_trace_on()) {
-          AM_TRY(am_gemm_bf16(&gx, st));
-          TR(15, i, h->qkv, (size_t)nr * C * 2);
-          AM_TRY(am_head_post(&hp, st));
-        } else {
-          AM_TRY(am_gemm_headpost_bf16(&gx, &hp, st));
-        }
-        TR(16, i, h->Qb, (size_t)(b1 - b0) * h->T * h->H * hp.sq_pad * HD * 2);
-        const int Spad = pad_to(h->ctxS, 64);
-        am_attn_args ax = {};
-        ax.Q = h->Qb;
-        ax.K = l.kx + (size_t)b0 * h->T * h->H * Spad * HD;
-        ax.Vt = l.vtx + (size_t)b0 * h->T * h->H * HD * Spad;
-        ax.O = h->ao;
-        ax.nseq = (b1 - b0) * h->T; ax.heads = h->H; ax.sq = L; ax.sq_pad = pad_to(L, 256);
-        ax.sk = h->ctxS; ax.sk_pad = Spad; ax.nchunks = 1; ax.chunk_stride = 0;
-        ax.ldo = C; ax.scale = scale; ax.defer_log2 = h->cfg.attn_defer_log2;
-        AM_TRY(am_attention_bf16(&ax, st));
-        TR(17, i, h->ao, (size_t)nr * C * 2);
-        {
-          am_gemm_args go = {};
-          go.A1 = h->ao; go.lda1 = C; go.K1 = C; go.W = l.w_xo; go.ldw = C; go.bias = l.b_xo; go.residual = hrun;
-          go.C = hrun; go.ldc = C; go.M = (int)nr; go.N = C; go.K = C;
-          if (h->ln_fold) go.ln_part = h->ln_part + 2 * r0 * ceil_div(C, 256);
-          AM_TRY(am_gemm_bf16(&go, st));
-          if (h->ln_fold) AM_TRY(finalize_stats(h, h->hwork, r0, nr, st));
-        }
-        TR(18, i, hrun, (size_t)nr * C * 2);
-      }
-      b0 = b1;
+  const int64_t R1 = R / h->B;                       // rows of one batch row
+  for (int b0 = 0, b1; b0 < h->B; b0 = b1) {
+    const bool zero = !h->ctx_zero.empty() && h->ctx_zero[b0];
+    for (b1 = b0 + 1; b1 < h->B && (!h->ctx_zero.empty() && h->ctx_zero[b1]) == zero;) ++b1;
+    const int64_t r0 = (int64_t)b0 * R1, nr = (int64_t)(b1 - b0) * R1;
+    bf16_t* hrun = h->hwork + (size_t)r0 * C;
+    if (zero) {
+      if (h->ln_fold) AM_TRY(am_add_bias_rows_stats(hrun, l.b_xo, nr, C, LN_EPS, h->ln_stats + 2 * r0, st));
+      else AM_TRY(am_add_bias_rows(hrun, l.b_xo, nr, C, st));
+      TR(TR_X_BIAS_ONLY, i, hrun, (size_t)nr * C * 2);
+      continue;
     }
+    Gemm gx;                   // norm_x_attn (block.py:146) -> to_q -> head split, qk-norm
+    AM_TRY(ln_linear(h, l.xq, hrun, nr, h->ln_stats + 2 * r0, h->qkv, TR_NORM_X, i, st, &gx));
+    am_headpost_args hp = {};
+    hp.X = h->qkv; hp.ldx = C; hp.rows = nr; hp.seq_len = L; hp.rows_per_frame = L;
+    hp.heads = h->H; hp.nparts = 1; hp.kinds[0] = 0;
+    hp.w_q = l.x_nq; hp.eps = QK_EPS;
+    hp.out_q = h->Qb; hp.sq_pad = pad_to(L, 256);
+    AM_TRY(linear_head_split(gx, hp, TR_XQ, i, st));
+    TR(TR_X_HP_Q, i, h->Qb, (size_t)(b1 - b0) * h->T * h->H * hp.sq_pad * HD * 2);
+    const size_t kv0 = (size_t)b0 * h->T * h->H * pad_to(h->ctxS, 64) * HD;      // the run's first frame in the K / V^T cache
+    AM_TRY(attend(h, frame_attn_args(h, l.kx + kv0, l.vtx + kv0, (b1 - b0) * h->T, h->ctxS), false, st));
+    TR(TR_X_ATTN, i, h->ao, (size_t)nr * C * 2);
+    AM_TRY(residual_linear(h, h->ao, l.w_xo, l.b_xo, C, h->hwork, h->hwork, r0, nr, true, st));
+    TR(TR_X_TO_OUT, i, hrun, (size_t)nr * C * 2);
   }
-  // ---- feed-forward (block.py:152; diffusers FeedForward "gelu") ------------------
-  if (h->ln_fold) {          // norm_ff (block.py:152) inside ff.net.0
-    am_gemm_args g1 = {};
-    g1.A1 = h->hwork; g1.lda1 = C; g1.K1 = C; g1.W = l.wf_ff1; g1.ldw = C; g1.bias = l.d_ff1; g1.C = h->ffh; g1.ldc = F;
-    g1.M = (int)R; g1.N = F; g1.K = C; g1.act = 1; g1.ln_stats = h->ln_stats; g1.ln_colsum = l.cs_ff1;
-    AM_TRY(am_gemm_bf16(&g1, st));
-  } else {
-    AM_TRY(am_layernorm_bf16(h->hwork, h->z, l.ln_f_w, l.ln_f_b, R, C, 1e-5f, st));
-    TR(20, i, h->z, (size_t)R * C * 2);
-    AM_TRY(gemm(st, h->z, C, l.w_ff1, C, l.b_ff1, nullptr, h->ffh, F, R, F, C, 1));
-  }
-  TR(21, i, h->ffh, (size_t)R * F * 2);
+  // ---- feed-forward (block.py:152; diffusers FeedForward "gelu"): norm_ff -> ff.net.0 + GELU -> ff.net.2 + residual --------------
+  Gemm g1;
+  AM_TRY(ln_linear(h, l.ff1, h->hwork, R, h->ln_stats, h->ffh, TR_NORM_FF, i, st, &g1));
+  AM_TRY(g1.gelu().run(st));
+  TR(TR_FF1, i, h->ffh, (size_t)R * F * 2);
   bf16_t* dst = h->hwork;
   if (i < h->NL / 2) dst = h->skip[h->skip_top++];     // temporal_denoiser.py:231-232 (kept, not copied)
-  {
-    // the next reader of the row statistics is the next block's norm_s_attn - unless that block starts with its skip linear + norm_skip
-    // (which writes its own); behind the last block the reader is norm_out, folded into proj_out (am_forward_end, round 6)
-    const bool want = h->ln_fold && (i + 1 >= h->NL || !h->has_skip(i + 1));
-    am_gemm_args g2 = {};
-    g2.A1 = h->ffh; g2.lda1 = F; g2.K1 = F; g2.W = l.w_ff2; g2.ldw = F; g2.bias = l.b_ff2; g2.residual = h->hwork;
-    g2.C = dst; g2.ldc = C; g2.M = (int)R; g2.N = C; g2.K = F;
-    if (want) g2.ln_part = h->ln_part;
-    AM_TRY(am_gemm_bf16(&g2, st));
-    if (want) AM_TRY(finalize_stats(h, dst, 0, R, st));
-  }
-  TR(22, i, dst, (size_t)R * C * 2);
+  // the next reader of the row statistics is the next block's norm_s_attn - unless that block starts with its skip linear + norm_skip
+  // (which writes its own); behind the last block the reader is norm_out, folded into proj_out (am_forward_end)
+  AM_TRY(residual_linear(h, h->ffh, l.w_ff2, l.b_ff2, F, h->hwork, dst, 0, R, i + 1 >= h->NL || !h->has_skip(i + 1), st));
+  TR(TR_FF2, i, dst, (size_t)R * C * 2);
   h->hsrc = dst;
   h->next_layer = i + 1;
   h->pre_done = false;
@@ -872,25 +816,13 @@ extern "C" int am_forward_end(am_handle h, uint16_t* v_out, void* stream) {
   AM_CHECK(h && v_out, "am_forward_end: null argument");
   if (!h->in_forward || h->next_layer != h->NL) AM_FAIL(AM_ERR_STATE, "am_forward_end: %d of %d layers run", h->next_layer, h->NL);
   hipStream_t st = (hipStream_t)stream;
-  const int C = h->C;
-  // norm_out -> drop the time token -> proj_out (temporal_denoiser.py:239-242)
-  if (h->ln_fold && h->NL > 0) {
-    // round 6: norm_out inside proj_out like the three LayerNorms of a block - the last ff.net.2 left the row statistics of the
-    // residual stream (am_layer_post_attn: `want`), proj_out reads the un-normalised rows through its row map (time token dropped)
-    // and evaluates rstd (x W'^T - mean colsum) + d in its epilogue; the LayerNorm kernel and its R x C round trip are gone
-    am_gemm_args g = {};
-    g.A1 = h->hsrc; g.lda1 = C; g.K1 = C; g.W = h->wf_out; g.ldw = C; g.bias = h->d_out; g.C = v_out; g.ldc = h->Din;
-    g.M = (int)((int64_t)h->B * h->T * h->N); g.N = h->Din; g.K = C;
-    g.a_G = h->N; g.a_gs = h->L; g.a_off = 1;
-    g.ln_stats = h->ln_stats; g.ln_colsum = h->cs_out;
-    AM_TRY(am_gemm_bf16(&g, st));
-  } else {
-    AM_TRY(am_layernorm_bf16(h->hsrc, h->z, h->ln_o_w, h->ln_o_b, h->R, C, 1e-5f, st));
-    TR(24, 0, h->z, (size_t)h->R * C * 2);
-    AM_TRY(gemm(st, h->z, C, h->w_out, C, h->b_out, nullptr, v_out, h->Din, (int64_t)h->B * h->T * h->N, h->Din, C, 0,
-                nullptr, 0, 0, /*aG*/ h->N, /*ags*/ h->L, /*aoff*/ 1));
-  }
-  TR(25, 0, v_out, (size_t)h->B * h->T * h->N * h->Din * 2);
+  // norm_out -> drop the time token -> proj_out (temporal_denoiser.py:239-242).  Folded like the three LayerNorms of a block: the last
+  // ff.net.2 left the row statistics of the residual stream, proj_out reads the un-normalised rows through its row map.
+  Gemm g;
+  AM_TRY(ln_linear(h, h->out, h->hsrc, h->R, h->ln_stats, v_out, TR_NORM_OUT, 0, st, &g));
+  g.M = (int)((int64_t)h->B * h->T * h->N);
+  AM_TRY(g.a_rows(h->N, h->L, 1).run(st));
+  TR(TR_PROJ_OUT, 0, v_out, (size_t)h->B * h->T * h->N * h->Din * 2);
   h->in_forward = false;
   return AM_OK;
 }

@@ -672,3 +672,39 @@ def test_graph_with_split_cfg_batch_keeps_the_branches_apart(dev, golden_dir):
     v0, fr = gm(x_in[:1], c_in[:1], f_in[:1], tt, mask=m_in[:1])
     v1, _ = gm(x_in[1:], c_in[1:], f_in[1:], tt, mask=m_in[1:], freqs_rot=None)
     assert v0.data_ptr() != v1.data_ptr() and not torch.equal(v0, v1)
+
+
+def test_weight_table_names_counts_and_missing_keys(dev):
+    """am_load_weight / am_weights_missing answer from one weight table (am_model.hip): which state-dict keys a configuration has
+    (layer range, skip layers only from the middle on), how many elements each holds, and how many are still to be loaded."""
+    import ctypes as C
+    from actionmesh_amd.denoiser import HipEngine
+    from oracle import denoiser_oracle as O
+    hp = CASES["tiny_mixed"]
+    sd = O.synthetic_state_dict(O.OracleConfig(**hp), seed=0)
+    held_back = ("blocks.4.linear_skip.weight", "blocks.2.s_attn.to_k.weight", "norm_out.bias")
+    e = HipEngine.__new__(HipEngine)
+    with pytest.raises(RuntimeError, match="3 reference state-dict keys"):      # am_create and the loads have run: the handle is live
+        e.__init__(hp, {k: v for k, v in sd.items() if k not in held_back}, dev, 2, 4, 48, 20)
+    lib, h = e.lib, e.handle
+
+    def load(key, numel=None):
+        w = sd.get(key, torch.zeros(256)).detach().to("cpu", torch.float32).contiguous()
+        status = lib.am_load_weight(h, key.encode(), C.c_void_p(w.data_ptr()), w.numel() if numel is None else numel)
+        return status, lib.am_last_error().decode()
+
+    try:
+        assert lib.am_weights_missing(h) == 3
+        for key in ("blocks.0.norm_zz.weight", "blocks.0.norm_skip.weight", "blocks.5.norm_ff.weight"):
+            status, msg = load(key)                   # no such key; layer 0 has no skip; the configuration has five layers
+            assert status == -4 and f"'{key}'" in msg, (key, status, msg)
+        status, msg = load("blocks.1.s_attn.to_q.weight", 256 * 256 + 1)
+        assert status == -1 and f"expected {256 * 256}" in msg, (status, msg)
+        status, msg = load("blocks.3.norm_skip.bias", 255)
+        assert status == -1 and "expected 256" in msg, (status, msg)
+        assert lib.am_weights_missing(h) == 3         # refused loads count for nothing
+        for n, key in enumerate(held_back):
+            assert load(key)[0] == 0 and lib.am_weights_missing(h) == 2 - n
+        assert load(held_back[0])[0] == 0 and lib.am_weights_missing(h) == 0     # loading a key twice counts once
+    finally:
+        e.close()
