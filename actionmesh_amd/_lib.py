@@ -265,6 +265,18 @@ class AmDecimateApplyArgs(C.Structure):        # am_decimate_apply_args
     ]
 
 
+class AmDecimateBorderQuadricsArgs(C.Structure):       # am_decimate_border_quadrics_args
+    _fields_ = [
+        ("positions", C.c_void_p), ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("n_edges", C.c_int64), ("faces", C.c_void_p),
+        ("offsets", C.c_void_p), ("corners", C.c_void_p), ("half_edge_to_edge", C.c_void_p), ("edge_count", C.c_void_p),
+        ("border_weight", C.c_double), ("out_quadrics", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
+class AmDecimateBorderEdgesArgs(C.Structure):  # am_decimate_border_edges_args: the fields of am_decimate_edges_args
+    _fields_ = list(AmDecimateEdgesArgs._fields_)
+
+
 ISO_BAD_VERTEX_OFFSET, ISO_BAD_TRI_OFFSET, ISO_BAD_TABLE = 1, 2, 4      # am_iso_vertices' / am_iso_triangles' out_flag bits
 
 
@@ -351,6 +363,7 @@ STRUCTS = {
     "am_face_areas_args": AmFaceAreasArgs, "am_surface_sample_args": AmSurfaceSampleArgs,
     "am_decimate_quadrics_args": AmDecimateQuadricsArgs, "am_decimate_edges_args": AmDecimateEdgesArgs,
     "am_decimate_select_args": AmDecimateSelectArgs, "am_decimate_apply_args": AmDecimateApplyArgs,
+    "am_decimate_border_quadrics_args": AmDecimateBorderQuadricsArgs, "am_decimate_border_edges_args": AmDecimateBorderEdgesArgs,
     "am_iso_classify_args": AmIsoClassifyArgs, "am_iso_vertices_args": AmIsoVerticesArgs, "am_iso_triangles_args": AmIsoTrianglesArgs,
     "am_dmc_cells_args": AmDmcCellsArgs, "am_dmc_classify_args": AmDmcClassifyArgs, "am_dmc_vertices_args": AmDmcVerticesArgs,
     "am_dmc_triangles_args": AmDmcTrianglesArgs,
@@ -409,6 +422,8 @@ SYMBOLS = {
     "am_decimate_edges": (C.c_int, [C.POINTER(AmDecimateEdgesArgs), _P]),
     "am_decimate_select": (C.c_int, [C.POINTER(AmDecimateSelectArgs), _P]),
     "am_decimate_apply": (C.c_int, [C.POINTER(AmDecimateApplyArgs), _P]),
+    "am_decimate_border_quadrics": (C.c_int, [C.POINTER(AmDecimateBorderQuadricsArgs), _P]),
+    "am_decimate_border_edges": (C.c_int, [C.POINTER(AmDecimateBorderEdgesArgs), _P]),
     "am_iso_classify": (C.c_int, [C.POINTER(AmIsoClassifyArgs), _P]),
     "am_iso_vertices": (C.c_int, [C.POINTER(AmIsoVerticesArgs), _P]),
     "am_iso_triangles": (C.c_int, [C.POINTER(AmIsoTrianglesArgs), _P]),

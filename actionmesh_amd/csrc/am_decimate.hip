@@ -6,6 +6,8 @@
 //   am_decimate_quadrics   one thread per vertex: the area-weighted plane quadrics of its faces, summed in CSR order (a gather)
 //   am_decimate_edges      one thread per edge: lock and link tests, the Cramer solve or the u / v / midpoint fallback, the cost,
 //                          the no-flip test over both stars, the 64-bit key
+//   am_decimate_border_quadrics, am_decimate_border_edges   the same two for `borders="collapse"`: border planes in the gather, the
+//                          three vertex classes and the coned link condition in the tests; position, cost, flips and key are shared
 //   am_decimate_select     one thread per vertex, twice (m1: min key of its edges; m2: min of m1 over its closed neighbourhood), then
 //                          one thread per edge (selected iff its key is m2 at both ends)
 //   am_decimate_apply      one thread per kept edge: moves u, adds the quadrics, rewrites v -> u in v's corners, marks the two faces
@@ -49,6 +51,15 @@ __device__ bool adjacent(const mesh_view& m, int v, int begin, int end, int w) {
   return found;
 }
 
+// Q[i,j] += (w * P[i]) * P[j] over the upper triangle, P = (n, d)
+__device__ __forceinline__ void add_plane(double* q, vec3 n, double d, double w) {
+#pragma clang fp contract(off)
+  const double p[4] = {n.x, n.y, n.z, d};
+  int t = 0;
+  for (int a = 0; a < 4; ++a)
+    for (int b = a; b < 4; ++b, ++t) q[t] = q[t] + (w * p[a]) * p[b];
+}
+
 __global__ __launch_bounds__(MESH_THREADS) void decimate_quadrics_kernel(mesh_view m, const double* __restrict__ positions,
                                                                          double* __restrict__ out_quadrics) {
 #pragma clang fp contract(off)
@@ -70,10 +81,7 @@ __global__ __launch_bounds__(MESH_THREADS) void decimate_quadrics_kernel(mesh_vi
     const vec3 n = div3(cr, len);
     const double d = -dot3(n, p0);
     const double w = len / 2.0;
-    const double p[4] = {n.x, n.y, n.z, d};
-    int t = 0;
-    for (int a = 0; a < 4; ++a)
-      for (int b = a; b < 4; ++b, ++t) q[t] = q[t] + (w * p[a]) * p[b];
+    add_plane(q, n, d, w);
   }
   for (int i = 0; i < 10; ++i) out_quadrics[v * 10 + i] = q[i];
 }
@@ -148,6 +156,51 @@ __device__ bool walk_flips(const mesh_view& m, const double* __restrict__ positi
   return ok;
 }
 
+// Where a collapse of { u, v } puts the surviving vertex, and what it costs: the Cramer solve on Q_u + Q_v under the conditioning and
+// reach rules, else the cheapest of u, v and the midpoint (ties in that order).
+__device__ __forceinline__ void place(const double* __restrict__ quadrics, const double* __restrict__ positions, int u, int v, vec3& x,
+                                      double& cost) {
+#pragma clang fp contract(off)
+  double q[10];
+  for (int i = 0; i < 10; ++i) q[i] = quadrics[(int64_t)u * 10 + i] + quadrics[(int64_t)v * 10 + i];
+  const vec3 pu = load3(positions, u), pv = load3(positions, v);
+  const vec3 mid = {(pu.x + pv.x) * 0.5, (pu.y + pv.y) * 0.5, (pu.z + pv.z) * 0.5};
+  const vec3 E = sub3(pv, pu);
+  const double a = q[0], b = q[1], c = q[2], d = q[4], ee = q[5], f = q[7];
+  const double r0 = -q[3], r1 = -q[6], r2 = -q[8];
+  const double m0 = d * f - ee * ee, m1 = b * f - ee * c, m2 = b * ee - d * c;
+  const double det = (a * m0 - b * m1) + c * m2;
+  const double s = r1 * f - ee * r2, t = r1 * ee - d * r2, g = b * r2 - r1 * c;
+  const double dx = (r0 * m0 - b * s) + c * t;
+  const double dy = (a * s - r0 * m1) + c * g;
+  const double dz = (a * (d * r2 - r1 * ee) - b * g) + r0 * m2;
+  const double tr = (a + d) + f;
+  bool solved = false;
+  if (fabs(det) > AM_DECIMATE_COND * ((tr * tr) * tr)) {
+    const vec3 y = {dx / det, dy / det, dz / det};
+    const vec3 off = sub3(y, mid);
+    if (dot3(off, off) <= AM_DECIMATE_REACH * dot3(E, E)) {
+      x = y;
+      cost = quadric_cost(q, y);
+      solved = true;
+    }
+  }
+  if (!solved) {
+    x = pu;
+    cost = quadric_cost(q, pu);
+    const double cv = quadric_cost(q, pv), cm = quadric_cost(q, mid);
+    if (cv < cost) {
+      x = pv;
+      cost = cv;
+    }
+    if (cm < cost) {
+      x = mid;
+      cost = cm;
+    }
+  }
+  cost = cost > 0.0 ? cost : 0.0;
+}
+
 __global__ __launch_bounds__(MESH_THREADS) void decimate_edges_kernel(mesh_view m, const double* __restrict__ positions,
                                                                       const double* __restrict__ quadrics,
                                                                       const int32_t* __restrict__ edge_count,
@@ -184,45 +237,186 @@ __global__ __launch_bounds__(MESH_THREADS) void decimate_edges_kernel(mesh_view 
          m.offsets[a1 + 1] - m.offsets[a1] > 3;
   }
   if (ok) {
-    double q[10];
-    for (int i = 0; i < 10; ++i) q[i] = quadrics[(int64_t)u * 10 + i] + quadrics[(int64_t)v * 10 + i];
-    const vec3 pu = load3(positions, u), pv = load3(positions, v);
-    const vec3 mid = {(pu.x + pv.x) * 0.5, (pu.y + pv.y) * 0.5, (pu.z + pv.z) * 0.5};
-    const vec3 E = sub3(pv, pu);
-    const double a = q[0], b = q[1], c = q[2], d = q[4], ee = q[5], f = q[7];
-    const double r0 = -q[3], r1 = -q[6], r2 = -q[8];
-    const double m0 = d * f - ee * ee, m1 = b * f - ee * c, m2 = b * ee - d * c;
-    const double det = (a * m0 - b * m1) + c * m2;
-    const double s = r1 * f - ee * r2, t = r1 * ee - d * r2, g = b * r2 - r1 * c;
-    const double dx = (r0 * m0 - b * s) + c * t;
-    const double dy = (a * s - r0 * m1) + c * g;
-    const double dz = (a * (d * r2 - r1 * ee) - b * g) + r0 * m2;
-    const double tr = (a + d) + f;
-    bool solved = false;
-    if (fabs(det) > AM_DECIMATE_COND * ((tr * tr) * tr)) {
-      const vec3 y = {dx / det, dy / det, dz / det};
-      const vec3 off = sub3(y, mid);
-      if (dot3(off, off) <= AM_DECIMATE_REACH * dot3(E, E)) {
-        x = y;
-        cost = quadric_cost(q, y);
-        solved = true;
-      }
-    }
-    if (!solved) {
-      x = pu;
-      cost = quadric_cost(q, pu);
-      const double cv = quadric_cost(q, pv), cm = quadric_cost(q, mid);
-      if (cv < cost) {
-        x = pv;
-        cost = cv;
-      }
-      if (cm < cost) {
-        x = mid;
-        cost = cm;
-      }
-    }
-    cost = cost > 0.0 ? cost : 0.0;
+    place(quadrics, positions, u, v, x, cost);
     const bool fu = walk_flips(m, positions, u, ub, ue, v, apex[0], apex[1], x);
+    const bool fv = walk_flips(m, positions, v, vb, ve, u, apex[0], apex[1], x);
+    if (fu && fv) key = (int64_t)(((uint64_t)__float_as_uint((float)cost) << 32) | (uint64_t)mix32((uint32_t)e));
+  }
+  out_positions[3 * e] = x.x;
+  out_positions[3 * e + 1] = x.y;
+  out_positions[3 * e + 2] = x.z;
+  out_cost[e] = cost;
+  out_key[e] = key;
+}
+
+// ---- border collapses (the header's "Border collapses"): the two kernels that take the places of the two above -------------------------
+
+// the edge index of half-edge h where only the half-edge table is known; -1 (flag raised) when it is outside [0, n_edges)
+__device__ __forceinline__ int edge_index(const mesh_view& m, int h) {
+  const int e = m.he2e[h];
+  if (!in_range(e, m.n_edges)) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+    return -1;
+  }
+  return e;
+}
+
+// the count of edge e (inside [0, n_edges)); a count below 1 raises the flag: every edge of the table has a half-edge
+__device__ __forceinline__ int count_of(const mesh_view& m, const int32_t* __restrict__ edge_count, int e) {
+  const int n = edge_count[e];
+  if (n < 1) atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+  return n;
+}
+
+// one constraint plane of the border half-edge p -> q of a face with unit normal n
+__device__ __forceinline__ void add_border_plane(double* q, vec3 p, vec3 pq, vec3 n, double border_weight) {
+#pragma clang fp contract(off)
+  const vec3 E = sub3(pq, p);
+  vec3 mm = cross3(E, n);
+  const double ml = norm3(mm);
+  if (!(ml > AM_MESH_ZERO)) return;
+  mm = div3(mm, ml);
+  const double d = -dot3(mm, p);
+  add_plane(q, mm, d, border_weight * dot3(E, E));
+}
+
+__global__ __launch_bounds__(MESH_THREADS) void decimate_border_quadrics_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                                const int32_t* __restrict__ edge_count,
+                                                                                double border_weight, double* __restrict__ out_quadrics) {
+#pragma clang fp contract(off)
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
+  if (v >= m.n_vertices) return;
+  double q[10];
+  for (int i = 0; i < 10; ++i) q[i] = 0.0;
+  int begin, end;
+  csr_range(m, (int)v, begin, end);
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, (int)v);
+    if (c < 0) continue;
+    const int f3 = c - c % 3, k = c % 3;
+    int i[3];
+    if (!face_indices(m.faces + f3, m.n_vertices, m.flag, i[0], i[1], i[2])) continue;
+    const vec3 p0 = load3(positions, i[0]), p1 = load3(positions, i[1]), p2 = load3(positions, i[2]);
+    const vec3 cr = cross3(sub3(p1, p0), sub3(p2, p0));
+    const double len = norm3(cr);
+    if (!(len > AM_MESH_ZERO)) continue;
+    const vec3 n = div3(cr, len);
+    add_plane(q, n, -dot3(n, p0), len / 2.0);
+    const int hin = f3 + (k + 2) % 3;
+    const int eout = edge_index(m, c), ein = edge_index(m, hin);
+    const vec3 ps = load3(positions, (int)v);
+    if (eout >= 0 && count_of(m, edge_count, eout) == 1) add_border_plane(q, ps, load3(positions, i[(k + 1) % 3]), n, border_weight);
+    if (ein >= 0 && count_of(m, edge_count, ein) == 1) add_border_plane(q, load3(positions, i[(k + 2) % 3]), ps, n, border_weight);
+  }
+  for (int i = 0; i < 10; ++i) out_quadrics[v * 10 + i] = q[i];
+}
+
+// What one walk over the corners of an endpoint finds.
+struct border_star {
+  int n_border = 0;        // count-1 edges at the vertex
+  int n_faces = 0;         // faces that hold the partner
+  int n_half = 0;          // half-edges between the vertex and the partner
+  int apex_border = 0;     // faces that hold the partner whose edge from the vertex to the apex has count 1
+  int shared = 0;          // the header's weighted count of neighbours that are the partner's too
+  bool plain = true;       // every count is 1 or 2
+  bool sound = true;       // no table entry was refused
+};
+
+// One walk over the corners of endpoint s (partner o): the class of s and - on u's side, with v's range - the link counts.
+__device__ border_star walk_border_topology(const mesh_view& m, const int32_t* __restrict__ edge_count, int s, int begin, int end, int o,
+                                            bool count_link, int obegin, int oend, int* apex) {
+  border_star t;
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, s);
+    if (c < 0) {
+      t.sound = false;
+      continue;
+    }
+    int w1, w2;
+    if (!corner_others(m, c, w1, w2)) {
+      t.sound = false;
+      continue;
+    }
+    const int f3 = c - c % 3, k = c % 3;
+    const int e1 = edge_of(m, c, s, w1), e2 = edge_of(m, f3 + (k + 2) % 3, w2, s);
+    if (e1 < 0 || e2 < 0) {
+      t.sound = false;
+      continue;
+    }
+    const int c1 = count_of(m, edge_count, e1), c2 = count_of(m, edge_count, e2);
+    t.plain = t.plain && (c1 == 1 || c1 == 2) && (c2 == 1 || c2 == 2);
+    t.n_border += (c1 == 1) + (c2 == 1);
+    t.n_half += (w1 == o) + (w2 == o);
+    if (w1 == o || w2 == o) {
+      if (count_link && t.n_faces < 2) apex[t.n_faces] = w1 == o ? w2 : w1;
+      ++t.n_faces;
+      t.apex_border += (w1 == o ? c2 : c1) == 1;
+    }
+    if (!count_link) continue;
+    if (w1 != o && adjacent(m, o, obegin, oend, w1)) t.shared += c1 == 1 ? 2 : 1;
+    if (w2 != o && adjacent(m, o, obegin, oend, w2)) t.shared += c2 == 1 ? 2 : 1;
+  }
+  return t;
+}
+
+// Is the coned valence of apex a above 3?  Its face count, plus 2 when it is a border vertex: only an apex of two or three faces is walked.
+__device__ bool apex_valence(const mesh_view& m, const int32_t* __restrict__ edge_count, int a) {
+  int begin, end;
+  if (!csr_range(m, a, begin, end)) return false;
+  if (end - begin > 3) return true;
+  if (end - begin < 2) return false;
+  int apex[2];
+  const border_star t = walk_border_topology(m, edge_count, a, begin, end, -1, false, 0, 0, apex);
+  return t.sound && t.plain && t.n_border == 2;
+}
+
+__global__ __launch_bounds__(MESH_THREADS) void decimate_border_edges_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                             const double* __restrict__ quadrics,
+                                                                             const int32_t* __restrict__ edge_count,
+                                                                             double* __restrict__ out_positions,
+                                                                             double* __restrict__ out_cost, int64_t* __restrict__ out_key) {
+#pragma clang fp contract(off)
+  const int64_t e = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
+  if (e >= m.n_edges) return;
+  const int u = m.edges[2 * e], v = m.edges[2 * e + 1];
+  vec3 x = {0.0, 0.0, 0.0};
+  double cost = 0.0;
+  int64_t key = NO_KEY;
+  bool ok = true;
+  if (!in_range(u, m.n_vertices) || !in_range(v, m.n_vertices) || u > v) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+    ok = false;
+  }
+  const int count = count_of(m, edge_count, (int)e);
+  ok = ok && u != v;
+  int ub = 0, ue = 0, vb = 0, ve = 0;
+  if (ok) {
+    const bool ru = csr_range(m, u, ub, ue), rv = csr_range(m, v, vb, ve);
+    ok = ru && rv;
+  }
+  int apex[2] = {-1, -1};
+  if (ok) {
+    const border_star su = walk_border_topology(m, edge_count, u, ub, ue, v, true, vb, ve, apex);
+    if (su.sound && su.n_half != count) atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+    ok = su.sound && su.n_half == count && (count == 1 || count == 2) && su.plain && (su.n_border == 0 || su.n_border == 2);
+    if (ok) {
+      const border_star sv = walk_border_topology(m, edge_count, v, vb, ve, u, false, 0, 0, apex);
+      ok = sv.sound && sv.plain && (sv.n_border == 0 || sv.n_border == 2) && su.n_faces == count && su.shared == 2 * count;
+      ok = ok && ((ue - ub) + su.n_border) + ((ve - vb) + sv.n_border) - 4 > 3;        // the merged vertex's coned valence
+      if (count == 2)
+        ok = ok && !(su.n_border == 2 && sv.n_border == 2);
+      else
+        ok = ok && su.apex_border + sv.apex_border < 2;
+    }
+  }
+  if (ok) {
+    const int a0 = apex[0], a1 = apex[1];           // a0, and a1 of an interior edge, inside [0, n_vertices): corner_others checked them
+    ok = a0 != u && a0 != v && apex_valence(m, edge_count, a0);
+    if (count == 2) ok = ok && a0 != a1 && a1 != u && a1 != v && apex_valence(m, edge_count, a1);
+  }
+  if (ok) {
+    place(quadrics, positions, u, v, x, cost);
+    const bool fu = walk_flips(m, positions, u, ub, ue, v, apex[0], apex[1], x);       // apex[1] of a border edge is -1: no face holds it
     const bool fv = walk_flips(m, positions, v, vb, ve, u, apex[0], apex[1], x);
     if (fu && fv) key = (int64_t)(((uint64_t)__float_as_uint((float)cost) << 32) | (uint64_t)mix32((uint32_t)e));
   }
@@ -340,6 +534,39 @@ extern "C" int am_decimate_edges(const am_decimate_edges_args* a, void* stream) 
   const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
   AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
   hipLaunchKernelGGL(decimate_edges_kernel, dim3(mesh_blocks(a->n_edges)), dim3(MESH_THREADS), 0, st, m, a->positions, a->quadrics,
+                     a->edge_count, a->out_positions, a->out_cost, a->out_key);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+extern "C" int am_decimate_border_quadrics(const am_decimate_border_quadrics_args* a, void* stream) {
+  AM_CHECK(a != nullptr, "am_decimate_border_quadrics: null arguments");
+  AM_TRY(check_mesh("am_decimate_border_quadrics", a->n_vertices, a->n_faces));
+  AM_TRY(check_edges("am_decimate_border_quadrics", a->n_edges));
+  AM_CHECK(a->positions && a->faces && a->offsets && a->corners && a->half_edge_to_edge && a->edge_count && a->out_quadrics && a->out_flag,
+           "am_decimate_border_quadrics: null pointer");
+  AM_CHECK(a->border_weight >= 0.0 && a->border_weight <= 1.7976931348623157e308,          // a NaN fails the first, an infinity the second
+           "am_decimate_border_quadrics: border_weight %g is not finite and >= 0", a->border_weight);
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, nullptr, a->half_edge_to_edge, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(decimate_border_quadrics_kernel, dim3(mesh_blocks(a->n_vertices)), dim3(MESH_THREADS), 0, st, m, a->positions,
+                     a->edge_count, a->border_weight, a->out_quadrics);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+extern "C" int am_decimate_border_edges(const am_decimate_border_edges_args* a, void* stream) {
+  AM_CHECK(a != nullptr, "am_decimate_border_edges: null arguments");
+  AM_TRY(check_mesh("am_decimate_border_edges", a->n_vertices, a->n_faces));
+  AM_TRY(check_edges("am_decimate_border_edges", a->n_edges));
+  AM_CHECK(a->positions && a->quadrics && a->faces && a->offsets && a->corners && a->edges && a->half_edge_to_edge && a->edge_count &&
+               a->out_positions && a->out_cost && a->out_key && a->out_flag,
+           "am_decimate_border_edges: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(decimate_border_edges_kernel, dim3(mesh_blocks(a->n_edges)), dim3(MESH_THREADS), 0, st, m, a->positions, a->quadrics,
                      a->edge_count, a->out_positions, a->out_cost, a->out_key);
   AM_HIP(hipGetLastError());
   return AM_OK;

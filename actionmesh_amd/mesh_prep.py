@@ -137,23 +137,26 @@ def merge_and_clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, return_ind
 
 
 def process_mesh(vertices: torch.Tensor, faces: torch.Tensor, face_decimation: int = -1, floaters_threshold: float = 0.0,
-                 decimation: Optional[str] = None):
+                 decimation: Optional[str] = None, decimate_borders: str = "fixed"):
     """`MeshPostprocessor.process_mesh` on tensors, in the reference's order: the four clean-up steps of `merge_and_clean_mesh`, the
     quadric decimation to `face_decimation` faces, then - as the reference, only with floaters_threshold > 0 -
     `mesh_cleanup.remove_floaters`.  Returns (vertices, faces).  `decimation` says who decimates: None (the default) nobody - a
     `face_decimation` other than -1 below the mesh's face count then raises NotImplementedError (at or above it the reference skips
     the decimation too); "hip": `mesh_decimate.decimate_mesh`, rounds of parallel edge collapses on the mesh's device (not the
-    reference's `fast_simplification` schedule: mesh_decimate.py)."""
+    reference's `fast_simplification` schedule: mesh_decimate.py).  `decimate_borders` is its `borders`: "fixed" (the default) never
+    moves a border vertex, "collapse" lets an open mesh reach the target too."""
     check_mesh(vertices, faces, "process_mesh")
     if decimation not in (None, "hip"):
         raise ValueError(f"process_mesh: decimation must be None or 'hip', got {decimation!r}")
+    if decimate_borders not in ("fixed", "collapse"):
+        raise ValueError(f"process_mesh: decimate_borders must be 'fixed' or 'collapse', got {decimate_borders!r}")
     vertices, faces, _, _ = _clean(vertices, faces)
     if face_decimation != -1 and faces.shape[0] > face_decimation:
         if decimation is None:
             raise NotImplementedError(f"process_mesh: face_decimation={face_decimation} asks for quadric decimation of a mesh of "
                                       f"{faces.shape[0]} faces; pass decimation='hip' for it, or face_decimation=-1")
         from . import mesh_decimate
-        vertices, faces = mesh_decimate.decimate_mesh(vertices, faces, target_faces=face_decimation)
+        vertices, faces = mesh_decimate.decimate_mesh(vertices, faces, target_faces=face_decimation, borders=decimate_borders)
     if floaters_threshold > 0.0:
         vertices, faces = mesh_cleanup.remove_floaters(vertices, faces, threshold=floaters_threshold)
     return vertices, faces

@@ -7,6 +7,7 @@ parity tests and by the attention-processor seam (S3).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -1107,18 +1108,12 @@ def decimate_quadrics(positions: torch.Tensor, faces: torch.Tensor, topology, ou
     return out
 
 
-def decimate_edges(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch.Tensor, topology, edges: torch.Tensor,
-                   half_edge_to_edge: torch.Tensor, edge_count: torch.Tensor, out_positions: Optional[torch.Tensor] = None,
-                   out_cost: Optional[torch.Tensor] = None, out_key: Optional[torch.Tensor] = None,
-                   flag: Optional[torch.Tensor] = None):
-    """am_decimate_edges: for every undirected edge (E, 2) int32 of the live faces, the position a collapse would give the
-    surviving vertex (E, 3) fp64, its quadric cost (E,) fp64, and the int64 key (E,) - `_lib.DECIMATE_NO_KEY` where the edge is not a
-    candidate (the tests are the header's).  half_edge_to_edge (3 F,) and edge_count (E,) int32.  `flag` as in decimate_quadrics."""
-    what = "decimate_edges"
+def _decimate_edges(what: str, entry: str, a, positions, quadrics, faces, topology, edges, half_edge_to_edge, edge_count, out_positions,
+                    out_cost, out_key, flag):
+    """decimate_edges and decimate_border_edges: the same operands, checks and outputs behind two entry points."""
     V, dev = _positions(what, positions)
     _shaped(f"{what}: quadrics", quadrics, torch.float64, (V, 10), dev)
     F = _decimate_mesh(what, faces, topology, V, dev)
-    a = L.AmDecimateEdgesArgs()
     E = _decimate_edge_tables(what, a, edges, half_edge_to_edge, F, dev)
     a.edge_count = _shaped(f"{what}: edge_count", edge_count, torch.int32, (E,), dev).data_ptr()
     cand = _out(f"{what}: out_positions", out_positions, (E, 3), torch.float64, dev)
@@ -1128,9 +1123,58 @@ def decimate_edges(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch
     a.positions, a.quadrics, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), quadrics.data_ptr(), V, F, faces.data_ptr()
     a.offsets, a.corners = topology.offsets.data_ptr(), topology.corners.data_ptr()
     a.out_positions, a.out_cost, a.out_key, a.out_flag = cand.data_ptr(), cost.data_ptr(), key.data_ptr(), flag.data_ptr()
-    _call(positions, None, "am_decimate_edges", C.byref(a))
+    _call(positions, None, entry, C.byref(a))
     _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
     return cand, cost, key
+
+
+def decimate_edges(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch.Tensor, topology, edges: torch.Tensor,
+                   half_edge_to_edge: torch.Tensor, edge_count: torch.Tensor, out_positions: Optional[torch.Tensor] = None,
+                   out_cost: Optional[torch.Tensor] = None, out_key: Optional[torch.Tensor] = None,
+                   flag: Optional[torch.Tensor] = None):
+    """am_decimate_edges: for every undirected edge (E, 2) int32 of the live faces, the position a collapse would give the
+    surviving vertex (E, 3) fp64, its quadric cost (E,) fp64, and the int64 key (E,) - `_lib.DECIMATE_NO_KEY` where the edge is not a
+    candidate (the tests are the header's).  half_edge_to_edge (3 F,) and edge_count (E,) int32.  `flag` as in decimate_quadrics."""
+    return _decimate_edges("decimate_edges", "am_decimate_edges", L.AmDecimateEdgesArgs(), positions, quadrics, faces, topology, edges,
+                           half_edge_to_edge, edge_count, out_positions, out_cost, out_key, flag)
+
+
+def decimate_border_quadrics(positions: torch.Tensor, faces: torch.Tensor, topology, half_edge_to_edge: torch.Tensor,
+                             edge_count: torch.Tensor, border_weight: float = 1.0, out: Optional[torch.Tensor] = None,
+                             flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """am_decimate_border_quadrics: decimate_quadrics plus, for every half-edge whose edge has count 1, one constraint plane through
+    the edge and perpendicular to its face, weighted border_weight * |edge|^2 (finite, >= 0), in the header's order.
+    half_edge_to_edge (3 F,) and edge_count (E,) int32 are `mesh_topology.EdgeTables`'.  `flag` as in decimate_quadrics."""
+    what = "decimate_border_quadrics"
+    V, dev = _positions(what, positions)
+    F = _decimate_mesh(what, faces, topology, V, dev)
+    border_weight = float(border_weight)
+    if not (math.isfinite(border_weight) and border_weight >= 0.0):
+        raise ValueError(f"{what}: border_weight {border_weight} is not finite and >= 0")
+    if not isinstance(edge_count, torch.Tensor) or edge_count.dim() != 1 or edge_count.numel() < 1:
+        raise ValueError(f"{what}: expected a non-empty (E,) edge_count, got {tuple(getattr(edge_count, 'shape', ()))}")
+    E = edge_count.numel()
+    a = L.AmDecimateBorderQuadricsArgs()
+    a.n_edges, a.border_weight = E, border_weight
+    a.edge_count = _shaped(f"{what}: edge_count", edge_count, torch.int32, (E,), dev).data_ptr()
+    a.half_edge_to_edge = _shaped(f"{what}: half_edge_to_edge", half_edge_to_edge, torch.int32, (3 * F,), dev).data_ptr()
+    out = _out(f"{what}: out", out, (V, 10), torch.float64, dev)
+    flag, own = _flag_word(what, flag, dev)
+    a.positions, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), V, F, faces.data_ptr()
+    a.offsets, a.corners, a.out_quadrics, a.out_flag = topology.offsets.data_ptr(), topology.corners.data_ptr(), out.data_ptr(), flag.data_ptr()
+    _call(positions, None, "am_decimate_border_quadrics", C.byref(a))
+    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
+    return out
+
+
+def decimate_border_edges(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch.Tensor, topology, edges: torch.Tensor,
+                          half_edge_to_edge: torch.Tensor, edge_count: torch.Tensor, out_positions: Optional[torch.Tensor] = None,
+                          out_cost: Optional[torch.Tensor] = None, out_key: Optional[torch.Tensor] = None,
+                          flag: Optional[torch.Tensor] = None):
+    """am_decimate_border_edges: decimate_edges with the header's border rule - border vertices move along their border, border
+    edges collapse - for the same operands and outputs.  An edge_count that the faces contradict raises the flag's edge bit."""
+    return _decimate_edges("decimate_border_edges", "am_decimate_border_edges", L.AmDecimateBorderEdgesArgs(), positions, quadrics, faces,
+                           topology, edges, half_edge_to_edge, edge_count, out_positions, out_cost, out_key, flag)
 
 
 def decimate_select(n_vertices: int, faces: torch.Tensor, topology, edges: torch.Tensor, half_edge_to_edge: torch.Tensor,

@@ -1030,6 +1030,99 @@ typedef struct {
 } am_decimate_apply_args;
 int am_decimate_apply(const am_decimate_apply_args* args, void* stream);
 
+/* Border collapses (`borders="collapse"` of mesh_decimate.py): am_decimate_border_quadrics and am_decimate_border_edges take the
+ * places of am_decimate_quadrics and am_decimate_edges in the round above; am_decimate_select and am_decimate_apply serve as they
+ * are (the selection's independence does not depend on borders, and apply marks dead exactly the faces of v that hold u: two for an
+ * interior edge, one for a border edge).  Tables, arithmetic rules, flag bits and the restatement (tests/_decimate_border_ref.py,
+ * tests/test_mesh_decimate_border_*) are those of the text above.  On a mesh without border every output equals the old kernels' bits.
+ *
+ * VERTEX CLASSES, from edge_count over the half-edges 3 f + k and 3 f + (k + 2) % 3 of every corner 3 f + k of the vertex (an edge
+ * of count 2 is met twice, one of count 1 once):
+ *   interior  every such count is 2;
+ *   border    every such count is 1 or 2, and exactly two of them are 1;
+ *   locked    anything else: a count above 2, or a number of count-1 edges other than 0 or 2.  Never moved or removed.
+ *
+ * TOPOLOGY, the rule.  Close the surface with a cone: one imaginary vertex W and one imaginary face (q, p, W) for every half-edge
+ * p -> q of count 1.  In that complex the `opposite` vertices of an edge { u, v } are the third vertices of its faces: two real
+ * apexes for an edge of count 2, one real apex and W for an edge of count 1.  An edge with u < v, edge_count 1 or 2 and two
+ * endpoints that are not locked passes when, in the coned complex,
+ *   (a) the common neighbours of u and v are exactly the opposite vertices, and those two differ (neither is u or v);
+ *   (b) no edge lies in the link of u and in the link of v: for the pair { apex, W } that is "the faces (u, apex, W) and (v, apex, W)
+ *       do not both exist"; for two real apexes the rule stays today's stricter one, no OTHER face of u or v holds both apexes;
+ *   (c) every real apex has coned valence > 3: its face count offsets[a + 1] - offsets[a], plus 2 when it is a border vertex
+ *       (a locked apex counts its real faces only);
+ *   (d) the merged vertex keeps coned valence > 3: (coned valence of u) + (coned valence of v) - 4 > 3.  Under (a) to (c) this always
+ *       holds between two interior vertices (today's (b) never removes a vertex of three faces); on a border it keeps a collapse
+ *       from leaving an isolated triangle: the two-triangle strip, whose coned complex is two glued tetrahedra, comes back whole as
+ *       that closed mesh does today.
+ * The cases that follow, which the kernel carries (n_faces(u, v): the faces of u that hold v; a neighbour w of u is met once per
+ * face of u that holds it, so `shared` below weighs a neighbour met through a count-1 edge { u, w } twice):
+ *   every edge                               (d), with the endpoints' classes and face counts offsets[s + 1] - offsets[s];
+ *   edge_count[e] == 2, u and v interior     today's rule, unchanged: n_faces == 2, shared == 4, (b), (c);
+ *   edge_count[e] == 2, one endpoint border  the same tests; the merged vertex is a border vertex;
+ *   edge_count[e] == 2, both border          never: W is a common neighbour and not opposite (the collapse would pinch the surface);
+ *   edge_count[e] == 1                       n_faces == 1, shared == 2 (the apex and nobody else: on a border loop of three edges
+ *                                            the other border neighbours of u and v coincide, are shared and are not the apex),
+ *                                            not both { u, apex } and { v, apex } of count 1 (the face would be an isolated
+ *                                            triangle), (c).  An ear - a border vertex of one face whose third edge is interior -
+ *                                            collapses along either of its border edges and takes its face with it, (d) allowing.
+ *   shared = the sum, over the corners of u and over both neighbours w != v of the corner that are also neighbours of v, of
+ *            (edge_count{ u, w } == 1 ? 2 : 1).
+ * The number of half-edges { u, v } met over the corners of u must equal edge_count[e] (AM_DECIMATE_BAD_EDGE otherwise, and so
+ * is a count below 1).
+ *
+ * am_decimate_border_quadrics, per vertex: Q = 0; for each corner 3 f + k of the vertex in CSR order: FIRST the face's plane exactly
+ * as am_decimate_quadrics adds it (a face with len <= AM_MESH_ZERO adds nothing, its border planes included), THEN, for the
+ * corner's outgoing half-edge 3 f + k and then its incoming half-edge 3 f + (k + 2) % 3, when that edge has count 1, one constraint
+ * plane through the edge and perpendicular to the face.  With n the face's unit normal from above and p -> q the half-edge in face
+ * order:
+ *   E = q - p;  m = E x n;  ml = sqrt(m . m);  a plane with ml <= AM_MESH_ZERO adds nothing;  m = m / ml (three divisions);
+ *   d = -(m . p);  w = border_weight * (E . E);  P = (mx, my, mz, d);  Q[i,j] = Q[i,j] + (w * P[i]) * P[j]   in the order above.
+ * border_weight is the caller's, finite and >= 0; mesh_decimate.py's default is 1.0.  The argument for that value, and nothing
+ * stronger: a face's plane weighs its area, about 0.43 L^2 for an edge length L, and an interior vertex sums 5 to 6 of them; a
+ * border vertex sums two border planes of L^2 each, so leaving the border curve by a distance costs about what leaving the
+ * surface by the same distance does.  Quadrics are summed on collapse and never recomputed, as above.
+ *
+ * am_decimate_border_edges, per edge: an edge that fails the topology gets (0, 0, 0), cost 0 and AM_DECIMATE_NO_KEY.  Otherwise
+ * position, cost and key are EXACTLY am_decimate_edges' expressions on Q_u + Q_v: the solve with its conditioning and reach rules,
+ * else u, v, mid; the no-flip test over every face of u without v and of v without u; the key.  (Remark, not a rule: on a straight
+ * border in a flat region the solve is singular, and the fallback keeps the vertex on the line.)  A collapse removes
+ * edge_count[e] faces, 1 or 2. */
+typedef struct {
+  const double* positions;
+  int64_t n_vertices;
+  int64_t n_faces;
+  int64_t n_edges;              /* >= 1 */
+  const int32_t* faces;
+  const int32_t* offsets;
+  const int32_t* corners;
+  const int32_t* half_edge_to_edge;
+  const int32_t* edge_count;
+  double border_weight;         /* finite, >= 0 */
+  double* out_quadrics;         /* (n_vertices, 10) */
+  int32_t* out_flag;
+} am_decimate_border_quadrics_args;
+int am_decimate_border_quadrics(const am_decimate_border_quadrics_args* args, void* stream);
+
+typedef struct {
+  const double* positions;
+  const double* quadrics;
+  int64_t n_vertices;
+  int64_t n_faces;
+  int64_t n_edges;              /* >= 1 */
+  const int32_t* faces;
+  const int32_t* offsets;
+  const int32_t* corners;
+  const int32_t* edges;
+  const int32_t* half_edge_to_edge;
+  const int32_t* edge_count;
+  double* out_positions;        /* (n_edges, 3) */
+  double* out_cost;             /* [n_edges] */
+  int64_t* out_key;             /* [n_edges] */
+  int32_t* out_flag;
+} am_decimate_border_edges_args;
+int am_decimate_border_edges(const am_decimate_border_edges_args* args, void* stream);
+
 /* Iso-surface extraction (INTEGRATION seam S11): marching tetrahedra on a regular grid, the three kernels behind
  * actionmesh_amd/isosurface.py, which stands in for the `diso` dual marching cubes inside TripoSG's hierarchical_extract_geometry
  * (actionmesh/external/triposg.py:13, 193-199).  The two prefix sums between the kernels, the sizing of the outputs and the removal

@@ -28,6 +28,8 @@ BASELINE.json's "end-to-end video->4D wall-clock" restricted to the stages this 
                                                   on the device (actionmesh_amd/mesh_decimate.py; MeshPostprocessor.process_mesh, pipeline.py:418) -
                                                   and Stage II animates the decimated mesh; a decimated mesh has no map back to the given one, so
                                                   the animation stays on it
+    python tools/e2e_synthetic.py --config 3 --face-decimation N --decimate-borders collapse     the same with process_mesh(decimate_borders="collapse"):
+                                                  border collapses permitted; the torus is closed, so the mesh is the same bits
 Both are PLUMBING records on random-init weights (no checkpoint is reachable offline): not BASELINE's end-to-end metric.
 """
 import argparse
@@ -128,7 +130,7 @@ def dirty_mesh(v, f, cols: int, seed: int = 2):
 
 def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44, clip: str = None, label: str = None,
         raw_frames: bool = False, features: str = "hip", mesh_prep: bool = False, face_decimation: int = 0, field_grid: int = 0,
-        iso_method: str = "tetrahedra"):
+        iso_method: str = "tetrahedra", decimate_borders: str = "fixed"):
     from actionmesh_amd import LatentBank, generate_3d_latents, generate_vertex_animation
     from actionmesh_amd import mesh_prep as MP
     t_build = time.perf_counter()
@@ -189,7 +191,8 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         if face_decimation:    # the reference's Stage-0 post-processing: clean-up, then the quadric decimation, both on the device
-            anchor_v, faces = MP.process_mesh(raw_v, raw_f, face_decimation=face_decimation, decimation="hip")
+            anchor_v, faces = MP.process_mesh(raw_v, raw_f, face_decimation=face_decimation, decimation="hip",
+                                              decimate_borders=decimate_borders)
             merge_map = pre_faces = None
         else:
             anchor_v, faces, merge_map, pre_faces = MP.merge_and_clean_mesh(raw_v, raw_f)
@@ -295,6 +298,9 @@ def main():
     ap.add_argument("--mesh-prep", action="store_true", help="start from a dirty mesh and run the {video+3D} mesh glue around Stage II (implied by --config 3)")
     ap.add_argument("--face-decimation", type=int, default=0,
                     help="with --mesh-prep / --config 3: decimate the cleaned mesh to this many faces on the device (process_mesh(decimation='hip'))")
+    ap.add_argument("--decimate-borders", default="fixed", choices=["fixed", "collapse"],
+                    help="with --face-decimation: process_mesh(decimate_borders=...) - 'collapse' lets an open mesh reach the target too; "
+                         "on the closed meshes of this tool both give the same bits")
     ap.add_argument("--field-grid", type=int, default=0, metavar="N",
                     help="with --face-decimation: start from an analytic torus field on N^3 points instead of a prepared mesh - "
                          "extract_isosurface on the device, then the clean-up and the decimation (adds seconds.isosurface)")
@@ -307,6 +313,8 @@ def main():
         ap.error("--raw-frames needs --clip (or --config)")
     if a.face_decimation and not (a.mesh_prep or a.config == 3):
         ap.error("--face-decimation needs --mesh-prep (or --config 3)")
+    if a.decimate_borders != "fixed" and not a.face_decimation:
+        ap.error("--decimate-borders needs --face-decimation")
     if a.field_grid and not a.face_decimation:
         ap.error("--field-grid needs --face-decimation (the extracted mesh has as many faces as the grid gives it)")
     dev = torch.device("cuda:0")
@@ -322,7 +330,7 @@ def main():
                  "(dirty mesh -> merge_and_clean_mesh -> normalize_mesh -> sample_surface; denormalize_mesh + expand_to_original at the end)")
     print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames,
                          features=a.features, mesh_prep=a.mesh_prep, face_decimation=a.face_decimation,
-                         field_grid=a.field_grid, iso_method=a.iso_method)))
+                         field_grid=a.field_grid, iso_method=a.iso_method, decimate_borders=a.decimate_borders)))
 
 
 if __name__ == "__main__":

@@ -14,9 +14,14 @@ implementation anyone would ship, and labelled as that in the output.
 over sequential greedy, both through the numpy restatement) and stores them, with the seconds the greedy restatement took, under
 "quality".
 
+`--borders collapse` measures `decimate_mesh(..., borders="collapse")` instead and writes the "timing" section of
+profiles/mesh_decimate_borders.json: on the closed noisy sphere the two modes ALTERNATE in one process (the outputs are the same
+bits, so the difference is the price of am_decimate_border_edges and of the prefix trimming on a mesh without border), then the same
+sphere with one cap cut off (the faces whose centroid has z > 0.8): rounds and time with "collapse", and where "fixed" stops.
+
 Writes profiles/mesh_decimate.json, keeping the sections it does not measure; no test asserts a time.
 
-    python tools/mesh_decimate_timing.py [--out profiles/mesh_decimate.json] [--quality]
+    python tools/mesh_decimate_timing.py [--out profiles/mesh_decimate.json] [--quality] [--borders collapse]
 """
 import argparse
 import json
@@ -69,6 +74,47 @@ def timed(fn, repeats, warmup, dev):
     return {"median_ms": round(statistics.median(times), 3), "min_ms": round(min(times), 3), "max_ms": round(max(times), 3), "n": repeats}
 
 
+def cut_cap(v, f, z=0.8):
+    """The mesh without the faces whose centroid lies above z, unused vertices dropped: an open mesh with one border loop."""
+    f = f[v[f].mean(1)[:, 2] <= z]
+    used = np.unique(f)
+    remap = np.full(v.shape[0], -1, dtype=np.int64)
+    remap[used] = np.arange(used.shape[0])
+    return v[used], remap[f]
+
+
+def border_timing(n, target, dev, repeats=20, warmup=3):
+    from actionmesh_amd import mesh_decimate as MD
+    v, f = noisy_sphere(n)
+    rows = {}
+    for name, (mv, mf) in (("closed", (v, f)), ("cap_cut_off", cut_cap(v, f))):
+        verts, faces = torch.from_numpy(mv).float().to(dev), torch.from_numpy(mf).to(dev)
+        results = {b: MD.decimate_mesh(verts, faces, target, return_rounds=True, borders=b) for b in ("fixed", "collapse")}
+        times = {"fixed": [], "collapse": []}
+        for k in range(warmup + repeats):                  # the two modes alternate: what drifts, drifts for both
+            for b in ("fixed", "collapse"):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                MD.decimate_mesh(verts, faces, target, borders=b)
+                torch.cuda.synchronize(dev)
+                if k >= warmup:
+                    times[b].append((time.perf_counter() - t0) * 1e3)
+        row = {"subdivisions": n, "vertices": int(mv.shape[0]), "faces": int(mf.shape[0]), "target_faces": target,
+               "same_bits": all(torch.equal(x, y) for x, y in zip(results["fixed"][:2], results["collapse"][:2]))
+               if results["fixed"][1].shape == results["collapse"][1].shape else False}
+        for b in ("fixed", "collapse"):
+            t = times[b]
+            row[b] = {"faces_after": int(results[b][1].shape[0]), "rounds": results[b][2], "median_ms": round(statistics.median(t), 3),
+                      "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "n": repeats,
+                      "ms_per_round": round(statistics.median(t) / max(results[b][2], 1), 3)}
+        rows[name] = row
+        print(json.dumps({name: row}))
+    return {"what": "decimate_mesh on the noisy subdivided octahedral sphere of profiles/mesh_decimate.json and on the same sphere without "
+                    "the faces whose centroid has z > 0.8, fp32 vertices, one MI355X; borders='fixed' and borders='collapse' alternating "
+                    "in one process, wall clock around a device synchronisation, median of 20 after 3 warm-up calls each",
+            "device": torch.cuda.get_device_name(dev), "rows": rows}
+
+
 def quality():
     import _decimate_ref as R
     from actionmesh_amd import mesh_decimate as MD
@@ -93,17 +139,23 @@ def quality():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_decimate.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/mesh_decimate.json, with --borders collapse profiles/mesh_decimate_borders.json")
     ap.add_argument("--subdivisions", type=int, nargs="+", default=[224, 112])
     ap.add_argument("--target", type=int, default=40000)
     ap.add_argument("--quality", action="store_true", help="only re-measure the quality ratios (no GPU)")
+    ap.add_argument("--borders", choices=("fixed", "collapse"), default="fixed",
+                    help="collapse: time borders='collapse' against 'fixed' on the closed sphere and on the sphere with one cap cut off")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "mesh_decimate_borders.json" if a.borders == "collapse" else "mesh_decimate.json")
     out = {}
     if os.path.exists(a.out):
         with open(a.out) as fh:
             out = json.load(fh)
     if a.quality:
         out["quality"] = quality()
+    elif a.borders == "collapse":
+        out["timing"] = border_timing(a.subdivisions[0], a.target, torch.device("cuda:0"))
     else:
         from actionmesh_amd import mesh_decimate as MD
         dev = torch.device("cuda:0")
