@@ -137,11 +137,11 @@ class AmRenderCamera(C.Structure):     # am_render_camera
 
 class AmRenderArgs(C.Structure):       # am_render_args
     _fields_ = [
-        ("verts", C.c_void_p), ("faces", C.c_void_p), ("faces_host", C.c_void_p),
+        ("verts", C.c_void_p), ("faces", C.c_void_p), ("offsets", C.c_void_p), ("corners", C.c_void_p),
         ("n_frames", C.c_int32), ("n_verts", C.c_int32), ("n_faces", C.c_int32), ("n_cameras", C.c_int32),
         ("cameras", AmRenderCamera * RENDER_MAX_CAMERAS), ("image_size", C.c_int32),
         ("out_rgba", C.c_void_p), ("out_mask", C.c_void_p), ("out_normal", C.c_void_p),
-        ("out_face", C.c_void_p), ("out_bary", C.c_void_p),
+        ("out_face", C.c_void_p), ("out_bary", C.c_void_p), ("out_flag", C.c_void_p),
     ]
 
 
@@ -228,7 +228,7 @@ class AmSurfaceSampleArgs(C.Structure):        # am_surface_sample_args
 
 
 DECIMATE_NO_KEY = 2 ** 63 - 1               # AM_DECIMATE_NO_KEY
-MESH_BAD_FACE, MESH_BAD_CSR = 1, 2          # the out_flag bits of am_vertex_normals / am_face_areas / am_surface_sample
+MESH_BAD_FACE, MESH_BAD_CSR = 1, 2          # the out_flag bits of am_vertex_normals / am_face_areas / am_surface_sample / am_render_normals
 DECIMATE_BAD_FACE, DECIMATE_BAD_CSR, DECIMATE_BAD_EDGE, DECIMATE_BAD_KEPT = MESH_BAD_FACE, MESH_BAD_CSR, 4, 8      # am_decimate_*'s out_flag bits
 
 

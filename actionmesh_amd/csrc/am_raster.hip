@@ -2,9 +2,9 @@
 // MeshRasterizer with bin_size=0, blur 0, one face per pixel, perspective-correct clipped barycentrics - followed by
 // soft_normal_shading and make_normal_image), for every (frame, camera) image of one animated mesh in a fixed number of launches.
 //
-//   vertex->face table   once per call (one topology for all frames): counts by integer atomics, one-block scan, fill by atomics,
-//                        then each vertex sorts its own list - the table, and so every sum below, is in face-index order;
-//   vertex normals       one thread per (frame, vertex): sum of cross(v2 - v1, v0 - v1) over its faces, normalised (eps 1e-6);
+//   vertex normals       one thread per (frame, vertex): sum of cross(v2 - v1, v0 - v1) over its faces, normalised (eps 1e-6).  Its
+//                        faces are corner / 3 along the caller's vertex -> corner CSR (am_vertex_normals' table: ascending corner
+//                        id), so every sum is in face-index order;
 //   projection           one thread per (frame, camera, vertex): {x_ndc, y_ndc, view z};
 //   raster               one thread per (image, face): a face whose pixel bounding box holds at most SMALL_BOX sub-pixels
 //                        tests them itself; a larger one is queued, and raster_big spreads each queued face over BIG_SPLIT
@@ -13,8 +13,9 @@
 //                        its bits, so the nearest face wins and ties go to the lowest face index, whatever the arrival order;
 //   resolve              one thread per output pixel: mask from the 2 x 2 sub-pixels, normal from sub-pixel (2i, 2j).
 // The coverage test is a function of (face, sub-pixel) alone, evaluated by the same code in raster and resolve, without
-// contraction: the result is bit-identical run to run and independent of how the images are batched.
-#include "am_common.h"
+// contraction: the result is bit-identical run to run and independent of how the images are batched.  Faces and CSR are read
+// through am_geometry.h: every index is compared with its bound before it is an address, and a bad one raises the call's flag.
+#include "am_geometry.h"
 
 namespace {
 
@@ -75,10 +76,11 @@ struct FaceSetup {
 
 // PyTorch3D's per-face rejections (every vertex behind the camera, |area| <= 1e-8, index outside the mesh) and the bounding box.
 __device__ inline bool face_setup(const int32_t* __restrict__ faces, const float4* __restrict__ proj, int f, int V, int W,
-                                  FaceSetup& s) {
+                                  int32_t* __restrict__ flag, FaceSetup& s) {
 #pragma clang fp contract(off)
-  const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-  if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) return false;
+  __builtin_assume(V > 0);           // render_check; each range test is then one unsigned compare and the three index loads stay together
+  int i0, i1, i2;
+  if (!face_indices(faces + 3 * f, V, flag, i0, i1, i2)) return false;
   s.v0 = proj[i0];
   s.v1 = proj[i1];
   s.v2 = proj[i2];
@@ -98,78 +100,20 @@ __device__ inline void zb_test(unsigned long long* __restrict__ zb, const FaceSe
   if (key < *p) atomicMin(p, key);   // the plain read only filters: atomicMin decides
 }
 
-// ---- vertex -> face table ----------------------------------------------------------------------------------------------
-__global__ void adj_count_kernel(const int32_t* __restrict__ faces, int F, int V, int* __restrict__ cnt) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  for (int k = 0; k < 3; ++k) {
-    const int v = faces[3 * f + k];
-    if ((unsigned)v < (unsigned)V) atomicAdd(cnt + v, 1);
-  }
-}
-
-// exclusive scan of cnt[0..V) into off[0..V], cursor = off (cursor may be cnt itself: each thread reads its entry first); one block
-__global__ __launch_bounds__(1024) void adj_scan_kernel(const int* cnt, int V, int* __restrict__ off, int* cursor) {
-  __shared__ int part[1024];
-  int carry = 0;
-  for (int base = 0; base < V; base += 1024) {
-    const int i = base + (int)threadIdx.x;
-    const int x = i < V ? cnt[i] : 0;
-    part[threadIdx.x] = x;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {        // Hillis-Steele inclusive scan
-      const int y = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
-      __syncthreads();
-      part[threadIdx.x] += y;
-      __syncthreads();
-    }
-    if (i < V) {
-      off[i] = carry + part[threadIdx.x] - x;
-      cursor[i] = off[i];
-    }
-    carry += part[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) off[V] = carry;
-}
-
-__global__ void adj_fill_kernel(const int32_t* __restrict__ faces, int F, int V, int* __restrict__ cursor, int* __restrict__ adj) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  for (int k = 0; k < 3; ++k) {
-    const int v = faces[3 * f + k];
-    if ((unsigned)v < (unsigned)V) adj[atomicAdd(cursor + v, 1)] = f;
-  }
-}
-
-__global__ void adj_sort_kernel(const int* __restrict__ off, int V, int* __restrict__ adj) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  const int lo = off[v], hi = off[v + 1];
-  for (int i = lo + 1; i < hi; ++i) {           // insertion sort: a vertex has a handful of faces
-    const int x = adj[i];
-    int j = i - 1;
-    while (j >= lo && adj[j] > x) {
-      adj[j + 1] = adj[j];
-      --j;
-    }
-    adj[j + 1] = x;
-  }
-}
-
 // ---- per-frame vertex normals and per-(frame, camera) projection ----------------------------------------------------------
-__global__ void vnormal_kernel(const float* __restrict__ X, const int32_t* __restrict__ faces, const int* __restrict__ off,
-                               const int* __restrict__ adj, int V, int64_t TV, float* __restrict__ vn) {
+__global__ void vnormal_kernel(mesh_view m, const float* __restrict__ X, int64_t TV, float* __restrict__ vn) {
 #pragma clang fp contract(off)
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= TV) return;
-  const int v = (int)(g % V);
+  const int v = (int)(g % m.n_vertices);
   const float* Xt = X + (g - v) * 3;
   float nx = 0.f, ny = 0.f, nz = 0.f;
-  for (int k = off[v]; k < off[v + 1]; ++k) {
-    const int f = adj[k];
-    const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
+  int begin, end;
+  csr_range(m, v, begin, end);
+  for (int j = begin; j < end; ++j) {
+    const int c = corner_at(m, j, v);
+    int i0, i1, i2;
+    if (c < 0 || !face_indices(m.faces + 3 * (c / 3), m.n_vertices, m.flag, i0, i1, i2)) continue;
     const float *p0 = Xt + 3 * i0, *p1 = Xt + 3 * i1, *p2 = Xt + 3 * i2;
     const float ax = p2[0] - p1[0], ay = p2[1] - p1[1], az = p2[2] - p1[2];
     const float bx = p0[0] - p1[0], by = p0[1] - p1[1], bz = p0[2] - p1[2];
@@ -198,12 +142,12 @@ __global__ void project_kernel(const float* __restrict__ X, int V, int C, Render
 // ---- rasterisation --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(RT_THREADS) void raster_small_kernel(const int32_t* __restrict__ faces, const float4* __restrict__ proj,
                                                                   int V, int F, int W, unsigned long long* __restrict__ zb,
-                                                                  unsigned* __restrict__ queue) {
+                                                                  unsigned* __restrict__ queue, int32_t* __restrict__ flag) {
   const int f = blockIdx.x * RT_THREADS + threadIdx.x;
   const int img = blockIdx.y;
   if (f >= F) return;
   FaceSetup s;
-  if (!face_setup(faces, proj + (int64_t)img * V, f, V, W, s)) return;
+  if (!face_setup(faces, proj + (int64_t)img * V, f, V, W, flag, s)) return;
   const int bw = s.c_hi - s.c_lo + 1;
   if ((int64_t)bw * (s.r_hi - s.r_lo + 1) > SMALL_BOX) {
     queue[1 + atomicAdd(queue, 1u)] = (unsigned)img * (unsigned)F + (unsigned)f;
@@ -216,13 +160,13 @@ __global__ __launch_bounds__(RT_THREADS) void raster_small_kernel(const int32_t*
 
 __global__ __launch_bounds__(RT_THREADS) void raster_big_kernel(const int32_t* __restrict__ faces, const float4* __restrict__ proj,
                                                                 int V, int F, int W, unsigned long long* __restrict__ zb,
-                                                                const unsigned* __restrict__ queue) {
+                                                                const unsigned* __restrict__ queue, int32_t* __restrict__ flag) {
   const unsigned n = queue[0];
   for (unsigned e = blockIdx.x; e < n; e += gridDim.x) {
     const unsigned code = queue[1 + e];
     const int img = (int)(code / (unsigned)F), f = (int)(code % (unsigned)F);
     FaceSetup s;
-    if (!face_setup(faces, proj + (int64_t)img * V, f, V, W, s)) continue;
+    if (!face_setup(faces, proj + (int64_t)img * V, f, V, W, flag, s)) continue;
     const int bw = s.c_hi - s.c_lo + 1;
     const int64_t area = (int64_t)bw * (s.r_hi - s.r_lo + 1);
     unsigned long long* z = zb + (int64_t)img * W * W;
@@ -236,7 +180,8 @@ __global__ __launch_bounds__(RT_THREADS) void resolve_kernel(const int32_t* __re
                                                              const float* __restrict__ vn, const unsigned long long* __restrict__ zb,
                                                              int V, int C, int S, RenderCams cams, uint8_t* __restrict__ out_rgba,
                                                              float* __restrict__ out_mask, float* __restrict__ out_normal,
-                                                             int32_t* __restrict__ out_face, float* __restrict__ out_bary) {
+                                                             int32_t* __restrict__ out_face, float* __restrict__ out_bary,
+                                                             int32_t* __restrict__ flag) {
 #pragma clang fp contract(off)
   const int pix = blockIdx.x * RT_THREADS + threadIdx.x;
   const int img = blockIdx.y;
@@ -252,8 +197,8 @@ __global__ __launch_bounds__(RT_THREADS) void resolve_kernel(const int32_t* __re
     const int f = key == ZB_EMPTY ? -1 : (int)(unsigned)(key & 0xffffffffu);
     covered += f >= 0;
     float b[3] = {-1.f, -1.f, -1.f};
-    if (f >= 0 && (k == 0 || out_bary)) {
-      const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+    int i0, i1, i2;
+    if (f >= 0 && (k == 0 || out_bary) && face_indices(faces + 3 * f, V, flag, i0, i1, i2)) {     // a face the raster accepted
       float z;
       cover(pr[i0], pr[i1], pr[i2], ndc_of(c, W), ndc_of(r, W), b, z);      // the raster's own test: covered again
       if (k == 0) {
@@ -283,16 +228,13 @@ __global__ __launch_bounds__(RT_THREADS) void resolve_kernel(const int32_t* __re
   if (out_mask) out_mask[o] = mask;
 }
 
-struct RenderLayout { size_t off, cursor, adj, vn, proj, zb, queue, total; };
+struct RenderLayout { size_t vn, proj, zb, queue, total; };
 
 RenderLayout render_layout(int T, int V, int F, int C, int S) {
   auto a = [](size_t x) { return (x + 255) / 256 * 256; };
   RenderLayout l;
   const size_t imgs = (size_t)T * C, W = 2 * (size_t)S;
-  l.off = 0;
-  l.cursor = l.off + a(sizeof(int) * ((size_t)V + 1));
-  l.adj = l.cursor + a(sizeof(int) * (size_t)V);
-  l.vn = l.adj + a(sizeof(int) * 3 * (size_t)F);
+  l.vn = 0;
   l.proj = l.vn + a(sizeof(float) * 3 * (size_t)T * V);
   l.zb = l.proj + a(sizeof(float4) * imgs * V);
   l.queue = l.zb + a(sizeof(unsigned long long) * imgs * W * W);
@@ -307,7 +249,7 @@ int render_check(const am_render_args* a) {
   AM_CHECK(a->n_cameras >= 1 && a->n_cameras <= AM_RENDER_MAX_CAMERAS, "am_render_normals: %d cameras, 1 .. %d supported",
            a->n_cameras, AM_RENDER_MAX_CAMERAS);
   AM_CHECK(a->image_size >= 1 && a->image_size <= 4096, "am_render_normals: image size %d outside 1 .. 4096", a->image_size);
-  AM_CHECK(a->verts && a->faces && a->faces_host && a->out_rgba, "am_render_normals: null pointer");
+  AM_CHECK(a->verts && a->faces && a->offsets && a->corners && a->out_flag && a->out_rgba, "am_render_normals: null pointer");
   const int64_t imgs = (int64_t)a->n_frames * a->n_cameras;
   AM_CHECK(imgs <= 65535, "am_render_normals: %lld images exceed the grid's y extent", (long long)imgs);
   AM_CHECK((int64_t)a->n_frames * a->n_verts < ((int64_t)1 << 31) / 3, "am_render_normals: %d x %d vertices overflow a 32-bit index",
@@ -315,11 +257,6 @@ int render_check(const am_render_args* a) {
   AM_CHECK(imgs * a->n_faces < ((int64_t)1 << 32) - 1, "am_render_normals: %lld images x %d faces overflow the raster queue",
            (long long)imgs, a->n_faces);
   AM_CHECK((int64_t)a->n_faces * 3 < ((int64_t)1 << 31), "am_render_normals: %d faces overflow a 32-bit index", a->n_faces);
-  for (int64_t k = 0; k < (int64_t)a->n_faces * 3; ++k) {
-    const int32_t v = a->faces_host[k];
-    AM_CHECK(v >= 0 && v < a->n_verts, "am_render_normals: face %lld has vertex index %d outside [0, %d)", (long long)(k / 3), v,
-             a->n_verts);
-  }
   return AM_OK;
 }
 
@@ -338,9 +275,6 @@ extern "C" int am_render_normals(const am_render_args* a, void* workspace_dev, s
            l.total, workspace_bytes);
   hipStream_t st = (hipStream_t)stream;
   char* ws = reinterpret_cast<char*>(workspace_dev);
-  int* off = reinterpret_cast<int*>(ws + l.off);
-  int* cursor = reinterpret_cast<int*>(ws + l.cursor);
-  int* adj = reinterpret_cast<int*>(ws + l.adj);
   float* vn = reinterpret_cast<float*>(ws + l.vn);
   float4* proj = reinterpret_cast<float4*>(ws + l.proj);
   unsigned long long* zb = reinterpret_cast<unsigned long long*>(ws + l.zb);
@@ -349,29 +283,23 @@ extern "C" int am_render_normals(const am_render_args* a, void* workspace_dev, s
   RenderCams cams;
   for (int c = 0; c < AM_RENDER_MAX_CAMERAS; ++c) cams.c[c] = a->cameras[c];
 
-  AM_HIP(hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)V, st));      // the counts live in `cursor` until the scan
+  const mesh_view m = {V, F, 0, a->faces, a->offsets, a->corners, nullptr, nullptr, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
   AM_HIP(hipMemsetAsync(zb, 0xff, sizeof(unsigned long long) * (size_t)imgs * W * W, st));
   AM_HIP(hipMemsetAsync(queue, 0, sizeof(unsigned), st));
-  hipLaunchKernelGGL(adj_count_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, a->faces, F, V, cursor);
-  AM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(adj_scan_kernel, dim3(1), dim3(1024), 0, st, cursor, V, off, cursor);
-  AM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(adj_fill_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, a->faces, F, V, cursor, adj);
-  AM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(adj_sort_kernel, dim3(ceil_div(V, 256)), dim3(256), 0, st, off, V, adj);
-  AM_HIP(hipGetLastError());
   const int64_t TV = (int64_t)T * V;
-  hipLaunchKernelGGL(vnormal_kernel, dim3(ceil_div(TV, 256)), dim3(256), 0, st, a->verts, a->faces, off, adj, V, TV, vn);
+  hipLaunchKernelGGL(vnormal_kernel, dim3(ceil_div(TV, 256)), dim3(256), 0, st, m, a->verts, TV, vn);
   AM_HIP(hipGetLastError());
   hipLaunchKernelGGL(project_kernel, dim3(ceil_div(V, 256), imgs), dim3(256), 0, st, a->verts, V, C, cams, proj);
   AM_HIP(hipGetLastError());
   hipLaunchKernelGGL(raster_small_kernel, dim3(ceil_div(F, RT_THREADS), imgs), dim3(RT_THREADS), 0, st, a->faces, proj, V, F, W, zb,
-                     queue);
+                     queue, a->out_flag);
   AM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(raster_big_kernel, dim3(BIG_BLOCKS, BIG_SPLIT), dim3(RT_THREADS), 0, st, a->faces, proj, V, F, W, zb, queue);
+  hipLaunchKernelGGL(raster_big_kernel, dim3(BIG_BLOCKS, BIG_SPLIT), dim3(RT_THREADS), 0, st, a->faces, proj, V, F, W, zb, queue,
+                     a->out_flag);
   AM_HIP(hipGetLastError());
   hipLaunchKernelGGL(resolve_kernel, dim3(ceil_div((int64_t)S * S, RT_THREADS), imgs), dim3(RT_THREADS), 0, st, a->faces, proj, vn, zb,
-                     V, C, S, cams, a->out_rgba, a->out_mask, a->out_normal, a->out_face, a->out_bary);
+                     V, C, S, cams, a->out_rgba, a->out_mask, a->out_normal, a->out_face, a->out_bary, a->out_flag);
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

@@ -1529,10 +1529,11 @@ def displacement_f32(logits: torch.Tensor, out_dim: int, out: torch.Tensor, kind
 def render_normals(vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequence[dict], image_size: int,
                    fragments: bool = False, floats: bool = False) -> dict:
     """am_render_normals: the normal-map preview of an animated mesh.  vertices (T, V, 3) fp32 on the device, faces (F, 3) integer
-    (any device: a host copy is what the library checks against V), cameras: up to 16 dicts with "R" (3, 3), "T" (3,),
-    "focal_length" (fx, fy) and "principal_point" (px, py).  Returns {"rgba": uint8 (T, C, S, S, 4)} plus, with `floats`,
-    "mask" (T, C, S, S) and "normal" (T, C, S, S, 3), and with `fragments`, "pix_to_face" int32 (T, C, 2S, 2S) and "bary"
-    (T, C, 2S, 2S, 3) - all on the device of `vertices`."""
+    (any device: they are moved to the vertices'), cameras: up to 16 dicts with "R" (3, 3), "T" (3,), "focal_length" (fx, fy) and
+    "principal_point" (px, py).  Returns {"rgba": uint8 (T, C, S, S, 4)} plus, with `floats`, "mask" (T, C, S, S) and "normal"
+    (T, C, S, S, 3), and with `fragments`, "pix_to_face" int32 (T, C, 2S, 2S) and "bary" (T, C, 2S, 2S, 3) - all on the device of
+    `vertices`.  The faces are validated on the device: ONE device-to-host read behind the launch (the flag) turns a vertex index
+    outside [0, V) into a ValueError."""
     _need(vertices, torch.float32, "vertices")
     if vertices.dim() != 3 or vertices.shape[-1] != 3:
         raise ValueError(f"render_normals: vertices must be (T, V, 3), got {tuple(vertices.shape)}")
@@ -1543,17 +1544,18 @@ def render_normals(vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequenc
     T, V = vertices.shape[0], vertices.shape[1]
     F, Cn, S = faces.shape[0], len(cameras), int(image_size)
     dev = vertices.device
-    faces_host = faces.detach().to("cpu", torch.int32).contiguous()
-    faces_dev = faces_host.to(dev)
-    out = {"rgba": torch.empty((T, Cn, S, S, 4), dtype=torch.uint8, device=dev)}
+    topology = MeshTopology(faces.detach().to(dev, torch.int32), V)
+    out = {"rgba": _out("rgba", None, (T, Cn, S, S, 4), torch.uint8, dev)}
     if floats:
-        out["mask"] = torch.empty((T, Cn, S, S), dtype=torch.float32, device=dev)
-        out["normal"] = torch.empty((T, Cn, S, S, 3), dtype=torch.float32, device=dev)
+        out["mask"] = _out("mask", None, (T, Cn, S, S), torch.float32, dev)
+        out["normal"] = _out("normal", None, (T, Cn, S, S, 3), torch.float32, dev)
     if fragments:
-        out["pix_to_face"] = torch.empty((T, Cn, 2 * S, 2 * S), dtype=torch.int32, device=dev)
-        out["bary"] = torch.empty((T, Cn, 2 * S, 2 * S, 3), dtype=torch.float32, device=dev)
+        out["pix_to_face"] = _out("pix_to_face", None, (T, Cn, 2 * S, 2 * S), torch.int32, dev)
+        out["bary"] = _out("bary", None, (T, Cn, 2 * S, 2 * S, 3), torch.float32, dev)
+    flag, own = _flag_word("render_normals", None, dev)
     a = L.AmRenderArgs()
-    a.verts, a.faces, a.faces_host = vertices.data_ptr(), faces_dev.data_ptr(), faces_host.data_ptr()
+    a.verts, a.faces = vertices.data_ptr(), topology.faces.data_ptr()
+    a.offsets, a.corners, a.out_flag = topology.offsets.data_ptr(), topology.corners.data_ptr(), flag.data_ptr()
     a.n_frames, a.n_verts, a.n_faces, a.n_cameras, a.image_size = T, V, F, Cn, S
     for k, cam in enumerate(cameras):
         c = a.cameras[k]
@@ -1570,4 +1572,5 @@ def render_normals(vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequenc
     a.out_face, a.out_bary = _p(out.get("pix_to_face")), _p(out.get("bary"))
     ws, need = _workspace(dev, "am_render_workspace_bytes", T, V, F, Cn, S, at_least=1)
     _call(vertices, None, "am_render_normals", C.byref(a), ws.data_ptr(), need)
+    _raise_own_flag("render_normals", flag, own, _MESH_FLAGS, V=V)
     return out

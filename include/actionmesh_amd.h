@@ -535,8 +535,13 @@ int am_nn_grid_search(const am_nn_grid_search_args* args, void* stream);
  *                   vertex's projection, to the part of the cone inside the box (often none of it);
  *   resolve to S x S: mask = covered sub-pixels / 4; normal of sub-pixel (2i, 2j) through n @ R + T / 2, normalised,
  *                   (n + 1) / 2, clamped; rgba8 = trunc(255 * (normal * mask + 1 - mask)), alpha = trunc(255 * mask).
- * faces_host is the host copy of `faces` (the same (n_faces, 3) array): every index is checked against n_verts on it before
- * anything is launched.  The optional outputs (NULL = not written) are the float forms and the 2S x 2S fragments.
+ * offsets / corners are the vertex -> corner CSR of `faces` as am_vertex_normals defines it below (int32[n_verts + 1] and
+ * int32[3 n_faces], ascending corner id): corner / 3 along a vertex's corners is its faces in face-index order, one entry per
+ * occurrence, which is the order of the sum above.  Faces and CSR are validated on the device as there: every index is compared
+ * with its bound before it is used as an address, a face that names a vertex outside [0, n_verts) is skipped by the normals and
+ * by the raster, a bad corner adds nothing, and out_flag (device int32[1], cleared in stream order by the call) then holds
+ * AM_MESH_BAD_FACE / AM_MESH_BAD_CSR; the caller, who reads the flag together with the images, treats the call as failed.
+ * The optional outputs (NULL = not written) are the float forms and the 2S x 2S fragments.
  * am_render_workspace_bytes() bytes of device scratch must be passed for the same sizes. */
 #define AM_RENDER_MAX_CAMERAS 16
 typedef struct {
@@ -547,7 +552,8 @@ typedef struct {
 typedef struct {
   const float* verts;           /* (n_frames, n_verts, 3) fp32 */
   const int32_t* faces;         /* (n_faces, 3) int32 */
-  const int32_t* faces_host;    /* host memory: the same (n_faces, 3) array */
+  const int32_t* offsets;       /* (n_verts + 1) int32: the vertex -> corner CSR of `faces` */
+  const int32_t* corners;       /* (3 n_faces) int32 */
   int32_t n_frames;
   int32_t n_verts;
   int32_t n_faces;
@@ -559,6 +565,7 @@ typedef struct {
   float* out_normal;            /* optional (n_frames, n_cameras, S, S, 3): (n + 1) / 2 before the mask blend */
   int32_t* out_face;            /* optional (n_frames, n_cameras, 2S, 2S): face index, -1 = empty */
   float* out_bary;              /* optional (n_frames, n_cameras, 2S, 2S, 3): clipped barycentrics, -1 = empty */
+  int32_t* out_flag;            /* int32[1]: 0, or AM_MESH_BAD_FACE | AM_MESH_BAD_CSR */
 } am_render_args;
 size_t am_render_workspace_bytes(int n_frames, int n_verts, int n_faces, int n_cameras, int image_size);
 int am_render_normals(const am_render_args* args, void* workspace_dev, size_t workspace_bytes, void* stream);

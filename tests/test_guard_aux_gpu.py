@@ -20,6 +20,7 @@ import test_render_gpu as tr
 from _guard import SENTINEL, Arena, Padded64
 from actionmesh_amd import _lib as L
 from actionmesh_amd import image_preprocess as IP
+from actionmesh_amd.mesh_topology import MeshTopology
 from test_fps_cpu import fps_restatement
 from test_nn_plans_gpu import brute, nn_plan
 
@@ -189,14 +190,23 @@ RENDER_OUT = {"rgba": (torch.uint8, lambda S: (S, S, 4)), "mask": (torch.float32
               "bary": (torch.float32, lambda S: (2 * S, 2 * S, 3))}
 
 
-def _render(lib, dev, VA, FA, faces_host, cams, T, V, F, S, names, zero, short=False):
+def _mesh_inputs(faces, V, dev):
+    """faces (F, 3) int32 numpy -> the faces and the vertex -> corner CSR of MeshTopology, each in a poisoned arena"""
+    topo = MeshTopology(torch.from_numpy(faces).to(dev), V)
+    return tuple(Input(t, dev) for t in (topo.faces, topo.offsets, topo.corners))
+
+
+def _render(lib, dev, VA, mesh, cams, T, V, F, S, names, zero, short=False, flag_bits=0):
+    """One call on (faces, offsets, corners) = `mesh`; the flag word, in an arena of its own, must end at `flag_bits`."""
     Cn = len(cams)
     need = lib.am_render_workspace_bytes(T, V, F, Cn, S)
     assert need > 0
     outs = {k: out_arena((T, Cn) + RENDER_OUT[k][1](S), RENDER_OUT[k][0], dev) for k in names}
     ws = workspace(need, dev, zero)
+    flag = out_arena((1,), torch.int32, dev)
+    FA, OA, CA = mesh
     a = L.AmRenderArgs()
-    a.verts, a.faces, a.faces_host = VA.ptr, FA.ptr, faces_host.ctypes.data
+    a.verts, a.faces, a.offsets, a.corners, a.out_flag = VA.ptr, FA.ptr, OA.ptr, CA.ptr, flag.view.data_ptr()
     a.n_frames, a.n_verts, a.n_faces, a.n_cameras, a.image_size = T, V, F, Cn, S
     for k, cam in enumerate(cams):
         c = a.cameras[k]
@@ -213,13 +223,15 @@ def _render(lib, dev, VA, FA, faces_host, cams, T, V, F, S, names, zero, short=F
     torch.cuda.synchronize()
     for k, o in outs.items():
         o.assert_untouched(k)
-    ws.assert_untouched("workspace")
-    VA.unchanged("vertices"), FA.unchanged("faces")
+    ws.assert_untouched("workspace"), flag.assert_untouched("out_flag")
+    VA.unchanged("vertices"), FA.unchanged("faces"), OA.unchanged("offsets"), CA.unchanged("corners")
     if short:
         refused(lib, status, need)
         assert (ws.view == 0xA5).all() and (outs["rgba"].view == 0xA5).all(), "something was launched"
+        assert int(flag.view) == SENTINEL[torch.int32], "the flag was cleared although nothing may be launched"
         return None
     assert status == 0, lib.am_last_error()
+    assert int(flag.view) == flag_bits, f"out_flag {int(flag.view)}, expected {flag_bits}"
     return {k: o.view.clone() for k, o in outs.items()}
 
 
@@ -227,8 +239,8 @@ def _render(lib, dev, VA, FA, faces_host, cams, T, V, F, S, names, zero, short=F
 def test_render_normals_guards(dev, lib, T, V, F, Cn, S):
     verts, faces = _ball_mesh(T, V, F, 1000 * V + F)
     cams = _cameras(Cn)
-    VA, FA = Input(torch.from_numpy(verts), dev), Input(torch.from_numpy(faces), dev)
-    common = (lib, dev, VA, FA, faces, cams, T, V, F, S)
+    VA, mesh = Input(torch.from_numpy(verts), dev), _mesh_inputs(faces, V, dev)
+    common = (lib, dev, VA, mesh, cams, T, V, F, S)
     full = both_fills(lambda zero: _render(*common, tuple(RENDER_OUT), zero))
     alone = both_fills(lambda zero: _render(*common, ("rgba",), zero))
     assert torch.equal(alone["rgba"], full["rgba"]), "out_rgba depends on which optional outputs are asked for"
@@ -245,10 +257,32 @@ def test_render_normals_guards(dev, lib, T, V, F, Cn, S):
         for t in range(T):
             Vt = Input(torch.from_numpy(verts[t: t + 1]), dev)
             for c in range(Cn):
-                single = _render(lib, dev, Vt, FA, faces, cams[c: c + 1], 1, V, F, S, tuple(RENDER_OUT), False)
+                single = _render(lib, dev, Vt, mesh, cams[c: c + 1], 1, V, F, S, tuple(RENDER_OUT), False)
                 for k in full:
                     assert torch.equal(single[k][0, 0].view(torch.uint8), full[k][t, c].view(torch.uint8)), (k, t, c)
     _render(*common, tuple(RENDER_OUT), False, short=True)
+
+
+def test_render_normals_reports_a_foreign_csr(dev, lib):
+    """The octahedron of test_render_gpu, one camera, S = 8.  A clean call leaves the flag at 0.  Offsets that descend at one vertex,
+    and a corner listed under a vertex it does not name, are each answered with AM_OK and AM_MESH_BAD_CSR alone, and nothing outside
+    the outputs, the workspace and the flag word is written."""
+    verts, faces = tr.octahedron((0.0, 0.0, 0.0), 0.5)
+    V, F, S = len(verts), len(faces), 8
+    VA = Input(torch.from_numpy(verts[None].astype(np.float32)), dev)
+    FA, OA, CA = _mesh_inputs(faces.astype(np.int32), V, dev)
+    assert OA.a.view.tolist() == [0, 4, 8, 12, 16, 20, 24]                  # four faces on every vertex
+    common = (lib, dev, VA)
+    shape = ([tr.cam()], 1, V, F, S, tuple(RENDER_OUT), False)
+    clean = _render(*common, (FA, OA, CA), *shape, flag_bits=0)
+    assert int((clean["face"] >= 0).sum()) > 0
+    offsets = OA.a.view.clone()
+    offsets[3] = 6                                                          # vertex 2: [8, 6)
+    _render(*common, (FA, Input(offsets, dev), CA), *shape, flag_bits=L.MESH_BAD_CSR)
+    corners = CA.a.view.clone()
+    corners[0] = corners[4]                                                 # a corner of vertex 1 in the list of vertex 0
+    assert int(FA.a.view.reshape(-1)[corners[0]]) == 1
+    _render(*common, (FA, OA, Input(corners, dev)), *shape, flag_bits=L.MESH_BAD_CSR)
 
 
 # ---- am_mask_refine --------------------------------------------------------------------------------------------------------------

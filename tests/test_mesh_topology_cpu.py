@@ -96,6 +96,33 @@ def test_referenced_vertices_and_compact_rows(faces, n_vertices):
     assert MT.compact_rows(rows, torch.zeros(n, dtype=torch.bool), 0).shape == (0, 3)
 
 
+def sparse_icosphere_faces():
+    from test_render_gpu import sparse_icosphere            # 2562 used vertices scattered over 3072 rows
+    return sparse_icosphere()[1]
+
+
+@pytest.mark.parametrize("faces,n_vertices", [(sparse_icosphere_faces, 3072), (lambda: RANDOM_FACES, N_RANDOM_VERTICES),
+                                              (lambda: np.array([[0, 1, 2], [3, 3, 1], [2, 2, 2], [1, 4, 1]]), 6)],
+                         ids=["sparse-3072", "random-7x300", "repeats-in-a-face"])
+def test_corners_over_three_are_the_faces_on_a_vertex_in_ascending_order(faces, n_vertices):
+    """What am_render_normals sums along: `corners[offsets[v] : offsets[v + 1]] // 3` is the ascending list of the faces on v, one
+    entry per occurrence of v in a face; a vertex on no face has an empty list."""
+    faces = faces()
+    want = [[] for _ in range(n_vertices)]
+    for f, tri in enumerate(faces.tolist()):
+        for v in tri:
+            want[v].append(f)
+    t = MT.MeshTopology(torch.from_numpy(faces), n_vertices)
+    offsets, corners = t.offsets.tolist(), t.corners.tolist()
+    assert offsets[0] == 0 and offsets[-1] == 3 * len(faces)
+    for v in range(n_vertices):
+        assert [c // 3 for c in corners[offsets[v]:offsets[v + 1]]] == want[v], v
+    if n_vertices == 6:
+        assert want[2] == [0, 2, 2, 2] and want[1] == [0, 1, 3, 3] and want[5] == []
+    if n_vertices == 3072:
+        assert sum(len(w) == 0 for w in want) == 3072 - 2562
+
+
 def test_the_names_the_other_modules_keep():
     assert mesh_prep.MeshTopology is MT.MeshTopology and mesh_decimate.MeshTopology is MT.MeshTopology
     assert mesh_decimate.EdgeTables is MT.EdgeTables

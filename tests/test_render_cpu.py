@@ -49,31 +49,28 @@ def test_resample_list_matches_the_reference_cases():
 
 
 def test_render_argument_validation_without_gpu():
-    """am_render_normals rejects bad arguments before anything touches the device; the message comes from am_last_error."""
+    """am_render_normals rejects bad counts, sizes and pointers before anything touches the device; the message comes from
+    am_last_error.  (The face indices and the CSR are validated on the device: tests/test_render_gpu.py, test_guard_aux_gpu.py.)"""
     lib = _lib.lib()
     assert lib.am_render_normals(None, None, 0, None) != 0
     assert b"null" in lib.am_last_error()
-    faces = np.array([[0, 1, 2], [1, 2, 3]], dtype=np.int32)
 
     def args(**kw):
         a = _lib.AmRenderArgs()
-        a.verts, a.faces, a.faces_host, a.out_rgba = 16, 16, faces.ctypes.data, 16      # never dereferenced: the checks fail first
+        a.verts = a.faces = a.offsets = a.corners = a.out_flag = a.out_rgba = 16        # never dereferenced: the checks fail first
         a.n_frames, a.n_verts, a.n_faces, a.n_cameras, a.image_size = 1, 4, 2, 1, 8
         for k, v in kw.items():
             setattr(a, k, v)
         return a
     big = 1 << 30
-    for kw, msg in ((dict(faces_host=None), b"null pointer"), (dict(verts=None), b"null pointer"), (dict(out_rgba=None), b"null pointer"),
+    for kw, msg in ((dict(faces=None), b"null pointer"), (dict(offsets=None), b"null pointer"), (dict(corners=None), b"null pointer"),
+                    (dict(out_flag=None), b"null pointer"), (dict(verts=None), b"null pointer"), (dict(out_rgba=None), b"null pointer"),
                     (dict(n_faces=0), b"empty"), (dict(n_verts=0), b"empty"), (dict(n_frames=0), b"empty"),
-                    (dict(n_verts=3), b"outside [0, 3)"), (dict(n_cameras=17), b"cameras"), (dict(image_size=0), b"image size"),
+                    (dict(n_cameras=17), b"cameras"), (dict(image_size=0), b"image size"),
                     (dict(n_frames=70000), b"grid"), (dict(n_frames=20000, n_verts=big // 1000), b"overflow")):
         a = args(**kw)
         assert lib.am_render_normals(ctypes.byref(a), None, 0, None) != 0, kw
         assert msg in lib.am_last_error(), (kw, lib.am_last_error())
-    bad = np.array([[0, 1, 2], [1, 2, -1]], dtype=np.int32)
-    a = args(faces_host=bad.ctypes.data)
-    assert lib.am_render_normals(ctypes.byref(a), None, 0, None) != 0
-    assert b"face 1" in lib.am_last_error()
     a = args()                                                   # valid sizes: only the missing workspace is left to refuse
     assert lib.am_render_normals(ctypes.byref(a), None, 0, None) != 0
     assert b"workspace" in lib.am_last_error()

@@ -174,28 +174,26 @@ def test_icosphere_matches_restatement():
     assert check_against_restatement(V, F, cams, 128) > 3 * 128 * 128 * 0.8
 
 
-SCAN_CHUNK = 1024                   # csrc/am_raster.hip: adj_scan_kernel scans the per-vertex face counts 1024 at a time with a carry
-
-
-def test_vertex_table_scan_carries_across_chunks():
-    """2562 used vertices scattered by a permutation over 3072 rows (the other 510 are on no face): three full chunks of
-    adj_scan_kernel, non-trivial counts on both sides of every chunk border and zero counts inside.  A wrong carry gives a vertex
-    the face list of another one, which moves its normal; the unused rows' normals must never show."""
+def sparse_icosphere():
+    """A jittered level-4 icosphere whose 2562 vertices are scattered by a permutation over 3072 rows; the other 510 rows hold
+    random positions and are on no face."""
     V0, F0 = icosphere(4, 0.8)
     rng = np.random.default_rng(7)
     V0 = V0 * rng.uniform(0.9, 1.1, size=(len(V0), 1))
     n = 3072
-    # mirrors the loop of adj_scan_kernel: ceil(V / 1024) trips of one block, the carry crossing every border between them
-    assert len(V0) == 2562 and n % SCAN_CHUNK == 0 and n // SCAN_CHUNK == 3 and len(V0) > 2 * SCAN_CHUNK
+    assert len(V0) == 2562
     rows = rng.permutation(n)[: len(V0)]
     V = rng.normal(0, 0.3, size=(n, 3))
     V[rows] = V0
-    F = rows[F0]
-    valence = np.bincount(F.reshape(-1), minlength=n)
-    assert (valence == 0).sum() == n - len(V0)
-    for border in (SCAN_CHUNK, 2 * SCAN_CHUNK):
-        assert valence[:border].sum() > 0 and valence[border - 8: border + 8].max() > 0 and valence[border:].sum() > 0
-        assert (valence[border - 64: border + 64] == 0).any()
+    return V, rows[F0]
+
+
+def test_unused_vertices_never_show_and_face_lists_hold_over_the_index_range():
+    """The sparse mesh above: used and unused rows interleaved over the whole index range.  A vertex that got the face list of
+    another one would have a moved normal; the unused rows' positions and normals must never show."""
+    V, F = sparse_icosphere()
+    valence = np.bincount(F.reshape(-1), minlength=len(V))
+    assert (valence == 0).sum() == len(V) - 2562
     cams = [R.uniform_cameras(distance=3.0)[t] for t in R.VISUALIZER_CAMERAS]
     got = render(V, F, cams, 48)
     assert check_against_restatement(V, F, cams, 48, got) > 3 * 48 * 48 * 0.8
@@ -339,6 +337,19 @@ def test_deterministic_and_batch_independent():
             s = render(Vt[t], F, [cams[c]], 96)
             for k in a:
                 assert np.array_equal(a[k][t, c].view(np.uint8), s[k][0, 0].view(np.uint8)), (k, t, c)
+
+
+def test_face_index_outside_the_mesh_is_a_value_error():
+    """The faces are validated on the device: one index equal to V is reported behind the launch, in the mesh stage's words."""
+    from actionmesh_amd import ops
+    V, F = octahedron((0.0, 0.0, 0.0), 0.5)
+    verts = torch.as_tensor(V, dtype=torch.float32)[None].to(DEV)
+    clean = ops.render_normals(verts, torch.as_tensor(F), [cam()], 8)
+    assert int(clean["rgba"][..., 3].max()) > 0
+    bad = F.copy()
+    bad[5, 1] = len(V)
+    with pytest.raises(ValueError, match=r"a face names a vertex outside \[0, 6\)"):
+        ops.render_normals(verts, torch.as_tensor(bad), [cam()], 8)
 
 
 def test_visualizer_end_to_end(tmp_path):
