@@ -43,6 +43,14 @@ GEMM_ABLATE_STORE, GEMM_ABLATE_READ, GEMM_ABLATE_MASK = 0x800, 0x1000, 0x1800
 GEMM_SKEW_SHIFT, GEMM_SKEW_MASK = 13, 0xe000
 GEMM_NO_GELU_TABLE = 0x10000
 
+# am_attn_args.defer_log2 and the row stride of am_attn_args.state (the AM_ATTN_* defines of include/actionmesh_amd.h, which explains
+# them; tests/test_host_cpu.py holds the two lists equal)
+ATTN_STATE_LD = 132
+ATTN_REBASE_ALWAYS, ATTN_REBASE_DEFERRED = 0, 8
+ATTN_4WAVE, ATTN_4X64, ATTN_BALANCED, ATTN_8WAVE, ATTN_4X64_DEFERRED = 50, 60, 70, 90, 28
+ATTN_VARIANTS, ATTN_ABLATE_4X64 = 100, 3000
+ATTN_FP8_ABLATE, ATTN_FP8_4X64, ATTN_FP8_8WAVE, ATTN_FP8_PRODUCT_ABLATE, ATTN_FP8_FAST = 5000, 5100, 5200, 5300, 5400
+
 
 class AmGemmArgs(C.Structure):
     _fields_ = [

@@ -65,15 +65,14 @@
 // concatenated tile streams, each with its own valid-key count.
 #include <algorithm>
 
-#include "am_common.h"
+#include "am_attention_host.h"
 
 namespace {
 
-constexpr int KVBLK = 64;          // keys per sub-tile
-constexpr int HD = 128;
+constexpr int KVBLK = AM_ATTN_KEY_TILE;        // keys per sub-tile
+constexpr int HD = AM_ATTN_HD;
 constexpr int SUB_B = KVBLK * HD * 2;          // one K or V^T sub-tile: 16 KiB
-constexpr int PART_LD = HD + 4;                // floats per partial row: O[128], m, l, pad (16-B aligned rows)
-constexpr int SPLIT_Z = 16;
+constexpr int PART_LD = AM_ATTN_STATE_LD;      // floats per partial row: O[128], m, l, pad (16-B aligned rows)
 // Geometry (template NW = waves per workgroup, NSUB = 64-key sub-tiles per barrier):
 //   NW = 8, NSUB = 2: one 8-wave workgroup per CU, 256 query rows, 128 KiB LDS
 //   NW = 4, NSUB = 1: two independent 4-wave workgroups per CU (128 query rows, 64 KiB LDS each): the two
@@ -917,85 +916,108 @@ int am_attention_combine_launch(const am_attn_args* a, const float* part, int Z,
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
-int am_attention64_main(const am_attn_args* a, int tiles_per_chunk, int nblk_main, int defer, void* stream);  // am_attention64.hip
+int am_attn_partials(am_attn_family family, size_t floats, float** out) {
+  static float* buf[2][64] = {};
+  static size_t cap[2][64] = {};
+  int dev = 0;
+  AM_HIP(hipGetDevice(&dev));
+  AM_CHECK(dev >= 0 && dev < 64, "am_attn_partials: device index %d", dev);
+  if (cap[family][dev] < floats) {
+    if (buf[family][dev]) AM_HIP(hipFree(buf[family][dev]));
+    buf[family][dev] = nullptr; cap[family][dev] = 0;
+    ++g_am_scratch_generation;
+    AM_HIP(hipMalloc(reinterpret_cast<void**>(&buf[family][dev]), floats * sizeof(float)));
+    cap[family][dev] = floats;
+  }
+  *out = buf[family][dev];
+  return AM_OK;
+}
 namespace {
 
-// MAIN: 0 = this file's 8-wave kernel, 1 = balanced two-phase variant, 2 = the 4x64 kernel of am_attention64.hip,
-// 3 = product dispatch: 4x64 for long key streams (>= 16 tiles: its pipeline needs a few tiles to fill and its
-// per-workgroup prologue is heavier - cross-attention with 257 keys runs 15 % faster on the 8-wave kernel).
-// The split tail always runs the 8-wave kernel (same 256-row query blocks).
-template <int DEFER, int NW, int NSUB, int MAIN = 0>
-int launch(const am_attn_args* a, void* stream) {
-  constexpr bool BALANCED = MAIN == 1;
-  const bool use64 = MAIN == 2 || (MAIN == 3 && ceil_div(a->sk, KVBLK) * a->nchunks >= 16);
+// The kernel that takes the main grid.  The split tail always runs this file's 8-wave code (see launch).
+enum class Main {
+  Wave8,      // this file's 8-wave kernel, in the geometry launch<> is instantiated for
+  Balanced,   // its balanced two-phase variant
+  X64,        // the 4x64 kernel of am_attention64.hip
+  Product,    // 4x64 for long key streams (>= 16 tiles: its pipeline needs a few tiles to fill and its per-workgroup prologue is
+              // heavier - cross-attention with 257 keys runs 15 % faster on the 8-wave kernel), the 8-wave kernel otherwise
+};
+
+template <int DEFER, int NW, int NSUB>
+int launch(const am_attn_args* a, void* stream, Main main) {
+  const bool use64 = main == Main::X64 || (main == Main::Product && ceil_div(a->sk, KVBLK) * a->nchunks >= 16);
   using G = Geo<NW, NSUB>;
-  // The split tail (a short last query block cut SPLIT_Z ways over the key range) always runs the 4-wave / 128-row geometry: at most
-  // G::QBLK / 2 <= 128 rows are valid, so one 128-row block holds them, half as many waves walk keys for padding rows, and two
+  // The split tail (a short last query block cut AM_ATTN_SPLIT_Z ways over the key range) always runs the 4-wave / 128-row geometry: at
+  // most G::QBLK / 2 <= 128 rows are valid, so one 128-row block holds them, half as many waves walk keys for padding rows, and two
   // workgroups share a CU (round 4; profiles/r04z_split_tail.txt - before, it ran in the caller's 256-row geometry: 143 + 9 us).
   using GS = Geo<4, 1>;
   constexpr int RATIO = G::QBLK / GS::QBLK;
-  AM_ONCE_PER_DEVICE({
-    if (BALANCED)
+  if (main == Main::Balanced)
+    AM_ONCE_PER_DEVICE({
       AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_balanced_kernel<DEFER>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 4 * SUB_B));
+    });
+  AM_ONCE_PER_DEVICE({
     AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<DEFER, false, NW, NSUB>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM));
     AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<DEFER, true, 4, 1>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, GS::SMEM));
   });
   const int tiles_per_chunk = ceil_div(a->sk, KVBLK);
-  const int all_supers = ceil_div(tiles_per_chunk, NSUB) * a->nchunks;
-  const int nblk = ceil_div(a->sq, G::QBLK);
   const int bh = a->nseq * a->heads;
-  const int tail_rows = a->sq - (nblk - 1) * G::QBLK;
+  const am_attn_qblocks q = am_attn_plan_qblocks(a, G::QBLK);
   // split the short last query block over the key range when it would otherwise add a round
-  static float* part = nullptr;       // library-owned scratch, grown on demand
-  static size_t part_elems = 0;
-  // (32 cuts instead of 16 change nothing - measured: the pass re-reads every K / V^T byte of the launch for 16 query rows, 537 MB at the
-  // headline shape = 107 us at 5 TB/s, and sits at 116 us: it is at its HBM floor)
-  const int Z = SPLIT_Z;
-  const size_t need = (size_t)bh * Z * GS::QBLK * PART_LD;
-  // a->rows: 0 = every query block; 1 = only the blocks the 4x64 kernel takes ("main": all but a short last block);
-  // 2 = only what rows = 1 leaves out.  The main/rest boundary depends on the query geometry alone, so the calls of a
-  // two-pass sequence (different nchunks) agree on it.
-  const bool tail_geom = nblk >= 9 && tail_rows <= G::QBLK / 2;
-  const bool can_split = (int64_t)tiles_per_chunk * a->nchunks >= 2 * SPLIT_Z && all_supers >= 2 * SPLIT_Z && need * sizeof(float) <= (256u << 20);
-  const bool split = tail_geom && can_split;
+  const size_t need = am_attn_part_floats(a, GS::QBLK);
+  const bool split = q.tail_rest && am_attn_bf16_splits(a, NSUB, need);
   if (a->rows == 1) {
     AM_CHECK(use64, "am_attention_bf16: rows = 1 / two-pass needs the 4x64 kernel (>= 16 key tiles in the chunks walked)");
-    AM_TRY(am_attention64_main(a, tiles_per_chunk, tail_geom ? nblk - 1 : nblk, DEFER, stream));
+    AM_TRY(am_attention64_main(a, tiles_per_chunk, q.nblk_main, DEFER, stream));
     AM_HIP(hipGetLastError());
     return AM_OK;
   }
-  if (a->rows == 2 && !tail_geom) return AM_OK;
-  if (split && part_elems < need) {
-    if (part) AM_HIP(hipFree(part));
-    part = nullptr; part_elems = 0;
-    ++g_am_scratch_generation;
-    AM_HIP(hipMalloc(reinterpret_cast<void**>(&part), need * sizeof(float)));
-    part_elems = need;
-  }
+  if (a->rows == 2 && !q.tail_rest) return AM_OK;
+  float* part = nullptr;
+  if (split) AM_TRY(am_attn_partials(AM_ATTN_FAMILY_BF16, need, &part));
   hipStream_t st = (hipStream_t)stream;
+  const int nblk_grid = split ? q.nblk - 1 : q.nblk;       // rows = 0: an un-split "rest" block rides in the main grid
   if (a->rows == 2) {
     if (!split)          // the short last block alone, un-split (key stream too short to cut 16 ways)
       hipLaunchKernelGGL((attn_fwd_kernel<DEFER, false, NW, NSUB>), dim3(1, bh), dim3(G::THREADS), G::SMEM, st, *a,
-                         tiles_per_chunk, nblk - 1, (float*)nullptr);
-  } else if (use64)
-    AM_TRY(am_attention64_main(a, tiles_per_chunk, split ? nblk - 1 : nblk, DEFER, stream));
-  else if (BALANCED)
-    hipLaunchKernelGGL((attn_fwd_balanced_kernel<DEFER>), dim3(split ? nblk - 1 : nblk, bh), dim3(512), 4 * SUB_B, st, *a,
-                       tiles_per_chunk);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<DEFER, false, NW, NSUB>), dim3(split ? nblk - 1 : nblk, bh), dim3(G::THREADS), G::SMEM,
+                         tiles_per_chunk, q.nblk - 1, (float*)nullptr);
+  } else if (use64) {
+    AM_TRY(am_attention64_main(a, tiles_per_chunk, nblk_grid, DEFER, stream));
+  } else if (main == Main::Balanced) {
+    hipLaunchKernelGGL((attn_fwd_balanced_kernel<DEFER>), dim3(nblk_grid, bh), dim3(512), 4 * SUB_B, st, *a, tiles_per_chunk);
+  } else {
+    hipLaunchKernelGGL((attn_fwd_kernel<DEFER, false, NW, NSUB>), dim3(nblk_grid, bh), dim3(G::THREADS), G::SMEM,
                        st, *a, tiles_per_chunk, 0, (float*)nullptr);
+  }
   if (split) {
-    hipLaunchKernelGGL((attn_fwd_kernel<DEFER, true, 4, 1>), dim3(1, bh, Z), dim3(GS::THREADS), GS::SMEM, st, *a,
-                       tiles_per_chunk, (nblk - 1) * RATIO, part);
-    hipLaunchKernelGGL(attn_combine_kernel, dim3(tail_rows, bh), dim3(128), 0, st, *a, part, Z, (nblk - 1) * RATIO, tail_rows,
-                       GS::QBLK);
+    hipLaunchKernelGGL((attn_fwd_kernel<DEFER, true, 4, 1>), dim3(1, bh, AM_ATTN_SPLIT_Z), dim3(GS::THREADS), GS::SMEM, st, *a,
+                       tiles_per_chunk, (q.nblk - 1) * RATIO, part);
+    hipLaunchKernelGGL(attn_combine_kernel, dim3(q.tail_rows, bh), dim3(128), 0, st, *a, part, AM_ATTN_SPLIT_Z, (q.nblk - 1) * RATIO,
+                       q.tail_rows, GS::QBLK);
   }
   AM_HIP(hipGetLastError());
   return AM_OK;
+}
+
+// am_attn_args.defer_log2 (the AM_ATTN_* codes of include/actionmesh_amd.h), decoded once: the re-base threshold, the kernel of the main
+// grid, and whether the 8-wave code runs in its 4-wave geometry (two independent 4-wave workgroups per CU, 64 KiB of LDS each).
+struct Choice { int defer; Main main; bool wave4; };
+bool decode(int code, Choice* c) {
+  static const struct { int base; Main main; bool wave4; } bases[] = {
+      {0, Main::Product, false}, {AM_ATTN_4WAVE, Main::Wave8, true}, {AM_ATTN_4X64, Main::X64, false},
+      {AM_ATTN_BALANCED, Main::Balanced, false}, {AM_ATTN_8WAVE, Main::Wave8, false}};
+  for (const auto& b : bases)
+    for (int defer : {AM_ATTN_REBASE_ALWAYS, AM_ATTN_REBASE_DEFERRED})
+      if (code == b.base + defer) { *c = {defer, b.main, b.wave4}; return true; }
+  bool x64_deferred = code == AM_ATTN_4X64_DEFERRED;       // same kernel family, exact deferred re-base (am_attention64_main reads the code)
+#ifdef AM_ATTN_ABLATIONS
+  x64_deferred |= code >= AM_ATTN_ABLATE_4X64;             // 4x64 timing ablations
+#endif
+  if (x64_deferred) *c = {AM_ATTN_REBASE_DEFERRED, Main::X64, false};
+  return x64_deferred;
 }
 
 }  // namespace
@@ -1033,63 +1055,40 @@ static int launch_resident(const am_attn_args* a, void* stream) {
 }
 
 #ifdef AM_ATTN_ABLATIONS
-int am_attention_variant(const am_attn_args* a, void* stream);   // am_attention_variants.hip
+int am_attention_variant(const am_attn_args* a, void* stream);   // the A/B build's experimental schedules
 #endif
 
-// defer_log2: 0 = exact online softmax, re-based whenever a row max grows; 8 = product: deferred re-base (threshold 2^8)
-// on the 8-wave kernel, the lazy re-base of am_attention64.hip (+ its exact fallback launch) on the 4x64 kernel.
-// Other codes force one kernel for A/B runs and parity tests: +60 the 4x64 kernel, +90 the 8-wave kernel,
-// +50 / +70 its geometry / schedule variants; 28 = the 4x64 kernel with the exact deferred re-base on its own.
-// Builds with -DAM_ATTN_ABLATIONS also accept the experimental schedules of am_attention_variants.hip
-// (defer_log2 >= 100, used by tools/kernel_bench.py for A/B measurements).
+// The meaning of defer_log2: the AM_ATTN_* codes beside am_attn_args (include/actionmesh_amd.h).
 extern "C" int am_attention_bf16(const am_attn_args* a, void* stream) {
-  AM_CHECK(a != nullptr, "am_attention_bf16: null args");
+  AM_TRY(am_attn_check_args(a, "am_attention_bf16"));
   AM_CHECK(a->Q && a->K && a->Vt && a->O, "am_attention_bf16: null operand");
-  AM_CHECK(a->nseq > 0 && a->heads > 0 && a->sq > 0 && a->sk > 0 && a->nchunks > 0,
-           "am_attention_bf16: empty problem");
-  AM_CHECK(a->sq_pad % 256 == 0 && a->sq_pad >= a->sq, "am_attention_bf16: sq_pad=%d must be a multiple of 256 and >= sq=%d",
-           a->sq_pad, a->sq);
-  AM_CHECK(a->sk_pad % KVBLK == 0 && a->sk_pad >= a->sk, "am_attention_bf16: sk_pad=%d must be a multiple of %d and >= sk=%d",
-           a->sk_pad, KVBLK, a->sk);
   AM_CHECK(a->ldo % 4 == 0 && a->ldo >= a->heads * HD, "am_attention_bf16: ldo=%d too small / misaligned", a->ldo);
   AM_CHECK(a->nchunks == 1 || a->chunk_stride >= (int64_t)a->nseq * a->heads * a->sk_pad * HD,
            "am_attention_bf16: chunk_stride too small");
   AM_CHECK(((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->Vt) % 16 == 0 && (uintptr_t)a->O % 8 == 0,
            "am_attention_bf16: operands misaligned");
-  AM_CHECK((int64_t)a->nseq * a->heads <= 65535, "am_attention_bf16: nseq*heads=%lld exceeds grid.y",
-           (long long)a->nseq * a->heads);
-  AM_CHECK(a->rows >= 0 && a->rows <= 2 && a->state_mode >= 0 && a->state_mode <= 2, "am_attention_bf16: bad rows / state_mode");
-  AM_CHECK(a->state_mode == 0 || (a->rows == 1 && a->state != nullptr && (uintptr_t)a->state % 16 == 0),
-           "am_attention_bf16: state_mode needs rows = 1 and a 16-byte aligned state buffer");
-  AM_CHECK(a->chunk_total == 0 || (a->rows == 1 && a->chunk_total > 0 && a->chunk_first >= 0 && a->chunk_first < a->chunk_total &&
-                                   a->nchunks <= a->chunk_total),
-           "am_attention_bf16: chunk_first/chunk_total need rows = 1, 0 <= first < total, nchunks <= total");
-  AM_CHECK(a->rows != 1 || a->defer_log2 == 0 || a->defer_log2 == 8 || a->defer_log2 == 60 || a->defer_log2 == 68 || a->defer_log2 == 28,
+  AM_CHECK(a->chunk_total == 0 || a->rows == 1, "am_attention_bf16: chunk_first / chunk_total need rows = 1");
+  const int code = a->defer_log2;
+  AM_CHECK(a->rows != 1 || code == AM_ATTN_REBASE_ALWAYS || code == AM_ATTN_REBASE_DEFERRED || code == AM_ATTN_4X64 + AM_ATTN_REBASE_ALWAYS ||
+               code == AM_ATTN_4X64 + AM_ATTN_REBASE_DEFERRED || code == AM_ATTN_4X64_DEFERRED,
            "am_attention_bf16: rows = 1 runs on the product dispatch only");
+  Choice c;
+  if (!decode(code, &c)) {
+#ifdef AM_ATTN_ABLATIONS
+    if (code >= AM_ATTN_VARIANTS) return am_attention_variant(a, stream);
+#endif
+    AM_FAIL(AM_ERR_INVALID, "am_attention_bf16: defer_log2 must be 0 or 8 (got %d)", code);
+  }
   // Short key streams (< 16 tiles: the cross-attention's 257 context tokens, the encoders' sequences) run the 8-wave kernel's
   // code in its OTHER geometry - two independent 4-wave workgroups per CU, 64 KiB of LDS each: a workgroup that walks 5 key tiles is
   // mostly prologue (Q fragments, the first K / V^T tiles in flight) and epilogue, and the second resident workgroup covers them.
   // Same arithmetic per row: bit-identical output; 15-18 % faster at the cross shapes (profiles/r04y_cross_attn_geometry.txt).
   const bool short_stream = a->rows == 0 && (int64_t)ceil_div(a->sk, KVBLK) * a->nchunks < 16;
-  if (short_stream && (a->defer_log2 == 0 || a->defer_log2 == 8) && resident_eligible(a))
-    return a->defer_log2 == 0 ? launch_resident<0>(a, stream) : launch_resident<8>(a, stream);
-  switch (a->defer_log2) {
-    case 0: return short_stream ? launch<0, 4, 1>(a, stream) : launch<0, 8, 2, 3>(a, stream);
-    case 8: return short_stream ? launch<8, 4, 1>(a, stream) : launch<8, 8, 2, 3>(a, stream);
-    case 90: return launch<0, 8, 2>(a, stream);      // forced 8-wave kernel (A/B, tests)
-    case 98: return launch<8, 8, 2>(a, stream);
-    case 50: return launch<0, 4, 1>(a, stream);     // geometry A/B: two 4-wave workgroups per CU
-    case 58: return launch<8, 4, 1>(a, stream);
-    case 60: return launch<0, 8, 2, 2>(a, stream);   // 4 waves x 64 rows, one wave per SIMD (am_attention64.hip)
-    case 68: return launch<8, 8, 2, 2>(a, stream);
-    case 28: return launch<8, 8, 2, 2>(a, stream);   // same kernel family, exact deferred re-base (no lazy pass)
-    case 70: return launch<0, 8, 2, 1>(a, stream);   // balanced two-phase schedule
-    case 78: return launch<8, 8, 2, 1>(a, stream);
-    default:
-#ifdef AM_ATTN_ABLATIONS
-      if (a->defer_log2 >= 3000) return launch<8, 8, 2, 2>(a, stream);     // 4x64 timing ablations
-      if (a->defer_log2 >= 100) return am_attention_variant(a, stream);
-#endif
-      AM_FAIL(AM_ERR_INVALID, "am_attention_bf16: defer_log2 must be 0 or 8 (got %d)", a->defer_log2);
+  if (short_stream && c.main == Main::Product) {
+    if (resident_eligible(a)) return c.defer == 0 ? launch_resident<0>(a, stream) : launch_resident<8>(a, stream);
+    c.main = Main::Wave8;
+    c.wave4 = true;
   }
+  if (c.defer == 0) return c.wave4 ? launch<0, 4, 1>(a, stream, c.main) : launch<0, 8, 2>(a, stream, c.main);
+  return c.wave4 ? launch<8, 4, 1>(a, stream, c.main) : launch<8, 8, 2>(a, stream, c.main);
 }

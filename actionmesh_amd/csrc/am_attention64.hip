@@ -32,7 +32,7 @@
 // IEEE mode off for this file, so fmaxf chains become v_max3_f32 without canonicalising v_max's; hipcc owns the
 // MFMA -> VALU hazards of its own instructions, the asm statements carry theirs (DESIGN.md 4.1 lists the three
 // that bit: SrcC write-after-read, in-flight results at loop exit, operand registers re-used too early).
-#include "am_common.h"
+#include "am_attention_host.h"
 
 namespace {
 
@@ -240,7 +240,7 @@ struct ExpSumPackT {
 // 4 = no barrier / DMA drain, 8 = no exp/sum/pack at all, 16 = no LDS fragment reads (stale registers)
 // STATE (two-pass attention, am_attn_args.state_mode): 0 = one pass; 1 = save the un-normalised (O, m, l) of every row
 // to p.state instead of writing O; 2 = resume from p.state, finish, write O.
-constexpr int STATE_LD = 132;      // floats per saved row: O[128], m, l, pad (16-byte aligned rows)
+constexpr int STATE_LD = AM_ATTN_STATE_LD;      // floats per saved row: O[128], m, l, pad (16-byte aligned rows)
 // LAZY: no row max in the loop.  m_run starts at tile 0's row max rounded up to a whole octave; the scores of a tile are exponentiated relative to the
 // m_run they were born with; the tile's row sums (computed anyway) tell afterwards whether m_run has fallen behind
 // (sum > 2^12), and the rare re-base multiplies O, l and the not yet consumed P by an exact power of two and moves m_run up
@@ -948,29 +948,29 @@ static int launch64(const am_attn_args* a, int tiles_per_chunk, int nblk_main, v
 }
 int am_attention64_main(const am_attn_args* a, int tiles_per_chunk, int nblk_main, int defer, void* stream) {
 #ifdef AM_ATTN_ABLATIONS
-  switch (a->defer_log2) {     // 3000 + ABL: timing ablations (tools/kernel_bench.py --ablate64)
-    case 3001: return launch64<8, 1, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3002: return launch64<8, 2, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3004: return launch64<8, 4, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3008: return launch64<8, 8, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3010: return launch64<8, 10, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3014: return launch64<8, 14, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3016: return launch64<8, 16, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3030: return launch64<8, 30, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3032: return launch64<8, 32, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3064: return launch64<8, 64, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3128: return launch64<8, 128, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3132: return launch64<8, 132, 0, true>(a, tiles_per_chunk, nblk_main, stream);
-    case 3142: return launch64<8, 142, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+  switch (a->defer_log2 - AM_ATTN_ABLATE_4X64) {     // + ABL: timing ablations (tools/kernel_bench.py --ablate64)
+    case 1: return launch64<8, 1, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 2: return launch64<8, 2, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 4: return launch64<8, 4, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 8: return launch64<8, 8, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 10: return launch64<8, 10, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 14: return launch64<8, 14, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 16: return launch64<8, 16, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 30: return launch64<8, 30, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 32: return launch64<8, 32, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 64: return launch64<8, 64, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 128: return launch64<8, 128, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 132: return launch64<8, 132, 0, true>(a, tiles_per_chunk, nblk_main, stream);
+    case 142: return launch64<8, 142, 0, true>(a, tiles_per_chunk, nblk_main, stream);
     default: break;
   }
 #endif
   // defer > 0: the lazy kernel (+ exact fallback); defer == 0: the exact kernel with an immediate re-base;
-  // a->defer_log2 == 28: the exact kernel with the deferred re-base on its own (A/B, tests)
+  // a->defer_log2 == AM_ATTN_4X64_DEFERRED: the exact kernel with the deferred re-base on its own (A/B, tests)
 #ifdef AM_F16
   const bool exact = true;                 // float16 build: P in IEEE half cannot carry the lazy re-base's 2^+-60 lags - running row max only
 #else
-  const bool exact = a->defer_log2 == 28;
+  const bool exact = a->defer_log2 == AM_ATTN_4X64_DEFERRED;
 #endif
   if (a->state_mode == 1)
     return defer == 0 ? launch64<0, 0, 1>(a, tiles_per_chunk, nblk_main, stream)
@@ -988,7 +988,7 @@ int am_attention64_main(const am_attn_args* a, int tiles_per_chunk, int nblk_mai
 #ifdef AM_ATTN_ABLATIONS
 // per-phase s_memtime stamps of workgroup (0,0): prof[4 waves][8 tiles (64..71)][8 slots]  (tools/attn_profile.py --k64)
 extern "C" int am_attention64_profile(const am_attn_args* a, unsigned long long* prof_dev, void* stream) {
-  const bool lazy = a->defer_log2 != 28;
+  const bool lazy = a->defer_log2 != AM_ATTN_4X64_DEFERRED;
   const void* fn = lazy ? reinterpret_cast<const void*>(attn_fwd64_kernel<8, 0, true, 0, true>)
                         : reinterpret_cast<const void*>(attn_fwd64_kernel<8, 0, true>);
   AM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_B));

@@ -29,7 +29,7 @@
 // past a chunk's end are a wave-uniform branch taken once per chunk; fragment reads and LDS-DMA issue sit in the matrix
 // interval, between MFMAs, where the wave only waits for the pipe.  (Row sums on the matrix pipe - one more MFMA against a
 // block of ones - were written and dropped: 24 more registers, and at 256 the kernel spills.)
-#include "am_common.h"
+#include "am_attention_host.h"
 
 namespace {
 
@@ -40,8 +40,8 @@ typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 #ifndef AM_F8_PKSUM
 #define AM_F8_PKSUM 1      // row sums as packed adds: 17.55 -> 17.15 ms at the headline launch (profiles/r03k_ab.txt)
 #endif
-constexpr int HD8 = 128;
-constexpr int KT = 64;                 // keys per tile
+constexpr int HD8 = AM_ATTN_HD;
+constexpr int KT = AM_ATTN_KEY_TILE;   // keys per tile
 constexpr int STAGE_BYTES = 16384;     // K8 tile [64][128] + V8T tile [128][64]
 constexpr int NSTAGE = 8;             // ring slots (tiles are staged five ahead)
 constexpr float P_SHIFT = 5.f;         // probabilities are carried as 2^5 p (row sums too: the factor cancels in O / l)
@@ -153,8 +153,7 @@ struct f8_args {
   float* state;                    // MODE 1 / 2: un-normalised (O, m, l) per row, [seq*heads][sq_pad][F8_STATE_LD]
   float* part;                     // MODE 3: partials of the split last block, [seq*heads][Z][256][F8_STATE_LD]
 };
-constexpr int F8_STATE_LD = 132;   // floats per saved row: O[128], m, l, pad - the layout of the bf16 kernels (am_attention64.hip)
-constexpr int F8_SPLIT_Z = 16;
+constexpr int F8_STATE_LD = AM_ATTN_STATE_LD;   // floats per saved row: O[128], m, l, pad - the layout of the bf16 kernels (am_attention64.hip)
 
 // ABL: timing ablations (numerically meaningless; tools/kernel_bench.py --ablate-fp8): 1 no exponentials, 2 no LDS-DMA in the
 // loop, 4 no fragment reads in the loop, 8 no MFMAs in the loop, 16 no row max.
@@ -1451,28 +1450,17 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
 
 }  // namespace
 
-int am_attention_combine_launch(const am_attn_args* a, const float* part, int Z, int qblk_base, int rows, void* stream);   // am_attention.hip
-
-static int check_args(const am_attn_args* a, const char* who) {
-  AM_CHECK(a != nullptr, "%s: null args", who);
-  AM_CHECK(a->nseq > 0 && a->heads > 0 && a->sq > 0 && a->sk > 0 && a->nchunks > 0, "%s: empty problem", who);
-  AM_CHECK(a->sq_pad % 256 == 0 && a->sq_pad >= a->sq, "%s: sq_pad=%d must be a multiple of 256 and >= sq=%d", who, a->sq_pad, a->sq);
-  AM_CHECK(a->sk_pad % KT == 0 && a->sk_pad >= a->sk, "%s: sk_pad=%d must be a multiple of 64 and >= sk=%d", who, a->sk_pad, a->sk);
+static int check_operands(const am_attn_args* a, const char* who) {
+  AM_TRY(am_attn_check_args(a, who));
   AM_CHECK((a->nchunks == 1 && a->chunk_total == 0) || a->chunk_stride >= (int64_t)a->nseq * a->heads * a->sk_pad * HD8,
            "%s: chunk_stride too small", who);
-  AM_CHECK(a->rows >= 0 && a->rows <= 2 && a->state_mode >= 0 && a->state_mode <= 2, "%s: bad rows / state_mode", who);
-  AM_CHECK(a->state_mode == 0 || (a->rows == 1 && a->state != nullptr && (uintptr_t)a->state % 16 == 0),
-           "%s: state_mode needs rows = 1 and a 16-byte aligned state buffer", who);
-  AM_CHECK(a->chunk_total == 0 || (a->chunk_total > 0 && a->chunk_first >= 0 && a->chunk_first < a->chunk_total && a->nchunks <= a->chunk_total),
-           "%s: chunk_first / chunk_total need 0 <= first < total, nchunks <= total", who);
-  AM_CHECK((int64_t)a->nseq * a->heads <= 65535, "%s: nseq*heads exceeds grid.y", who);
   return AM_OK;
 }
 
 // chunk_first / chunk_total select the chunks that are quantised (the ones an attention call with the same arguments walks); Q is
 // quantised unless rows == 2 (the caller has done it with the rows = 1 call of the same layer).
 extern "C" int am_attention_quantize_fp8(const am_attn_args* a, uint8_t* q8, uint8_t* k8, uint8_t* vt8, void* stream) {
-  AM_TRY(check_args(a, "am_attention_quantize_fp8"));
+  AM_TRY(check_operands(a, "am_attention_quantize_fp8"));
   AM_CHECK(a->K && a->Vt && k8 && vt8 && (a->rows == 2 || (a->Q && q8)), "am_attention_quantize_fp8: null operand");
   AM_CHECK(((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->Vt | (uintptr_t)q8 | (uintptr_t)k8 | (uintptr_t)vt8) % 16 == 0 &&
                a->chunk_stride % 16 == 0, "am_attention_quantize_fp8: operands misaligned");
@@ -1495,28 +1483,38 @@ extern "C" int am_attention_quantize_fp8(const am_attn_args* a, uint8_t* q8, uin
   return AM_OK;
 }
 
-extern "C" int am_attention_fp8(const am_attn_args* a, const uint8_t* q8, const uint8_t* k8, const uint8_t* vt8, void* stream) {
-  AM_TRY(check_args(a, "am_attention_fp8"));
-  AM_CHECK(q8 && k8 && vt8 && a->O, "am_attention_fp8: null operand");
-  AM_CHECK(((uintptr_t)q8 | (uintptr_t)k8 | (uintptr_t)vt8) % 16 == 0 && (uintptr_t)a->O % 8 == 0 && a->chunk_stride % 16 == 0,
-           "am_attention_fp8: operands misaligned");
-  AM_CHECK(a->ldo % 4 == 0 && a->ldo >= a->heads * HD8, "am_attention_fp8: ldo=%d too small / misaligned", a->ldo);
-  AM_CHECK((int64_t)HD8 * a->sk_pad * 1 < (1ll << 31), "am_attention_fp8: sk_pad too large for 32-bit lane offsets");
-  const int abl = a->defer_log2 >= 5000 ? a->defer_log2 - 5000 : 0;     // 5000 + ABL: timing ablations (one-pass form only)
-  AM_CHECK(abl == 0 || abl == 200 || abl == 100 || abl == 400 || (a->rows == 0 && a->state_mode == 0), "am_attention_fp8: ablation codes run the one-pass form only");
-#define F8_ATTR(...) AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_BYTES))
-#define X64_ATTR(...) AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8x64_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_BYTES))
-  AM_ONCE_PER_DEVICE({ X64_ATTR(0, 0); X64_ATTR(1, 0); X64_ATTR(2, 0); X64_ATTR(8, 0); X64_ATTR(0, 1); X64_ATTR(0, 2); });
-#undef X64_ATTR
-#define P_ATTR(...) AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8p_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES))
-#ifdef AM_ATTN_ABLATIONS
-  AM_ONCE_PER_DEVICE({ P_ATTR(12, 0, 0); P_ATTR(24, 0, 0); P_ATTR(40, 0, 0); P_ATTR(10, 0, 0); P_ATTR(62, 0, 0); P_ATTR(4, 0, 0); P_ATTR(16, 0, 0); P_ATTR(32, 0, 0); });
-#endif
-  AM_ONCE_PER_DEVICE({ P_ATTR(0, 0, 0); P_ATTR(1, 0, 0); P_ATTR(2, 0, 0); P_ATTR(8, 0, 0); P_ATTR(0, 1, 0); P_ATTR(0, 2, 0); P_ATTR(0, 0, 1); P_ATTR(0, 1, 1); P_ATTR(0, 2, 1); });
-#undef P_ATTR
-  AM_ONCE_PER_DEVICE({ F8_ATTR(0, 0); F8_ATTR(1, 0); F8_ATTR(2, 0); F8_ATTR(4, 0); F8_ATTR(8, 0); F8_ATTR(16, 0); F8_ATTR(17, 0); F8_ATTR(6, 0);
-                       F8_ATTR(32, 0); F8_ATTR(64, 0); F8_ATTR(40, 0); F8_ATTR(0, 1); F8_ATTR(0, 2); F8_ATTR(0, 3); });
-#undef F8_ATTR
+// One launcher per kernel.  Every instantiation needs more than 64 KiB of dynamic LDS; it raises its own limit the first time it is
+// launched on a device, so the switch statements below are the only list of instantiations.
+template <int ABL, int MODE>
+static int launch_fp8(const f8_args& p, dim3 grid, hipStream_t st) {
+  AM_ONCE_PER_DEVICE({
+    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8_kernel<ABL, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               NSTAGE * STAGE_BYTES));
+  });
+  hipLaunchKernelGGL((attn_fp8_kernel<ABL, MODE>), grid, dim3(512), NSTAGE * STAGE_BYTES, st, p);
+  return AM_OK;
+}
+template <int ABL, int MODE, bool PROF = false>
+static int launch_fp8x64(const f8_args& p, dim3 grid, hipStream_t st, unsigned long long* prof = nullptr) {
+  AM_ONCE_PER_DEVICE({
+    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8x64_kernel<ABL, MODE, PROF>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               NSTAGE * STAGE_BYTES));
+  });
+  hipLaunchKernelGGL((attn_fp8x64_kernel<ABL, MODE, PROF>), grid, dim3(256), NSTAGE * STAGE_BYTES, st, p, prof);
+  return AM_OK;
+}
+template <int ABL, int MODE, int FAST = 0, bool PROF = false>
+static int launch_fp8p(const f8_args& p, dim3 grid, hipStream_t st, unsigned long long* prof = nullptr) {
+  AM_ONCE_PER_DEVICE({
+    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8p_kernel<ABL, MODE, FAST, PROF>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               P_LDS_BYTES));
+  });
+  hipLaunchKernelGGL((attn_fp8p_kernel<ABL, MODE, FAST, PROF>), grid, dim3(512), P_LDS_BYTES, st, p, prof);
+  return AM_OK;
+}
+
+// the kernels' view of a call: all query blocks from block 0, no partials
+static f8_args kernel_args(const am_attn_args* a, const uint8_t* q8, const uint8_t* k8, const uint8_t* vt8) {
   f8_args p;
   p.Q = q8; p.K = k8; p.Vt = vt8; p.O = a->O;
   p.heads = a->heads; p.sq = a->sq; p.sq_pad = a->sq_pad; p.sk = a->sk; p.sk_pad = a->sk_pad;
@@ -1524,141 +1522,131 @@ extern "C" int am_attention_fp8(const am_attn_args* a, const uint8_t* q8, const 
   p.chunk_stride = (a->nchunks > 1 || a->chunk_total > 0) ? a->chunk_stride : 0;
   p.chunk_first = a->chunk_total > 0 ? a->chunk_first : 0; p.chunk_total = a->chunk_total;
   p.qblk_base = 0; p.state = a->state; p.part = nullptr;
+  return p;
+}
+
+// The meaning of defer_log2: the AM_ATTN_FP8_* codes beside am_attn_args (include/actionmesh_amd.h).
+extern "C" int am_attention_fp8(const am_attn_args* a, const uint8_t* q8, const uint8_t* k8, const uint8_t* vt8, void* stream) {
+  AM_TRY(check_operands(a, "am_attention_fp8"));
+  AM_CHECK(q8 && k8 && vt8 && a->O, "am_attention_fp8: null operand");
+  AM_CHECK(((uintptr_t)q8 | (uintptr_t)k8 | (uintptr_t)vt8) % 16 == 0 && (uintptr_t)a->O % 8 == 0 && a->chunk_stride % 16 == 0,
+           "am_attention_fp8: operands misaligned");
+  AM_CHECK(a->ldo % 4 == 0 && a->ldo >= a->heads * HD8, "am_attention_fp8: ldo=%d too small / misaligned", a->ldo);
+  AM_CHECK((int64_t)HD8 * a->sk_pad * 1 < (1ll << 31), "am_attention_fp8: sk_pad too large for 32-bit lane offsets");
+  // defer_log2 decoded once.  Anything below the first base is the product dispatch.
+  const int code = a->defer_log2 >= AM_ATTN_FP8_ABLATE ? a->defer_log2 : AM_ATTN_FP8_ABLATE;
+  const bool fast = code == AM_ATTN_FP8_FAST;
+  const bool want8 = code == AM_ATTN_FP8_8WAVE || (code > AM_ATTN_FP8_ABLATE && code < AM_ATTN_FP8_4X64);
+  const bool want64 = code >= AM_ATTN_FP8_4X64 && code < AM_ATTN_FP8_8WAVE;     // measured 12 % slower than the product kernel: kept for the A/B
+  const int xabl = want64 ? code - AM_ATTN_FP8_4X64 : 0;
+  const int pabl = code >= AM_ATTN_FP8_PRODUCT_ABLATE && code < AM_ATTN_FP8_FAST ? code - AM_ATTN_FP8_PRODUCT_ABLATE : 0;
+  // the 8-wave kernel's ablation; fp8_fast on a stream too short for the product kernel runs the exact-exp2 form
+  const int abl8 = code == AM_ATTN_FP8_8WAVE || fast ? 0 : code - AM_ATTN_FP8_ABLATE;
+  AM_CHECK(code == AM_ATTN_FP8_ABLATE || code == AM_ATTN_FP8_4X64 || code == AM_ATTN_FP8_8WAVE || fast || (a->rows == 0 && a->state_mode == 0),
+           "am_attention_fp8: ablation codes run the one-pass form only");
+  f8_args p = kernel_args(a, q8, k8, vt8);
   hipStream_t st = (hipStream_t)stream;
   const int bh = a->nseq * a->heads;
-  // The same main / rest boundary as the bf16 kernels (query geometry alone): a short last block (<= 128 of 256 rows, >= 9 blocks)
-  // is "rest"; it is split 16 ways over the key range when the stream is long enough, and merged by attn_combine.
-  const int nblk = (a->sq + 255) / 256, tail_rows = a->sq - (nblk - 1) * 256;
-  const bool tail_geom = nblk >= 9 && tail_rows <= 128;
+  // The main / rest boundary of the bf16 kernels' 256-row blocks; a "rest" block runs in a launch of its own, split when the stream is long enough.
+  const am_attn_qblocks q = am_attn_plan_qblocks(a, 256);
   const int all_tiles = p.nchunks * p.tiles_per_chunk;
-  static float* part = nullptr;            // library-owned scratch, grown on demand (launches on a device come from one thread)
-  static size_t part_elems = 0;
-  const size_t need = (size_t)bh * F8_SPLIT_Z * 256 * F8_STATE_LD;
-  const bool split = tail_geom && all_tiles >= 4 * F8_SPLIT_Z && need * sizeof(float) <= (256u << 20);
-  const int nblk_main = tail_geom ? nblk - 1 : nblk;
-#define F8_LAUNCH(A, M, GRID) hipLaunchKernelGGL((attn_fp8_kernel<A, M>), GRID, dim3(512), NSTAGE * STAGE_BYTES, st, p)
-#define X64_LAUNCH(A, M, GRID) hipLaunchKernelGGL((attn_fp8x64_kernel<A, M>), GRID, dim3(256), NSTAGE * STAGE_BYTES, st, p, (unsigned long long*)nullptr)
-  // Product kernel of the main grid: the 4 x 64 form (round 4) for key streams of at least 8 tiles; defer_log2 = 5100 + ABL selects its
-  // timing ablations, 5200 forces the 8-wave kernel (same-box A/B, tests), 5000 + ABL are the 8-wave kernel's ablations as before.
-  const bool want8 = a->defer_log2 == 5200 || (abl != 0 && abl < 100);
-  const bool want64 = abl >= 100 && abl < 200;              // 5100 + ABL: the 4 x 64 form (measured 12 % slower: kept for the A/B)
-  const int xabl = want64 ? abl - 100 : 0;
-  const int pabl = abl >= 300 && abl < 400 ? abl - 300 : 0; // 5300 + ABL: timing ablations of the product (free-running) kernel
-  const bool fast = abl == 400;                             // 5400: the exponent-field form of the probabilities (attn_dtype "fp8_fast")
+  const size_t need = am_attn_part_floats(a, 256);
+  const bool split = q.tail_rest && am_attn_fp8_splits(a, need);
+  // Product kernel of the main grid: the free-running form for key streams of at least 8 tiles, the 8-wave kernel below that
+  // (ACTIONMESH_AMD_FP8_8WAVE: at any length)
   const bool long_stream = all_tiles >= 8 && getenv("ACTIONMESH_AMD_FP8_8WAVE") == nullptr;
   const bool use_x64 = want64 && long_stream;
   const bool use_p = !want8 && !want64 && long_stream;
-#define P_LAUNCH(A, M, F, GRID) hipLaunchKernelGGL((attn_fp8p_kernel<A, M, F>), GRID, dim3(512), P_LDS_BYTES, st, p, (unsigned long long*)nullptr)
-  if (a->rows != 2 && use_p) {
-    const dim3 grid(nblk_main, bh);
-    if (fast) {
-      if (a->state_mode == 1) P_LAUNCH(0, 1, 1, grid);
-      else if (a->state_mode == 2) P_LAUNCH(0, 2, 1, grid);
-      else P_LAUNCH(0, 0, 1, grid);
-    } else if (a->state_mode == 1) P_LAUNCH(0, 1, 0, grid);
-    else if (a->state_mode == 2) P_LAUNCH(0, 2, 0, grid);
-    else switch (pabl) {
-      case 0: P_LAUNCH(0, 0, 0, grid); break;
-      case 1: P_LAUNCH(1, 0, 0, grid); break;
-      case 2: P_LAUNCH(2, 0, 0, grid); break;
-      case 8: P_LAUNCH(8, 0, 0, grid); break;
+  const dim3 grid(q.nblk_main, bh);
+  // the main grid: per kernel, the one-pass form with its timing ablations, then the two-pass forms
+  if (a->rows == 2) {
+    // nothing of it
+  } else if (use_x64) {
+    if (a->state_mode == 0) switch (xabl) {
+      case 0: AM_TRY((launch_fp8x64<0, 0>(p, grid, st))); break;
+      case 1: AM_TRY((launch_fp8x64<1, 0>(p, grid, st))); break;
+      case 2: AM_TRY((launch_fp8x64<2, 0>(p, grid, st))); break;
+      case 8: AM_TRY((launch_fp8x64<8, 0>(p, grid, st))); break;
+      default: AM_FAIL(AM_ERR_INVALID, "am_attention_fp8: unknown 4x64 ablation code %d", a->defer_log2);
+    }
+    else if (a->state_mode == 1) AM_TRY((launch_fp8x64<0, 1>(p, grid, st)));
+    else AM_TRY((launch_fp8x64<0, 2>(p, grid, st)));
+  } else if (use_p && !fast) {
+    if (a->state_mode == 0) switch (pabl) {
+      case 0: AM_TRY((launch_fp8p<0, 0>(p, grid, st))); break;
+      case 1: AM_TRY((launch_fp8p<1, 0>(p, grid, st))); break;
+      case 2: AM_TRY((launch_fp8p<2, 0>(p, grid, st))); break;
+      case 8: AM_TRY((launch_fp8p<8, 0>(p, grid, st))); break;
 #ifdef AM_ATTN_ABLATIONS
-      case 12: P_LAUNCH(12, 0, 0, grid); break;
-      case 24: P_LAUNCH(24, 0, 0, grid); break;
-      case 40: P_LAUNCH(40, 0, 0, grid); break;
-      case 10: P_LAUNCH(10, 0, 0, grid); break;
-      case 62: P_LAUNCH(62, 0, 0, grid); break;
-      case 4: P_LAUNCH(4, 0, 0, grid); break;
-      case 16: P_LAUNCH(16, 0, 0, grid); break;
-      case 32: P_LAUNCH(32, 0, 0, grid); break;
+      case 12: AM_TRY((launch_fp8p<12, 0>(p, grid, st))); break;
+      case 24: AM_TRY((launch_fp8p<24, 0>(p, grid, st))); break;
+      case 40: AM_TRY((launch_fp8p<40, 0>(p, grid, st))); break;
+      case 10: AM_TRY((launch_fp8p<10, 0>(p, grid, st))); break;
+      case 62: AM_TRY((launch_fp8p<62, 0>(p, grid, st))); break;
+      case 4: AM_TRY((launch_fp8p<4, 0>(p, grid, st))); break;
+      case 16: AM_TRY((launch_fp8p<16, 0>(p, grid, st))); break;
+      case 32: AM_TRY((launch_fp8p<32, 0>(p, grid, st))); break;
 #endif
       default: AM_FAIL(AM_ERR_INVALID, "am_attention_fp8: unknown ablation code %d", a->defer_log2);
     }
-  } else
-#undef P_LAUNCH
-  if (a->rows != 2 && use_x64) {
-    const dim3 grid(nblk_main, bh);
-    if (a->state_mode == 1) X64_LAUNCH(0, 1, grid);
-    else if (a->state_mode == 2) X64_LAUNCH(0, 2, grid);
-    else switch (xabl) {
-      case 0: X64_LAUNCH(0, 0, grid); break;
-      case 1: X64_LAUNCH(1, 0, grid); break;
-      case 2: X64_LAUNCH(2, 0, grid); break;
-      case 8: X64_LAUNCH(8, 0, grid); break;
-      default: AM_FAIL(AM_ERR_INVALID, "am_attention_fp8: unknown 4x64 ablation code %d", a->defer_log2);
-    }
-  } else if (a->rows != 2) {                       // the main grid
-    const dim3 grid(nblk_main, bh);
-    if (a->state_mode == 1) F8_LAUNCH(0, 1, grid);
-    else if (a->state_mode == 2) F8_LAUNCH(0, 2, grid);
-    else switch (abl == 200 || abl == 400 ? 0 : abl) {   // fp8_fast (400) on a stream too short for the product kernel: the exact-exp2 form
-      case 0: F8_LAUNCH(0, 0, grid); break;
-      case 1: F8_LAUNCH(1, 0, grid); break;
-      case 2: F8_LAUNCH(2, 0, grid); break;
-      case 4: F8_LAUNCH(4, 0, grid); break;
-      case 6: F8_LAUNCH(6, 0, grid); break;
-      case 8: F8_LAUNCH(8, 0, grid); break;
-      case 16: F8_LAUNCH(16, 0, grid); break;
-      case 17: F8_LAUNCH(17, 0, grid); break;
-      case 32: F8_LAUNCH(32, 0, grid); break;
-      case 64: F8_LAUNCH(64, 0, grid); break;
-      case 40: F8_LAUNCH(40, 0, grid); break;
+    else if (a->state_mode == 1) AM_TRY((launch_fp8p<0, 1>(p, grid, st)));
+    else AM_TRY((launch_fp8p<0, 2>(p, grid, st)));
+  } else if (use_p) {
+    if (a->state_mode == 0) AM_TRY((launch_fp8p<0, 0, 1>(p, grid, st)));
+    else if (a->state_mode == 1) AM_TRY((launch_fp8p<0, 1, 1>(p, grid, st)));
+    else AM_TRY((launch_fp8p<0, 2, 1>(p, grid, st)));
+  } else {
+    if (a->state_mode == 0) switch (abl8) {
+      case 0: AM_TRY((launch_fp8<0, 0>(p, grid, st))); break;
+      case 1: AM_TRY((launch_fp8<1, 0>(p, grid, st))); break;
+      case 2: AM_TRY((launch_fp8<2, 0>(p, grid, st))); break;
+      case 4: AM_TRY((launch_fp8<4, 0>(p, grid, st))); break;
+      case 8: AM_TRY((launch_fp8<8, 0>(p, grid, st))); break;
+      case 16: AM_TRY((launch_fp8<16, 0>(p, grid, st))); break;
+      case 17: AM_TRY((launch_fp8<17, 0>(p, grid, st))); break;
+      case 6: AM_TRY((launch_fp8<6, 0>(p, grid, st))); break;
+      case 32: AM_TRY((launch_fp8<32, 0>(p, grid, st))); break;
+      case 64: AM_TRY((launch_fp8<64, 0>(p, grid, st))); break;
+      case 40: AM_TRY((launch_fp8<40, 0>(p, grid, st))); break;
       default: AM_FAIL(AM_ERR_INVALID, "am_attention_fp8: unknown ablation code %d", a->defer_log2);
     }
+    else if (a->state_mode == 1) AM_TRY((launch_fp8<0, 1>(p, grid, st)));
+    else AM_TRY((launch_fp8<0, 2>(p, grid, st)));
   }
-  if (a->rows != 1 && tail_geom) {          // the short last block
-    p.qblk_base = nblk - 1;
+  if (a->rows != 1 && q.tail_rest) {          // the short last block
+    p.qblk_base = q.nblk - 1;
     p.state = nullptr;
     if (split) {
-      if (part_elems < need) {
-        if (part) AM_HIP(hipFree(part));
-        part = nullptr; part_elems = 0;
-        ++g_am_scratch_generation;
-        AM_HIP(hipMalloc(reinterpret_cast<void**>(&part), need * sizeof(float)));
-        part_elems = need;
-      }
-      p.part = part;
-      F8_LAUNCH(0, 3, dim3(1, bh, F8_SPLIT_Z));
-      AM_TRY(am_attention_combine_launch(a, part, F8_SPLIT_Z, nblk - 1, tail_rows, stream));
+      AM_TRY(am_attn_partials(AM_ATTN_FAMILY_FP8, need, &p.part));
+      AM_TRY((launch_fp8<0, 3>(p, dim3(1, bh, AM_ATTN_SPLIT_Z), st)));
+      AM_TRY(am_attention_combine_launch(a, p.part, AM_ATTN_SPLIT_Z, q.nblk - 1, q.tail_rows, stream));
     } else {
-      F8_LAUNCH(0, 0, dim3(1, bh));
+      AM_TRY((launch_fp8<0, 0>(p, dim3(1, bh), st)));
     }
   }
-#undef F8_LAUNCH
-#undef X64_LAUNCH
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
 
 #ifdef AM_ATTN_ABLATIONS
+// per-phase s_memtime stamps of workgroup (0,0): one pass over chunk 0's layout, every query block in one grid
+static f8_args profile_args(const am_attn_args* a, const uint8_t* q8, const uint8_t* k8, const uint8_t* vt8) {
+  f8_args p = kernel_args(a, q8, k8, vt8);
+  p.chunk_stride = 0; p.chunk_first = 0; p.chunk_total = 0; p.state = nullptr;
+  return p;
+}
 extern "C" int am_attention_fp8p_profile(const am_attn_args* a, const uint8_t* q8, const uint8_t* k8, const uint8_t* vt8,
                                          unsigned long long* prof_dev, void* stream) {
-  AM_TRY(check_args(a, "am_attention_fp8p_profile"));
-  AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8p_kernel<0, 0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             P_LDS_BYTES));
-  f8_args p;
-  p.Q = q8; p.K = k8; p.Vt = vt8; p.O = a->O;
-  p.heads = a->heads; p.sq = a->sq; p.sq_pad = a->sq_pad; p.sk = a->sk; p.sk_pad = a->sk_pad;
-  p.nchunks = a->nchunks; p.tiles_per_chunk = (a->sk + KT - 1) / KT; p.ldo = a->ldo;
-  p.chunk_stride = 0; p.chunk_first = 0; p.chunk_total = 0; p.qblk_base = 0; p.state = nullptr; p.part = nullptr;
-  hipLaunchKernelGGL((attn_fp8p_kernel<0, 0, 0, true>), dim3((a->sq + 255) / 256, a->nseq * a->heads), dim3(512), P_LDS_BYTES,
-                     (hipStream_t)stream, p, prof_dev);
+  AM_TRY(check_operands(a, "am_attention_fp8p_profile"));
+  AM_TRY((launch_fp8p<0, 0, 0, true>(profile_args(a, q8, k8, vt8), dim3((a->sq + 255) / 256, a->nseq * a->heads), (hipStream_t)stream, prof_dev)));
   AM_HIP(hipGetLastError());
   return AM_OK;
 }
-// per-phase s_memtime stamps of workgroup (0,0) of the 4 x 64 kernel: prof[4 waves][8 tiles (64..71)][8 slots]  (tools/attn_profile.py --fp8x64)
+// the 4 x 64 kernel: prof[4 waves][8 tiles (64..71)][8 slots]  (tools/attn_profile.py --fp8x64)
 extern "C" int am_attention_fp8x64_profile(const am_attn_args* a, const uint8_t* q8, const uint8_t* k8, const uint8_t* vt8,
                                            unsigned long long* prof_dev, void* stream) {
-  AM_TRY(check_args(a, "am_attention_fp8x64_profile"));
-  AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8x64_kernel<0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             NSTAGE * STAGE_BYTES));
-  f8_args p;
-  p.Q = q8; p.K = k8; p.Vt = vt8; p.O = a->O;
-  p.heads = a->heads; p.sq = a->sq; p.sq_pad = a->sq_pad; p.sk = a->sk; p.sk_pad = a->sk_pad;
-  p.nchunks = a->nchunks; p.tiles_per_chunk = (a->sk + KT - 1) / KT; p.ldo = a->ldo;
-  p.chunk_stride = 0; p.chunk_first = 0; p.chunk_total = 0; p.qblk_base = 0; p.state = nullptr; p.part = nullptr;
-  hipLaunchKernelGGL((attn_fp8x64_kernel<0, 0, true>), dim3((a->sq + 255) / 256, a->nseq * a->heads), dim3(256), NSTAGE * STAGE_BYTES,
-                     (hipStream_t)stream, p, prof_dev);
+  AM_TRY(check_operands(a, "am_attention_fp8x64_profile"));
+  AM_TRY((launch_fp8x64<0, 0, true>(profile_args(a, q8, k8, vt8), dim3((a->sq + 255) / 256, a->nseq * a->heads), (hipStream_t)stream, prof_dev)));
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

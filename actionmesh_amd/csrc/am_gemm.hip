@@ -1220,6 +1220,39 @@ static void launch_tail(const am_gemm_args& args, int m_main, hipStream_t st) {
   }
 }
 
+// The launch plan both entries share: whether the 256x256 tile runs, its main rows and grid, and the start-skew field.
+struct Gemm256Plan {
+  bool big;                            // the 256x256 tile runs
+  int rem, m_main, tiles_m, tiles_n;   // M % 256; the main grid and its rows [0, m_main): rows [m_main, M) go to launch_tail
+  int skew;                            // the AM_GEMM_SKEW field the kernel gets: the caller's when `act` carries one, else the library's choice
+};
+// `act`: the switches the entry honours.  `skew_counts_tail`: whether the rounds of workgroups that size the library's skew count all M
+// rows (am_gemm_bf16) or the main grid's (am_gemm_headpost_bf16).
+static Gemm256Plan gemm256_plan(int M, int N, int act, bool skew_counts_tail) {
+  Gemm256Plan p;
+  // the 256x256 tiles need a grid that fills the 256 CUs; mid-sized problems (the context encoder's 16 x 257 rows) get four times as many 128x128 workgroups
+  p.big = !(act & AM_GEMM_FORCE_128) && N >= 8 && M >= 1 &&
+          ((act & AM_GEMM_FORCE_256) || (N >= 256 && M >= 1024 && (int64_t)ceil_div(M, B2) * ceil_div(N, B2) >= 192));
+  // M = B*T*(N+1) is 256*k + a small remainder for every reference shape (the +1 time token per frame): a last 256-row tile holding a
+  // few rows would cost a whole extra round of workgroups.  The remainder rows go to the tail kernel in a second, tiny launch instead.
+  p.rem = M % B2;
+  p.m_main = (p.rem != 0 && p.rem <= 128 && M > 8 * B2) ? M - p.rem : M;
+  p.tiles_m = ceil_div(p.m_main, B2), p.tiles_n = ceil_div(N, B2);
+  // start skew per XCD in units of 1.5 us: the more rounds of workgroups a GEMM has, the better the 7-unit tail amortises
+  // (24-32 rounds: 6 us per XCD; 8 rounds: 1.5 us); a skew field of 7 turns it off (A/B runs)
+  p.skew = act & AM_GEMM_SKEW_MASK;
+  if (p.big && p.skew == 0)
+    p.skew = gemm_skew_units((int)(((int64_t)(skew_counts_tail ? ceil_div(M, B2) : p.tiles_m) * p.tiles_n) / 256)) << AM_GEMM_SKEW_SHIFT;
+  return p;
+}
+// dynamic LDS above 64 KiB, all four kernels
+static int gemm_set_lds_attributes() {
+  const std::pair<const void*, int> kernels[] = {{(const void*)gemm_bf16_kernel, SMEM_BYTES}, {(const void*)gemm256_bf16_kernel, SMEM2_BYTES},
+      {(const void*)gemm256pp_bf16_kernel<false>, SMEM2PP_GELU_BYTES}, {(const void*)gemm256pp_bf16_kernel<true>, SMEM2PP_BYTES}};
+  AM_ONCE_PER_DEVICE({ for (const auto& k : kernels) AM_HIP(hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, k.second)); });
+  return AM_OK;
+}
+
 extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_gemm_bf16: null args");
   AM_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "am_gemm_bf16: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
@@ -1248,51 +1281,26 @@ extern "C" int am_gemm_bf16(const am_gemm_args* a, void* stream) {
     AM_CHECK(a->c_G == 0, "am_gemm_bf16: ln_part needs the identity C row map");
     AM_CHECK((uintptr_t)a->ln_part % 8 == 0, "am_gemm_bf16: ln_part misaligned");
   }
-  AM_ONCE_PER_DEVICE({
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES));
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_bf16_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2_BYTES));
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256pp_bf16_kernel<false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2PP_GELU_BYTES));
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256pp_bf16_kernel<true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2PP_BYTES));
-  });
+  AM_TRY(gemm_set_lds_attributes());
   // the switches of `act` (AM_GEMM_* in include/actionmesh_amd.h): tests compare the two tilings and the two GELU forms, A/B runs the loops
   am_gemm_args args = *a;
-  const bool force_small = (args.act & AM_GEMM_FORCE_128) != 0;
   const bool legacy = (args.act & AM_GEMM_LOCKSTEP) != 0;
-  const bool force_big = (args.act & AM_GEMM_FORCE_256) != 0;
-  const int abl = args.act & (AM_GEMM_ABLATE_MASK | AM_GEMM_SKEW_MASK);   // the kernels read these two fields themselves
+  const int abl = args.act & AM_GEMM_ABLATE_MASK;                         // the kernels read this field and the skew themselves
   const bool no_gelu_table = (args.act & AM_GEMM_NO_GELU_TABLE) != 0;
   args.act &= AM_GEMM_ACT_MASK;
   AM_CHECK(args.act == 0 || args.act == AM_GEMM_ACT_GELU, "am_gemm_bf16: unknown activation %d", args.act);
-  // the 256x256 tiles need a grid that fills the 256 CUs; mid-sized problems (the context encoder's 16 x 257 rows)
-  // get four times as many 128x128 workgroups instead
-  const bool big = !force_small && args.N >= 8 && args.M >= 1 &&
-                   (force_big || (args.N >= 256 && args.M >= 1024 && (int64_t)ceil_div(args.M, B2) * ceil_div(args.N, B2) >= 192));
+  const Gemm256Plan plan = gemm256_plan(args.M, args.N, a->act, true);
   // both 256x256 kernels (and gemm_tail_kernel behind them) fetch the bias four floats per lane as one f32x4_t: a 16-byte access.
   // The 128x128 kernel reads it float by float and takes any bias
-  AM_CHECK(!big || (uintptr_t)args.bias % 16 == 0, "am_gemm_bf16: the 256x256 tile needs a 16-byte aligned bias");
-  args.act |= abl;
+  AM_CHECK(!plan.big || (uintptr_t)args.bias % 16 == 0, "am_gemm_bf16: the 256x256 tile needs a 16-byte aligned bias");
+  args.act |= abl | plan.skew;
   // ln_part: full 256-row tiles of the ping-pong kernel write their slices from the store loop (N % 256 == 0); every other row -
   // edge tiles, the 128x128 kernel's rows, the lockstep kernel - gets them from am_row_part below, reading C back
   float* const ln_part = args.ln_part;
   int64_t part_done = 0;                                       // rows [0, part_done) are covered by the fused epilogue
   args.ln_part = nullptr;
-  if (big && (abl & AM_GEMM_SKEW_MASK) == 0) {
-    // start skew per XCD in units of 1.5 us: the more rounds of workgroups a GEMM has, the better the 7-unit tail amortises
-    // (24-32 rounds: 6 us per XCD; 8 rounds: 1.5 us); a skew field of 7 turns it off (A/B runs)
-    const int rounds = (int)(((int64_t)ceil_div(args.M, B2) * ceil_div(args.N, B2)) / 256);
-    args.act |= gemm_skew_units(rounds) << AM_GEMM_SKEW_SHIFT;
-  }
-  if (big) {
-    // M = B*T*(N+1) is 256*k + a small remainder for every reference shape (the +1 time token per
-    // frame): a last 256-row tile holding a few rows would cost a whole extra round of workgroups.
-    // The remainder rows go to the 128x128 kernel in a second, tiny launch instead.
-    const int rem = args.M % B2;
-    const int m_main = (rem != 0 && rem <= 128 && args.M > 8 * B2) ? args.M - rem : args.M;
-    const int tiles_m = ceil_div(m_main, B2), tiles_n = ceil_div(args.N, B2);
+  if (plan.big) {
+    const int m_main = plan.m_main, tiles_m = plan.tiles_m, tiles_n = plan.tiles_n;
     if (legacy) {
       hipLaunchKernelGGL(gemm256_bf16_kernel, dim3(tiles_m * tiles_n), dim3(512), SMEM2_BYTES,
                          (hipStream_t)stream, args, tiles_m, tiles_n, 0);
@@ -1331,12 +1339,11 @@ extern "C" int am_gemm_headpost_bf16(const am_gemm_args* g, const am_headpost_ar
            "am_gemm_headpost_bf16: the GEMM's output (C, ldc, M, N) must be the head split's input (X, ldx, rows, heads * nparts * 128)");
   bool has_v = false;
   for (int i = 0; i < hp->nparts; ++i) has_v |= hp->kinds[i] == 2;
-  const int rem = g->M % B2;
-  const bool tail_split = rem != 0 && rem <= 128 && g->M > 8 * B2;
+  // the plan of the plain entry without its force switches (any of them falls back): the fused epilogue runs where the 256x256 tile does
+  const Gemm256Plan plan = gemm256_plan(g->M, g->N, g->act & AM_GEMM_ABLATE_MASK, false);
   AM_CHECK(g->ln_part == nullptr, "am_gemm_headpost_bf16: no row statistics of a head-split output");
   const bool fuse = (g->act & AM_GEMM_ACT_MASK) == 0 && !g->residual && (!g->bias || g->ln_stats) && !g->A2 && g->a_G == 0 && g->c_G == 0 && g->N % 256 == 0 && g->M % 16 == 0 &&
-                    g->N >= 256 && g->M >= 1024 && (int64_t)ceil_div(g->M, B2) * ceil_div(g->N, B2) >= 192 &&
-                    (!has_v || hp->seq_len % 16 == 0) && (!tail_split || rem <= hp->seq_len) && hp->rows % hp->seq_len == 0 &&
+                    plan.big && (!has_v || hp->seq_len % 16 == 0) && (plan.m_main == g->M || plan.rem <= hp->seq_len) && hp->rows % hp->seq_len == 0 &&
                     !(g->act & (AM_GEMM_FORCE_128 | AM_GEMM_LOCKSTEP | AM_GEMM_FORCE_256)) && getenv("ACTIONMESH_AMD_NO_FUSED_QKV") == nullptr;
   if (!fuse) {
     AM_TRY(am_gemm_bf16(g, stream));
@@ -1348,18 +1355,10 @@ extern "C" int am_gemm_headpost_bf16(const am_gemm_args* g, const am_headpost_ar
     AM_CHECK(g->ln_colsum && (uintptr_t)g->ln_stats % 8 == 0 && (uintptr_t)g->ln_colsum % 16 == 0 && (g->bias == nullptr || (uintptr_t)g->bias % 16 == 0),
              "am_gemm_headpost_bf16: ln_stats / ln_colsum / bias missing or misaligned");
   AM_TRY(am_head_post_check(hp));
-  AM_ONCE_PER_DEVICE({
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256pp_bf16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2PP_BYTES));
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES));
-  });
+  AM_TRY(gemm_set_lds_attributes());
   am_gemm_args args = *g;
-  args.act = g->act & AM_GEMM_ABLATE_MASK;   // the epilogue's timing ablations (tools/kernel_bench.py); 0 on the product path
-  const int m_main = tail_split ? args.M - rem : args.M;
-  const int tiles_m = ceil_div(m_main, B2), tiles_n = ceil_div(args.N, B2);
-  {
-    const int rounds = (int)(((int64_t)tiles_m * tiles_n) / 256);
-    args.act |= gemm_skew_units(rounds) << AM_GEMM_SKEW_SHIFT;
-  }
+  args.act = (g->act & AM_GEMM_ABLATE_MASK) | plan.skew;   // the epilogue's timing ablations (tools/kernel_bench.py); 0 on the product path
+  const int m_main = plan.m_main, tiles_m = plan.tiles_m, tiles_n = plan.tiles_n;
   am_gemm_args main_args = args;
   main_args.M = m_main;                      // the fused epilogue bounds its rows by M: the main grid owns [0, m_main)
   hipLaunchKernelGGL(gemm256pp_bf16_kernel<true>, dim3(tiles_m * tiles_n), dim3(512), SMEM2PP_BYTES, (hipStream_t)stream, main_args, tiles_m,

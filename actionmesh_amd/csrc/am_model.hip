@@ -20,10 +20,8 @@ int am_add_bias_rows_stats(bf16_t* h, const float* bias, int64_t rows, int C, fl
 
 namespace {
 constexpr int HD = 128;                                 // head dimension
-constexpr int STATE_ROW = 132;                          // floats per query row of the two-pass attention state (am_attn_args.state)
 constexpr float LN_EPS = 1e-5f, QK_EPS = 1e-6f;         // LayerNorm / qk-RMSNorm
 constexpr float SOFTMAX_SCALE = 0.08838834764831845f;   // 1/sqrt(128)
-constexpr int FP8_FAST_PROBS = 5400;                    // am_attn_args.defer_log2 code: the exponent-field form of the probabilities (am_attention_fp8)
 inline int pad_to(int64_t x, int m) { return (int)round_up(x, m); }
 }  // namespace
 
@@ -353,7 +351,7 @@ int attend(am_model* h, am_attn_args at, bool inflated, hipStream_t st) {
   const bool counted = inflated && at.state_mode != 2 && at.rows != 2;
   if (inflated && h->cfg.attn_fp8) {
     at.chunk_stride = (int64_t)h->chunk_stride8;
-    if (h->cfg.attn_fp8 == 2) at.defer_log2 = FP8_FAST_PROBS;
+    if (h->cfg.attn_fp8 == 2) at.defer_log2 = AM_ATTN_FP8_FAST;
     AM_TRY(am_attention_fp8(&at, h->Q8, h->K8, h->Vt8, st));
     h->n_attn_fp8 += counted;
   } else {
@@ -378,7 +376,7 @@ extern "C" int am_create(const am_config* cfg, am_handle* out) {
            "am_create: workspace bounds must be positive");
   AM_CHECK(cfg->world_size >= 1 && cfg->rank >= 0 && cfg->rank < cfg->world_size, "am_create: rank %d / world %d",
            cfg->rank, cfg->world_size);
-  AM_CHECK(cfg->attn_defer_log2 == 0 || cfg->attn_defer_log2 == 8, "am_create: attn_defer_log2 must be 0 or 8");
+  AM_CHECK(cfg->attn_defer_log2 == AM_ATTN_REBASE_ALWAYS || cfg->attn_defer_log2 == AM_ATTN_REBASE_DEFERRED, "am_create: attn_defer_log2 must be 0 or 8");
   AM_CHECK(cfg->attn_fp8 >= 0 && cfg->attn_fp8 <= 2, "am_create: attn_fp8 must be 0 (bf16), 1 (fp8) or 2 (fp8, exponent-field probabilities)");
   int ndev = 0;
   AM_HIP(hipGetDeviceCount(&ndev));
@@ -696,15 +694,15 @@ extern "C" int am_layer_attn_local(am_handle h, int i, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   h->local_done = false;
   const int tiles = (h->T * h->L + 63) / 64;
-  const bool product = h->cfg.attn_defer_log2 == 0 || h->cfg.attn_defer_log2 == 8;
+  const bool product = h->cfg.attn_defer_log2 == AM_ATTN_REBASE_ALWAYS || h->cfg.attn_defer_log2 == AM_ATTN_REBASE_DEFERRED;
   if (h->P < 2 || !h->inflated(i) || tiles < 16 || !product) return AM_OK;
   am_attn_args at = self_attn_args(h);
   if (!h->attn_state)
-    AM_TRY(dev_alloc_t(h, &h->attn_state, (size_t)h->maxB * h->H * pad_to((int64_t)h->maxT * h->maxL, 256) * STATE_ROW));
+    AM_TRY(dev_alloc_t(h, &h->attn_state, (size_t)h->maxB * h->H * pad_to((int64_t)h->maxT * h->maxL, 256) * AM_ATTN_STATE_LD));
   at.rows = 1; at.state_mode = 1; at.state = h->attn_state;
   at.nchunks = 1; at.chunk_first = h->rank; at.chunk_total = h->P;
   AM_TRY(attend(h, at, true, st));
-  TR(TR_ATTN_LOCAL_STATE, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * STATE_ROW * 4);
+  TR(TR_ATTN_LOCAL_STATE, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * AM_ATTN_STATE_LD * 4);
   h->local_done = true;
   return AM_OK;
 }
@@ -741,7 +739,7 @@ extern "C" int am_layer_post_attn(am_handle h, int i, void* stream) {
         }
       }
       TR(TR_Q_BEFORE_ATTN, i, h->Qb, (size_t)at.nseq * at.heads * at.sq_pad * HD * 2);
-      TR(TR_STATE_BEFORE_RESUME, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * STATE_ROW * 4);
+      TR(TR_STATE_BEFORE_RESUME, i, h->attn_state, (size_t)at.nseq * at.heads * at.sq_pad * AM_ATTN_STATE_LD * 4);
     }
     AM_TRY(attend(h, at, true, st));
     TR(TR_ATTN_RESUME, i, h->ao, (size_t)Rs * C * 2);

@@ -314,7 +314,7 @@ def gemm_head_post(a: torch.Tensor, w: torch.Tensor, heads: int, kinds: Sequence
     return outs
 
 
-STATE_LD = 132   # floats per row of a two-pass attention state: O[128], m, l, pad
+STATE_LD = L.ATTN_STATE_LD   # floats per row of a two-pass attention state: O[128], m, l, pad
 
 
 def _attn_args(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: int, out: Optional[torch.Tensor], nchunks: int,
@@ -344,7 +344,7 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: 
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: int,
-              out: Optional[torch.Tensor] = None, nchunks: int = 1, defer_log2: int = 8,
+              out: Optional[torch.Tensor] = None, nchunks: int = 1, defer_log2: int = L.ATTN_REBASE_DEFERRED,
               scale: Optional[float] = None, rows: int = 0, state_mode: int = 0,
               state: Optional[torch.Tensor] = None, chunk_first: int = 0, chunk_total: int = 0) -> torch.Tensor:
     """softmax(q k^T * scale) v on pre-laid-out operands.
@@ -369,7 +369,7 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, s
     rows / state_mode / state / chunk_first / chunk_total: the two-pass forms, as in `attention`.  `quantize_out`: caller-owned uint8
     (q8, k8, vt8) of the shapes of q / k / vt that receive the quantisation (default: fresh tensors)."""
     # defer_log2 carries the timing ablations of the fp8 kernel (tools/kernel_bench.py)
-    a, out = _attn_args(q, k, vt, sq, sk, out, nchunks, scale, 5000 + ablate if ablate else 0, rows, state_mode, state, chunk_first,
+    a, out = _attn_args(q, k, vt, sq, sk, out, nchunks, scale, L.ATTN_FP8_ABLATE + ablate if ablate else 0, rows, state_mode, state, chunk_first,
                         chunk_total)
     if quantized is None:
         if quantize_out is not None:

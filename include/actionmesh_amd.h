@@ -298,6 +298,33 @@ typedef struct {
   int32_t chunk_first, chunk_total, rows, state_mode;
   float* state;
 } am_attn_args;
+/* Floats per query row of `state`: O[128], m, l, pad (16-byte aligned rows). */
+#define AM_ATTN_STATE_LD 132
+/* am_attn_args.defer_log2 as am_attention_bf16 reads it.  A product caller passes one of the two re-base thresholds:
+ *   AM_ATTN_REBASE_ALWAYS    exact online softmax, re-based whenever a row max grows;
+ *   AM_ATTN_REBASE_DEFERRED  the product: deferred re-base (threshold 2^8) on the 8-wave kernel, the lazy re-base of the 4x64 kernel
+ *                            (+ its exact fallback launch) on long key streams.
+ * The product dispatch picks the kernel from the shape (short key streams: the 8-wave code in its 4-wave geometry or the
+ * resident-key-stream kernel; long ones: the 4x64 kernel).  Every other code is a DIAGNOSTIC AND TEST SWITCH that forces one kernel
+ * for A/B runs and parity tests: a base below plus one of the two thresholds. */
+#define AM_ATTN_REBASE_ALWAYS   0
+#define AM_ATTN_REBASE_DEFERRED 8
+#define AM_ATTN_4WAVE           50     /* + threshold: the 8-wave kernel's code as two 4-wave workgroups per CU (geometry A/B) */
+#define AM_ATTN_4X64            60     /* + threshold: 4 waves x 64 rows, one wave per SIMD */
+#define AM_ATTN_BALANCED        70     /* + threshold: the balanced two-phase schedule of the 8-wave kernel */
+#define AM_ATTN_8WAVE           90     /* + threshold: the 8-wave kernel at any key-stream length */
+#define AM_ATTN_4X64_DEFERRED   28     /* the 4x64 kernel with the exact deferred re-base on its own (no lazy pass) */
+/* builds with -DAM_ATTN_ABLATIONS only (tools/kernel_bench.py): the experimental schedules of the A/B build from this code on, and
+ * from AM_ATTN_ABLATE_4X64 on the 4x64 kernel's timing ablations (+ ABL; numerically meaningless) */
+#define AM_ATTN_VARIANTS        100
+#define AM_ATTN_ABLATE_4X64     3000
+/* am_attn_args.defer_log2 as am_attention_fp8 reads it: 0 = the product dispatch (the free-running kernel for key streams of at least
+ * 8 tiles, the 8-wave kernel below); otherwise one of these bases.  The "+ ABL" forms are timing ablations of the one-pass form. */
+#define AM_ATTN_FP8_ABLATE         5000   /* + ABL: the 8-wave kernel and its timing ablations */
+#define AM_ATTN_FP8_4X64           5100   /* + ABL: the 4 x 64 form (same-box A/B) */
+#define AM_ATTN_FP8_8WAVE          5200   /* the 8-wave kernel at any key-stream length (same-box A/B, tests) */
+#define AM_ATTN_FP8_PRODUCT_ABLATE 5300   /* + ABL: timing ablations of the product (free-running) kernel */
+#define AM_ATTN_FP8_FAST           5400   /* the product kernel with the exponent-field form of the probabilities (am_config.attn_fp8 = 2) */
 int am_attention_bf16(const am_attn_args* args, void* stream);
 /* Diagnostic: the long-key-stream kernel keeps no running row max in its loop (it re-bases lazily from the row sums);
  * a workgroup that meets a single-tile jump of more than 2^60 is recomputed by an exact kernel launched behind it.

@@ -62,10 +62,12 @@ def test_struct_layouts_match_header(tmp_path):
 
 
 def test_header_constants_match_the_binding(tmp_path):
-    """The bits of am_gemm_args.act (the header's AM_GEMM_* defines) and the camera limit, as a C compiler evaluates them, against the
-    constants of _lib: the same names without the AM_ prefix, none missing on either side."""
-    names = set(re.findall(r"^#define (AM_GEMM_\w+)", _headers(), re.M))
-    assert names == {"AM_" + n for n in dir(_lib) if n.startswith("GEMM_")}, names
+    """The bits of am_gemm_args.act (the header's AM_GEMM_* defines), the codes of am_attn_args.defer_log2 and the state row stride
+    (AM_ATTN_*) and the camera limit, as a C compiler evaluates them, against the constants of _lib: the same names without the AM_
+    prefix, none missing on either side."""
+    names = set(re.findall(r"^#define (AM_(?:GEMM|ATTN)_\w+)", _headers(), re.M))
+    assert names == {"AM_" + n for n in dir(_lib) if n.startswith(("GEMM_", "ATTN_"))}, names
+    assert sum(n.startswith("AM_ATTN_") for n in names) >= 15, names
     got = _probe(tmp_path, [f'printf("{n} %d\\n", (int)({n}));' for n in sorted(names | {"AM_RENDER_MAX_CAMERAS"})])
     for n, v in got.items():
         assert v == getattr(_lib, n[3:]), n
@@ -87,6 +89,25 @@ def test_argument_validation_without_gpu():
     assert b"multiple of 64" in lib.am_last_error()
     a = _lib.AmAttnArgs()
     assert lib.am_attention_bf16(ctypes.byref(a), None) != 0
+    # the checks the attention entries share: every entry refuses each row of one table, in its own name, before it looks at an operand
+    # or a device (the operand pointers are never followed)
+    good = dict(nseq=1, heads=2, sq=300, sq_pad=512, sk=300, sk_pad=320, nchunks=1, ldo=256, scale=1.0, chunk_stride=2 * 320 * 128)
+    bad = [(dict(sq_pad=500), b"sq_pad"), (dict(sk_pad=256), b"sk_pad"), (dict(rows=3), b"rows"), (dict(rows=1, state_mode=1), b"state buffer"),
+           (dict(rows=1, chunk_first=2, chunk_total=2), b"chunk_first"), (dict(nseq=2, heads=32768), b"grid.y")]
+    buf = (ctypes.c_uint8 * 64)()
+    ptr = (ctypes.addressof(buf) + 15) & ~15
+    entries = {"am_attention_bf16": lambda a: lib.am_attention_bf16(ctypes.byref(a), None),
+               "am_attention_fp8": lambda a: lib.am_attention_fp8(ctypes.byref(a), ptr, ptr, ptr, None),
+               "am_attention_quantize_fp8": lambda a: lib.am_attention_quantize_fp8(ctypes.byref(a), ptr, ptr, ptr, None)}
+    for change, word in bad:
+        for name, call in entries.items():
+            a = _lib.AmAttnArgs()
+            a.Q = a.K = a.Vt = a.O = ptr
+            for k, v in {**good, **change}.items():
+                setattr(a, k, v)
+            assert call(a) != 0, (name, change)
+            msg = lib.am_last_error()
+            assert msg.startswith(name.encode() + b":") and word in msg, (name, change, msg)
     with pytest.raises(RuntimeError):
         _lib.check(-1, "x")
 
