@@ -113,6 +113,20 @@ class AmNnGridSearchArgs(C.Structure):     # am_nn_grid_search_args
     ]
 
 
+ICP_NO_NEIGHBOUR = 1                       # AM_ICP_NO_NEIGHBOUR: am_icp_step's out_flag bit
+
+
+class AmIcpArgs(C.Structure):              # am_icp_args
+    _fields_ = [
+        ("pred", C.c_void_p), ("gt", C.c_void_p), ("rot_init", C.c_void_p), ("n_pred", C.c_int64), ("n_gt", C.c_int64),
+        ("batch", C.c_int32), ("update", C.c_int32),
+        ("params", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("best", C.c_void_p),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("bias_correction1", C.c_double), ("bias_correction2", C.c_double),
+        ("out_loss", C.c_void_p), ("out_rot", C.c_void_p), ("out_sums", C.c_void_p), ("out_grad", C.c_void_p), ("out_flag", C.c_void_p),
+    ]
+
+
 class AmAttnArgs(C.Structure):
     _fields_ = [
         ("Q", C.c_void_p), ("K", C.c_void_p), ("Vt", C.c_void_p), ("O", C.c_void_p),
@@ -364,7 +378,7 @@ class AmPeerRing(C.Structure):          # include/actionmesh_amd_sharded.h
 STRUCTS = {
     "am_config": AmConfig, "am_gemm_args": AmGemmArgs, "am_headpost_args": AmHeadPostArgs, "am_attn_args": AmAttnArgs,
     "am_attn_f32_args": AmAttnF32Args, "am_nn_args": AmNnArgs, "am_nn_grid": AmNnGrid, "am_nn_grid_build_args": AmNnGridBuildArgs,
-    "am_nn_grid_search_args": AmNnGridSearchArgs, "am_render_camera": AmRenderCamera, "am_render_args": AmRenderArgs,
+    "am_nn_grid_search_args": AmNnGridSearchArgs, "am_icp_args": AmIcpArgs, "am_render_camera": AmRenderCamera, "am_render_args": AmRenderArgs,
     "am_fps_args": AmFpsArgs, "am_image_frame": AmImageFrame, "am_image_alpha_stats_args": AmImageAlphaStatsArgs,
     "am_image_resample_args": AmImageResampleArgs, "am_image_materialize_args": AmImageMaterializeArgs,
     "am_mask_refine_args": AmMaskRefineArgs, "am_graph_args": AmGraphArgs, "am_vertex_normals_args": AmVertexNormalsArgs,
@@ -410,6 +424,8 @@ SYMBOLS = {
     "am_nn_grid_cells": (C.c_int, [C.POINTER(AmNnGridBuildArgs), _P]),
     "am_nn_grid_build": (C.c_int, [C.POINTER(AmNnGridBuildArgs), _P]),
     "am_nn_grid_search": (C.c_int, [C.POINTER(AmNnGridSearchArgs), _P]),
+    "am_icp_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "am_icp_step": (C.c_int, [C.POINTER(AmIcpArgs), _P, C.c_size_t, _P]),
     "am_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "am_render_normals": (C.c_int, [C.POINTER(AmRenderArgs), _P, C.c_size_t, _P]),
     "am_fps_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),

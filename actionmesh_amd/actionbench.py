@@ -8,6 +8,8 @@ as the reference has them.  No CPU fallback: inputs are moved to `device` (defau
 
 Every search takes `nn`: "brute" (am_nn_search, the default of the library functions) or "grid" (am_nn_grid_*: the same indices and
 distances bit for bit through a uniform grid, so every metric and the ICP's whole trajectory are the same numbers).
+The ICP takes `step` / `icp`: "autograd" (the default: the graph over the two searches) or "fused" (am_icp_step: one device step per
+iteration and no host read inside the loop; deterministic, not the autograd trajectory's bits).
 
 The second half is the reference's dataset evaluator (actionbench/evaluate_dataset.py) with its names, defaults and file formats -
 uid/surfaces.npy against uid/mesh_*.glb, a CSV and a summary JSON, resumable - on the stdlib's csv / json instead of pandas, a natural
@@ -37,6 +39,10 @@ NN_METHODS = ("brute", "grid")
 # The evaluator's default method: whichever profiles/nn_grid.json (tools/nn_grid_timing.py) measured faster on a whole gradient_icp by
 # more than the spread between repeats, else "brute" (DESIGN section 6, row N12).
 EVALUATOR_NN = "brute"
+ICP_STEPS = ("autograd", "fused")
+# The evaluator's ICP iteration: "autograd" (the graph below, the default) or "fused" (am_icp_step: matching, gradient, Adam step and
+# best-so-far record on the device, no host read inside the loop; profiles/icp_fused.json).
+EVALUATOR_ICP = "autograd"
 
 
 def _search(points: torch.Tensor, queries: torch.Tensor, precise: bool, nn: str, check: bool = True):
@@ -200,13 +206,22 @@ def chamfer_distance_sq(x: torch.Tensor, y: torch.Tensor, nn: str = "brute", y_g
 
 @torch.enable_grad()
 def gradient_icp(pc_pred: torch.Tensor, pc_gt: torch.Tensor, lr: float = 0.01, n_iter: int = 200, _chamfer=None,
-                 nn: str = "brute") -> ScaleRotateTranslate:
+                 nn: str = "brute", step: str = "autograd") -> ScaleRotateTranslate:
     """icp.py:54-111: the similarity (anisotropic scale) transform from pc_pred (P, 3) to pc_gt (Q, 3): Adam on a 6-D rotation,
     a translation and a per-axis scale from 24 canonical starting orientations at once; the best loss seen wins.
     nn="grid": ONE grid over pc_gt for the call, shared by the 24 candidates; the grid over the 24 transformed clouds is rebuilt every
-    iteration.  The matched indices are brute force's, so the optimiser's trajectory and the result are the same bits."""
+    iteration.  The matched indices are brute force's, so the optimiser's trajectory and the result are the same bits.
+    step="fused": every iteration is one am_icp_step (ops.icp_step) - the same matching, the gradient from 13 sums over the matched
+    pairs, Adam and the best-so-far record in fp64 on the device - and the host reads `best` and the flag once, after the loop.  Its
+    trajectory is deterministic but not the autograd one's bits (fp64 sums against fp32 ones); brute-force matching only."""
     if nn not in NN_METHODS:
         raise ValueError(f"nn must be one of {NN_METHODS}, got {nn!r}")
+    if step not in ICP_STEPS:
+        raise ValueError(f"step must be one of {ICP_STEPS}, got {step!r}")
+    if step == "fused":
+        if nn != "brute" or _chamfer is not None:
+            raise ValueError('step="fused" matches by brute force inside am_icp_step: it takes neither nn="grid" nor _chamfer')
+        return _gradient_icp_fused(pc_pred, pc_gt, lr, n_iter)
     if _chamfer is not None:
         chamfer = _chamfer
     elif nn == "grid":
@@ -239,6 +254,21 @@ def gradient_icp(pc_pred: torch.Tensor, pc_gt: torch.Tensor, lr: float = 0.01, n
     return out
 
 
+def _gradient_icp_fused(pc_pred: torch.Tensor, pc_gt: torch.Tensor, lr: float, n_iter: int) -> ScaleRotateTranslate:
+    pred, gt = pc_pred.detach().float().contiguous(), pc_gt.detach().float().contiguous()
+    R_init = canonical_rotation_matrices().to(pred.device).contiguous()
+    state = ops.IcpState(len(R_init), pred.device)
+    for t in range(1, n_iter + 1):
+        ops.icp_step(state, pred, gt, R_init, t, lr=lr)
+    best, flag = state.best.cpu(), int(state.out_flag.cpu())      # the only host reads: both after the loop
+    if flag & ops.L.ICP_NO_NEIGHBOUR:
+        raise ValueError(ops.NO_NEIGHBOUR_TEXT)
+    dev = pred.device
+    out = ScaleRotateTranslate(best[:9].reshape(1, 3, 3).to(dev), best[9:12].reshape(1, 3).to(dev), best[12:15].reshape(1, 3).to(dev))
+    out.loss = float(best[15])
+    return out
+
+
 def sample_point_cloud(point_cloud: torch.Tensor, n_pts: int, seed: int = 44) -> torch.Tensor:
     """actionbench/sample_point_cloud.py:12-36: one RandomState(seed) permutation shared by all timesteps."""
     n_src = point_cloud.shape[1]
@@ -250,19 +280,20 @@ def sample_point_cloud(point_cloud: torch.Tensor, n_pts: int, seed: int = 44) ->
 
 def compute_chamfer_3d_4d(gt_pc: torch.Tensor, pred_pc: torch.Tensor, device="cuda:0", is_4D: bool = False,
                           pred_pc_4D: Optional[torch.Tensor] = None, n_pts_icp: int = 10_000, seed: int = 44,
-                          n_iter: int = 200, nn: str = "brute") -> Tuple[float, float, float]:
+                          n_iter: int = 200, nn: str = "brute", icp: str = "autograd") -> Tuple[float, float, float]:
     """benchmark.py:67-153 from point clouds: gt_pc (T, N, 3), pred_pc (T, M, 3) sampled per frame, pred_pc_4D (T, M, 3)
     sampled with frame-to-frame correspondence (is_4D).  (The reference samples these from trimesh objects with trimesh /
     pytorch3d samplers - sample_mesh.py - whose random streams are theirs; hand it the same clouds and the rest follows
     benchmark.py line by line.)  Returns (cd_3d: per-frame ICP, cd_4d: first-frame ICP, cd_motion)."""
+    icp_nn = "brute" if icp == "fused" else nn         # the fused iteration matches by brute force; `nn` still serves the metrics
     n_ts = pred_pc.shape[0]
     pred_pc_icp = sample_point_cloud(pred_pc, n_pts=n_pts_icp, seed=seed)
     gt_pc_icp = sample_point_cloud(gt_pc, n_pts=n_pts_icp, seed=seed)
     pred_pc, gt_pc = _dev(pred_pc, device), _dev(gt_pc, device)
     pred_pc_icp, gt_pc_icp = _dev(pred_pc_icp, device), _dev(gt_pc_icp, device)
-    icp_list = [gradient_icp(pc_gt=gt_pc_icp[k], pc_pred=pred_pc_icp[k], lr=0.01, n_iter=n_iter, nn=nn) for k in range(n_ts)]
+    icp_list = [gradient_icp(pc_gt=gt_pc_icp[k], pc_pred=pred_pc_icp[k], lr=0.01, n_iter=n_iter, nn=icp_nn, step=icp) for k in range(n_ts)]
     icp_3d = icp_list[0].stack(*icp_list[1:])
-    icp_u4d = gradient_icp(pc_gt=gt_pc_icp[0], pc_pred=pred_pc_icp[0], lr=0.01, n_iter=n_iter, nn=nn)
+    icp_u4d = gradient_icp(pc_gt=gt_pc_icp[0], pc_pred=pred_pc_icp[0], lr=0.01, n_iter=n_iter, nn=icp_nn, step=icp)
     aligned_3d, aligned_u4d = icp_3d.transform_points(pred_pc), icp_u4d.transform_points(pred_pc)
     cd_3d = np.mean([compute_chamfer_score(gt=gt_pc[k], pred=aligned_3d[k], nn=nn) for k in range(n_ts)])
     cd_4d = np.mean([compute_chamfer_score(gt=gt_pc[k], pred=aligned_u4d[k], nn=nn) for k in range(n_ts)])
@@ -400,7 +431,8 @@ def _one_topology(meshes) -> bool:
 
 
 def compute_chamfer_3d_4d_meshes(gt_pc: torch.Tensor, pred_meshes, device="cuda", is_4D: bool = False, n_pts_icp: int = 10_000,
-                                 n_pts_chamfer: int = 100_000, seed: int = 44, n_iter: int = 200, nn: str = "brute") -> Tuple[float, float, float]:
+                                 n_pts_chamfer: int = 100_000, seed: int = 44, n_iter: int = 200, nn: str = "brute",
+                                 icp: str = "autograd") -> Tuple[float, float, float]:
     """benchmark.py:67-153 from meshes: sample (sample_meshes), then compute_chamfer_3d_4d.  Meshes of one topology are sampled as a
     vertex stack; per-frame topologies frame by frame (seed + frame, sample_mesh.py:237-243).  The synchronized sampling of is_4D
     needs one topology, as the reference's assertion does."""
@@ -418,14 +450,16 @@ def compute_chamfer_3d_4d_meshes(gt_pc: torch.Tensor, pred_meshes, device="cuda"
                                              synchronized=False, seed=seed + t)[0] for t, (v, f) in enumerate(pred_meshes)])
         pred_pc_4d = None
     return compute_chamfer_3d_4d(gt_pc, pred_pc, device=device, is_4D=is_4D, pred_pc_4D=pred_pc_4d, n_pts_icp=n_pts_icp, seed=seed,
-                                 n_iter=n_iter, nn=nn)
+                                 n_iter=n_iter, nn=nn, icp=icp)
 
 
 def evaluate_sample(uid: str, gt_root: Path, pred_root: Path, device: str = "cuda", n_pts_icp: int = 10_000, n_pts_chamfer: int = 100_000,
                     seed: int = 44, mesh_pattern: str = "mesh_*.glb", is_4d: bool = True, n_iter: int = 200, nn: str = EVALUATOR_NN,
-                    _metrics: Optional[Callable] = None) -> SampleResult:
+                    _metrics: Optional[Callable] = None, icp: str = EVALUATOR_ICP) -> SampleResult:
     """Evaluate a single sample: SampleResult with the metrics, or with status "error" and the message.  `_metrics`: the function
-    called as compute_chamfer_3d_4d_meshes is (tests inject one)."""
+    called as compute_chamfer_3d_4d_meshes is (tests inject one).  `icp` travels on only when it is not the default, so the default
+    call is the one it was before the keyword existed."""
+    icp_kw = {} if icp == EVALUATOR_ICP else {"icp": icp}
     metrics = compute_chamfer_3d_4d_meshes if _metrics is None else _metrics
     result = SampleResult(uid=uid)
     try:
@@ -444,7 +478,7 @@ def evaluate_sample(uid: str, gt_root: Path, pred_root: Path, device: str = "cud
             result.status, result.error_message = "error", str(e)
             return result
         cd_3d, cd_4d, cd_motion = metrics(gt_pc=gt_pc, pred_meshes=pred_meshes, device=device, is_4D=is_4d, n_pts_icp=n_pts_icp,
-                                          n_pts_chamfer=n_pts_chamfer, seed=seed, n_iter=n_iter, nn=nn)
+                                          n_pts_chamfer=n_pts_chamfer, seed=seed, n_iter=n_iter, nn=nn, **icp_kw)
         result.cd_3d, result.cd_4d, result.cd_motion, result.status = float(cd_3d), float(cd_4d), float(cd_motion), "success"
     except Exception as e:           # the reference records every failure of a sample and goes on
         result.status, result.error_message = "error", str(e)
@@ -485,9 +519,13 @@ def save_results(results: DatasetResults, output_path: Path) -> None:
 
 def evaluate_dataset(gt_root: str, pred_root: str, output_csv: Optional[str] = None, device: str = "cuda", n_pts_icp: int = 10_000,
                      n_pts_chamfer: int = 100_000, seed: int = 44, mesh_pattern: str = "mesh_*.glb", recompute: bool = False,
-                     is_4d: bool = True, n_iter: int = 200, nn: str = EVALUATOR_NN, _metrics: Optional[Callable] = None) -> DatasetResults:
+                     is_4d: bool = True, n_iter: int = 200, nn: str = EVALUATOR_NN, _metrics: Optional[Callable] = None,
+                     icp: str = EVALUATOR_ICP) -> DatasetResults:
     """Evaluate all samples of the dataset.  Results are saved after each sample, and the successful rows of an existing CSV are
     taken over on restart (failed ones are retried) unless recompute=True."""
+    if icp not in ICP_STEPS:
+        raise ValueError(f"icp must be one of {ICP_STEPS}, got {icp!r}")
+    icp_kw = {} if icp == EVALUATOR_ICP else {"icp": icp}
     gt_root, pred_root = Path(gt_root), Path(pred_root)
     output_path = Path(output_csv) if output_csv else None
     uids = find_uids(gt_root, pred_root, mesh_pattern)
@@ -506,7 +544,7 @@ def evaluate_dataset(gt_root: str, pred_root: str, output_csv: Optional[str] = N
                 continue
             logger.info(f"[{uid}] Retrying previously failed sample")
         result = evaluate_sample(uid=uid, gt_root=gt_root, pred_root=pred_root, device=device, n_pts_icp=n_pts_icp, n_pts_chamfer=n_pts_chamfer,
-                                 seed=seed, mesh_pattern=mesh_pattern, is_4d=is_4d, n_iter=n_iter, nn=nn, _metrics=_metrics)
+                                 seed=seed, mesh_pattern=mesh_pattern, is_4d=is_4d, n_iter=n_iter, nn=nn, _metrics=_metrics, **icp_kw)
         results.add(result)
         if result.status == "success":
             logger.info(f"[{uid}] CD_3D={result.cd_3d:.3f}, CD_4D={result.cd_4d:.3f}, CD_Motion={result.cd_motion:.3f}")
@@ -557,12 +595,15 @@ def main(argv=None) -> DatasetResults:
     parser.add_argument("--recompute", action="store_true", help="Recompute all samples even if already done")
     parser.add_argument("--3d-only", action="store_true", dest="three_d_only", help="Compute 3D metrics only (skip 4D/motion metrics)")
     parser.add_argument("--nn", choices=NN_METHODS, default=EVALUATOR_NN, help="Nearest-neighbour search: brute force or the grid (same numbers)")
+    parser.add_argument("--icp", choices=ICP_STEPS, default=EVALUATOR_ICP,
+                        help="ICP iteration: the autograd graph, or the fused device step (no host read inside the loop)")
     parser.add_argument("--n_iter", type=int, default=200, help="ICP iterations")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     results = evaluate_dataset(gt_root=args.gt_root, pred_root=args.pred_root, output_csv=args.output_csv, device=args.device,
                                n_pts_icp=args.n_pts_icp, n_pts_chamfer=args.n_pts_chamfer, seed=args.seed, mesh_pattern=args.mesh_pattern,
-                               recompute=args.recompute, is_4d=not args.three_d_only, n_iter=args.n_iter, nn=args.nn)
+                               recompute=args.recompute, is_4d=not args.three_d_only, n_iter=args.n_iter, nn=args.nn,
+                               **({} if args.icp == EVALUATOR_ICP else {"icp": args.icp}))
     print_summary(results)
     return results
 

@@ -469,6 +469,9 @@ def flow_step(v: torch.Tensor, latents: torch.Tensor, scales: Sequence[float], d
                                  un, T, N, D)
 
 
+NO_NEIGHBOUR_TEXT = "nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)"
+
+
 def nearest_neighbors(points: torch.Tensor, queries: torch.Tensor, precise: bool = True,
                       check: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """am_nn_search: for every query its nearest point (exact, brute force).  points (P, 3) or (B, P, 3) fp32, queries
@@ -500,7 +503,7 @@ def nearest_neighbors(points: torch.Tensor, queries: torch.Tensor, precise: bool
     _call(queries, None, "am_nn_search", C.byref(a), ws.data_ptr(), need)
     if check and bool((idx < 0).any()):
         # the kernel's strict `<` never fires for a query whose distances are all NaN: index -1 would wrap in a later gather
-        raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
+        raise ValueError(NO_NEIGHBOUR_TEXT)
     return idx, d2
 
 
@@ -511,7 +514,85 @@ def nn_indices_valid(*indices: torch.Tensor) -> None:
         b = (i < 0).any()
         bad = b if bad is None else (bad | b)
     if bad is not None and bool(bad):
-        raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
+        raise ValueError(NO_NEIGHBOUR_TEXT)
+
+
+class IcpState:
+    """What am_icp_step keeps between the iterations of one ICP call, allocated once: params (B, 12) fp32 = [T, d6, s] at the
+    reference's start (T = 0, d6 = (1, 0, 0, 0, 1, 0), s = 1), Adam's adam_m and adam_v (B, 12) fp32 at 0, best (16) fp32 =
+    [R, T, s, loss] with the loss at +inf, the outputs of the last step - out_loss (B,), out_rot (B, 9), and out_sums (B, 2, 13) /
+    out_grad (B, 12) fp64 once a step has asked for them - the flag word, and the workspace, sized on the first step and reused while
+    the cloud sizes stay.  Every tensor may be replaced by a caller's buffer of the same shape and dtype."""
+
+    def __init__(self, batch: int, device):
+        if batch < 1:
+            raise ValueError(f"IcpState: batch {batch} < 1")
+        self.batch, self.device = int(batch), torch.device(device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.params = torch.tensor([0.0, 0, 0, 1, 0, 0, 0, 1, 0, 1, 1, 1], **f32).repeat(batch, 1)
+        self.adam_m, self.adam_v = torch.zeros((batch, 12), **f32), torch.zeros((batch, 12), **f32)
+        self.best = torch.zeros((16,), **f32)
+        self.best[15] = float("inf")
+        self.out_loss, self.out_rot = torch.zeros((batch,), **f32), torch.zeros((batch, 9), **f32)
+        self.out_sums: Optional[torch.Tensor] = None
+        self.out_grad: Optional[torch.Tensor] = None
+        self.out_flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.workspace: Optional[torch.Tensor] = None
+        self.workspace_bytes = 0              # am_icp_workspace_bytes of the sizes of `_sized_for`
+        self._sized_for = None
+
+
+def icp_step(state: IcpState, pred: torch.Tensor, gt: torch.Tensor, rot_init: torch.Tensor, t: int, lr: float = 0.01,
+             betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, update: bool = True, return_sums: bool = False) -> IcpState:
+    """am_icp_step: iteration `t` (1, 2, ...: Adam's step count) of the ICP on pred (P, 3), gt (Q, 3) and rot_init (B, 3, 3) or (B, 9)
+    fp32, in place on `state`; no device-to-host read.  `update=False` computes the outputs and leaves params, adam_m, adam_v and best
+    as they are.  `return_sums` also fills state.out_sums and state.out_grad (fp64).  state.out_flag collects L.ICP_NO_NEIGHBOUR over
+    the steps: the caller reads it when it likes."""
+    _need(pred, torch.float32, "pred"); _need(gt, torch.float32, "gt"); _need(rot_init, torch.float32, "rot_init")
+    if pred.dim() != 2 or gt.dim() != 2 or pred.shape[1] != 3 or gt.shape[1] != 3:
+        raise ValueError(f"icp_step: expected (P, 3) and (Q, 3) clouds, got {tuple(pred.shape)} / {tuple(gt.shape)}")
+    P, Q, B = pred.shape[0], gt.shape[0], state.batch
+    if P == 0 or Q == 0:
+        raise ValueError("icp_step: empty point cloud")
+    if tuple(rot_init.shape) not in ((B, 3, 3), (B, 9)):
+        raise ValueError(f"icp_step: rot_init {tuple(rot_init.shape)} does not hold the state's {B} candidates")
+    if int(t) < 1:
+        raise ValueError(f"icp_step: step count {t} < 1")
+    want = {"params": (B, 12), "adam_m": (B, 12), "adam_v": (B, 12), "best": (16,), "out_loss": (B,), "out_rot": (B, 9)}
+    for name, shape in want.items():
+        ten = _need(getattr(state, name), torch.float32, f"state.{name}")
+        if tuple(ten.shape) != shape:
+            raise ValueError(f"icp_step: state.{name} {tuple(ten.shape)} != {shape}")
+    _need(state.out_flag, torch.int32, "state.out_flag")
+    for ten in (gt, rot_init, state.params, state.adam_m, state.adam_v, state.best, state.out_loss, state.out_rot, state.out_flag):
+        if ten.device != pred.device:
+            raise ValueError("icp_step: the clouds, rot_init and the state are on different devices")
+    if return_sums:
+        if state.out_sums is None:
+            state.out_sums = torch.zeros((B, 2, 13), dtype=torch.float64, device=pred.device)
+        if state.out_grad is None:
+            state.out_grad = torch.zeros((B, 12), dtype=torch.float64, device=pred.device)
+        for name, shape in (("out_sums", (B, 2, 13)), ("out_grad", (B, 12))):
+            ten = _need(getattr(state, name), torch.float64, f"state.{name}")
+            if tuple(ten.shape) != shape or ten.device != pred.device:
+                raise ValueError(f"icp_step: state.{name} {tuple(ten.shape)} != {shape} on the clouds' device")
+    if state._sized_for != (P, Q):
+        need = _entry(None, "am_icp_workspace_bytes")[1](P, Q, B)
+        if state.workspace is None or state.workspace.numel() < need:
+            state.workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=pred.device)
+        state.workspace_bytes, state._sized_for = need, (P, Q)
+    _need(state.workspace, torch.uint8, "state.workspace")
+    a = L.AmIcpArgs()
+    a.pred, a.gt, a.rot_init, a.n_pred, a.n_gt, a.batch = pred.data_ptr(), gt.data_ptr(), rot_init.data_ptr(), P, Q, B
+    a.update = 1 if update else 0
+    a.params, a.adam_m, a.adam_v, a.best = state.params.data_ptr(), state.adam_m.data_ptr(), state.adam_v.data_ptr(), state.best.data_ptr()
+    a.lr, a.beta1, a.beta2, a.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+    a.bias_correction1, a.bias_correction2 = 1.0 - float(betas[0]) ** int(t), 1.0 - float(betas[1]) ** int(t)
+    a.out_loss, a.out_rot, a.out_flag = state.out_loss.data_ptr(), state.out_rot.data_ptr(), state.out_flag.data_ptr()
+    if return_sums:
+        a.out_sums, a.out_grad = state.out_sums.data_ptr(), state.out_grad.data_ptr()
+    _call(pred, None, "am_icp_step", C.byref(a), state.workspace.data_ptr(), min(state.workspace_bytes, state.workspace.numel()))
+    return state
 
 
 class NnGrid:
@@ -636,7 +717,7 @@ def nn_grid_search(grid: NnGrid, queries: torch.Tensor, precise: bool = True, qu
         bad = torch.stack(((idx < 0).any().to(torch.int32), flag[0])).tolist()
         _nn_grid_raise(bad[1], "nn_grid_search")
         if bad[0]:
-            raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
+            raise ValueError(NO_NEIGHBOUR_TEXT)
     else:
         grid.flags |= flag
     return idx, d2
@@ -650,7 +731,7 @@ def nn_grid_valid(grids: Sequence[NnGrid], *indices: torch.Tensor) -> None:
         g.flags.zero_()
         _nn_grid_raise(f, "nn_grid_search")
     if any(got[len(grids):]):
-        raise ValueError("nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)")
+        raise ValueError(NO_NEIGHBOUR_TEXT)
 
 
 def nearest_neighbors_grid(points: torch.Tensor, queries: torch.Tensor, precise: bool = True,

@@ -546,6 +546,73 @@ int am_nn_grid_cells(const am_nn_grid_build_args* args, void* stream);
 int am_nn_grid_build(const am_nn_grid_build_args* args, void* stream);
 int am_nn_grid_search(const am_nn_grid_search_args* args, void* stream);
 
+/* One iteration of the ActionBench ICP on the device (csrc/am_icp.hip; actionbench/icp.py:86-106): the two nearest-neighbour matchings
+ * of the Chamfer loss, its gradient with respect to the 12 parameters of every candidate, one Adam step and the best-so-far record,
+ * without an index tensor, a gather, a scatter or a host read.  B = batch candidates share pred (P = n_pred points p_i) and gt
+ * (Q = n_gt points y_j).  fl32 / fl64: one operation rounded on its own, no contraction anywhere; dot(u, v) = (u0 v0 + u1 v1) + u2 v2
+ * and cross(u, v) = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0), two products and one difference each.
+ *
+ * params (B, 12) fp32 = [T (3), d6 (6), s (3)] per candidate.  Everything below is per candidate b.
+ *  1. THE ROTATION, fp64 on the widened fp32 values: a1 = d6[0:3], a2 = d6[3:6];
+ *       n1 = max(sqrt(dot(a1, a1)), 1e-12), b1 = a1 / n1;  d = dot(b1, a2), u = a2 - d b1;
+ *       n2 = max(sqrt(dot(u, u)), 1e-12), b2 = u / n2;  b3 = cross(b1, b2);  G = rows (b1, b2, b3);
+ *       R64[a][j] = (Ri[a][0] G[0][j] + Ri[a][1] G[1][j]) + Ri[a][2] G[2][j] with Ri = rot_init[b] (row-major 3 x 3);
+ *       R = fl32(R64) = out_rot[b]: the ONE matrix that the points, the gradient of s and the best-so-far record use.
+ *  2. THE POINTS, fp32:  x_i[j] = ((fl(s0 p_i0) R[0][j] + fl(s1 p_i1) R[1][j]) + fl(s2 p_i2) R[2][j]) + T[j], formed by one device
+ *     function wherever a transformed point is needed, so both directions see the same bits.
+ *  3. THE MATCHING, am_nn_search's fp32 arithmetic and tie rule: d2 = (dx dx + dy dy) + dz dz, the candidates visited in ascending
+ *     index and accepted on d2 < best only (best starts at +inf: the lowest index wins a tie, a NaN or infinite d2 never wins).
+ *       direction 0: for every i, n(i) = argmin_j d2(x_i, y_j);   direction 1: for every j, m(j) = argmin_i d2(y_j, x_i).
+ *     A query without a winner (index -1) contributes NO term, sets AM_ICP_NO_NEIGHBOUR in out_flag, and is never used as an index.
+ *  4. THE 13 TERMS of a matched pair (x, y, p: the untransformed point of x), fp32 then widened:  r = x - y;
+ *       [0] (r0 r0 + r1 r1) + r2 r2;   [1 + j] r_j;   [4 + 3 a + j] fl(p_a r_j).
+ *     sums (B, 2, 13) fp64 = their sums per direction, in a FIXED order: inside a wave of 64 consecutive queries
+ *     v[l] += v[l + off] for off = 32, 16, 8, 4, 2, 1; the 4 waves of a workgroup (256 consecutive queries) left to right; the workgroups
+ *     in ascending index.  No floating-point atomics: two runs give the same bits.
+ *  5. THE GRADIENT, fp64.  w0 = 1 / P, w1 = 1 / Q, c2 = 2 / B (the reference calls loss.mean().backward()).
+ *       A[k] = w0 sums[0][k] + w1 sums[1][k];   out_loss = fl32(A[0]);   gT[j] = c2 A[1 + j];   M[a][j] = c2 A[4 + 3 a + j];
+ *       gR[a][j] = s_a M[a][j];   gs[a] = (M[a][0] R[a][0] + M[a][1] R[a][1]) + M[a][2] R[a][2]   (R widened);
+ *       gG[i][j] = (Ri[0][i] gR[0][j] + Ri[1][i] gR[1][j]) + Ri[2][i] gR[2][j];   g1, g2, g3 = the rows of gG;
+ *       g1 = g1 + cross(b2, g3);   g2 = g2 + cross(g3, b1);
+ *       t2 = dot(g2, b2), gu = (g2 - t2 b2) / n2;   t1 = dot(gu, b1), ga2 = gu - t1 b1;
+ *       g1 = g1 - (d gu + t1 a2);   t0 = dot(g1, b1), ga1 = (g1 - t0 b1) / n1;
+ *     out_grad (B, 12) fp64 = [gT, ga1, ga2, gs].
+ *  6. ADAM (torch.optim.Adam's defaults), fp64 on the widened fp32 state, per parameter with its gradient g:
+ *       m' = beta1 m + (1 - beta1) g;   v' = beta2 v + (1 - beta2) (g g);
+ *       param' = param - (lr / bias_correction1) (m' / (sqrt(v') / sqrt(bias_correction2) + eps));
+ *     params, adam_m and adam_v are rounded to fp32 once, at the store.  The caller passes bias_correction{1,2} = 1 - beta{1,2}^t of
+ *     its step count t, computed in double as torch does.
+ *  7. BEST SO FAR (icp.py:99-106).  best (16) fp32 = [R (9), T (3), s (3), loss]; the caller starts the loss at +inf.  With c the
+ *     candidate of the smallest out_loss (accepted on < only, in ascending index: the lowest index wins a tie, a NaN never wins): if
+ *     out_loss[c] < best[15], best = [out_rot[c] - the R that produced the loss -, T and s of c AFTER step 6, out_loss[c]].
+ * update == 0 computes the outputs and leaves params, adam_m, adam_v and best untouched.  out_flag (device int32[1]) is only ever
+ * ORed into: the caller zeroes it once and reads it after any number of steps.  The workspace holds the per-workgroup partial sums
+ * and must be am_icp_workspace_bytes (0 for sizes the call would refuse) bytes, 8-byte aligned; its content on entry is irrelevant.
+ * Launch plan: one pairs launch of (ceil(P / 256) + ceil(Q / 256)) x B workgroups (queries one per lane, points staged through LDS in
+ * tiles of 512, transformed while staged in direction 1), then one workgroup that sums, differentiates, steps and records. */
+#define AM_ICP_NO_NEIGHBOUR 1          /* out_flag: a query had no finite distance to any point (NaN / inf coordinates) */
+typedef struct {
+  const float* pred;        /* (n_pred, 3) */
+  const float* gt;          /* (n_gt, 3) */
+  const float* rot_init;    /* (batch, 9) */
+  int64_t n_pred;
+  int64_t n_gt;
+  int32_t batch;
+  int32_t update;
+  float* params;            /* (batch, 12) state */
+  float* adam_m;            /* (batch, 12) state */
+  float* adam_v;            /* (batch, 12) state */
+  float* best;              /* (16) state */
+  double lr, beta1, beta2, eps, bias_correction1, bias_correction2;
+  float* out_loss;          /* (batch) */
+  float* out_rot;           /* (batch, 9) */
+  double* out_sums;         /* (batch, 2, 13) or null */
+  double* out_grad;         /* (batch, 12) or null */
+  int32_t* out_flag;
+} am_icp_args;
+size_t am_icp_workspace_bytes(int64_t n_pred, int64_t n_gt, int batch);
+int am_icp_step(const am_icp_args* args, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Preview rendering (INTEGRATION seam S6; reference actionmesh/render/{renderer,visualizer}.py, PyTorch3D's
  * MeshRasterizer + soft_normal_shading): normal maps of ONE animated mesh - n_frames vertex sets on one topology - seen by
  * n_cameras PerspectiveCameras, every (frame, camera) image of the call in a fixed number of launches.
