@@ -3,11 +3,13 @@
 // include/actionmesh_amd.h's; all geometry is fp64, every operation rounded on its own (the file is built with -ffp-contract=off), so
 // positions, quadrics, costs and keys are compared bit for bit with a numpy restatement.
 //
-//   am_decimate_quadrics   one thread per vertex: the area-weighted plane quadrics of its faces, summed in CSR order (a gather)
-//   am_decimate_edges      one thread per edge: lock and link tests, the Cramer solve or the u / v / midpoint fallback, the cost,
-//                          the no-flip test over both stars, the 64-bit key
-//   am_decimate_border_quadrics, am_decimate_border_edges   the same two for `borders="collapse"`: border planes in the gather, the
-//                          three vertex classes and the coned link condition in the tests; position, cost, flips and key are shared
+//   am_decimate_quadrics, am_decimate_border_quadrics   one thread per vertex: the area-weighted plane quadrics of its faces, summed in
+//                          CSR order (a gather); with `BORDERS` also the two border planes of every corner
+//   am_decimate_edges, am_decimate_border_edges   one thread per edge: the topology rule - lock and link tests, with `BORDERS` the three
+//                          vertex classes and the coned link condition -, then the Cramer solve or the u / v / midpoint fallback, the
+//                          cost, the no-flip test over both stars, the 64-bit key
+// `BORDERS` is a template parameter (`borders="collapse"`): one text of each kernel, two instantiations, and the fixed-mode one never reads
+// the border tables.
 //   am_decimate_select     one thread per vertex, twice (m1: min key of its edges; m2: min of m1 over its closed neighbourhood), then
 //                          one thread per edge (selected iff its key is m2 at both ends)
 //   am_decimate_apply      one thread per kept edge: moves u, adds the quadrics, rewrites v -> u in v's corners, marks the two faces
@@ -60,7 +62,41 @@ __device__ __forceinline__ void add_plane(double* q, vec3 n, double d, double w)
     for (int b = a; b < 4; ++b, ++t) q[t] = q[t] + (w * p[a]) * p[b];
 }
 
+// ---- what only `BORDERS` reads (the header's "Border collapses") ------------------------------------------------------------------------
+
+// the edge index of half-edge h where only the half-edge table is known; -1 (flag raised) when it is outside [0, n_edges)
+__device__ __forceinline__ int edge_index(const mesh_view& m, int h) {
+  const int e = m.he2e[h];
+  if (!in_range(e, m.n_edges)) {
+    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+    return -1;
+  }
+  return e;
+}
+
+// the count of edge e (inside [0, n_edges)); a count below 1 raises the flag: every edge of the table has a half-edge
+__device__ __forceinline__ int count_of(const mesh_view& m, const int32_t* __restrict__ edge_count, int e) {
+  const int n = edge_count[e];
+  if (n < 1) atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+  return n;
+}
+
+// one constraint plane of the border half-edge p -> q of a face with unit normal n
+__device__ __forceinline__ void add_border_plane(double* q, vec3 p, vec3 pq, vec3 n, double border_weight) {
+#pragma clang fp contract(off)
+  const vec3 E = sub3(pq, p);
+  vec3 mm = cross3(E, n);
+  const double ml = norm3(mm);
+  if (!(ml > AM_MESH_ZERO)) return;
+  mm = div3(mm, ml);
+  const double d = -dot3(mm, p);
+  add_plane(q, mm, d, border_weight * dot3(E, E));
+}
+
+// The gather.  Without BORDERS, edge_count and m.he2e are null and never read, and border_weight is unused.
+template <bool BORDERS>
 __global__ __launch_bounds__(MESH_THREADS) void decimate_quadrics_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                         const int32_t* __restrict__ edge_count, double border_weight,
                                                                          double* __restrict__ out_quadrics) {
 #pragma clang fp contract(off)
   const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
@@ -72,16 +108,22 @@ __global__ __launch_bounds__(MESH_THREADS) void decimate_quadrics_kernel(mesh_vi
   for (int j = begin; j < end; ++j) {
     const int c = corner_at(m, j, (int)v);
     if (c < 0) continue;
-    int i0, i1, i2;
-    if (!face_indices(m.faces + (c - c % 3), m.n_vertices, m.flag, i0, i1, i2)) continue;
-    const vec3 p0 = load3(positions, i0), p1 = load3(positions, i1), p2 = load3(positions, i2);
+    const int f3 = c - c % 3, k = c % 3;
+    int i[3];
+    if (!face_indices(m.faces + f3, m.n_vertices, m.flag, i[0], i[1], i[2])) continue;
+    const vec3 p0 = load3(positions, i[0]), p1 = load3(positions, i[1]), p2 = load3(positions, i[2]);
     const vec3 cr = cross3(sub3(p1, p0), sub3(p2, p0));
     const double len = norm3(cr);
     if (!(len > AM_MESH_ZERO)) continue;
     const vec3 n = div3(cr, len);
-    const double d = -dot3(n, p0);
-    const double w = len / 2.0;
-    add_plane(q, n, d, w);
+    add_plane(q, n, -dot3(n, p0), len / 2.0);
+    if constexpr (BORDERS) {
+      const int hin = f3 + (k + 2) % 3;
+      const int eout = edge_index(m, c), ein = edge_index(m, hin);
+      const vec3 ps = load3(positions, (int)v);
+      if (eout >= 0 && count_of(m, edge_count, eout) == 1) add_border_plane(q, ps, load3(positions, i[(k + 1) % 3]), n, border_weight);
+      if (ein >= 0 && count_of(m, edge_count, ein) == 1) add_border_plane(q, load3(positions, i[(k + 2) % 3]), ps, n, border_weight);
+    }
   }
   for (int i = 0; i < 10; ++i) out_quadrics[v * 10 + i] = q[i];
 }
@@ -201,114 +243,17 @@ __device__ __forceinline__ void place(const double* __restrict__ quadrics, const
   cost = cost > 0.0 ? cost : 0.0;
 }
 
-__global__ __launch_bounds__(MESH_THREADS) void decimate_edges_kernel(mesh_view m, const double* __restrict__ positions,
-                                                                      const double* __restrict__ quadrics,
-                                                                      const int32_t* __restrict__ edge_count,
-                                                                      double* __restrict__ out_positions, double* __restrict__ out_cost,
-                                                                      int64_t* __restrict__ out_key) {
-#pragma clang fp contract(off)
-  const int64_t e = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
-  if (e >= m.n_edges) return;
-  const int u = m.edges[2 * e], v = m.edges[2 * e + 1];
-  vec3 x = {0.0, 0.0, 0.0};
-  double cost = 0.0;
-  int64_t key = NO_KEY;
-  bool ok = true;
-  if (!in_range(u, m.n_vertices) || !in_range(v, m.n_vertices) || u > v) {
-    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
-    ok = false;
-  }
-  ok = ok && u != v && edge_count[e] == 2;
-  int ub = 0, ue = 0, vb = 0, ve = 0;
-  if (ok) {
-    const bool ru = csr_range(m, u, ub, ue), rv = csr_range(m, v, vb, ve);
-    ok = ru && rv;
-  }
-  int apex[2] = {-1, -1};
+// The fixed-border rule on an edge { u, v } of count 2: may it collapse, and its two apexes.  Both endpoints are walked whatever the
+// first walk found: a bad table entry in either star raises its flag.
+__device__ bool fixed_rule(const mesh_view& m, const int32_t* __restrict__ edge_count, int u, int ub, int ue, int v, int vb, int ve,
+                           int* apex) {
   int n_apex = 0, shared = 0;
-  if (ok) {
-    const bool tu = walk_topology(m, edge_count, u, ub, ue, v, true, vb, ve, apex, n_apex, shared);
-    const bool tv = walk_topology(m, edge_count, v, vb, ve, u, false, 0, 0, apex, n_apex, shared);
-    ok = tu && tv && n_apex == 2 && shared == 4;
-  }
-  if (ok) {
-    const int a0 = apex[0], a1 = apex[1];           // inside [0, n_vertices): corner_others checked them
-    ok = a0 != a1 && a0 != u && a0 != v && a1 != u && a1 != v && m.offsets[a0 + 1] - m.offsets[a0] > 3 &&
+  const bool tu = walk_topology(m, edge_count, u, ub, ue, v, true, vb, ve, apex, n_apex, shared);
+  const bool tv = walk_topology(m, edge_count, v, vb, ve, u, false, 0, 0, apex, n_apex, shared);
+  if (!(tu && tv && n_apex == 2 && shared == 4)) return false;
+  const int a0 = apex[0], a1 = apex[1];           // inside [0, n_vertices): corner_others checked them
+  return a0 != a1 && a0 != u && a0 != v && a1 != u && a1 != v && m.offsets[a0 + 1] - m.offsets[a0] > 3 &&
          m.offsets[a1 + 1] - m.offsets[a1] > 3;
-  }
-  if (ok) {
-    place(quadrics, positions, u, v, x, cost);
-    const bool fu = walk_flips(m, positions, u, ub, ue, v, apex[0], apex[1], x);
-    const bool fv = walk_flips(m, positions, v, vb, ve, u, apex[0], apex[1], x);
-    if (fu && fv) key = (int64_t)(((uint64_t)__float_as_uint((float)cost) << 32) | (uint64_t)mix32((uint32_t)e));
-  }
-  out_positions[3 * e] = x.x;
-  out_positions[3 * e + 1] = x.y;
-  out_positions[3 * e + 2] = x.z;
-  out_cost[e] = cost;
-  out_key[e] = key;
-}
-
-// ---- border collapses (the header's "Border collapses"): the two kernels that take the places of the two above -------------------------
-
-// the edge index of half-edge h where only the half-edge table is known; -1 (flag raised) when it is outside [0, n_edges)
-__device__ __forceinline__ int edge_index(const mesh_view& m, int h) {
-  const int e = m.he2e[h];
-  if (!in_range(e, m.n_edges)) {
-    atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
-    return -1;
-  }
-  return e;
-}
-
-// the count of edge e (inside [0, n_edges)); a count below 1 raises the flag: every edge of the table has a half-edge
-__device__ __forceinline__ int count_of(const mesh_view& m, const int32_t* __restrict__ edge_count, int e) {
-  const int n = edge_count[e];
-  if (n < 1) atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
-  return n;
-}
-
-// one constraint plane of the border half-edge p -> q of a face with unit normal n
-__device__ __forceinline__ void add_border_plane(double* q, vec3 p, vec3 pq, vec3 n, double border_weight) {
-#pragma clang fp contract(off)
-  const vec3 E = sub3(pq, p);
-  vec3 mm = cross3(E, n);
-  const double ml = norm3(mm);
-  if (!(ml > AM_MESH_ZERO)) return;
-  mm = div3(mm, ml);
-  const double d = -dot3(mm, p);
-  add_plane(q, mm, d, border_weight * dot3(E, E));
-}
-
-__global__ __launch_bounds__(MESH_THREADS) void decimate_border_quadrics_kernel(mesh_view m, const double* __restrict__ positions,
-                                                                                const int32_t* __restrict__ edge_count,
-                                                                                double border_weight, double* __restrict__ out_quadrics) {
-#pragma clang fp contract(off)
-  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
-  if (v >= m.n_vertices) return;
-  double q[10];
-  for (int i = 0; i < 10; ++i) q[i] = 0.0;
-  int begin, end;
-  csr_range(m, (int)v, begin, end);
-  for (int j = begin; j < end; ++j) {
-    const int c = corner_at(m, j, (int)v);
-    if (c < 0) continue;
-    const int f3 = c - c % 3, k = c % 3;
-    int i[3];
-    if (!face_indices(m.faces + f3, m.n_vertices, m.flag, i[0], i[1], i[2])) continue;
-    const vec3 p0 = load3(positions, i[0]), p1 = load3(positions, i[1]), p2 = load3(positions, i[2]);
-    const vec3 cr = cross3(sub3(p1, p0), sub3(p2, p0));
-    const double len = norm3(cr);
-    if (!(len > AM_MESH_ZERO)) continue;
-    const vec3 n = div3(cr, len);
-    add_plane(q, n, -dot3(n, p0), len / 2.0);
-    const int hin = f3 + (k + 2) % 3;
-    const int eout = edge_index(m, c), ein = edge_index(m, hin);
-    const vec3 ps = load3(positions, (int)v);
-    if (eout >= 0 && count_of(m, edge_count, eout) == 1) add_border_plane(q, ps, load3(positions, i[(k + 1) % 3]), n, border_weight);
-    if (ein >= 0 && count_of(m, edge_count, ein) == 1) add_border_plane(q, load3(positions, i[(k + 2) % 3]), ps, n, border_weight);
-  }
-  for (int i = 0; i < 10; ++i) out_quadrics[v * 10 + i] = q[i];
 }
 
 // What one walk over the corners of an endpoint finds.
@@ -370,11 +315,36 @@ __device__ bool apex_valence(const mesh_view& m, const int32_t* __restrict__ edg
   return t.sound && t.plain && t.n_border == 2;
 }
 
-__global__ __launch_bounds__(MESH_THREADS) void decimate_border_edges_kernel(mesh_view m, const double* __restrict__ positions,
-                                                                             const double* __restrict__ quadrics,
-                                                                             const int32_t* __restrict__ edge_count,
-                                                                             double* __restrict__ out_positions,
-                                                                             double* __restrict__ out_cost, int64_t* __restrict__ out_key) {
+// The border rule on an edge { u, v } of `count` half-edges: may it collapse, and its apexes (one, apex[0], for a border edge).  v is
+// walked only when u passed.
+__device__ bool border_rule(const mesh_view& m, const int32_t* __restrict__ edge_count, int count, int u, int ub, int ue, int v, int vb,
+                            int ve, int* apex) {
+  const border_star su = walk_border_topology(m, edge_count, u, ub, ue, v, true, vb, ve, apex);
+  if (su.sound && su.n_half != count) atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
+  bool ok = su.sound && su.n_half == count && (count == 1 || count == 2) && su.plain && (su.n_border == 0 || su.n_border == 2);
+  if (!ok) return false;
+  const border_star sv = walk_border_topology(m, edge_count, v, vb, ve, u, false, 0, 0, apex);
+  ok = sv.sound && sv.plain && (sv.n_border == 0 || sv.n_border == 2) && su.n_faces == count && su.shared == 2 * count;
+  ok = ok && ((ue - ub) + su.n_border) + ((ve - vb) + sv.n_border) - 4 > 3;        // the merged vertex's coned valence
+  if (count == 2)
+    ok = ok && !(su.n_border == 2 && sv.n_border == 2);
+  else
+    ok = ok && su.apex_border + sv.apex_border < 2;
+  if (!ok) return false;
+  const int a0 = apex[0], a1 = apex[1];           // a0, and a1 of an interior edge, inside [0, n_vertices): corner_others checked them
+  ok = a0 != u && a0 != v && apex_valence(m, edge_count, a0);
+  if (count == 2) ok = ok && a0 != a1 && a1 != u && a1 != v && apex_valence(m, edge_count, a1);
+  return ok;
+}
+
+// The edge evaluation: the rule of the mode between a prologue and a tail that the modes share.  Fixed mode goes on with count-2 edges
+// only; with BORDERS the count is read - and a count below 1 flagged - for every edge, a refused one too.
+template <bool BORDERS>
+__global__ __launch_bounds__(MESH_THREADS) void decimate_edges_kernel(mesh_view m, const double* __restrict__ positions,
+                                                                      const double* __restrict__ quadrics,
+                                                                      const int32_t* __restrict__ edge_count,
+                                                                      double* __restrict__ out_positions, double* __restrict__ out_cost,
+                                                                      int64_t* __restrict__ out_key) {
 #pragma clang fp contract(off)
   const int64_t e = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (e >= m.n_edges) return;
@@ -387,8 +357,8 @@ __global__ __launch_bounds__(MESH_THREADS) void decimate_border_edges_kernel(mes
     atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
     ok = false;
   }
-  const int count = count_of(m, edge_count, (int)e);
-  ok = ok && u != v;
+  const int count = BORDERS ? count_of(m, edge_count, (int)e) : 2;
+  ok = ok && u != v && (BORDERS || edge_count[e] == 2);
   int ub = 0, ue = 0, vb = 0, ve = 0;
   if (ok) {
     const bool ru = csr_range(m, u, ub, ue), rv = csr_range(m, v, vb, ve);
@@ -396,23 +366,10 @@ __global__ __launch_bounds__(MESH_THREADS) void decimate_border_edges_kernel(mes
   }
   int apex[2] = {-1, -1};
   if (ok) {
-    const border_star su = walk_border_topology(m, edge_count, u, ub, ue, v, true, vb, ve, apex);
-    if (su.sound && su.n_half != count) atomicOr(m.flag, AM_DECIMATE_BAD_EDGE);
-    ok = su.sound && su.n_half == count && (count == 1 || count == 2) && su.plain && (su.n_border == 0 || su.n_border == 2);
-    if (ok) {
-      const border_star sv = walk_border_topology(m, edge_count, v, vb, ve, u, false, 0, 0, apex);
-      ok = sv.sound && sv.plain && (sv.n_border == 0 || sv.n_border == 2) && su.n_faces == count && su.shared == 2 * count;
-      ok = ok && ((ue - ub) + su.n_border) + ((ve - vb) + sv.n_border) - 4 > 3;        // the merged vertex's coned valence
-      if (count == 2)
-        ok = ok && !(su.n_border == 2 && sv.n_border == 2);
-      else
-        ok = ok && su.apex_border + sv.apex_border < 2;
-    }
-  }
-  if (ok) {
-    const int a0 = apex[0], a1 = apex[1];           // a0, and a1 of an interior edge, inside [0, n_vertices): corner_others checked them
-    ok = a0 != u && a0 != v && apex_valence(m, edge_count, a0);
-    if (count == 2) ok = ok && a0 != a1 && a1 != u && a1 != v && apex_valence(m, edge_count, a1);
+    if constexpr (BORDERS)
+      ok = border_rule(m, edge_count, count, u, ub, ue, v, vb, ve, apex);
+    else
+      ok = fixed_rule(m, edge_count, u, ub, ue, v, vb, ve, apex);
   }
   if (ok) {
     place(quadrics, positions, u, v, x, cost);
@@ -509,34 +466,49 @@ int check_edges(const char* who, int64_t n_edges) {
   return AM_OK;
 }
 
+// The gather's launch behind an entry's checks: `a` gives the fields the two argument structs share, the caller those only the border
+// struct has (null and 0 in fixed mode).
+template <bool BORDERS, class Args>
+int launch_quadrics(const Args* a, int64_t n_edges, const int32_t* half_edge_to_edge, const int32_t* edge_count, double border_weight,
+                    void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, n_edges, a->faces, a->offsets, a->corners, nullptr, half_edge_to_edge, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(decimate_quadrics_kernel<BORDERS>, dim3(mesh_blocks(a->n_vertices)), dim3(MESH_THREADS), 0, st, m, a->positions,
+                     edge_count, border_weight, a->out_quadrics);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+// An edge entry whole (the two argument structs have the same fields): the checks in the entry's name `who`, then the launch.
+template <bool BORDERS, class Args>
+int decimate_edges(const char* who, const Args* a, void* stream) {
+  AM_CHECK(a != nullptr, "%s: null arguments", who);
+  AM_TRY(check_mesh(who, a->n_vertices, a->n_faces));
+  AM_TRY(check_edges(who, a->n_edges));
+  AM_CHECK(a->positions && a->quadrics && a->faces && a->offsets && a->corners && a->edges && a->half_edge_to_edge && a->edge_count &&
+               a->out_positions && a->out_cost && a->out_key && a->out_flag,
+           "%s: null pointer", who);
+  hipStream_t st = (hipStream_t)stream;
+  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
+  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(decimate_edges_kernel<BORDERS>, dim3(mesh_blocks(a->n_edges)), dim3(MESH_THREADS), 0, st, m, a->positions, a->quadrics,
+                     a->edge_count, a->out_positions, a->out_cost, a->out_key);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
 }  // namespace
 
 extern "C" int am_decimate_quadrics(const am_decimate_quadrics_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_decimate_quadrics: null arguments");
   AM_TRY(check_mesh("am_decimate_quadrics", a->n_vertices, a->n_faces));
   AM_CHECK(a->positions && a->faces && a->offsets && a->corners && a->out_quadrics && a->out_flag, "am_decimate_quadrics: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const mesh_view m = {a->n_vertices, a->n_faces, 0, a->faces, a->offsets, a->corners, nullptr, nullptr, a->out_flag};
-  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(decimate_quadrics_kernel, dim3(mesh_blocks(a->n_vertices)), dim3(MESH_THREADS), 0, st, m, a->positions, a->out_quadrics);
-  AM_HIP(hipGetLastError());
-  return AM_OK;
+  return launch_quadrics<false>(a, 0, nullptr, nullptr, 0.0, stream);
 }
 
 extern "C" int am_decimate_edges(const am_decimate_edges_args* a, void* stream) {
-  AM_CHECK(a != nullptr, "am_decimate_edges: null arguments");
-  AM_TRY(check_mesh("am_decimate_edges", a->n_vertices, a->n_faces));
-  AM_TRY(check_edges("am_decimate_edges", a->n_edges));
-  AM_CHECK(a->positions && a->quadrics && a->faces && a->offsets && a->corners && a->edges && a->half_edge_to_edge && a->edge_count &&
-               a->out_positions && a->out_cost && a->out_key && a->out_flag,
-           "am_decimate_edges: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
-  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(decimate_edges_kernel, dim3(mesh_blocks(a->n_edges)), dim3(MESH_THREADS), 0, st, m, a->positions, a->quadrics,
-                     a->edge_count, a->out_positions, a->out_cost, a->out_key);
-  AM_HIP(hipGetLastError());
-  return AM_OK;
+  return decimate_edges<false>("am_decimate_edges", a, stream);
 }
 
 extern "C" int am_decimate_border_quadrics(const am_decimate_border_quadrics_args* a, void* stream) {
@@ -547,29 +519,11 @@ extern "C" int am_decimate_border_quadrics(const am_decimate_border_quadrics_arg
            "am_decimate_border_quadrics: null pointer");
   AM_CHECK(a->border_weight >= 0.0 && a->border_weight <= 1.7976931348623157e308,          // a NaN fails the first, an infinity the second
            "am_decimate_border_quadrics: border_weight %g is not finite and >= 0", a->border_weight);
-  hipStream_t st = (hipStream_t)stream;
-  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, nullptr, a->half_edge_to_edge, a->out_flag};
-  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(decimate_border_quadrics_kernel, dim3(mesh_blocks(a->n_vertices)), dim3(MESH_THREADS), 0, st, m, a->positions,
-                     a->edge_count, a->border_weight, a->out_quadrics);
-  AM_HIP(hipGetLastError());
-  return AM_OK;
+  return launch_quadrics<true>(a, a->n_edges, a->half_edge_to_edge, a->edge_count, a->border_weight, stream);
 }
 
 extern "C" int am_decimate_border_edges(const am_decimate_border_edges_args* a, void* stream) {
-  AM_CHECK(a != nullptr, "am_decimate_border_edges: null arguments");
-  AM_TRY(check_mesh("am_decimate_border_edges", a->n_vertices, a->n_faces));
-  AM_TRY(check_edges("am_decimate_border_edges", a->n_edges));
-  AM_CHECK(a->positions && a->quadrics && a->faces && a->offsets && a->corners && a->edges && a->half_edge_to_edge && a->edge_count &&
-               a->out_positions && a->out_cost && a->out_key && a->out_flag,
-           "am_decimate_border_edges: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const mesh_view m = {a->n_vertices, a->n_faces, a->n_edges, a->faces, a->offsets, a->corners, a->edges, a->half_edge_to_edge, a->out_flag};
-  AM_HIP(hipMemsetAsync(a->out_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(decimate_border_edges_kernel, dim3(mesh_blocks(a->n_edges)), dim3(MESH_THREADS), 0, st, m, a->positions, a->quadrics,
-                     a->edge_count, a->out_positions, a->out_cost, a->out_key);
-  AM_HIP(hipGetLastError());
-  return AM_OK;
+  return decimate_edges<true>("am_decimate_border_edges", a, stream);
 }
 
 extern "C" int am_decimate_select(const am_decimate_select_args* a, void* stream) {

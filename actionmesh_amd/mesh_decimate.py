@@ -89,6 +89,11 @@ def _check_borders(borders: str, border_weight: float) -> float:
     return weight
 
 
+def _by_key(selected: torch.Tensor, key: torch.Tensor) -> torch.Tensor:
+    """The edge indices with the selected edges first, the smallest keys first (one sort on the device)."""
+    return torch.sort(torch.where(selected != 0, key, torch.full_like(key, NO_KEY))).indices
+
+
 def decimate_rounds(positions: torch.Tensor, faces: torch.Tensor, target_faces: int, backend=None, observer=None, borders: str = "fixed",
                     border_weight: float = 1.0):
     """The round loop on fp64 positions (V, 3) and int32 faces (F, 3), both contiguous.  Returns (positions (V, 3) fp64 - the
@@ -124,8 +129,7 @@ def decimate_rounds(positions: torch.Tensor, faces: torch.Tensor, target_faces: 
                      key=key, m1=m1, m2=m2, selected=selected)
         if collapse:
             # the shortest prefix, in key order, of the selected edges whose faces (1 or 2 each) reach F - target: on the device
-            masked = torch.where(selected != 0, key, torch.full_like(key, NO_KEY))
-            order = torch.sort(masked).indices
+            order = _by_key(selected, key)
             removed = torch.cumsum(torch.where(selected[order] != 0, tables.edge_count[order].long(), 0), 0)
             n_kept = torch.minimum((removed < F - target_faces).sum() + 1, (selected != 0).sum())
             n_removed = removed[torch.clamp(n_kept - 1, min=0)] * (n_kept > 0)
@@ -146,8 +150,7 @@ def decimate_rounds(positions: torch.Tensor, faces: torch.Tensor, target_faces: 
         else:
             n_kept = min(n_selected, (F - target_faces + 1) // 2)
             n_removed = 2 * n_kept
-            masked = torch.where(selected != 0, key, torch.full_like(key, NO_KEY))
-            kept = torch.sort(masked).indices[:n_kept].to(torch.int32).contiguous()         # the smallest keys first
+            kept = _by_key(selected, key)[:n_kept].to(torch.int32).contiguous()
         round_map = torch.arange(V, device=dev, dtype=torch.int32)
         dead = backend.apply(positions, quadrics, faces, topology, tables.edges, cand, kept, round_map, flag=flags[2:3])
         merged = round_map.long()[merged]

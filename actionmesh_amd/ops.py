@@ -1040,6 +1040,16 @@ def _mesh_operands(what: str, vertices: torch.Tensor, faces: torch.Tensor, frame
     return T, V, F, (stride[0] if vertices.dim() == 3 and T > 1 else 3 * V)
 
 
+def _topology_tables(what: str, topology, V: int, F: int):
+    """The vertex -> corner CSR of a mesh of V vertices and F faces: int32, contiguous, (V + 1) offsets and (3 F) corners."""
+    offsets = _need(topology.offsets, torch.int32, f"{what}: topology.offsets")
+    corners = _need(topology.corners, torch.int32, f"{what}: topology.corners")
+    if offsets.numel() != V + 1 or corners.numel() != 3 * F:
+        raise ValueError(f"{what}: the topology is of {offsets.numel() - 1} vertices and {corners.numel() // 3} faces, the mesh has "
+                         f"{V} and {F}")
+    return offsets, corners
+
+
 def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, topology=None, features: bool = False, return_face_normals: bool = False,
                    out: Optional[torch.Tensor] = None, out_face_normals: Optional[torch.Tensor] = None):
     """am_vertex_normals: trimesh's angle-weighted vertex normals followed by the reference's fp32 F.normalize (the contract is the
@@ -1052,11 +1062,7 @@ def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, topology=None, f
     T, V, F, stride = _mesh_operands("vertex_normals", vertices, faces, frames=True)
     if topology is None:
         topology = MeshTopology(faces, V)
-    offsets = _need(topology.offsets, torch.int32, "vertex_normals: topology.offsets")
-    corners = _need(topology.corners, torch.int32, "vertex_normals: topology.corners")
-    if offsets.numel() != V + 1 or corners.numel() != 3 * F:
-        raise ValueError(f"vertex_normals: the topology is of {offsets.numel() - 1} vertices and {corners.numel() // 3} faces, the mesh "
-                         f"has {V} and {F}")
+    offsets, corners = _topology_tables("vertex_normals", topology, V, F)
     dev = vertices.device
     lead = tuple(vertices.shape[:-2])
     out = _out("vertex_normals: out", out, lead + (V, 6 if features else 3), torch.float32, dev)
@@ -1146,11 +1152,7 @@ def _decimate_mesh(what: str, faces: torch.Tensor, topology, V: int, dev=None) -
     F = faces.shape[0]
     if not 1 <= V <= _MESH_MAX or F > _MESH_MAX:
         raise ValueError(f"{what}: {V} vertices and {F} faces are outside 1 .. (2^31 - 1) / 3")
-    offsets = _need(topology.offsets, torch.int32, f"{what}: topology.offsets")
-    corners = _need(topology.corners, torch.int32, f"{what}: topology.corners")
-    if offsets.numel() != V + 1 or corners.numel() != 3 * F:
-        raise ValueError(f"{what}: the topology is of {offsets.numel() - 1} vertices and {corners.numel() // 3} faces, the mesh has "
-                         f"{V} and {F}")
+    offsets, corners = _topology_tables(what, topology, V, F)
     if offsets.device != faces.device or corners.device != faces.device:
         raise ValueError(f"{what}: the topology is not on {faces.device}")
     if dev is not None and faces.device != dev:
@@ -1170,23 +1172,29 @@ def _decimate_edge_tables(what: str, a, edges: torch.Tensor, half_edge_to_edge: 
     return E
 
 
+def _decimate_quadrics(what: str, entry: str, a, positions, faces, topology, out, flag, border_operands=None):
+    """decimate_quadrics and decimate_border_quadrics: the same operands, checks and output behind two entry points.
+    `border_operands(F, dev)` checks and sets what only the border entry takes, in its place: behind the mesh, before the output."""
+    V, dev = _positions(what, positions)
+    F = _decimate_mesh(what, faces, topology, V, dev)
+    if border_operands is not None:
+        border_operands(F, dev)
+    out = _out(f"{what}: out", out, (V, 10), torch.float64, dev)
+    flag, own = _flag_word(what, flag, dev)
+    a.positions, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), V, F, faces.data_ptr()
+    a.offsets, a.corners, a.out_quadrics, a.out_flag = topology.offsets.data_ptr(), topology.corners.data_ptr(), out.data_ptr(), flag.data_ptr()
+    _call(positions, None, entry, C.byref(a))
+    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
+    return out
+
+
 def decimate_quadrics(positions: torch.Tensor, faces: torch.Tensor, topology, out: Optional[torch.Tensor] = None,
                       flag: Optional[torch.Tensor] = None) -> torch.Tensor:
     """am_decimate_quadrics: the area-weighted plane quadrics (V, 10) fp64 of every vertex, summed over its faces in the CSR order
     of `topology` (a `mesh_topology.MeshTopology` of `faces`).  positions (V, 3) fp64, faces (F, 3) int32.  Without `flag`, ONE
     device-to-host read behind the launch turns a bad face index or CSR into a ValueError; with the caller's int32 (1,) `flag`
     nothing is read here."""
-    what = "decimate_quadrics"
-    V, dev = _positions(what, positions)
-    F = _decimate_mesh(what, faces, topology, V, dev)
-    out = _out(f"{what}: out", out, (V, 10), torch.float64, dev)
-    flag, own = _flag_word(what, flag, dev)
-    a = L.AmDecimateQuadricsArgs()
-    a.positions, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), V, F, faces.data_ptr()
-    a.offsets, a.corners, a.out_quadrics, a.out_flag = topology.offsets.data_ptr(), topology.corners.data_ptr(), out.data_ptr(), flag.data_ptr()
-    _call(positions, None, "am_decimate_quadrics", C.byref(a))
-    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
-    return out
+    return _decimate_quadrics("decimate_quadrics", "am_decimate_quadrics", L.AmDecimateQuadricsArgs(), positions, faces, topology, out, flag)
 
 
 def _decimate_edges(what: str, entry: str, a, positions, quadrics, faces, topology, edges, half_edge_to_edge, edge_count, out_positions,
@@ -1227,25 +1235,20 @@ def decimate_border_quadrics(positions: torch.Tensor, faces: torch.Tensor, topol
     the edge and perpendicular to its face, weighted border_weight * |edge|^2 (finite, >= 0), in the header's order.
     half_edge_to_edge (3 F,) and edge_count (E,) int32 are `mesh_topology.EdgeTables`'.  `flag` as in decimate_quadrics."""
     what = "decimate_border_quadrics"
-    V, dev = _positions(what, positions)
-    F = _decimate_mesh(what, faces, topology, V, dev)
-    border_weight = float(border_weight)
-    if not (math.isfinite(border_weight) and border_weight >= 0.0):
-        raise ValueError(f"{what}: border_weight {border_weight} is not finite and >= 0")
-    if not isinstance(edge_count, torch.Tensor) or edge_count.dim() != 1 or edge_count.numel() < 1:
-        raise ValueError(f"{what}: expected a non-empty (E,) edge_count, got {tuple(getattr(edge_count, 'shape', ()))}")
-    E = edge_count.numel()
     a = L.AmDecimateBorderQuadricsArgs()
-    a.n_edges, a.border_weight = E, border_weight
-    a.edge_count = _shaped(f"{what}: edge_count", edge_count, torch.int32, (E,), dev).data_ptr()
-    a.half_edge_to_edge = _shaped(f"{what}: half_edge_to_edge", half_edge_to_edge, torch.int32, (3 * F,), dev).data_ptr()
-    out = _out(f"{what}: out", out, (V, 10), torch.float64, dev)
-    flag, own = _flag_word(what, flag, dev)
-    a.positions, a.n_vertices, a.n_faces, a.faces = positions.data_ptr(), V, F, faces.data_ptr()
-    a.offsets, a.corners, a.out_quadrics, a.out_flag = topology.offsets.data_ptr(), topology.corners.data_ptr(), out.data_ptr(), flag.data_ptr()
-    _call(positions, None, "am_decimate_border_quadrics", C.byref(a))
-    _raise_own_flag(what, flag, own, _DECIMATE_FLAGS, V=V)
-    return out
+
+    def border_operands(F, dev):
+        weight = float(border_weight)
+        if not (math.isfinite(weight) and weight >= 0.0):
+            raise ValueError(f"{what}: border_weight {weight} is not finite and >= 0")
+        if not isinstance(edge_count, torch.Tensor) or edge_count.dim() != 1 or edge_count.numel() < 1:
+            raise ValueError(f"{what}: expected a non-empty (E,) edge_count, got {tuple(getattr(edge_count, 'shape', ()))}")
+        E = edge_count.numel()
+        a.n_edges, a.border_weight = E, weight
+        a.edge_count = _shaped(f"{what}: edge_count", edge_count, torch.int32, (E,), dev).data_ptr()
+        a.half_edge_to_edge = _shaped(f"{what}: half_edge_to_edge", half_edge_to_edge, torch.int32, (3 * F,), dev).data_ptr()
+
+    return _decimate_quadrics(what, "am_decimate_border_quadrics", a, positions, faces, topology, out, flag, border_operands)
 
 
 def decimate_border_edges(positions: torch.Tensor, quadrics: torch.Tensor, faces: torch.Tensor, topology, edges: torch.Tensor,

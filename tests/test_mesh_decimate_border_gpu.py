@@ -143,6 +143,28 @@ def test_closed_mesh_equals_the_fixed_mode_bit_for_bit(dev):
     assert fixed[3] == moved[3] and all(same_bits(a, b.cpu().numpy()) for a, b in zip(moved[:3], fixed[:3]))
 
 
+def test_closed_mesh_kernels_equal_the_fixed_mode_kernels_bit_for_bit(dev):
+    """Kernel by kernel what the loop test above shows end to end: without a border the two instantiations of the gather and of the edge
+    evaluation give the same bits, whatever the border weight."""
+    from actionmesh_amd import ops
+    v, f = R.icosphere(2)
+    assert f.shape[0] == 320
+    V = v.shape[0]
+    offsets, corners = R.np_topology(f.astype(np.int32), V)
+    edges, he2e, count = R.np_edges(f.astype(np.int32), V)
+    assert (count == 2).all()
+    pos, faces, edges, he2e, count = (torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+                                      for x in (v.astype(np.float64), f.astype(np.int32), edges, he2e, count))
+    topo = Topology(torch.from_numpy(offsets).to(dev), torch.from_numpy(corners).to(dev))
+    q = ops.decimate_quadrics(pos, faces, topo)
+    assert same_bits(ops.decimate_border_quadrics(pos, faces, topo, he2e, count, border_weight=0.37), q.cpu().numpy())
+    fixed = ops.decimate_edges(pos, q, faces, topo, edges, he2e, count)
+    moved = ops.decimate_border_edges(pos, q, faces, topo, edges, he2e, count)
+    for a, b in zip(moved, fixed):          # candidates, cost, key
+        assert same_bits(a, b.cpu().numpy())
+    assert (fixed[2] != R.NO_KEY).any()
+
+
 @pytest.mark.parametrize("what", ["offset out of order", "corner of another vertex", "edge with u > v", "half-edge entry out of range",
                                   "edge_count 0", "edge_count 7"])
 def test_corrupted_tables_raise_through_the_flag(dev, what):

@@ -154,7 +154,7 @@ def _worker(rank, world, port, q, cfg_groups=1, overlap=False):
             assert eng.local_calls == [i for i in range(cfg.num_layers) if eng.is_inflated(i)]
         _buf, v = gather_frames(v_local, plan, None)
         if rank == 0:
-            q.put(v)
+            q.put(v.numpy())            # by value: a queued tensor is a file descriptor the parent fetches from THIS process, gone by then
     finally:
         dist.destroy_process_group()
 
@@ -166,7 +166,7 @@ def _run_world(world, cfg_groups, overlap=False):
     procs = [ctxm.Process(target=_worker, args=(r, world, port, q, cfg_groups, overlap)) for r in range(world)]
     for p in procs:
         p.start()
-    v = q.get(timeout=240)
+    v = torch.from_numpy(q.get(timeout=240))
     for p in procs:
         p.join(60)
         assert p.exitcode == 0
@@ -264,7 +264,7 @@ def _denoiser_worker(rank, world, port, q):
         v2, cache2 = model.forward(x, ctx, fs, t, mask, cache)
         assert cache2 is cache and torch.equal(v, v2)
         if rank == 0:
-            q.put(v)
+            q.put(v.numpy())            # by value, as in _worker
     finally:
         dist.destroy_process_group()
 
@@ -278,7 +278,7 @@ def test_hipdenoiser_multirank_plumbing(world):
     procs = [ctxm.Process(target=_denoiser_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
-    v = q.get(timeout=240)
+    v = torch.from_numpy(q.get(timeout=240))
     for p in procs:
         p.join(60)
         assert p.exitcode == 0
@@ -341,7 +341,7 @@ def _sampler_worker(rank, world, port, q, cfg_parallel, split):
             lat = sched.denoise(model, cfgd, x[:1].clone(), ctx[1:2], device="cpu", mask=mask[:1], framestep=fs[:1])
             outs.append(lat.clone())
             ncoll.append((calls["all"], calls["bytes"]))
-        q.put((rank, outs[0], outs[1], ncoll))
+        q.put((rank, outs[0].numpy(), outs[1].numpy(), ncoll))         # by value, as in _worker
     finally:
         dist.destroy_process_group()
 
@@ -356,7 +356,7 @@ def test_sampler_keeps_latents_sharded_across_steps(world, cfg_parallel, split):
     procs = [ctxm.Process(target=_sampler_worker, args=(r, world, port, q, cfg_parallel, split)) for r in range(world)]
     for p in procs:
         p.start()
-    got = [q.get(timeout=500) for _ in range(world)]
+    got = [(rank, torch.from_numpy(a), torch.from_numpy(b), ncoll) for rank, a, b, ncoll in (q.get(timeout=500) for _ in range(world))]
     for p in procs:
         p.join(60)
         assert p.exitcode == 0
