@@ -4,24 +4,20 @@
 // lane of the search holds exactly one matched pair in registers when its loop ends: the sums are formed there.
 //
 //   icp_pairs_kernel   grid = (query blocks of direction 0 + query blocks of direction 1, 1, batch), 256 threads, one query each.
-//                      The inner loop is nn_search_kernel<float, 1>'s (am_pointcloud.hip, whose bits are pinned and which is left
-//                      alone): points staged through LDS in tiles of 512 as {x, y, z, 0}, all lanes read the same point (broadcast).
+//                      The search is am_points.h's staged scan, the one nn_search_kernel<float, 1> runs (am_pointcloud.hip).
 //                      Direction 0: queries x_i, points y_j.  Direction 1: queries y_j, points x_i, transformed while staged.
 //                      Lane 0 of the workgroup forms R in fp64 first (a few hundred fp64 operations beside 256 x n_points distances).
 //                      Epilogue: 13 fp64 terms per lane -> __shfl_down tree over the 64 lanes -> the 4 waves through LDS -> one
 //                      (13) partial per workgroup in the workspace.  No float atomics.
 //   icp_update_kernel  ONE workgroup: the partials summed in workgroup order, then one candidate per lane: loss, chain rule, Adam;
 //                      then the smallest loss of the batch against the stored best.
-#include "am_common.h"
+#include "am_points.h"
 
 namespace {
 
-constexpr int ICP_THREADS = 256;
+constexpr int ICP_THREADS = NN_THREADS;
 constexpr int ICP_WAVES = ICP_THREADS / 64;
-constexpr int ICP_TILE = 512;
 constexpr int ICP_TERMS = 13;
-
-struct IcpVec4 { float x, y, z, w; };
 
 // step 1's results: what the points need (R, with T and s beside it) and what the backward pass needs again
 struct IcpXf { float R[9], T[3], s[3]; };
@@ -71,40 +67,20 @@ __device__ __forceinline__ void icp_x(const IcpXf& f, float p0, float p1, float 
 // steps 3 and 4 for the query of this lane: its 13 terms (all zero for a lane past the last query or without a winner)
 template <int DIR>
 __device__ __forceinline__ bool icp_pair_terms(const float* __restrict__ pred, int64_t P, const float* __restrict__ gt, int64_t Q,
-                                               const IcpXf& f, IcpVec4* tile, int blk, double (&t)[ICP_TERMS]) {
-#pragma clang fp contract(off)
-  const float* qsrc = DIR == 0 ? pred : gt;
-  const float* psrc = DIR == 0 ? gt : pred;
+                                               const IcpXf& f, Vec4<float> (&tile)[NN_TILE], int blk, double (&t)[ICP_TERMS]) {
+  const float* __restrict__ qsrc = DIR == 0 ? pred : gt;
+  const float* __restrict__ psrc = DIR == 0 ? gt : pred;
   const int64_t NQ = DIR == 0 ? P : Q, NP = DIR == 0 ? Q : P;
   const int64_t q = (int64_t)blk * ICP_THREADS + threadIdx.x;
   const bool live = q < NQ;
   const int64_t qc = live ? q : NQ - 1;                 // clamp: the extra lanes redo the last query and contribute nothing
   const float a0 = qsrc[qc * 3 + 0], a1 = qsrc[qc * 3 + 1], a2 = qsrc[qc * 3 + 2];
-  float qx = a0, qy = a1, qz = a2;
-  if (DIR == 0) icp_x(f, a0, a1, a2, qx, qy, qz);
-  float best = INFINITY;
-  int32_t bi = -1;
-  for (int64_t base = 0; base < NP; base += ICP_TILE) {
-    const int n = (int)(NP - base < ICP_TILE ? NP - base : ICP_TILE);
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += ICP_THREADS) {
-      const float* s = psrc + (base + i) * 3;
-      float u0 = s[0], u1 = s[1], u2 = s[2];
-      if (DIR == 1) icp_x(f, s[0], s[1], s[2], u0, u1, u2);
-      tile[i] = IcpVec4{u0, u1, u2, 0.f};
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int i = 0; i < n; ++i) {
-      const IcpVec4 p = tile[i];
-      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-      const float d2 = (dx * dx + dy * dy) + dz * dz;
-      if (d2 < best) {          // strict: the first (lowest-index) minimum wins; NaN and +inf never do
-        best = d2;
-        bi = (int32_t)(base + i);
-      }
-    }
-  }
+  float qx[1] = {a0}, qy[1] = {a1}, qz[1] = {a2};
+  if (DIR == 0) icp_x(f, a0, a1, a2, qx[0], qy[0], qz[0]);
+  float best[1] = {INFINITY};
+  int32_t win[1] = {-1};
+  scan_staged<float, 1>(psrc, 0, NP, [&f](float& x, float& y, float& z) { if (DIR == 1) icp_x(f, x, y, z, x, y, z); }, tile, qx, qy, qz, best, win);
+  const int32_t bi = win[0];
 #pragma unroll
   for (int k = 0; k < ICP_TERMS; ++k) t[k] = 0.0;
   if (!live) return false;
@@ -112,7 +88,7 @@ __device__ __forceinline__ bool icp_pair_terms(const float* __restrict__ pred, i
   float p[3], x[3], y[3];
   if (DIR == 0) {
     p[0] = a0, p[1] = a1, p[2] = a2;
-    x[0] = qx, x[1] = qy, x[2] = qz;
+    x[0] = qx[0], x[1] = qy[0], x[2] = qz[0];
     for (int j = 0; j < 3; ++j) y[j] = gt[(int64_t)bi * 3 + j];
   } else {
     y[0] = a0, y[1] = a1, y[2] = a2;
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_pairs_kernel(const float* __r
                                                                 int64_t Q, const float* __restrict__ rot_init,
                                                                 const float* __restrict__ params, int nblk0, int nblk1,
                                                                 double* __restrict__ part, int32_t* __restrict__ out_flag) {
-  __shared__ IcpVec4 tile[ICP_TILE];
+  __shared__ Vec4<float> tile[NN_TILE];
   __shared__ IcpXf s_xf;
   __shared__ double red[ICP_WAVES][ICP_TERMS];
   const int b = blockIdx.z;
@@ -296,17 +272,10 @@ IcpPlan icp_plan(int64_t P, int64_t Q, int batch) {
   return pl;
 }
 
-bool icp_sizes_ok(int64_t P, int64_t Q, int batch) {
-  return P >= 1 && Q >= 1 && batch >= 1 && P < (int64_t)1 << 31 && Q < (int64_t)1 << 31 && batch <= 65535;
-}
-
 int icp_check(const am_icp_args* a) {
   AM_CHECK(a != nullptr, "am_icp_step: null arguments");
-  AM_CHECK(a->batch >= 1 && a->n_pred >= 1 && a->n_gt >= 1, "am_icp_step: empty problem (batch %d, %lld pred points, %lld gt points)",
-           a->batch, (long long)a->n_pred, (long long)a->n_gt);
-  AM_CHECK(a->n_pred < (int64_t)1 << 31 && a->n_gt < (int64_t)1 << 31, "am_icp_step: %lld / %lld points do not fit a 32-bit index",
-           (long long)a->n_pred, (long long)a->n_gt);
-  AM_CHECK(a->batch <= 65535, "am_icp_step: batch %d exceeds the grid's z extent", a->batch);
+  AM_TRY(check_cloud("am_icp_step", a->batch, a->n_pred, "pred points", 'z'));
+  AM_TRY(check_cloud("am_icp_step", a->batch, a->n_gt, "gt points", 'z'));
   AM_CHECK(a->pred && a->gt && a->rot_init && a->params && a->adam_m && a->adam_v && a->best && a->out_loss && a->out_rot && a->out_flag,
            "am_icp_step: null pointer");
   AM_CHECK(!a->update || (a->bias_correction1 > 0.0 && a->bias_correction2 > 0.0),
@@ -318,14 +287,13 @@ int icp_check(const am_icp_args* a) {
 }  // namespace
 
 extern "C" size_t am_icp_workspace_bytes(int64_t n_pred, int64_t n_gt, int batch) {
-  return icp_sizes_ok(n_pred, n_gt, batch) ? icp_plan(n_pred, n_gt, batch).bytes : 0;
+  return cloud_ok(batch, n_pred) && cloud_ok(batch, n_gt) && batch <= 65535 ? icp_plan(n_pred, n_gt, batch).bytes : 0;
 }
 
 extern "C" int am_icp_step(const am_icp_args* a, void* workspace_dev, size_t workspace_bytes, void* stream) {
   AM_TRY(icp_check(a));
   const IcpPlan pl = icp_plan(a->n_pred, a->n_gt, a->batch);
-  AM_CHECK(workspace_dev != nullptr && workspace_bytes >= pl.bytes, "am_icp_step: workspace of %zu bytes needed, %zu given", pl.bytes,
-           workspace_dev ? workspace_bytes : (size_t)0);
+  AM_TRY(check_workspace("am_icp_step", workspace_dev, workspace_bytes, pl.bytes));
   AM_CHECK((uintptr_t)workspace_dev % 8 == 0 && (uintptr_t)a->out_sums % 8 == 0 && (uintptr_t)a->out_grad % 8 == 0,
            "am_icp_step: the workspace, out_sums and out_grad must be 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;

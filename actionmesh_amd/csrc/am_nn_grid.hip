@@ -20,7 +20,7 @@
 //     of cells along x is ONE range of the sorted copy, so a ring is scanned as (2r + 1)^2 rows: full rows on the shell's four
 //     faces, the two end cells elsewhere.  Each range is two cell_start loads, compared with 0 <= begin <= end <= n_points before
 //     any record is loaded, then 16-byte loads of the records.
-#include "am_common.h"
+#include "am_points.h"
 
 namespace {
 
@@ -34,28 +34,25 @@ __device__ __forceinline__ uint32_t fmap(float f) {
   return (u >> 31) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float funmap(uint32_t u) { return __uint_as_float((u >> 31) ? (u & 0x7fffffffu) : ~u); }
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
+// the header's clamped cell along one axis (step 2 of the search), of a point and of a query alike: only an in-range t is converted
+__device__ __forceinline__ int cell_axis(float v, float lo, float inv, int G) {
+  int c = 0;
+  if (inv != 0.f) {
+    const float d = v - lo;
+    const float t = d * inv;
+    if (t >= (float)G)
+      c = G - 1;
+    else if (t >= 0.f)
+      c = (int)floorf(t);
+  }
+  return c;
+}
 // the header's cell of a point: the extra cell `ncell` for a non-finite one
 __device__ __forceinline__ int cell_of(float x, float y, float z, const float* __restrict__ frame, int G, int ncell) {
-#pragma clang fp contract(off)
   if (!finite3(x, y, z)) return ncell;
-  const float p[3] = {x, y, z};
-  int c[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float inv = frame[4 + k];
-    if (inv == 0.f) {
-      c[k] = 0;
-    } else {
-      const float d = p[k] - frame[k];
-      const float t = d * inv;
-      const int f = (int)floorf(t);
-      c[k] = f < G - 1 ? f : G - 1;
-      if (c[k] < 0) c[k] = 0;             // unreachable for a frame this library wrote (p_k >= lo_k); keeps a foreign frame in range
-    }
-  }
-  return (c[2] * G + c[1]) * G + c[0];
+  const int c0 = cell_axis(x, frame[0], frame[4], G), c1 = cell_axis(y, frame[1], frame[5], G), c2 = cell_axis(z, frame[2], frame[6], G);
+  return (c2 * G + c1) * G + c0;
 }
 
 // extrema words of the workspace: [min: batch x 4][max: batch x 4][slab min: batch x 3 x G][slab max: batch x 3 x G][cells: batch x P]
@@ -204,11 +201,7 @@ __global__ __launch_bounds__(GRID_THREADS) void grid_start_kernel(int64_t P, int
   }
 }
 
-template <typename T>
-struct Best {
-  T d2;
-  int32_t index;
-};
+template <typename T> struct Best { T d2; int32_t index; };
 
 // the records of cells first .. last (one row along x): false, with the flag raised, when the range is not inside the sorted copy
 template <typename T>
@@ -227,12 +220,7 @@ __device__ __forceinline__ bool scan_cells(const int32_t* __restrict__ cs, const
       atomicOr(flag, AM_NN_GRID_BAD_INDEX);
       continue;
     }
-    const T dx = qx - (T)p.x, dy = qy - (T)p.y, dz = qz - (T)p.z;
-    const T d2 = (dx * dx + dy * dy) + dz * dz;
-    if (d2 < best.d2 || (d2 == best.d2 && idx < best.index)) {
-      best.d2 = d2;
-      best.index = idx;
-    }
+    take_any_order(best.d2, best.index, dist2(qx, qy, qz, (T)p.x, (T)p.y, (T)p.z), idx);
   }
   return true;
 }
@@ -267,18 +255,7 @@ __global__ __launch_bounds__(GRID_THREADS) void grid_search_kernel(am_nn_grid g,
     if (finite3(qf[0], qf[1], qf[2])) {
       int c[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float inv = frame[4 + k];
-        c[k] = 0;
-        if (inv != 0.f) {
-          const float d = qf[k] - frame[k];
-          const float t = d * inv;
-          if (t >= (float)G)
-            c[k] = G - 1;
-          else if (t >= 0.f)
-            c[k] = (int)floorf(t);
-        }
-      }
+      for (int k = 0; k < 3; ++k) c[k] = cell_axis(qf[k], frame[k], frame[4 + k], G);
       const T q[3] = {(T)qf[0], (T)qf[1], (T)qf[2]};
       bool ok = true;
       for (int r = 0; r < G && ok; ++r) {                                  // at most G rings
@@ -323,9 +300,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 int grid_check(const char* who, const am_nn_grid* g, bool building) {
   AM_CHECK(g->cells >= 1 && g->cells <= AM_NN_GRID_MAX_CELLS, "%s: %d cells per axis outside 1 .. %d", who, g->cells, AM_NN_GRID_MAX_CELLS);
-  AM_CHECK(g->batch >= 1 && g->n_points >= 1, "%s: empty problem (batch %d, %lld points)", who, g->batch, (long long)g->n_points);
-  AM_CHECK(g->n_points < (int64_t)1 << 31, "%s: %lld points do not fit a 32-bit index", who, (long long)g->n_points);
-  AM_CHECK(g->batch <= 65535, "%s: batch %d exceeds the grid's y extent", who, g->batch);
+  AM_TRY(check_cloud(who, g->batch, g->n_points, "points", 'y'));
   AM_CHECK(g->frame && g->slabs && g->cell_start && g->sorted && (g->order || !building), "%s: null grid pointer", who);
   AM_CHECK(aligned16(g->frame) && aligned16(g->slabs) && aligned16(g->cell_start) && aligned16(g->order) && aligned16(g->sorted),
            "%s: the grid's arrays must be 16-byte aligned", who);
@@ -338,9 +313,7 @@ int build_check(const char* who, const am_nn_grid_build_args* a) {
   AM_CHECK(a->points != nullptr, "%s: null pointer", who);
   AM_CHECK(a->points_bstride == 0 || a->points_bstride >= 3 * a->grid.n_points, "%s: batch stride %lld below 3 * %lld points", who,
            (long long)a->points_bstride, (long long)a->grid.n_points);
-  const size_t need = am_nn_grid_workspace_bytes(a->grid.n_points, a->grid.batch, a->grid.cells);
-  AM_CHECK(a->workspace != nullptr && a->workspace_bytes >= need, "%s: workspace of %zu bytes needed, %zu given", who, need,
-           (size_t)a->workspace_bytes);
+  AM_TRY(check_workspace(who, a->workspace, (size_t)a->workspace_bytes, am_nn_grid_workspace_bytes(a->grid.n_points, a->grid.batch, a->grid.cells)));
   AM_CHECK(aligned16(a->workspace), "%s: the workspace must be 16-byte aligned", who);
   return AM_OK;
 }
@@ -357,14 +330,14 @@ void search_launch(const am_nn_grid_search_args* a, hipStream_t st) {
 }  // namespace
 
 extern "C" size_t am_nn_grid_bytes(int64_t n_points, int batch, int cells) {
-  if (n_points < 1 || n_points >= (int64_t)1 << 31 || batch < 1 || cells < 1 || cells > AM_NN_GRID_MAX_CELLS) return 0;
+  if (!cloud_ok(batch, n_points) || cells < 1 || cells > AM_NN_GRID_MAX_CELLS) return 0;
   const size_t B = (size_t)batch, P = (size_t)n_points, G = (size_t)cells;
   return pad16(B * 8 * sizeof(float)) + pad16(B * 6 * G * sizeof(float)) + pad16(B * (G * G * G + 2) * sizeof(int32_t)) +
          pad16(B * P * sizeof(int32_t)) + pad16(B * P * 4 * sizeof(float));
 }
 
 extern "C" size_t am_nn_grid_workspace_bytes(int64_t n_points, int batch, int cells) {
-  if (n_points < 1 || n_points >= (int64_t)1 << 31 || batch < 1 || cells < 1 || cells > AM_NN_GRID_MAX_CELLS) return 0;
+  if (!cloud_ok(batch, n_points) || cells < 1 || cells > AM_NN_GRID_MAX_CELLS) return 0;
   return pad16(sizeof(uint32_t) * (size_t)batch * (8 + 6 * (size_t)cells)) + pad16(sizeof(int32_t) * (size_t)batch * (size_t)n_points);
 }
 
@@ -407,9 +380,7 @@ extern "C" int am_nn_grid_build(const am_nn_grid_build_args* a, void* stream) {
 extern "C" int am_nn_grid_search(const am_nn_grid_search_args* a, void* stream) {
   AM_CHECK(a != nullptr, "am_nn_grid_search: null arguments");
   AM_TRY(grid_check("am_nn_grid_search", &a->grid, false));
-  AM_CHECK(a->batch >= 1 && a->n_queries >= 1, "am_nn_grid_search: empty problem (batch %d, %lld queries)", a->batch,
-           (long long)a->n_queries);
-  AM_CHECK(a->n_queries < (int64_t)1 << 31, "am_nn_grid_search: %lld queries do not fit a 32-bit index", (long long)a->n_queries);
+  AM_TRY(check_cloud("am_nn_grid_search", a->batch, a->n_queries, "queries", 0));       // one lane per query: the batch is no grid axis
   AM_CHECK(a->grid.batch == a->batch || a->grid.batch == 1, "am_nn_grid_search: %d grids for a batch of %d (one shared grid or one each)",
            a->grid.batch, a->batch);
   AM_CHECK(a->queries && a->out_index && a->out_d2 && a->out_flag, "am_nn_grid_search: null pointer");

@@ -4,28 +4,20 @@
 // pointer chasing, which is the wrong trade on 256 CUs - 100 000 x 100 000 pairs are 1.2e11 fp64 lane-operations, a few ms.
 //
 //   grid = (query blocks, point splits, batch); block = 256 threads x QPT queries each, held in registers.
-//   A block walks its split of the points in tiles of TILE, staged once into LDS as {x, y, z, 0} in the compute type
-//   (the float -> double conversion is paid per tile, not per pair); all lanes read the same point (LDS broadcast).
-//   d2 = ((dx*dx) + (dy*dy)) + dz*dz with contraction OFF: the summation of cKDTree (and of the numpy oracle), so the
-//   fp64 result is bit-identical to the reference's; ties keep the lowest point index.
+//   A block walks its split of the points with am_points.h's staged scan; the distance (the summation of cKDTree, so the
+//   fp64 result is bit-identical to the reference's) and the tie rule (the lowest point index) are stated there.
 //   With more than one split the partial (d2, index) pairs go to a workspace and nn_reduce_kernel takes the minimum
 //   (lowest split first, so the tie rule survives).
 // precise = 1: fp64 arithmetic, d2 out as double (metrics).  precise = 0: fp32 (the ICP inner loop, 4800 searches).
-#include "am_common.h"
+#include "am_points.h"
 
 namespace {
-
-constexpr int NN_THREADS = 256;
-constexpr int NN_TILE = 512;
-
-template <typename T> struct Vec4 { T x, y, z, w; };
 
 template <typename T, int QPT>
 __global__ __launch_bounds__(NN_THREADS) void nn_search_kernel(const float* __restrict__ pts, int64_t P, int64_t p_bstride,
                                                                const float* __restrict__ qry, int64_t Q, int64_t q_bstride,
                                                                int64_t chunk, int nsplit, T* __restrict__ out_d2,
                                                                int32_t* __restrict__ out_idx) {
-#pragma clang fp contract(off)
   __shared__ Vec4<T> tile[NN_TILE];
   const int b = blockIdx.z, split = blockIdx.y;
   pts += (int64_t)b * p_bstride;
@@ -35,37 +27,12 @@ __global__ __launch_bounds__(NN_THREADS) void nn_search_kernel(const float* __re
   int32_t bi[QPT];
 #pragma unroll
   for (int j = 0; j < QPT; ++j) {
-    const int64_t q = q0 + j < Q ? q0 + j : Q - 1;      // clamp: the extra lanes redo the last query and do not store
-    qx[j] = (T)qry[q * 3 + 0];
-    qy[j] = (T)qry[q * 3 + 1];
-    qz[j] = (T)qry[q * 3 + 2];
-    best[j] = (T)INFINITY;
-    bi[j] = -1;
+    const int64_t qi = q0 + j < Q ? q0 + j : Q - 1;      // clamp: the extra lanes redo the last query and do not store
+    qx[j] = (T)qry[qi * 3 + 0], qy[j] = (T)qry[qi * 3 + 1], qz[j] = (T)qry[qi * 3 + 2];
+    best[j] = (T)INFINITY, bi[j] = -1;
   }
   const int64_t p_lo = (int64_t)split * chunk;
-  const int64_t p_hi = p_lo + chunk < P ? p_lo + chunk : P;
-  for (int64_t base = p_lo; base < p_hi; base += NN_TILE) {
-    const int n = (int)(p_hi - base < NN_TILE ? p_hi - base : NN_TILE);
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += NN_THREADS) {
-      const float* s = pts + (base + i) * 3;
-      tile[i] = Vec4<T>{(T)s[0], (T)s[1], (T)s[2], (T)0};
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int i = 0; i < n; ++i) {
-      const Vec4<T> p = tile[i];
-#pragma unroll
-      for (int j = 0; j < QPT; ++j) {
-        const T dx = qx[j] - p.x, dy = qy[j] - p.y, dz = qz[j] - p.z;
-        const T d2 = (dx * dx + dy * dy) + dz * dz;
-        if (d2 < best[j]) {          // strict: the first (lowest-index) minimum wins
-          best[j] = d2;
-          bi[j] = (int32_t)(base + i);
-        }
-      }
-    }
-  }
+  scan_staged<T, QPT>(pts, p_lo, p_lo + chunk < P ? p_lo + chunk : P, StageAsIs{}, tile, qx, qy, qz, best, bi);
   const int64_t o = ((int64_t)b * nsplit + split) * Q;
 #pragma unroll
   for (int j = 0; j < QPT; ++j)
@@ -82,16 +49,11 @@ __global__ void nn_reduce_kernel(const T* __restrict__ part_d2, const int32_t* _
   const int b = blockIdx.y;
   if (q >= Q) return;
   T best = (T)INFINITY;
-  int32_t bi = -1;
-  for (int s = 0; s < nsplit; ++s) {
-    const T d = part_d2[((int64_t)b * nsplit + s) * Q + q];
-    if (d < best) {
-      best = d;
-      bi = part_idx[((int64_t)b * nsplit + s) * Q + q];
-    }
-  }
+  int32_t win = -1;
+  for (int s = 0; s < nsplit; ++s)              // ascending splits hold ascending indices: the rule picks the split, its index is read once
+    take_ascending(best, win, part_d2[((int64_t)b * nsplit + s) * Q + q], (int32_t)s);
   out_d2[(int64_t)b * Q + q] = best;
-  out_idx[(int64_t)b * Q + q] = bi;
+  out_idx[(int64_t)b * Q + q] = win < 0 ? -1 : part_idx[((int64_t)b * nsplit + win) * Q + q];
 }
 
 struct NnPlan { int qpt, qblocks, nsplit; int64_t chunk; };
@@ -136,10 +98,8 @@ int nn_launch(const am_nn_args* a, const NnPlan& pl, void* ws, hipStream_t st) {
 
 int nn_check(const am_nn_args* a) {
   AM_CHECK(a != nullptr, "am_nn_search: null arguments");
-  AM_CHECK(a->batch >= 1 && a->n_points >= 1 && a->n_queries >= 1, "am_nn_search: empty problem (batch %d, %lld points, %lld queries)",
-           a->batch, (long long)a->n_points, (long long)a->n_queries);
-  AM_CHECK(a->n_points < (int64_t)1 << 31, "am_nn_search: %lld points do not fit a 32-bit index", (long long)a->n_points);
-  AM_CHECK(a->batch <= 65535, "am_nn_search: batch %d exceeds the grid's z extent", a->batch);
+  AM_CHECK(a->n_queries >= 1, "am_nn_search: empty problem (%lld queries)", (long long)a->n_queries);
+  AM_TRY(check_cloud("am_nn_search", a->batch, a->n_points, "points", 'z'));
   AM_CHECK(a->points && a->queries && a->out_d2 && a->out_index, "am_nn_search: null pointer");
   return AM_OK;
 }
@@ -157,8 +117,7 @@ extern "C" int am_nn_search(const am_nn_args* a, void* workspace_dev, size_t wor
   AM_TRY(nn_check(a));
   const NnPlan pl = nn_plan(a->n_points, a->n_queries, a->batch);
   const size_t need = am_nn_workspace_bytes(a->n_points, a->n_queries, a->batch, a->precise);
-  AM_CHECK(need == 0 || (workspace_dev != nullptr && workspace_bytes >= need), "am_nn_search: workspace of %zu bytes needed, %zu given",
-           need, workspace_bytes);
+  AM_TRY(check_workspace("am_nn_search", workspace_dev, workspace_bytes, need));
   return a->precise ? nn_launch<double>(a, pl, workspace_dev, (hipStream_t)stream)
                     : nn_launch<float>(a, pl, workspace_dev, (hipStream_t)stream);
 }

@@ -472,6 +472,46 @@ def flow_step(v: torch.Tensor, latents: torch.Tensor, scales: Sequence[float], d
 NO_NEIGHBOUR_TEXT = "nearest_neighbors: a query has no finite distance to any point (NaN / inf coordinates in the inputs)"
 
 
+def _cloud(who: str, t: torch.Tensor, name: str, dims=(2, 3)) -> int:
+    """The check every cloud of the point searches passes: a contiguous fp32 device tensor (n, 3) - or (B, n, 3) where `dims` allows it -
+    that is not empty (no points, or a batch of 0).  Returns n."""
+    _need(t, torch.float32, name)
+    if t.dim() not in dims or t.shape[-1] != 3:
+        raise ValueError(f"{who}: expected (..., n, 3) {name}, got {tuple(t.shape)}")
+    if 0 in t.shape:
+        raise ValueError(f"{who}: empty point cloud")
+    return t.shape[-2]
+
+
+def _nn_outputs(who: str, queries: torch.Tensor, point_batch: Optional[int], precise: bool):
+    """(batch, index int32, d2) of a search: `point_batch` is the points' (or the grid's) batch, None when one cloud serves every
+    batch entry.  A 3-D operand sets the batch and the outputs are (batch, Q); with none they are (Q,)."""
+    batch = queries.shape[0] if queries.dim() == 3 else None
+    if point_batch is not None and batch not in (None, point_batch):
+        raise ValueError(f"{who}: points batch {point_batch} != queries batch {batch}")
+    batch = point_batch if batch is None else batch
+    shape = (queries.shape[-2],) if batch is None else (batch, queries.shape[-2])
+    return (1 if batch is None else batch, torch.empty(shape, dtype=torch.int32, device=queries.device),
+            torch.empty(shape, dtype=torch.float64 if precise else torch.float32, device=queries.device))
+
+
+def _nn_valid(flags: Sequence[torch.Tensor], indices: Sequence[torch.Tensor]) -> None:
+    """The check behind the searches, ONE device-to-host read for any number of grid flag words and index tensors: a raised flag or an
+    index -1 - the kernels' candidate rules never take a NaN distance, and -1 would wrap in a later gather - is an error.  Every raised
+    flag is consumed and named by the one error, so none is left to fire on a later check."""
+    words = [f.view(1) for f in flags] + [(i < 0).any().view(1) for i in indices]
+    got = (words[0] if len(words) == 1 else torch.cat(words)).tolist() if words else []      # one word: no launch beside its own
+    bits = 0
+    for f, word in zip(flags, got):
+        if word:
+            f.zero_()
+            bits |= word
+    if bits:
+        raise ValueError(f"nn_grid_search: bad grid ({', '.join(t for b, t in _NN_GRID_FLAGS.items() if bits & b)})")
+    if any(got[len(flags):]):
+        raise ValueError(NO_NEIGHBOUR_TEXT)
+
+
 def nearest_neighbors(points: torch.Tensor, queries: torch.Tensor, precise: bool = True,
                       check: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """am_nn_search: for every query its nearest point (exact, brute force).  points (P, 3) or (B, P, 3) fp32, queries
@@ -481,19 +521,8 @@ def nearest_neighbors(points: torch.Tensor, queries: torch.Tensor, precise: bool
     `check` (default): one device-to-host read behind the search that turns "no finite distance" (index -1) into an error.
     Callers inside a loop of searches (the ICP: 4800 of them) pass check=False and validate once per batch instead
     (`nn_indices_valid`), so the stream is not serialised per search."""
-    _need(points, torch.float32, "points"); _need(queries, torch.float32, "queries")
-    if points.shape[-1] != 3 or queries.shape[-1] != 3 or points.dim() not in (2, 3) or queries.dim() not in (2, 3):
-        raise ValueError(f"nearest_neighbors: expected (..., n, 3) operands, got {tuple(points.shape)} / {tuple(queries.shape)}")
-    batch = max(points.shape[0] if points.dim() == 3 else 1, queries.shape[0] if queries.dim() == 3 else 1)
-    for name, t in (("points", points), ("queries", queries)):
-        if t.dim() == 3 and t.shape[0] != batch:
-            raise ValueError(f"nearest_neighbors: {name} batch {t.shape[0]} != {batch}")
-    P, Q = points.shape[-2], queries.shape[-2]
-    if P == 0 or Q == 0:
-        raise ValueError("nearest_neighbors: empty point cloud")
-    out_shape = (batch, Q) if (points.dim() == 3 or queries.dim() == 3) else (Q,)
-    idx = torch.empty(out_shape, dtype=torch.int32, device=queries.device)
-    d2 = torch.empty(out_shape, dtype=torch.float64 if precise else torch.float32, device=queries.device)
+    P, Q = _cloud("nearest_neighbors", points, "points"), _cloud("nearest_neighbors", queries, "queries")
+    batch, idx, d2 = _nn_outputs("nearest_neighbors", queries, points.shape[0] if points.dim() == 3 else None, precise)
     ws, need = _workspace(queries.device, "am_nn_workspace_bytes", P, Q, batch, 1 if precise else 0, at_least=1)
     a = L.AmNnArgs()
     a.points, a.n_points, a.points_bstride = points.data_ptr(), P, (P * 3 if points.dim() == 3 else 0)
@@ -501,20 +530,14 @@ def nearest_neighbors(points: torch.Tensor, queries: torch.Tensor, precise: bool
     a.batch, a.precise = batch, 1 if precise else 0
     a.out_index, a.out_d2 = idx.data_ptr(), d2.data_ptr()
     _call(queries, None, "am_nn_search", C.byref(a), ws.data_ptr(), need)
-    if check and bool((idx < 0).any()):
-        # the kernel's strict `<` never fires for a query whose distances are all NaN: index -1 would wrap in a later gather
-        raise ValueError(NO_NEIGHBOUR_TEXT)
+    if check:
+        _nn_valid((), (idx,))
     return idx, d2
 
 
 def nn_indices_valid(*indices: torch.Tensor) -> None:
     """The deferred form of nearest_neighbors' check: ONE device-to-host read for any number of index tensors."""
-    bad = None
-    for i in indices:
-        b = (i < 0).any()
-        bad = b if bad is None else (bad | b)
-    if bad is not None and bool(bad):
-        raise ValueError(NO_NEIGHBOUR_TEXT)
+    _nn_valid((), indices)
 
 
 class IcpState:
@@ -548,12 +571,8 @@ def icp_step(state: IcpState, pred: torch.Tensor, gt: torch.Tensor, rot_init: to
     fp32, in place on `state`; no device-to-host read.  `update=False` computes the outputs and leaves params, adam_m, adam_v and best
     as they are.  `return_sums` also fills state.out_sums and state.out_grad (fp64).  state.out_flag collects L.ICP_NO_NEIGHBOUR over
     the steps: the caller reads it when it likes."""
-    _need(pred, torch.float32, "pred"); _need(gt, torch.float32, "gt"); _need(rot_init, torch.float32, "rot_init")
-    if pred.dim() != 2 or gt.dim() != 2 or pred.shape[1] != 3 or gt.shape[1] != 3:
-        raise ValueError(f"icp_step: expected (P, 3) and (Q, 3) clouds, got {tuple(pred.shape)} / {tuple(gt.shape)}")
-    P, Q, B = pred.shape[0], gt.shape[0], state.batch
-    if P == 0 or Q == 0:
-        raise ValueError("icp_step: empty point cloud")
+    P, Q, B = _cloud("icp_step", pred, "pred", dims=(2,)), _cloud("icp_step", gt, "gt", dims=(2,)), state.batch
+    _need(rot_init, torch.float32, "rot_init")
     if tuple(rot_init.shape) not in ((B, 3, 3), (B, 9)):
         raise ValueError(f"icp_step: rot_init {tuple(rot_init.shape)} does not hold the state's {B} candidates")
     if int(t) < 1:
@@ -641,11 +660,6 @@ _NN_GRID_FLAGS = {L.NN_GRID_BAD_ORDER: "an order entry outside the points", L.NN
                   L.NN_GRID_BAD_INDEX: "a sorted record with an index outside the points", L.NN_GRID_BAD_QUERY_ORDER: "a query_order entry outside the queries"}
 
 
-def _nn_grid_raise(flag: int, who: str) -> None:
-    if flag:
-        raise ValueError(f"{who}: bad grid ({', '.join(t for b, t in _NN_GRID_FLAGS.items() if flag & b)})")
-
-
 def nn_grid_default_cells(n_points: int) -> int:
     """G = clamp(ceil(cbrt(2 P)), 1, 128): about half a point per cell (tools/nn_grid_timing.py sweeps it)."""
     g = max(1, int(round((2.0 * n_points) ** (1.0 / 3.0))))
@@ -658,12 +672,7 @@ def nn_grid_default_cells(n_points: int) -> int:
 
 def nn_grid_build(points: torch.Tensor, cells: Optional[int] = None) -> NnGrid:
     """am_nn_grid_cells + a stable torch sort + am_nn_grid_build: the grid of points (P, 3) - one shared grid - or (B, P, 3) fp32."""
-    _need(points, torch.float32, "points")
-    if points.shape[-1] != 3 or points.dim() not in (2, 3):
-        raise ValueError(f"nn_grid_build: expected (P, 3) or (B, P, 3) points, got {tuple(points.shape)}")
-    P = points.shape[-2]
-    if P == 0:
-        raise ValueError("nn_grid_build: empty point cloud")
+    P = _cloud("nn_grid_build", points, "points")
     batch = points.shape[0] if points.dim() == 3 else 1
     G = nn_grid_default_cells(P) if cells is None else int(cells)
     if not 1 <= G <= L.NN_GRID_MAX_CELLS:
@@ -687,20 +696,10 @@ def nn_grid_search(grid: NnGrid, queries: torch.Tensor, precise: bool = True, qu
     fp32; a batched grid needs the same B (2-D queries are then shared).  `query_order`: int32 (Q,) or (B, Q), a permutation of the
     queries - the order in which lanes pick them (the query cloud's own NnGrid.order makes a wave share cells); results stay at the
     query's own position.  `check` as in nearest_neighbors; with check=False the kernel's flag is kept in grid.flags for nn_grid_valid."""
-    _need(queries, torch.float32, "queries")
-    if queries.shape[-1] != 3 or queries.dim() not in (2, 3):
-        raise ValueError(f"nn_grid_search: expected (Q, 3) or (B, Q, 3) queries, got {tuple(queries.shape)}")
+    Q = _cloud("nn_grid_search", queries, "queries")
     if queries.device != grid.device:
         raise ValueError("nn_grid_search: the queries and the grid are on different devices")
-    Q = queries.shape[-2]
-    if Q == 0:
-        raise ValueError("nn_grid_search: empty point cloud")
-    batch = max(1 if grid.shared else grid.batch, queries.shape[0] if queries.dim() == 3 else 1)
-    if (not grid.shared and grid.batch != batch) or (queries.dim() == 3 and queries.shape[0] != batch):
-        raise ValueError(f"nn_grid_search: grid batch {grid.batch} / queries {tuple(queries.shape)} do not make a batch of {batch}")
-    out_shape = (batch, Q) if (not grid.shared or queries.dim() == 3) else (Q,)
-    idx = torch.empty(out_shape, dtype=torch.int32, device=queries.device)
-    d2 = torch.empty(out_shape, dtype=torch.float64 if precise else torch.float32, device=queries.device)
+    batch, idx, d2 = _nn_outputs("nn_grid_search", queries, None if grid.shared else grid.batch, precise)
     flag = torch.empty((1,), dtype=torch.int32, device=queries.device)
     a = L.AmNnGridSearchArgs()
     a.grid = grid.struct()
@@ -714,10 +713,7 @@ def nn_grid_search(grid: NnGrid, queries: torch.Tensor, precise: bool = True, qu
     a.out_index, a.out_d2, a.out_flag = idx.data_ptr(), d2.data_ptr(), flag.data_ptr()
     _call(queries, None, "am_nn_grid_search", C.byref(a))
     if check:
-        bad = torch.stack(((idx < 0).any().to(torch.int32), flag[0])).tolist()
-        _nn_grid_raise(bad[1], "nn_grid_search")
-        if bad[0]:
-            raise ValueError(NO_NEIGHBOUR_TEXT)
+        _nn_valid((flag,), (idx,))
     else:
         grid.flags |= flag
     return idx, d2
@@ -725,25 +721,13 @@ def nn_grid_search(grid: NnGrid, queries: torch.Tensor, precise: bool = True, qu
 
 def nn_grid_valid(grids: Sequence[NnGrid], *indices: torch.Tensor) -> None:
     """The deferred check of check=False grid searches: ONE device-to-host read for the flags of `grids` and any number of index tensors."""
-    words = [g.flags[0] for g in grids] + [(i < 0).any().to(torch.int32) for i in indices]
-    got = torch.stack(words).tolist()
-    for g, f in zip(grids, got):
-        g.flags.zero_()
-        _nn_grid_raise(f, "nn_grid_search")
-    if any(got[len(grids):]):
-        raise ValueError(NO_NEIGHBOUR_TEXT)
+    _nn_valid([g.flags for g in grids], indices)
 
 
 def nearest_neighbors_grid(points: torch.Tensor, queries: torch.Tensor, precise: bool = True,
                            check: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-    """nearest_neighbors through a grid built for the call (default cells): the same operands, return types, bits and errors."""
-    _need(points, torch.float32, "points"); _need(queries, torch.float32, "queries")
-    if points.shape[-1] != 3 or queries.shape[-1] != 3 or points.dim() not in (2, 3) or queries.dim() not in (2, 3):
-        raise ValueError(f"nearest_neighbors: expected (..., n, 3) operands, got {tuple(points.shape)} / {tuple(queries.shape)}")
-    if points.dim() == 3 and queries.dim() == 3 and points.shape[0] != queries.shape[0]:
-        raise ValueError(f"nearest_neighbors: points batch {points.shape[0]} != {queries.shape[0]}")
-    if points.shape[-2] == 0 or queries.shape[-2] == 0:
-        raise ValueError("nearest_neighbors: empty point cloud")
+    """nearest_neighbors through a grid built for the call (default cells): the same operands, return types, bits and exception types
+    (the shape and batch errors are nn_grid_build's and nn_grid_search's, and name them)."""
     return nn_grid_search(nn_grid_build(points), queries, precise=precise, check=check)
 
 

@@ -463,8 +463,9 @@ int am_nn_search(const am_nn_args* args, void* workspace_dev, size_t workspace_b
  *               over the points whose three coordinates are all finite, in the total order of the IEEE bit patterns (-0 below +0);
  *               no such point: lo = 0, inv = 0.  inv_k = fl(G / fl(hi_k - lo_k)); when the extent is 0 or that quotient is not
  *               finite, inv_k = 0.
- *   cell of p   c_k = 0 when inv_k == 0 (the product is not formed), else c_k = min(G - 1, (int)floorf(fl(fl(p_k - lo_k) * inv_k)));
- *               cell = (c_z * G + c_y) * G + c_x.  A point with a non-finite coordinate goes to the extra cell G^3 and never matches.
+ *   cell of p   c_k = the clamped cell of step 2 of THE SEARCH below, of p_k in place of q_k (for a finite point of this cloud
+ *               0 <= t, so c_k = min(G - 1, (int)floorf(t))); cell = (c_z * G + c_y) * G + c_x.  A point with a non-finite
+ *               coordinate goes to the extra cell G^3 and never matches.
  *   order       int32[n_points]: the point indices sorted by (cell, index) - ties inside a cell in ascending index, so every array
  *               here is defined bit for bit.
  *   cell_start  int32[G^3 + 2]: cell_start[c] = number of points in cells below c; [G^3] starts the extra cell, [G^3 + 1] = n_points.

@@ -24,18 +24,26 @@ def default_cells(n_points):
     return min(g, 128)
 
 
-def cells_of(points, frame, G):
-    """the header's cell of every point: (cell (P,) int32, per-axis cells (P, 3), finite mask)"""
-    p = np.ascontiguousarray(points, dtype=F32)
-    finite = np.isfinite(p).all(axis=1)
+def cell_axes(p, frame, G):
+    """the header's clamped cell (step 2 of the search), per axis, of every row of finite coordinates p (n, 3): (n, 3) int64"""
     c = np.zeros(p.shape, dtype=np.int64)
     with np.errstate(all="ignore"):
         for k in range(3):
             inv = frame[4 + k]
             if inv != 0:
-                d = (p[finite, k] - frame[k]).astype(F32)
-                t = (d * inv).astype(F32)
-                c[finite, k] = np.minimum(G - 1, np.floor(t).astype(np.int64))
+                t = ((p[:, k] - frame[k]).astype(F32) * inv).astype(F32)
+                mid = (t >= 0) & (t < F32(G))
+                c[t >= F32(G), k] = G - 1
+                c[mid, k] = np.floor(t[mid]).astype(np.int64)
+    return c
+
+
+def cells_of(points, frame, G):
+    """the header's cell of every point: (cell (P,) int32, per-axis cells (P, 3), finite mask)"""
+    p = np.ascontiguousarray(points, dtype=F32)
+    finite = np.isfinite(p).all(axis=1)
+    c = np.zeros(p.shape, dtype=np.int64)
+    c[finite] = cell_axes(p[finite], frame, G)
     cell = (c[:, 2] * G + c[:, 1]) * G + c[:, 0]
     cell[~finite] = G ** 3
     return cell.astype(np.int32), c, finite
@@ -75,20 +83,6 @@ def build(points, G):
     return {"cells": G, "n_points": P, "frame": frame, "cell": cell, "order": order, "cell_start": cell_start, "sorted": srt, "slabs": slabs}
 
 
-def _query_cell(q, frame, G):
-    c = [0, 0, 0]
-    with np.errstate(all="ignore"):
-        for k in range(3):
-            inv = frame[4 + k]
-            if inv != 0:
-                t = F32(F32(q[k] - frame[k]) * inv)
-                if t >= F32(G):
-                    c[k] = G - 1
-                elif t >= 0:
-                    c[k] = int(np.floor(t))
-    return c
-
-
 def search(grid, queries, dtype=np.float64, count=None):
     """the header's ring walk for every query (Q, 3): (index int32, d2 dtype).  `count`: a list that receives the number of
     candidate points each query evaluated."""
@@ -103,7 +97,7 @@ def search(grid, queries, dtype=np.float64, count=None):
     for n, qf in enumerate(qs):
         evaluated = 0
         if np.isfinite(qf).all():
-            c = _query_cell(qf, frame, G)
+            c = [int(v) for v in cell_axes(qf[None, :], frame, G)[0]]
             q = qf.astype(dtype)
             best, bi = inf, -1
             for r in range(G):

@@ -87,6 +87,23 @@ def test_restatement_equals_brute_force_and_kdtree(name, G):
     assert (ours_i <= ki).all()                                           # ... and ours is the lowest-index one
 
 
+@pytest.mark.parametrize("name,G", RUNS, ids=[f"{n}-G{g or 'default'}" for n, g in RUNS])
+def test_one_cell_function_gives_the_point_form(name, G):
+    """the cell of a cloud's own point was min(G - 1, floor(t)) clamped at 0 (kept here as the thing compared against); the single
+    clamped form gives the same cell for every finite point of every case"""
+    pts = CASES[name][0]
+    G = R.default_cells(len(pts)) if G is None else G
+    frame = R.build(pts, G)["frame"]
+    p = pts[np.isfinite(pts).all(axis=1)]
+    old = np.zeros(p.shape, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            if frame[4 + k] != 0:
+                t = ((p[:, k] - frame[k]).astype(F32) * frame[4 + k]).astype(F32)
+                old[:, k] = np.maximum(0, np.minimum(G - 1, np.floor(t.astype(np.float64)).astype(np.int64)))
+    assert len(p) and np.array_equal(R.cell_axes(p, frame, G), old)
+
+
 def test_lattice_ties_go_to_the_lowest_index():
     pts, qry, _ = CASES["lattice"]
     grid = R.build(pts, 9)

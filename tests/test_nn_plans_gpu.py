@@ -11,7 +11,7 @@ from actionmesh_amd import ops
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-NN_THREADS, NN_TILE = 256, 512          # csrc/am_pointcloud.hip
+NN_THREADS, NN_TILE = 256, 512          # csrc/am_points.h
 
 
 def nn_plan(P, Q, batch):
