@@ -23,12 +23,33 @@
 // packing per lane, plus the fragment ds_reads and LDS-DMA issue for its next matrix interval).  K8 / V8T tiles (8 + 8 KiB
 // per 64 keys) arrive by LDS-DMA into a 4-deep ring, three tiles ahead, retired by one counted vmcnt(2) per tile.
 // Online softmax with a deferred re-base (threshold 2^3): p = 2^(s - m_run + 5), so p <= 2^8 fits e4m3 (max 448) and
-// probabilities down to 2^-14 of the row maximum survive the 2^-9 flush.  The VALU interval is what bounds this kernel, so
+// probabilities down to 2^-14 of the row maximum survive the 2^-9 flush (per form: the last paragraph).  The VALU interval is what bounds this kernel, so
 // it carries only what has to be there - 32 exp2, 16 packs, 11 max3 per lane and tile: the scores are born relative to the
 // running max (the QK^T accumulators start from a splat of 5 - m_run: no subtraction in front of the exponentials), and keys
 // past a chunk's end are a wave-uniform branch taken once per chunk; fragment reads and LDS-DMA issue sit in the matrix
 // interval, between MFMAs, where the wave only waits for the pipe.  (Row sums on the matrix pipe - one more MFMA against a
 // block of ones - were written and dropped: 24 more registers, and at 256 the kernel spills.)
+//
+// Range, row sums and non-finite operands, per form.  tests/test_fp8_range_gpu.py holds every form to this, element by element,
+// against the fp64 emulator of tests/_fp8_range.py (itself checked in tests/test_fp8_range_cpu.py).
+//   What reaches the numerator.  A key is packed to e4m3 against the running maximum m_run of the moment it is SEEN, d octaves above
+//   it: p8 = rne_e4m3(2^(5 - d)), subnormals of 2^-9 under 2^-6 (d > 11).  exp2 forms (8-wave, 4 x 64, product): the key counts iff
+//   d < 15 - 2^-9 for 14 <= d < 15, and the tie 2^-10 at d = 15 goes to 0.  fp8_fast: the byte rne(96 - 8 d), saturating at 0, is
+//   exponent-field arithmetic and e4m3's exponent field is spent at 2^-6: exact at whole octaves down to d = 11, linear subnormals
+//   (8 - 8 f) 2^-9 at d = 11 + f, and 0 from d = 12 on (exp2 would still give 2^-7).  A key seen BEFORE a larger one arrives is packed
+//   against the smaller m_run and rescaled in fp32 at the re-base: it is never flushed.  So what a key under the limit contributes
+//   depends on the order of the walk: one pass, each rank's two-pass ring order and the 16 independent key ranges of the split last
+//   block (each starts from its own maximum, merged in fp32) lose different keys of the same row.
+//   Which probabilities the row sum adds.  8-wave kernel (every short last block, every stream under 8 tiles, the split ranges) and
+//   4 x 64 kernel: the UNROUNDED fp32 exponentials - a flushed key stays in the denominator, and the output is scaled down by the
+//   lost share of the softmax mass (V = 1 gives 1 - share).  Product kernel and fp8_fast: the ROUNDED e4m3 P, on the matrix pipe -
+//   numerator and denominator see the same P, the softmax renormalises over the surviving keys and V = 1 gives exactly 1.
+//   3300 keys 15 octaves under one dominant key carry 9.1 % of the mass; at 12 octaves (fp8_fast's limit) 44.6 %.
+//   Non-finite operands.  The quantiser saturates +-inf (and everything beyond +-448) to +-448 and passes a NaN on as e4m3's NaN.
+//   A NaN in V at (key, channel c) makes channel c of every row of that head NaN, in every form, whatever the key's probability.
+//   A NaN in a query row makes that output row NaN, in every form.  A NaN in a key row makes every row of the head NaN in the exp2
+//   forms; fp8_fast DROPS that key silently - v_cvt_pk_u8_f32 writes byte 0 for a NaN score and the row max skips it - and the rows
+//   stay finite, the softmax over the other keys: a limit of that form, kept because a test in its loop would cost what it saves.
 #include "am_attention_host.h"
 
 namespace {
@@ -49,6 +70,13 @@ constexpr float DEFER_T = 3.f;         // deferred re-base threshold (log2 units
 constexpr int SCALE_ONE = 0x7f7f7f7f;  // E8M0 block scale 2^0
 
 __device__ inline float clamp_e4m3(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
+// The clamp alone turns a NaN into -448 (fmaxf returns its other operand), so a NaN operand would vanish where the bf16 kernels and
+// torch carry it.  0x7f - e4m3's NaN - where x is one, else 0, to be OR-ed over the packed byte.  Tested on the BITS: the library is
+// built with -fno-honor-nans, under which a floating-point x != x folds to false.
+__device__ inline uint32_t nan_e4m3(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7fffffffu) > 0x7f800000u ? 0x7fu : 0u; }
+__device__ inline uint32_t nan4_e4m3(uint32_t a, uint32_t b) {      // for the four bytes packed from bflo(a), bfhi(a), bflo(b), bfhi(b)
+  return nan_e4m3(bflo(a)) | (nan_e4m3(bfhi(a)) << 8) | (nan_e4m3(bflo(b)) << 16) | (nan_e4m3(bfhi(b)) << 24);
+}
 
 // key held by k-slot `pos` of a 64-key tile (see header)
 __host__ __device__ inline int kperm(int pos) {
@@ -99,8 +127,8 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const bf16_t* __restric
       w0 = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(bflo(a[2 * e + 1]) * mul), clamp_e4m3(bfhi(a[2 * e + 1]) * mul), w0, true);
       w1 = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(bflo(b[2 * e]) * mul), clamp_e4m3(bfhi(b[2 * e]) * mul), w1, false);
       w1 = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(bflo(b[2 * e + 1]) * mul), clamp_e4m3(bfhi(b[2 * e + 1]) * mul), w1, true);
-      o[e] = (uint32_t)w0;
-      o[2 + e] = (uint32_t)w1;
+      o[e] = (uint32_t)w0 | nan4_e4m3(a[2 * e], a[2 * e + 1]);
+      o[2 + e] = (uint32_t)w1 | nan4_e4m3(b[2 * e], b[2 * e + 1]);
     }
     *reinterpret_cast<u32x4_t*>(dst + i * 16) = o;
   }
@@ -124,15 +152,16 @@ __global__ __launch_bounds__(256) void quant_vt_kernel(const bf16_t* __restrict_
     auto at = [&](int key) {   // V^T position of `key` inside the tile: perm16 within its group of 16
       const int p = (key & ~15) | perm16(key & 15);
       const uint32_t x = w[p >> 1];
-      return clamp_e4m3((p & 1) ? bfhi(x) : bflo(x));
+      return (p & 1) ? bfhi(x) : bflo(x);
     };
     uint32_t o[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       int x = 0;
-      x = __builtin_amdgcn_cvt_pk_fp8_f32(at(kperm(4 * q)), at(kperm(4 * q + 1)), x, false);
-      x = __builtin_amdgcn_cvt_pk_fp8_f32(at(kperm(4 * q + 2)), at(kperm(4 * q + 3)), x, true);
-      o[q] = (uint32_t)x;
+      const float v0 = at(kperm(4 * q)), v1 = at(kperm(4 * q + 1)), v2 = at(kperm(4 * q + 2)), v3 = at(kperm(4 * q + 3));
+      x = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(v0), clamp_e4m3(v1), x, false);
+      x = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(v2), clamp_e4m3(v3), x, true);
+      o[q] = (uint32_t)x | nan_e4m3(v0) | (nan_e4m3(v1) << 8) | (nan_e4m3(v2) << 16) | (nan_e4m3(v3) << 24);
     }
     uint8_t* d = dst + row * sk_pad + tile * KT;
 #pragma unroll

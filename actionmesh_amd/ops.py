@@ -358,6 +358,21 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: i
     return out
 
 
+def _quantize_fp8(a, q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
+                  quantize_out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """am_attention_quantize_fp8 for the call `a` describes -> uint8 (q8, k8, vt8): the caller's `quantize_out`, or fresh tensors."""
+    if quantize_out is not None:
+        q8, k8, vt8 = (_need(t, torch.uint8, "quantize_out") for t in quantize_out)
+        if q8.shape != q.shape or k8.shape != k.shape or vt8.shape != vt.shape:
+            raise ValueError("attention_fp8: quantize_out must have the shapes of q, k, vt")
+    else:
+        q8 = torch.empty(q.shape, dtype=torch.uint8, device=q.device)
+        k8 = torch.empty(k.shape, dtype=torch.uint8, device=q.device)
+        vt8 = torch.empty(vt.shape, dtype=torch.uint8, device=q.device)
+    _call(q, q, "am_attention_quantize_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(), vt8.data_ptr())
+    return q8, k8, vt8
+
+
 def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: int,
                   out: Optional[torch.Tensor] = None, nchunks: int = 1, scale: Optional[float] = None,
                   quantized: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, ablate: int = 0,
@@ -371,21 +386,20 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, s
     # defer_log2 carries the timing ablations of the fp8 kernel (tools/kernel_bench.py)
     a, out = _attn_args(q, k, vt, sq, sk, out, nchunks, scale, L.ATTN_FP8_ABLATE + ablate if ablate else 0, rows, state_mode, state, chunk_first,
                         chunk_total)
-    if quantized is None:
-        if quantize_out is not None:
-            q8, k8, vt8 = (_need(t, torch.uint8, "quantize_out") for t in quantize_out)
-            if q8.shape != q.shape or k8.shape != k.shape or vt8.shape != vt.shape:
-                raise ValueError("attention_fp8: quantize_out must have the shapes of q, k, vt")
-        else:
-            q8 = torch.empty(q.shape, dtype=torch.uint8, device=q.device)
-            k8 = torch.empty(k.shape, dtype=torch.uint8, device=q.device)
-            vt8 = torch.empty(vt.shape, dtype=torch.uint8, device=q.device)
-        _call(q, q, "am_attention_quantize_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(), vt8.data_ptr())
-    else:
-        q8, k8, vt8 = quantized
+    q8, k8, vt8 = _quantize_fp8(a, q, k, vt, quantize_out) if quantized is None else quantized
     _call(q, q, "am_attention_fp8", C.byref(a), q8.data_ptr(), k8.data_ptr(), vt8.data_ptr())
     attention_fp8.last_quantized = (q8, k8, vt8)
     return out
+
+
+def attention_quantize_fp8(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, sq: int, sk: int,
+                           quantize_out: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], nchunks: int = 1,
+                           scale: Optional[float] = None, rows: int = 0, chunk_first: int = 0, chunk_total: int = 0) -> None:
+    """The quantiser of `attention_fp8` on its own, into the caller's uint8 (q8, k8, vt8).  Only the chunks (chunk_first + i) %
+    chunk_total, i < nchunks, are written (chunk_total = 0: chunks 0 .. nchunks - 1), and rows = 2 leaves q8 alone - as an attention
+    call with the same arguments reads them."""
+    a, _ = _attn_args(q, k, vt, sq, sk, None, nchunks, scale, 0, rows, 0, None, chunk_first, chunk_total)
+    _quantize_fp8(a, q, k, vt, quantize_out)
 
 
 def attention_fallback_count() -> int:

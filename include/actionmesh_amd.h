@@ -338,7 +338,22 @@ int am_attention_fallback_count(uint64_t* count);
  * bytes).  The forms of am_attention_bf16 (round 3): chunk_first / chunk_total ring walks (the quantiser converts exactly the
  * chunks an attention call with the same arguments walks; rows = 2 skips Q), rows = 1 / 2, state_mode 1 / 2 with the same
  * [seq*heads][sq_pad][132] state layout, and the short last query block split over the key range.  Stated tolerance vs fp32
- * SDPA: tests/test_attention_fp8.py. */
+ * SDPA: tests/test_attention_fp8.py.
+ * The quantiser is round-to-nearest-even e4m3 of the fp32 value (Q: times the fp32 product scale * log2 e), bit for bit torch's
+ * x.clamp(-448, 448).to(float8_e4m3fn): +-inf and everything beyond +-448 saturate to +-448, a NaN stays a NaN (0x7f under either sign bit), -0 and
+ * what rounds to it keep their sign, subnormals are multiples of 2^-9 with ties to even (2^-10 -> 0, 3 x 2^-10 -> 2^-8).
+ * Range of the probabilities, per form (am_attention_fp8.hip's header has the reasons; tests/test_fp8_range_gpu.py holds each
+ * form to it against the fp64 emulator of tests/_fp8_range.py):
+ *   - numerator: a key seen d octaves under the running maximum counts iff d < 15 (the 8-wave, 4 x 64 and product kernels: e4m3 of
+ *     2^(5 - d), the 2^-10 tie goes to 0) or d < 12 (AM_ATTN_FP8_FAST: linear subnormals from d = 11 on).  A key seen BEFORE the
+ *     maximum rises is rescaled in fp32 and never lost, so the keys lost depend on the order of the walk: one pass, a rank's
+ *     two-pass ring order, the independent key ranges of the split last block.
+ *   - row sum: the 8-wave kernel (also every short last block and every stream under 8 tiles) and the 4 x 64 kernel add the
+ *     unrounded fp32 probabilities - the output shrinks by the lost share of the softmax mass; the product kernel and
+ *     AM_ATTN_FP8_FAST add the rounded e4m3 ones - the softmax renormalises over the surviving keys (V = 1 gives 1).
+ *   - non-finite operands: a NaN in V poisons its channel in every row of the head, a NaN in a query row that output row, in every
+ *     form; a NaN in a key row makes every row of the head NaN, except under AM_ATTN_FP8_FAST, which drops that key silently (its
+ *     byte convert writes 0 for a NaN score) and stays finite. */
 int am_attention_quantize_fp8(const am_attn_args* args, uint8_t* q8, uint8_t* k8, uint8_t* vt8, void* stream);
 int am_attention_fp8(const am_attn_args* args, const uint8_t* q8, const uint8_t* k8, const uint8_t* vt8, void* stream);
 
