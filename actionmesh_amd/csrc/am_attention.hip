@@ -98,6 +98,194 @@ __device__ __forceinline__ void mask_keys(f32x16_t& s, int first, int tv) {
     if (first + (r & 3) + 8 * (r >> 2) >= tv) s[r] = -INFINITY;
 }
 
+// ---- the 64-key tile step, piece by piece: the three kernels below are composed of these -------------------------------------------
+// How the pieces take their operands is part of the tuning (hipcc, SLP vectoriser on): a small array that is filled or read through a
+// reference parameter (the two score blocks as s[2], the raw Q pieces, the four output blocks) is promoted as ONE wide vector, and the
+// kernel then comes out with other selects, moves and register counts.  So the score blocks travel as two variables, and the Q scaling
+// (per dword: per 16-byte piece the float16 build packs other products), the fragment offsets and the output block are per-element
+// functions by value whose loops stay with the caller.
+
+// fmaxf on MFMA outputs makes hipcc canonicalise every operand with an extra v_max
+__device__ __forceinline__ float max3(float a, float b, float cc) {
+  float d;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(cc));
+  return d;
+}
+
+// raw Q[row][ks*16 + hi*8 .. +8]: piece ks = 0..7 of the lane's query row (sq_pad % 256 == 0: always in bounds)
+__device__ __forceinline__ u32x4_t q_fetch(const bf16_t* Q, int sq_pad, int bh, int64_t row, int hi, int ks) {
+  const bf16_t* qp = Q + ((int64_t)bh * sq_pad + row) * HD + hi * 8;
+  return *reinterpret_cast<const u32x4_t*>(qp + ks * 16);
+}
+// one dword (two elements) of a raw Q row, pre-scaled to log2 units (c = scale * log2(e)) and re-rounded
+__device__ __forceinline__ uint32_t q_scale(uint32_t w, float c) { return pack_bf2(bflo(w) * c, bfhi(w) * c); }
+
+// DMA unit U (16 B) of a 1024-unit sub-tile lands lane-linearly at LDS byte 16 U; the bank swizzle of the LDS image (file header) is
+// applied to its SOURCE: where that unit lies in the first K tile and the first V^T tile of the (sequence, head) at k_bh / v_bh
+__device__ __forceinline__ void dma_unit_src(int U, const bf16_t* k_bh, const bf16_t* v_bh, int sk_pad, const bf16_t*& k_src,
+                                             const bf16_t*& v_src) {
+  const int kr = U >> 4, kc = (U & 15) ^ (kr & 15);
+  k_src = k_bh + kr * HD + kc * 8;
+  const int vr = U >> 3, vc = (U & 7) ^ ((vr >> 1) & 7);
+  v_src = v_bh + (int64_t)vr * sk_pad + vc * 8;
+}
+// fragment read offsets (bytes) inside a sub-tile, the read side of the same swizzle: K fragment ks = 0..7, V^T fragment kk = 0..3
+__device__ __forceinline__ int k_frag_off(int l31, int hi, int ks) { return l31 * 256 + (((ks * 2 + hi) ^ (l31 & 15)) << 4); }
+__device__ __forceinline__ int v_frag_off(int l31, int hi, int kk) { return l31 * 128 + (((kk * 2 + hi) ^ ((l31 >> 1) & 7)) << 4); }
+
+// S = K Q'^T for both 32-key blocks: the 16 K fragments are read 8 deep ahead of the MFMAs that consume them
+__device__ __forceinline__ void qk_block(const unsigned char* kp, const int (&k_off)[8], const bf16x8_t (&qf)[8], const f32x16_t& zero16,
+                                         f32x16_t& s0, f32x16_t& s1) {
+  bf16x8_t kf[8];
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + k_off[ks]);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    s0 = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s0);
+    kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + 32 * 256 + k_off[ks]);
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks)
+    s1 = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s1);
+}
+
+// the two half-lanes of a query row exchange their maxima with v_permlane32_swap (no LDS round trip)
+__device__ __forceinline__ float swap_max(float mx) {
+  const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
+  return max3(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
+}
+// row max of a 64-key tile of which `valid` keys are real: four independent v_max3 chains
+__device__ __forceinline__ float row_max64(f32x16_t& s0, f32x16_t& s1, int valid, int hi) {
+  // hipcc pads no hazards for inline asm: an MFMA result needs 12 wait states before a VALU read
+  asm volatile("s_nop 15" : "+v"(s0), "+v"(s1));
+  if (valid < KVBLK) {                          // rare: the partial last sub-tile of a chunk
+    mask_keys(s0, 0, valid - 4 * hi);
+    mask_keys(s1, 32, valid - 4 * hi);
+  }
+  float mxa[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) mxa[i] = max3(s0[i], s1[i], s0[i + 4]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s1[i + 4], s0[i + 8]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s1[i + 8], s0[i + 12]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s1[i + 12], mxa[i]);
+  return swap_max(max3(mxa[0], mxa[1], max3(mxa[2], mxa[3], mxa[3])));
+}
+
+// the deferred re-base of the online softmax: mx = this tile's row max; O is rescaled only when a row's max grows by more than DEFER
+template <int DEFER>
+__device__ __forceinline__ void rebase(float mx, float& m_run, float& l_run, f32x16_t (&o)[4], bool& first) {
+  mx -= m_run;                                  // how far this tile's max is above the running max
+  if (first || !__all(mx <= (float)DEFER)) {   // rare after the first tile
+    const float delta = first ? mx : fmaxf(mx, 0.f);
+    const float alpha = first ? 0.f : __builtin_amdgcn_exp2f(-delta);
+    first = false;
+    m_run += delta;
+    l_run *= alpha;
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+  }
+}
+
+// P = exp2(S - m_run) for one 32-key block, in place; four-way row sums
+__device__ __forceinline__ void exp_block(f32x16_t& sb, float m_run, f32x2_t (&rsa)[4]) {
+  const f32x2_t m2 = {m_run, m_run};
+#pragma unroll
+  for (int r = 0; r < 16; r += 2) {
+    const f32x2_t x = f32x2_t{sb[r], sb[r + 1]} - m2;      // v_pk_add_f32
+    const f32x2_t pp = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
+    sb[r] = pp[0];
+    sb[r + 1] = pp[1];
+    rsa[(r >> 1) & 3] += pp;
+  }
+}
+__device__ __forceinline__ void fold_row_sums(const f32x2_t (&rsa)[4], float& l_run) {
+  const f32x2_t rs = (rsa[0] + rsa[1]) + (rsa[2] + rsa[3]);
+  l_run += rs[0] + rs[1];
+}
+// P as bf16 B-operand fragments, straight from the S registers
+__device__ __forceinline__ void p_pack(const f32x16_t& s0, const f32x16_t& s1, bf16x8_t (&pf)[4]) {
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const f32x16_t& sb = kk < 2 ? s0 : s1;
+    u32x4_t w;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      w[e] = pack_bf2(sb[(kk & 1) * 8 + 2 * e], sb[(kk & 1) * 8 + 2 * e + 1]);
+    pf[kk] = __builtin_bit_cast(bf16x8_t, w);
+  }
+}
+
+// V^T fragments of the first two 16-key steps: requested ahead of the softmax that hides them.  The lane's offset is added first, on
+// purpose and unlike pv_block below: in pv_block's order the 8-wave geometry spends 12 more v_add_u32 here.
+__device__ __forceinline__ void pv_fetch(const unsigned char* vp, const int (&v_off)[4], bf16x8_t (&vf)[8]) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + v_off[kk] + d * 32 * 128);
+}
+// O^T += V^T P^T: the fragments of steps 2 and 3 are read under the MFMAs of steps 0 and 1
+__device__ __forceinline__ void pv_block(const unsigned char* vp, const int (&v_off)[4], bf16x8_t (&vf)[8], const bf16x8_t (&pf)[4],
+                                         f32x16_t (&o)[4]) {
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      o[d] = AM_MFMA_32x32x16(vf[kk * 4 + d], pf[kk], o[d]);
+      vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + d * 32 * 128 + v_off[kk + 2]);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int kk = 2; kk < 4; ++kk)
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      o[d] = AM_MFMA_32x32x16(vf[(kk - 2) * 4 + d], pf[kk], o[d]);
+}
+
+// one 64-key tile: S = K Q'^T, online softmax, O^T += V^T P^T (kp, vp: its K and V^T images in LDS)
+template <int DEFER>
+__device__ __forceinline__ void tile64(const unsigned char* kp, const unsigned char* vp, int valid, int hi, const int (&k_off)[8],
+                                       const int (&v_off)[4], const bf16x8_t (&qf)[8], const f32x16_t& zero16, f32x16_t (&o)[4],
+                                       float& m_run, float& l_run, bool& first) {
+  f32x16_t s0, s1;
+  qk_block(kp, k_off, qf, zero16, s0, s1);
+  bf16x8_t vf[8];
+  pv_fetch(vp, v_off, vf);                      // in flight under the softmax
+  rebase<DEFER>(row_max64(s0, s1, valid, hi), m_run, l_run, o, first);
+  f32x2_t rsa[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) rsa[i] = f32x2_t{0.f, 0.f};
+  exp_block(s0, m_run, rsa);
+  exp_block(s1, m_run, rsa);
+  fold_row_sums(rsa, l_run);
+  bf16x8_t pf[4];
+  p_pack(s0, s1, pf);
+  pv_block(vp, v_off, vf, pf, o);
+}
+
+// one 32-channel block of the lane's output row, normalised, straight from the MFMA layout: 8-byte pieces at op, op + 8, ...
+__device__ __forceinline__ void store_block(bf16_t* op, f32x16_t od, float inv) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    u32x2_t w;
+    w[0] = pack_bf2(od[4 * g] * inv, od[4 * g + 1] * inv);
+    w[1] = pack_bf2(od[4 * g + 2] * inv, od[4 * g + 3] * inv);
+    *reinterpret_cast<u32x2_t*>(op + 8 * g) = w;
+  }
+}
+
 // SPLIT: the workgroup handles only super-tiles [z*ns/Z, (z+1)*ns/Z) (z = blockIdx.z) of query block
 // `qblk_base + blockIdx.x` and writes un-normalised fp32 (O, m, l) partials for attn_combine_kernel.
 template <int DEFER, bool SPLIT, int NW, int NSUB>
@@ -118,16 +306,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
 
   // ---- Q fragments (B operand), pre-scaled to log2 units: Q[q0 + l31][ks*16 + hi*8 .. +8] ----
   bf16x8_t qf[8];
-  {
-    const bf16_t* qp = p.Q + ((int64_t)bh * p.sq_pad + q0 + l31) * HD + hi * 8;
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const u32x4_t raw = *reinterpret_cast<const u32x4_t*>(qp + ks * 16);
-      u32x4_t sc;
+  for (int ks = 0; ks < 8; ++ks) {
+    const u32x4_t raw = q_fetch(p.Q, p.sq_pad, bh, (int64_t)q0 + l31, hi, ks);
+    u32x4_t sc;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) sc[e] = pack_bf2(bflo(raw[e]) * c, bfhi(raw[e]) * c);
-      qf[ks] = __builtin_bit_cast(bf16x8_t, sc);
-    }
+    for (int e = 0; e < 4; ++e) sc[e] = q_scale(raw[e], c);
+    qf[ks] = __builtin_bit_cast(bf16x8_t, sc);
   }
 
   // ---- DMA descriptors: unit U = j*THREADS + wave*64 + lane (16 B each) of a 1024-unit sub-tile ----
@@ -138,11 +323,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
 #pragma unroll
   for (int j = 0; j < UPT; ++j) {
     u_byte[j] = (j * G::THREADS + wave * 64) * 16;           // wave-uniform LDS offset of the instruction
-    const int U = j * G::THREADS + wave * 64 + lane;
-    const int kr = U >> 4, kc = (U & 15) ^ (kr & 15);
-    k_lane[j] = p.K + (int64_t)bh * k_seq_stride + kr * HD + kc * 8;
-    const int vr = U >> 3, vc = (U & 7) ^ ((vr >> 1) & 7);
-    v_lane[j] = p.Vt + (int64_t)bh * k_seq_stride + (int64_t)vr * p.sk_pad + vc * 8;
+    dma_unit_src(j * G::THREADS + wave * 64 + lane, p.K + (int64_t)bh * k_seq_stride, p.Vt + (int64_t)bh * k_seq_stride, p.sk_pad,
+                 k_lane[j], v_lane[j]);
   }
   // key stream = nchunks x tiles_per_chunk sub-tiles, consumed as super-tiles of up to two
   // sub-tiles that never straddle a chunk
@@ -182,125 +364,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
   float l_run = 0.f;       // this half-lane's partial row sum
   bool first = true;
 
-  // fragment read offsets (bytes) inside a sub-tile
   int k_off[8], v_off[4];
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) k_off[ks] = l31 * 256 + (((ks * 2 + hi) ^ (l31 & 15)) << 4);
+  for (int ks = 0; ks < 8; ++ks) k_off[ks] = k_frag_off(l31, hi, ks);
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) v_off[kk] = l31 * 128 + (((kk * 2 + hi) ^ ((l31 >> 1) & 7)) << 4);
+  for (int kk = 0; kk < 4; ++kk) v_off[kk] = v_frag_off(l31, hi, kk);
   int c_tt = (s_begin % supers_per_chunk) * NSUB;   // compute cursor: sub-tile in chunk
 
-  auto max3 = [](float a, float b, float cc) __attribute__((always_inline)) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(cc));
-    return d;
-  };
-
-  // ---- one 64-key sub-tile: S = K Q'^T, online softmax, O^T += V^T P^T ------------------------
   auto sub_tile = [&](const unsigned char* kp, const unsigned char* vp, int valid) __attribute__((always_inline)) {
-    f32x16_t s[2];
-    {   // the 16 K fragments are read 8 deep ahead of the MFMAs that consume them
-      bf16x8_t kf[8];
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + k_off[ks]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        s[0] = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s[0]);
-        kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + 32 * 256 + k_off[ks]);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks)
-        s[1] = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s[1]);
-    }
-    // V^T fragments of the first two 16-key steps: in flight under the softmax
-    bf16x8_t vf[8];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-        vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + d * 32 * 128 + v_off[kk]);
-    // ---- row max (four independent v_max3 chains), relative to the running max ------------------
-    // hipcc pads no hazards for inline asm: an MFMA result needs 12 wait states before a VALU read
-    asm volatile("s_nop 15" : "+v"(s[0]), "+v"(s[1]));
-    if (valid < KVBLK) {                          // rare: the partial last sub-tile of a chunk
-      mask_keys(s[0], 0, valid - 4 * hi);
-      mask_keys(s[1], 32, valid - 4 * hi);
-    }
-    float mxa[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(s[0][i], s[1][i], s[0][i + 4]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 4], s[0][i + 8]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 8], s[0][i + 12]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 12], mxa[i]);
-    float mx = max3(mxa[0], mxa[1], max3(mxa[2], mxa[3], mxa[3]));
-    {
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-      mx = max3(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
-    }
-    mx -= m_run;                                  // how far this sub-tile's max is above the running max
-    if (first || !__all(mx <= (float)DEFER)) {   // rare after the first sub-tile (deferred rescale)
-      const float delta = first ? mx : fmaxf(mx, 0.f);
-      const float alpha = first ? 0.f : __builtin_amdgcn_exp2f(-delta);
-      first = false;
-      m_run += delta;
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-    }
-    // ---- P = exp2(S - m_run), row sums, bf16 B-operand fragments -----------------------------------
-    const f32x2_t m2 = {m_run, m_run};
-    f32x2_t rsa[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rsa[i] = f32x2_t{0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const f32x2_t x = f32x2_t{s[kb][r], s[kb][r + 1]} - m2;      // v_pk_add_f32
-        const f32x2_t pp = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
-        s[kb][r] = pp[0];
-        s[kb][r + 1] = pp[1];
-        rsa[(r >> 1) & 3] += pp;
-      }
-    {
-      const f32x2_t rs = (rsa[0] + rsa[1]) + (rsa[2] + rsa[3]);
-      l_run += rs[0] + rs[1];
-    }
-    bf16x8_t pf[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      u32x4_t w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        w[e] = pack_bf2(s[kk >> 1][(kk & 1) * 8 + 2 * e], s[kk >> 1][(kk & 1) * 8 + 2 * e + 1]);
-      pf[kk] = __builtin_bit_cast(bf16x8_t, w);
-    }
-    // ---- O^T += V^T P^T --------------------------------------------------------------------------------
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        o[d] = AM_MFMA_32x32x16(vf[kk * 4 + d], pf[kk], o[d]);
-        vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + d * 32 * 128 + v_off[kk + 2]);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int kk = 2; kk < 4; ++kk)
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-        o[d] = AM_MFMA_32x32x16(vf[(kk - 2) * 4 + d], pf[kk], o[d]);
+    tile64<DEFER>(kp, vp, valid, hi, k_off, v_off, qf, zero16, o, m_run, l_run, first);
   };
 
   auto super_tile = [&](int buf, bool more) __attribute__((always_inline)) {
@@ -340,14 +412,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
   if (q < p.sq) {       // O[q][head*128 + d]
     bf16_t* op = p.O + ((int64_t)seq * p.sq + q) * p.ldo + head * HD + 4 * hi;
 #pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        u32x2_t w;
-        w[0] = pack_bf2(o[d][4 * g] * inv, o[d][4 * g + 1] * inv);
-        w[1] = pack_bf2(o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv);
-        *reinterpret_cast<u32x2_t*>(op + d * 32 + 8 * g) = w;
-      }
+    for (int d = 0; d < 4; ++d) store_block(op + d * 32, o[d], inv);
   }
 }
 
@@ -360,8 +425,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(am_attn_args p, in
 // and then walks all the query blocks of its sequence against LDS that nobody writes any more: no barrier and no DMA wait in the
 // loop, the next block's Q rows are fetched while the current block computes, and the tail costs 8 + 4 MFMAs instead of 32 (its QK^T
 // only multiplies key block 0, its P.V only the first 16-key step; its padded keys score -inf, as everywhere).
-// Same layouts, same LDS images, same per-tile arithmetic as attn_fwd_kernel (its sub_tile, copied: that kernel's tuning is not
-// touched); the tail's keys are summed in another grouping, so results agree to rounding, not bit for bit.
+// Same layouts and LDS images as attn_fwd_kernel, and its tile step itself for the full tiles (tile64); the short tail is this kernel's
+// own, built from the same pieces: its keys are summed in another grouping, so results agree to rounding, not bit for bit.
 // The output rows leave through a 2 KiB staging slice per wave (one 32-channel block at a time, XOR-swizzled 8-byte units): the MFMA
 // layout holds one query row per lane, so direct stores were 8-byte pieces of 32 different rows per instruction - 512 line touches per
 // block and wave, the floor of the first form of this kernel; staged, a store instruction writes 64 contiguous bytes of 16 rows.
@@ -401,11 +466,11 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
     const bf16_t* vb = p.Vt + (int64_t)bh * k_seq_stride;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int U = j * 512 + tid;
-      const int kr = U >> 4, kc = (U & 15) ^ (kr & 15);
-      const int vr = U >> 3, vc = (U & 7) ^ ((vr >> 1) & 7);
-      const bf16_t* ks = kb + kr * HD + kc * 8;
-      const bf16_t* vs = vb + (int64_t)vr * p.sk_pad + vc * 8;
+      const bf16_t *ks, *vs;
+      // (through a local lambda: hipcc inlines a direct call at another point and then selects the swizzle's v_xor / v_and as
+      // v_bitop3_b32, with one more s_movk_i32)
+      auto unit_src = [&]() __attribute__((always_inline)) { dma_unit_src(j * 512 + tid, kb, vb, p.sk_pad, ks, vs); };
+      unit_src();
       const int ub = (j * 512 + wave * 64) * 16;
       for (int t = 0; t < n_full; ++t) {
         __builtin_amdgcn_global_load_lds((gbl_ptr_t)(ks + (int64_t)t * (KVBLK * HD)), (lds_ptr_t)(Ks + t * SUB_B + ub), 16, 0, 0);
@@ -421,42 +486,35 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
     }
   }
 
-  // fragment read offsets (bytes) inside a sub-tile
   int k_off[8], v_off[4];
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) k_off[ks] = l31 * 256 + (((ks * 2 + hi) ^ (l31 & 15)) << 4);
+  for (int ks = 0; ks < 8; ++ks) k_off[ks] = k_frag_off(l31, hi, ks);
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) v_off[kk] = l31 * 128 + (((kk * 2 + hi) ^ ((l31 >> 1) & 7)) << 4);
-  auto max3 = [](float a, float b, float cc) __attribute__((always_inline)) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(cc));
-    return d;
-  };
+  for (int kk = 0; kk < 4; ++kk) v_off[kk] = v_frag_off(l31, hi, kk);
   f32x16_t zero16;
 #pragma unroll
   for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
 
   // raw Q rows of the first block (the scaling to log2 units happens at the top of the block's iteration)
   u32x4_t qraw[8];
-  auto q_fetch = [&](int qb) __attribute__((always_inline)) {
-    const bf16_t* qp = p.Q + ((int64_t)bh * p.sq_pad + qb * 256 + wave * 32 + l31) * HD + hi * 8;      // sq_pad % 256 == 0: always in bounds
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) qraw[ks] = *reinterpret_cast<const u32x4_t*>(qp + ks * 16);
-  };
   bf16x8_t qf[8];
-  auto q_scale = [&]() __attribute__((always_inline)) {        // raw rows -> B-operand fragments in log2 units
+  auto fetch_block = [&](int qb) __attribute__((always_inline)) {
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) qraw[ks] = q_fetch(p.Q, p.sq_pad, bh, (int64_t)(qb * 256) + wave * 32 + l31, hi, ks);
+  };
+  fetch_block(qb_begin);
+  dma_drain_barrier();                                         // the key stream has landed and is visible to every wave (and so have the Q rows)
+  auto scale_block = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       u32x4_t sc;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) sc[e] = pack_bf2(bflo(qraw[ks][e]) * c, bfhi(qraw[ks][e]) * c);
+      for (int e = 0; e < 4; ++e) sc[e] = q_scale(qraw[ks][e], c);
       qf[ks] = __builtin_bit_cast(bf16x8_t, sc);
     }
   };
-  q_fetch(qb_begin);
-  dma_drain_barrier();                                         // the key stream has landed and is visible to every wave (and so have the Q rows)
-  q_scale();
-  if (qb_begin + 1 < qb_end) q_fetch(qb_begin + 1);
+  scale_block();
+  if (qb_begin + 1 < qb_end) fetch_block(qb_begin + 1);
 
   // Software pipeline over the query blocks: while block qb computes, the raw rows of block qb + 1 are in flight; they are scaled into
   // `qf` behind block qb's last MFMA and the rows of block qb + 2 are requested BEFORE block qb's output stores are issued - so the
@@ -471,105 +529,13 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
     float m_run = 0.f, l_run = 0.f;
     bool first = true;
 
-    // the deferred re-base of the online softmax (attn_fwd_kernel): mx = this tile's row max
-    auto rebase = [&](float mx) __attribute__((always_inline)) {
-      mx -= m_run;
-      if (first || !__all(mx <= (float)DEFER)) {
-        const float delta = first ? mx : fmaxf(mx, 0.f);
-        const float alpha = first ? 0.f : __builtin_amdgcn_exp2f(-delta);
-        first = false;
-        m_run += delta;
-        l_run *= alpha;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-      }
+    // ---- full 64-key tiles: the tile step of attn_fwd_kernel, operands from the resident images ----
+    // (through a local lambda, as attn_fwd_kernel's sub_tile: hipcc inlines a direct call at another point and then schedules the tile's
+    // LDS reads with other waits)
+    auto full_tile = [&](const unsigned char* kp, const unsigned char* vp) __attribute__((always_inline)) {
+      tile64<DEFER>(kp, vp, KVBLK, hi, k_off, v_off, qf, zero16, o, m_run, l_run, first);
     };
-    // ---- full 64-key tiles: attn_fwd_kernel's sub_tile, operands from the resident images ----
-    for (int t = 0; t < n_full; ++t) {
-      const unsigned char* kp = Ks + t * SUB_B;
-      const unsigned char* vp = Vs + t * SUB_B;
-      f32x16_t s[2];
-      {
-        bf16x8_t kf[8];
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + k_off[ks]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-          s[0] = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s[0]);
-          kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + 32 * 256 + k_off[ks]);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) s[1] = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s[1]);
-      }
-      bf16x8_t vf[8];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int d = 0; d < 4; ++d) vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + d * 32 * 128 + v_off[kk]);
-      asm volatile("s_nop 15" : "+v"(s[0]), "+v"(s[1]));        // MFMA results landed before the VALU reads them
-      float mxa[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) mxa[i] = max3(s[0][i], s[1][i], s[0][i + 4]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 4], s[0][i + 8]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 8], s[0][i + 12]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 12], mxa[i]);
-      float mx = max3(mxa[0], mxa[1], max3(mxa[2], mxa[3], mxa[3]));
-      {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-        mx = max3(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
-      }
-      rebase(mx);
-      const f32x2_t m2 = {m_run, m_run};
-      f32x2_t rsa[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rsa[i] = f32x2_t{0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2_t x = f32x2_t{s[kb][r], s[kb][r + 1]} - m2;
-          const f32x2_t pp = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
-          s[kb][r] = pp[0];
-          s[kb][r + 1] = pp[1];
-          rsa[(r >> 1) & 3] += pp;
-        }
-      {
-        const f32x2_t rs = (rsa[0] + rsa[1]) + (rsa[2] + rsa[3]);
-        l_run += rs[0] + rs[1];
-      }
-      bf16x8_t pf[4];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        u32x4_t w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = pack_bf2(s[kk >> 1][(kk & 1) * 8 + 2 * e], s[kk >> 1][(kk & 1) * 8 + 2 * e + 1]);
-        pf[kk] = __builtin_bit_cast(bf16x8_t, w);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          o[d] = AM_MFMA_32x32x16(vf[kk * 4 + d], pf[kk], o[d]);
-          vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + d * 32 * 128 + v_off[kk + 2]);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int kk = 2; kk < 4; ++kk)
-#pragma unroll
-        for (int d = 0; d < 4; ++d) o[d] = AM_MFMA_32x32x16(vf[(kk - 2) * 4 + d], pf[kk], o[d]);
-    }
+    for (int t = 0; t < n_full; ++t) full_tile(Ks + t * SUB_B, Vs + t * SUB_B);
     // ---- the short tail: key block 0 of its tile only (keys 0 .. 31, of which tail_valid <= 16 are real), one 16-key P.V step ----
     if (tail_valid > 0) {
       f32x16_t s0;
@@ -588,12 +554,8 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
       float mxa[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) mxa[i] = max3(s0[i], s0[i + 4], s0[i + 8]);
-      float mx = max3(max3(mxa[0], mxa[1], mxa[2]), mxa[3], max3(s0[12], s0[13], max3(s0[14], s0[15], s0[15])));
-      {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-        mx = max3(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
-      }
-      rebase(mx);
+      const float mx = max3(max3(mxa[0], mxa[1], mxa[2]), mxa[3], max3(s0[12], s0[13], max3(s0[14], s0[15], s0[15])));
+      rebase<DEFER>(swap_max(mx), m_run, l_run, o, first);
       float rs = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -609,8 +571,8 @@ __global__ __launch_bounds__(512, 2) void attn_resident_kernel(am_attn_args p, i
       for (int d = 0; d < 4; ++d) o[d] = AM_MFMA_32x32x16(vf[d], pf, o[d]);
     }
     // ---- the next block's Q (its loads are a block old), the request for the one after, then this block's output ----
-    if (qb + 1 < qb_end) q_scale();
-    if (qb + 2 < qb_end) q_fetch(qb + 2);
+    if (qb + 1 < qb_end) scale_block();
+    if (qb + 2 < qb_end) fetch_block(qb + 2);
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
     // staged through this wave's 2 KiB slice, one 32-channel block at a time: row r = 64 B = 8 units of 8 B, unit u at u ^ ((r >> 2) & 7)
@@ -678,16 +640,13 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_balanced_kernel(am_attn_args 
   const bool late = wave >= 4;
 
   bf16x8_t qf[8];
-  {
-    const bf16_t* qp = p.Q + ((int64_t)bh * p.sq_pad + q0 + l31) * HD + hi * 8;
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const u32x4_t raw = *reinterpret_cast<const u32x4_t*>(qp + ks * 16);
-      u32x4_t sc;
+  for (int ks = 0; ks < 8; ++ks) {
+    const u32x4_t raw = q_fetch(p.Q, p.sq_pad, bh, (int64_t)q0 + l31, hi, ks);
+    u32x4_t sc;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) sc[e] = pack_bf2(bflo(raw[e]) * c, bfhi(raw[e]) * c);
-      qf[ks] = __builtin_bit_cast(bf16x8_t, sc);
-    }
+    for (int e = 0; e < 4; ++e) sc[e] = q_scale(raw[e], c);
+    qf[ks] = __builtin_bit_cast(bf16x8_t, sc);
   }
   // this half-workgroup's half of every tile: units U = half*512 + j*256 + (wave&3)*64 + lane
   const int64_t k_seq_stride = (int64_t)p.sk_pad * HD;
@@ -698,11 +657,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_balanced_kernel(am_attn_args 
   for (int j = 0; j < 2; ++j) {
     const int ub = (wave >> 2) * 512 + j * 256 + (wave & 3) * 64;
     u_byte[j] = ub * 16;
-    const int U = ub + lane;
-    const int kr = U >> 4, kc = (U & 15) ^ (kr & 15);
-    k_lane[j] = p.K + (int64_t)bh * k_seq_stride + kr * HD + kc * 8;
-    const int vr = U >> 3, vc = (U & 7) ^ ((vr >> 1) & 7);
-    v_lane[j] = p.Vt + (int64_t)bh * k_seq_stride + (int64_t)vr * p.sk_pad + vc * 8;
+    dma_unit_src(ub + lane, p.K + (int64_t)bh * k_seq_stride, p.Vt + (int64_t)bh * k_seq_stride, p.sk_pad, k_lane[j], v_lane[j]);
   }
   const int total_tiles = p.nchunks * tiles_per_chunk;
   int dk_tt = 0, dv_tt = 0;
@@ -733,87 +688,23 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_balanced_kernel(am_attn_args 
   bool first = true;
   int k_off[8], v_off[4];
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) k_off[ks] = l31 * 256 + (((ks * 2 + hi) ^ (l31 & 15)) << 4);
+  for (int ks = 0; ks < 8; ++ks) k_off[ks] = k_frag_off(l31, hi, ks);
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) v_off[kk] = l31 * 128 + (((kk * 2 + hi) ^ ((l31 >> 1) & 7)) << 4);
+  for (int kk = 0; kk < 4; ++kk) v_off[kk] = v_frag_off(l31, hi, kk);
   int c_tt = 0;
   f32x2_t rsa[4];
-
-  auto max3 = [](float a, float b, float cc) __attribute__((always_inline)) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(cc));
-    return d;
-  };
-  auto exp_block = [&](f32x16_t& sb) __attribute__((always_inline)) {   // P = exp2(S - m_run) for one key block
-    const f32x2_t m2 = {m_run, m_run};
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const f32x2_t x = f32x2_t{sb[r], sb[r + 1]} - m2;
-      const f32x2_t pp = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
-      sb[r] = pp[0];
-      sb[r + 1] = pp[1];
-      rsa[(r >> 1) & 3] += pp;
-    }
-  };
 
   auto phase1 = [&](int buf, bool more) __attribute__((always_inline)) {
     dma_drain_barrier();
     if (more) dma_k(buf ^ 1);
-    const unsigned char* kp = Ks + buf * SUB_B;
-    {
-      bf16x8_t kf[8];
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + k_off[ks]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        s[0] = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s[0]);
-        kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + 32 * 256 + k_off[ks]);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks)
-        s[1] = AM_MFMA_32x32x16(kf[ks], qf[ks], ks == 0 ? zero16 : s[1]);
-    }
+    qk_block(Ks + buf * SUB_B, k_off, qf, zero16, s[0], s[1]);
     // ---- softmax, first half: row max, rescale, exp of key block 0 ------------------------------
-    asm volatile("s_nop 15" : "+v"(s[0]), "+v"(s[1]));     // MFMA result -> inline-asm VALU read hazard
     const int valid = p.sk - c_tt * KVBLK;
     if (++c_tt == tiles_per_chunk) c_tt = 0;
-    if (valid < KVBLK) {                                    // rare: the partial last tile of a chunk
-      mask_keys(s[0], 0, valid - 4 * hi);
-      mask_keys(s[1], 32, valid - 4 * hi);
-    }
-    float mxa[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(s[0][i], s[1][i], s[0][i + 4]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 4], s[0][i + 8]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 8], s[0][i + 12]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mxa[i] = max3(mxa[i], s[1][i + 12], mxa[i]);
-    float mx = max3(mxa[0], mxa[1], max3(mxa[2], mxa[3], mxa[3]));
-    {
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-      mx = max3(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
-    }
-    mx -= m_run;
-    if (first || !__all(mx <= (float)DEFER)) {
-      const float delta = first ? mx : fmaxf(mx, 0.f);
-      const float alpha = first ? 0.f : __builtin_amdgcn_exp2f(-delta);
-      first = false;
-      m_run += delta;
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-    }
+    rebase<DEFER>(row_max64(s[0], s[1], valid, hi), m_run, l_run, o, first);
 #pragma unroll
     for (int i = 0; i < 4; ++i) rsa[i] = f32x2_t{0.f, 0.f};
-    exp_block(s[0]);
+    exp_block(s[0], m_run, rsa);
   };
 
   auto phase2 = [&](int buf, bool more) __attribute__((always_inline)) {
@@ -821,42 +712,13 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_balanced_kernel(am_attn_args 
     if (more) dma_v(buf ^ 1);
     const unsigned char* vp = Vs + buf * SUB_B;
     bf16x8_t vf[8];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-        vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + d * 32 * 128 + v_off[kk]);
+    pv_fetch(vp, v_off, vf);
     // ---- softmax, second half: exp of key block 1, row sums, bf16 P ---------------------------------
-    exp_block(s[1]);
-    {
-      const f32x2_t rs = (rsa[0] + rsa[1]) + (rsa[2] + rsa[3]);
-      l_run += rs[0] + rs[1];
-    }
+    exp_block(s[1], m_run, rsa);
+    fold_row_sums(rsa, l_run);
     bf16x8_t pf[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      u32x4_t w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        w[e] = pack_bf2(s[kk >> 1][(kk & 1) * 8 + 2 * e], s[kk >> 1][(kk & 1) * 8 + 2 * e + 1]);
-      pf[kk] = __builtin_bit_cast(bf16x8_t, w);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        o[d] = AM_MFMA_32x32x16(vf[kk * 4 + d], pf[kk], o[d]);
-        vf[kk * 4 + d] = *reinterpret_cast<const bf16x8_t*>(vp + d * 32 * 128 + v_off[kk + 2]);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int kk = 2; kk < 4; ++kk)
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-        o[d] = AM_MFMA_32x32x16(vf[(kk - 2) * 4 + d], pf[kk], o[d]);
+    p_pack(s[0], s[1], pf);
+    pv_block(vp, v_off, vf, pf, o);
   };
 
   dma_k(0);
@@ -878,14 +740,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_balanced_kernel(am_attn_args 
   if (q < p.sq) {
     bf16_t* op = p.O + ((int64_t)seq * p.sq + q) * p.ldo + head * HD + 4 * hi;
 #pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        u32x2_t w;
-        w[0] = pack_bf2(o[d][4 * g] * inv, o[d][4 * g + 1] * inv);
-        w[1] = pack_bf2(o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv);
-        *reinterpret_cast<u32x2_t*>(op + d * 32 + 8 * g) = w;
-      }
+    for (int d = 0; d < 4; ++d) store_block(op + d * 32, o[d], inv);
   }
 }
 

@@ -5,8 +5,9 @@ Runs a fixed table of attention and GEMM calls in this (fresh) process, in a fix
 the sha256 of every output, by call.  The table reaches every host-side branch that picks a kernel or a launch plan:
 
   bf16 attention, in both libraries (bfloat16, float16); (nseq, H, sq, sk per chunk, chunks):
-    a short stream in the 4-wave geometry (1, 2, 300, 300, 1); the resident key stream (16, 8, 1030, 144, 1); three chunks on the 4x64
-    kernel (1, 2, 520, 1100, 3); the split tail (1, 2, 2320, 4200, 1) and (1, 1, 2432, 4097, 1) with exactly 128 tail rows; a short last
+    a short stream in the 4-wave geometry (1, 2, 300, 300, 1); the resident key stream (16, 8, 1030, 144, 1) and, with no tail tile,
+    (16, 8, 1030, 128, 1); three chunks on the 4x64 kernel (1, 2, 520, 1100, 3) and on the balanced kernel (code 78: the chunk advance of
+    its two DMA cursors); the split tail (1, 2, 2320, 4200, 1) and (1, 1, 2432, 4097, 1) with exactly 128 tail rows; a short last
     block that is not split (1, 2, 2320, 300, 1); the two-pass sequence rows = 1 / state_mode 1 -> state_mode 2 -> rows = 2 at
     (2, 2, 2320, 1100, 4); the forced kernels 28, 58, 60, 68, 78, 90, 98 at (1, 2, 520, 1100, 1)
   fp8 attention: forms 0, 100, 200, 400 at (1, 2, 2320, 2320, 1), (2, 1, 300, 4111, 2) and (1, 1, 256, 577, 1); a stream under 8 tiles
@@ -117,12 +118,14 @@ def main():
         for defer in (0, 8):
             attn(f"short stream defer={defer}", (1, 2, 300, 300, 1), defer_log2=defer)
             attn(f"resident defer={defer}", (16, 8, 1030, 144, 1), defer_log2=defer)
+            attn(f"resident, no tail tile defer={defer}", (16, 8, 1030, 128, 1), defer_log2=defer)
             attn(f"three chunks defer={defer}", (1, 2, 520, 1100, 3), defer_log2=defer)
             attn(f"split tail defer={defer}", (1, 2, 2320, 4200, 1), defer_log2=defer)
             attn(f"short last block, not split defer={defer}", (1, 2, 2320, 300, 1), defer_log2=defer)
             two_pass(ops.attention, f"attention {name} two-pass defer={defer}", (2, 2, 2320, 1100, 4), dtype, defer_log2=defer)
         for code in FORCED:
             attn(f"code {code}", (1, 2, 520, 1100, 1), defer_log2=code)
+        attn("code 78, three chunks", (1, 2, 520, 1100, 3), defer_log2=78)
         attn("split tail, nseq*H = 4", (2, 2, 2320, 4200, 1))
         again = sha(ops.attention(*operands(1, 1, 2432, 4097, 1, dtype), 2432, 4097))
         assert again == first, f"{name}: the split tail changed its output after the partials scratch grew"
