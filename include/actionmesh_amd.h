@@ -637,6 +637,11 @@ int am_icp_step(const am_icp_args* args, void* workspace_dev, size_t workspace_b
  *   projection:     view = X @ R + T (row vectors), x_ndc = fx * view.x / view.z + px, y likewise, depth = view.z;
  *   raster:         at 2S x 2S, pixel centre x = 1 - (2 col + 1) / W, y = 1 - (2 row + 1) / H; covered when the three
  *                   perspective-corrected, unclipped barycentrics are all > 0; the nearest face wins, ties -> lowest index.
+ *                   "> 0" is strict: a centre on an edge or on a vertex of a face is not covered by it, so a centre on the edge
+ *                   two faces share belongs to neither.  The barycentrics are p_i = t_i / max(t_0 + t_1 + t_2, 1e-8),
+ *                   t_i = w_i z_j z_k, w_i = edge function / (area + 1e-8); the depth is interpolated with p_i / sum(p) and a
+ *                   centre whose depth comes out negative is not covered.  In exact arithmetic that depth is z_0 z_1 z_2 / sum(w_i
+ *                   z_j z_k) with a positive sum, so a face with exactly one vertex behind the camera is covered nowhere.
  *                   A face is skipped (1) altogether when all three depths are negative, (2) altogether when the signed area
  *                   (twice it: the edge function of one projected vertex against the other two) is within 1e-8 of zero, and (3) at every
  *                   sub-pixel centre outside the closed box [min x, max x] x [min y, max y] of its three projected vertices -
@@ -645,6 +650,9 @@ int am_icp_step(const am_icp_args* args, void* workspace_dev, size_t workspace_b
  *                   vertex's projection, to the part of the cone inside the box (often none of it);
  *   resolve to S x S: mask = covered sub-pixels / 4; normal of sub-pixel (2i, 2j) through n @ R + T / 2, normalised,
  *                   (n + 1) / 2, clamped; rgba8 = trunc(255 * (normal * mask + 1 - mask)), alpha = trunc(255 * mask).
+ *                   An uncovered sub-pixel (2i, 2j) has n = 0.  n @ R + T / 2 can cancel: with T = (0, 0, 2) a view normal of exactly
+ *                   -z (a face parallel to the image that looks at the camera) maps to 0 up to rounding and has no stable
+ *                   colour - the reference's shading, not a defect here; the preview's cameras have |T| = 3.
  * offsets / corners are the vertex -> corner CSR of `faces` as am_vertex_normals defines it below (int32[n_verts + 1] and
  * int32[3 n_faces], ascending corner id): corner / 3 along a vertex's corners is its faces in face-index order, one entry per
  * occurrence, which is the order of the sum above.  Faces and CSR are validated on the device as there: every index is compared
