@@ -21,7 +21,10 @@
 // between two barriers one group runs its matrix interval - O += V^T(t) P^T(t) and S(t+1) = K(t+1) Q^T, 8 MFMAs of 64
 // cycles - at s_setprio 1 while its partner on every SIMD runs its softmax interval (32 exp2 / row max / row sum / fp8
 // packing per lane, plus the fragment ds_reads and LDS-DMA issue for its next matrix interval).  K8 / V8T tiles (8 + 8 KiB
-// per 64 keys) arrive by LDS-DMA into a 4-deep ring, three tiles ahead, retired by one counted vmcnt(2) per tile.
+// per 64 keys) arrive by LDS-DMA into a ring of NSTAGE = 8 slots, retired by one counted vmcnt per tile.  Per kernel (a wave moves
+// two pieces of a tile, in the 4 x 64 kernel four): 8-wave - tile t+5 is staged in the softmax interval of tile t, vmcnt(4) leaves
+// tiles t+4, t+5 in flight; 4 x 64 - tile t+4 is staged in iteration t, vmcnt(8) leaves tiles t+2, t+3 in flight; product kernel -
+// tile t+4 is staged in iteration t, vmcnt(4) leaves tiles t+2, t+3 in flight.
 // Online softmax with a deferred re-base (threshold 2^3): p = 2^(s - m_run + 5), so p <= 2^8 fits e4m3 (max 448) and
 // probabilities down to 2^-14 of the row maximum survive the 2^-9 flush (per form: the last paragraph).  The VALU interval is what bounds this kernel, so
 // it carries only what has to be there - 32 exp2, 16 packs, 11 max3 per lane and tile: the scores are born relative to the
@@ -77,6 +80,13 @@ __device__ inline uint32_t nan_e4m3(float x) { return (__builtin_bit_cast(uint32
 __device__ inline uint32_t nan4_e4m3(uint32_t a, uint32_t b) {      // for the four bytes packed from bflo(a), bfhi(a), bflo(b), bfhi(b)
   return nan_e4m3(bflo(a)) | (nan_e4m3(bfhi(a)) << 8) | (nan_e4m3(bflo(b)) << 16) | (nan_e4m3(bfhi(b)) << 24);
 }
+// Four values, clamped, as the four e4m3 bytes of one word (the NaN bytes are OR-ed over it by the caller)
+__device__ inline uint32_t pack4_e4m3(float v0, float v1, float v2, float v3) {
+  int w = 0;
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(v0), clamp_e4m3(v1), w, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(v2), clamp_e4m3(v3), w, true);
+  return (uint32_t)w;
+}
 
 // key held by k-slot `pos` of a 64-key tile (see header)
 __host__ __device__ inline int kperm(int pos) {
@@ -101,11 +111,27 @@ __device__ inline float other_half(float x, int hi) {
 // vmcnt(0) in front of every reload).  asm volatile statements keep their order among themselves and, with the "memory"
 // clobber, against the LDS reads / LDS-DMA around them.  hipcc pads nothing for an asm statement: every consumer of these
 // results sits behind at least four further MFMAs or a barrier plus tens of instructions (16-pass MFMA: 19 wait states).
-__device__ inline void mfma_f8_acc(f32x16_t& d, const i32x8_t& a, const i32x8_t& b, int one) {          // d += a x b
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(d) : "v"(a), "v"(b), "v"(one) : "memory");
-}
-__device__ inline void mfma_f8_init(f32x16_t& d, const i32x8_t& a, const i32x8_t& b, const f32x16_t& c, int one) {   // d = a x b + c
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %3, %4, %4 op_sel_hi:[0,0,0]" : "=&v"(d) : "v"(a), "v"(b), "v"(c), "v"(one) : "memory");
+// What varies between the kernels is the register file of the accumulator D and of the B operand (an AccVGPR operand is an
+// "a" constraint), and whether the A and B block scales are one register or two: family NAME is NAME_acc (d += a x b) and
+// NAME_init (d = a x b + c).
+#define F8_MFMA(C, SA, SB) "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, " C ", " SA ", " SB " op_sel_hi:[0,0,0]"
+#define F8_MFMA_FAMILY(NAME, D, B)                                                                                                   \
+  __device__ __forceinline__ void NAME##_acc(f32x16_t& d, const i32x8_t& a, const i32x8_t& b, int sa, int sb) {                       \
+    asm volatile(F8_MFMA("%0", "%3", "%4") : "+" D(d) : "v"(a), B(b), "v"(sa), "v"(sb) : "memory");                                   \
+  }                                                                                                                                  \
+  __device__ __forceinline__ void NAME##_init(f32x16_t& d, const i32x8_t& a, const i32x8_t& b, const f32x16_t& c, int sa, int sb) {   \
+    asm volatile(F8_MFMA("%3", "%4", "%5") : "=&" D(d) : "v"(a), B(b), "v"(c), "v"(sa), "v"(sb) : "memory");                          \
+  }
+F8_MFMA_FAMILY(mfma_vv, "v", "v")      // everything in arch VGPRs (the two 8-wave kernels: see attn_fp8p_kernel for why it names no AccVGPR)
+F8_MFMA_FAMILY(mfma_av, "a", "v")      // the accumulator in AccVGPRs (the 4 x 64 kernel's P.V)
+F8_MFMA_FAMILY(mfma_va, "v", "a")      // the B operand in AccVGPRs (the 4 x 64 kernel's QK^T: Q is parked there)
+#undef F8_MFMA_FAMILY
+__device__ __forceinline__ void mfma_f8_acc(f32x16_t& d, const i32x8_t& a, const i32x8_t& b, int one) { mfma_vv_acc(d, a, b, one, one); }
+__device__ __forceinline__ void mfma_f8_init(f32x16_t& d, const i32x8_t& a, const i32x8_t& b, const f32x16_t& c, int one) { mfma_vv_init(d, a, b, c, one, one); }
+
+// A lane's 32-byte MFMA operand from its two 16-byte loads
+__device__ __forceinline__ i32x8_t frag32(u32x4_t a, u32x4_t b) {
+  return i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
 }
 
 #define F8_BARRIER() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -119,16 +145,13 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const bf16_t* __restric
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (int64_t)gridDim.x * blockDim.x) {
     const u32x4_t a = *reinterpret_cast<const u32x4_t*>(src + i * 16);
     const u32x4_t b = *reinterpret_cast<const u32x4_t*>(src + i * 16 + 8);
+    auto pk = [&](uint32_t x, uint32_t y) { return pack4_e4m3(bflo(x) * mul, bfhi(x) * mul, bflo(y) * mul, bfhi(y) * mul); };
     u32x4_t o;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      int w0 = 0, w1 = 0;
-      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(bflo(a[2 * e]) * mul), clamp_e4m3(bfhi(a[2 * e]) * mul), w0, false);
-      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(bflo(a[2 * e + 1]) * mul), clamp_e4m3(bfhi(a[2 * e + 1]) * mul), w0, true);
-      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(bflo(b[2 * e]) * mul), clamp_e4m3(bfhi(b[2 * e]) * mul), w1, false);
-      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(bflo(b[2 * e + 1]) * mul), clamp_e4m3(bfhi(b[2 * e + 1]) * mul), w1, true);
-      o[e] = (uint32_t)w0 | nan4_e4m3(a[2 * e], a[2 * e + 1]);
-      o[2 + e] = (uint32_t)w1 | nan4_e4m3(b[2 * e], b[2 * e + 1]);
+      const uint32_t w0 = pk(a[2 * e], a[2 * e + 1]), w1 = pk(b[2 * e], b[2 * e + 1]);
+      o[e] = w0 | nan4_e4m3(a[2 * e], a[2 * e + 1]);
+      o[2 + e] = w1 | nan4_e4m3(b[2 * e], b[2 * e + 1]);
     }
     *reinterpret_cast<u32x4_t*>(dst + i * 16) = o;
   }
@@ -157,11 +180,8 @@ __global__ __launch_bounds__(256) void quant_vt_kernel(const bf16_t* __restrict_
     uint32_t o[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      int x = 0;
       const float v0 = at(kperm(4 * q)), v1 = at(kperm(4 * q + 1)), v2 = at(kperm(4 * q + 2)), v3 = at(kperm(4 * q + 3));
-      x = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(v0), clamp_e4m3(v1), x, false);
-      x = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(v2), clamp_e4m3(v3), x, true);
-      o[q] = (uint32_t)x | nan_e4m3(v0) | (nan_e4m3(v1) << 8) | (nan_e4m3(v2) << 16) | (nan_e4m3(v3) << 24);
+      o[q] = pack4_e4m3(v0, v1, v2, v3) | nan_e4m3(v0) | (nan_e4m3(v1) << 8) | (nan_e4m3(v2) << 16) | (nan_e4m3(v3) << 24);
     }
     uint8_t* d = dst + row * sk_pad + tile * KT;
 #pragma unroll
@@ -184,6 +204,151 @@ struct f8_args {
 };
 constexpr int F8_STATE_LD = AM_ATTN_STATE_LD;   // floats per saved row: O[128], m, l, pad - the layout of the bf16 kernels (am_attention64.hip)
 
+// ------------------------------------------------------------------------------------------------------------------
+// What the three kernels below share: everything but their schedules.  A 32-row query block is one wave's MFMA tile: lane
+// (row l31 = lane & 31, half hi = lane >> 5).
+// ------------------------------------------------------------------------------------------------------------------
+// Q fragment of k-step s of the row at `qrow8` (the row's 128 bytes): channels 64 s + 32 hi .. + 31.  The caller pins what it has
+// loaded ("+v" / "+a"), so that it has landed before any LDS-DMA piece is counted.
+__device__ __forceinline__ i32x8_t q_frag(const uint8_t* qrow8, int hi, int s) {
+  const uint8_t* qp = qrow8 + hi * 32 + s * 64;
+  return frag32(*reinterpret_cast<const u32x4_t*>(qp), *reinterpret_cast<const u32x4_t*>(qp + 16));
+}
+
+// The saved row (O[128], m, l) and the output row.  A lane holds channels 32 cb + 8 g + 4 hi .. + 3 of its row in registers
+// 4 g .. 4 g + 3 of block cb; `sp` / `op` is the row, chosen by the caller.  Per block and by value: the callers' O is an array of
+// four register sets, and an array handed over by reference is promoted to one wide vector.
+__device__ __forceinline__ f32x16_t load_state_block(const float* sp, int cb, int hi) {
+  f32x16_t o;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const f32x4_t t4 = *reinterpret_cast<const f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[4 * g + i] = t4[i];
+  }
+  return o;
+}
+__device__ __forceinline__ void store_state_block(float* sp, int cb, int hi, f32x16_t o) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    *reinterpret_cast<f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi) = f32x4_t{o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
+}
+__device__ __forceinline__ void store_state_ml(float* sp, int hi, float m, float l) {
+  if (hi == 0) { sp[HD8] = m; sp[HD8 + 1] = l; }
+}
+__device__ __forceinline__ void store_out_block(bf16_t* op, int cb, int hi, f32x16_t o, float inv) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const u32x2_t w = {pack_bf2(o[4 * g] * inv, o[4 * g + 1] * inv), pack_bf2(o[4 * g + 2] * inv, o[4 * g + 3] * inv)};
+    *reinterpret_cast<u32x2_t*>(op + cb * 32 + 8 * g + 4 * hi) = w;
+  }
+}
+__device__ __forceinline__ float* state_row(const f8_args& p, int64_t row) { return p.state + row * F8_STATE_LD; }       // row = sh * sq_pad + query row
+__device__ __forceinline__ bf16_t* out_row(const f8_args& p, int seq, int head, int qrow) { return p.O + ((int64_t)seq * p.sq + qrow) * p.ldo + head * HD8; }
+
+// Keys past a chunk's end (its last tile holds tail_valid of them) are set to -inf: register r of the keys-0-31 half `sa` / the
+// keys-32-63 half `sb` holds key 32 kb + (r & 3) + 8 (r >> 2) + 4 hi.  Rare, once per chunk: the 32 lane masks are computed here, in
+// the branch, not held in 64 SGPRs across the loop.
+__device__ __forceinline__ void mask_chunk_end(f32x16_t& sa, f32x16_t& sb, int tail_valid, int hi) {
+  int tv = tail_valid - 4 * hi;
+  asm volatile("" : "+v"(tv));
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if ((r & 3) + 8 * (r >> 2) >= tv) sa[r] = -INFINITY;
+    if (32 + (r & 3) + 8 * (r >> 2) >= tv) sb[r] = -INFINITY;
+  }
+}
+
+// The ring of NSTAGE slots, one tile each: K8 [64][128] at 0, V8T [128][64] at 8192.  Byte offset of tile tt's slot.
+__device__ __forceinline__ int ring_off(int tt) { return (tt & (NSTAGE - 1)) * STAGE_BYTES; }
+
+// The source of the next tile to stage, wave-uniform: it starts at tile t_begin of the walk over the chunks (chunk_first + i) %
+// chunk_total, advances one tile per call inside a chunk, jumps at a chunk's end, and past the `total` tiles the workgroup walks it
+// stays on the last one (the re-fetch lands in a ring slot nobody reads).  A tile goes to LDS in 1 KiB pieces, one wave-instruction
+// each, of 8 key rows of K8 / 16 channel rows of V8T: lane-linear destination, swizzle on the source unit (K: unit ^ ((row >> 1) & 7),
+// V^T: unit ^ ((row >> 2) & 3)); k_lane_off / v_lane_off are the lane's source offsets in piece `wave` (and in every piece 4 i further).
+struct TileSource {
+  const f8_args& p;
+  const int total;
+  uint32_t k_lane_off, v_lane_off;
+  const uint8_t *base_k, *base_v, *st_k, *st_v;
+  int st_n, st_ti, st_pos;                                   // tiles staged; tile in its chunk; the chunk's position in the walk
+  __device__ __forceinline__ int64_t chunk_off(int pos) const {          // physical chunk of walk position `pos`
+    int c = p.chunk_first + pos;
+    if (p.chunk_total > 0 && c >= p.chunk_total) c -= p.chunk_total;
+    return (int64_t)c * p.chunk_stride;
+  }
+  __device__ __forceinline__ TileSource(const f8_args& p, int sh, int wave, int lane, int t_begin, int total) : p(p), total(total) {
+    const int kr = wave * 8 + (lane >> 3);
+    k_lane_off = (uint32_t)kr * HD8 + (uint32_t)(((lane & 7) ^ ((kr >> 1) & 7)) << 4);
+    const int vr = wave * 16 + (lane >> 2);
+    v_lane_off = (uint32_t)vr * (uint32_t)p.sk_pad + (uint32_t)(((lane & 3) ^ ((vr >> 2) & 3)) << 4);
+    base_k = p.K + (int64_t)sh * ((int64_t)p.sk_pad * HD8);
+    base_v = p.Vt + (int64_t)sh * ((int64_t)p.sk_pad * HD8);
+    st_n = 0, st_ti = t_begin % p.tiles_per_chunk, st_pos = t_begin / p.tiles_per_chunk;
+    st_k = base_k + chunk_off(st_pos) + (int64_t)st_ti * KT * HD8;
+    st_v = base_v + chunk_off(st_pos) + (int64_t)st_ti * KT;
+  }
+  __device__ __forceinline__ int slot() const { return ring_off(st_n); }       // where the tile under the cursor goes
+  __device__ __forceinline__ void advance() {
+    ++st_n;
+    if (st_n < total) {
+      if (st_ti == p.tiles_per_chunk - 1) {
+        st_ti = 0;
+        ++st_pos;
+        st_k = base_k + chunk_off(st_pos);
+        st_v = base_v + chunk_off(st_pos);
+      } else {
+        ++st_ti;
+        st_k += KT * HD8;
+        st_v += KT;
+      }
+    }
+  }
+};
+
+// One piece by asm (the 4 x 64 and the product kernel): scalar base + 32-bit lane offset -> LDS at (M0) + lane * 16.  hipcc neither
+// tracks it nor pads it: the counted vmcnt in front of the tile barrier is the only wait there is.
+__device__ __forceinline__ const uint8_t* uniform(const uint8_t* q) {
+  const uint64_t u = reinterpret_cast<uint64_t>(q);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hh = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+  return reinterpret_cast<const uint8_t*>(((uint64_t)hh << 32) | lo);
+}
+__device__ __forceinline__ void dma_piece(const uint8_t* src, uint32_t lane_off, unsigned char* smem, unsigned lds_off) {
+  const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<uintptr_t>((lds_ptr_t)smem) + lds_off);
+  const uint8_t* s = uniform(src);
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(s), "s"(lds) : "memory");
+}
+
+// Fragment reads of a staged tile.  K8 tile: row = key, 8 units of 16 B; fragment (kb, s) is units 4 s + 2 hi + {0, 1} of key
+// 32 kb + l31, unit ^ ((row >> 1) & 7).  V8T tile: row = channel, 4 units; fragment cb is units 2 hi + {0, 1} of channel 32 cb + l31,
+// unit ^ ((row >> 2) & 3).  A kernel keeps the lane's offsets k_off[s][e] / v_off[e] in scalars of its own, one function call per
+// element: inside a struct the six are promoted to two vectors and the address arithmetic is scheduled as vector operations.
+__device__ __forceinline__ int k_frag_off(int l31, int hi, int s, int e) { return l31 * HD8 + (((4 * s + 2 * hi + e) ^ ((l31 >> 1) & 7)) << 4); }
+__device__ __forceinline__ int v_frag_off(int l31, int hi, int e) { return 8192 + l31 * 64 + (((2 * hi + e) ^ ((l31 >> 2) & 3)) << 4); }
+__device__ __forceinline__ i32x8_t read_k_frag(const unsigned char* smem, int tt, int kb, int off0, int off1) {      // 2 ds_read_b128 each
+  const unsigned char* slot = smem + ring_off(tt) + kb * 32 * HD8;
+  return frag32(*reinterpret_cast<const u32x4_t*>(slot + off0), *reinterpret_cast<const u32x4_t*>(slot + off1));
+}
+__device__ __forceinline__ i32x8_t read_v_frag(const unsigned char* smem, int tt, int cb, int off0, int off1) {
+  const unsigned char* slot = smem + ring_off(tt) + cb * 32 * 64;
+  return frag32(*reinterpret_cast<const u32x4_t*>(slot + off0), *reinterpret_cast<const u32x4_t*>(slot + off1));
+}
+
+// PROF: s_memtime stamps of workgroup (0, 0), tiles 64 .. 71: prof[wave][tile - 64][slot]
+template <bool PROF>
+struct Stamp {
+  unsigned long long* prof;
+  int sh, wave, lane;
+  __device__ __forceinline__ void operator()(int t, int slot) const {
+    if (PROF && blockIdx.x == 0 && sh == 0 && t >= 64 && t < 72) {
+      unsigned long long c;
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c));
+      if (lane == 0) prof[(wave * 8 + (t - 64)) * 8 + slot] = c;
+    }
+  }
+};
+
 // ABL: timing ablations (numerically meaningless; tools/kernel_bench.py --ablate-fp8): 1 no exponentials, 2 no LDS-DMA in the
 // loop, 4 no fragment reads in the loop, 8 no MFMAs in the loop, 16 no row max.
 // MODE (round 3, the forms the bf16 kernels already had): 0 = one pass; 1 = stop after the chunks walked and save the un-normalised
@@ -205,17 +370,10 @@ __global__ __launch_bounds__(512, 2) void attn_fp8_kernel(f8_args p) {
   // ---- Q fragments: lane (row l31, half hi), k-step s: channels 64 s + 32 hi .. + 31
   const int qrow = qblk * 256 + wave * 32 + l31;
   i32x8_t qf[2];
-  {
-    const uint8_t* qp = p.Q + ((int64_t)sh * p.sq_pad + qrow) * HD8 + hi * 32;
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const u32x4_t a = *reinterpret_cast<const u32x4_t*>(qp + s * 64);
-      const u32x4_t b = *reinterpret_cast<const u32x4_t*>(qp + s * 64 + 16);
-      qf[s] = i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-    }
+  for (int s = 0; s < 2; ++s) qf[s] = q_frag(p.Q + ((int64_t)sh * p.sq_pad + qrow) * HD8, hi, s);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(qf[s]));     // waited for here, before any LDS-DMA is in flight
-  }
+  for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(qf[s]));     // waited for here, before any LDS-DMA is in flight
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- LDS-DMA: per tile every wave moves one 1 KiB piece of K8 (8 key rows) and one of V8T (16 channel rows);
@@ -224,87 +382,34 @@ __global__ __launch_bounds__(512, 2) void attn_fp8_kernel(f8_args p) {
   const int t_begin = MODE == 3 ? (int)((int64_t)blockIdx.z * all_tiles / gridDim.z) : 0;
   const int t_end = MODE == 3 ? (int)((int64_t)(blockIdx.z + 1) * all_tiles / gridDim.z) : all_tiles;
   const int total_tiles = t_end - t_begin;                 // tiles this workgroup walks (local numbering 0 .. total_tiles-1)
-  const int kr = wave * 8 + (lane >> 3);
-  const uint32_t k_lane_off = (uint32_t)kr * HD8 + (uint32_t)(((lane & 7) ^ ((kr >> 1) & 7)) << 4);
-  const int vr = wave * 16 + (lane >> 2);
-  const uint32_t v_lane_off = (uint32_t)vr * (uint32_t)p.sk_pad + (uint32_t)(((lane & 3) ^ ((vr >> 2) & 3)) << 4);
-  // running source of the next tile to stage (wave-uniform): advances one tile per call, jumps at chunk ends, and stays
-  // on the last tile past the end of the stream (the re-fetch lands in a ring slot nobody reads)
-  const uint8_t* base_k = p.K + (int64_t)sh * p.sk_pad * HD8;
-  const uint8_t* base_v = p.Vt + (int64_t)sh * p.sk_pad * HD8;
-  int st_n = 0, st_ti = t_begin % p.tiles_per_chunk, st_pos = t_begin / p.tiles_per_chunk;     // st_pos: chunk position in the walk
-  auto chunk_off = [&](int pos) __attribute__((always_inline)) {          // physical chunk of walk position `pos`
-    int c = p.chunk_first + pos;
-    if (p.chunk_total > 0 && c >= p.chunk_total) c -= p.chunk_total;
-    return (int64_t)c * p.chunk_stride;
-  };
-  const uint8_t* st_k = base_k + chunk_off(st_pos) + (int64_t)st_ti * KT * HD8;
-  const uint8_t* st_v = base_v + chunk_off(st_pos) + (int64_t)st_ti * KT;
+  TileSource src(p, sh, wave, lane, t_begin, total_tiles);
   auto stage = [&]() __attribute__((always_inline)) {
-    unsigned char* slot = smem + (st_n & (NSTAGE - 1)) * STAGE_BYTES;
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(st_k + k_lane_off), (lds_ptr_t)(slot + wave * 1024), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(st_v + v_lane_off), (lds_ptr_t)(slot + 8192 + wave * 1024), 16, 0, 0);
-    ++st_n;
-    if (st_n < total_tiles) {
-      if (st_ti == p.tiles_per_chunk - 1) {
-        st_ti = 0;
-        ++st_pos;
-        st_k = base_k + chunk_off(st_pos);
-        st_v = base_v + chunk_off(st_pos);
-      } else {
-        ++st_ti;
-        st_k += KT * HD8;
-        st_v += KT;
-      }
-    }
+    unsigned char* slot = smem + src.slot();
+    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src.st_k + src.k_lane_off), (lds_ptr_t)(slot + wave * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src.st_v + src.v_lane_off), (lds_ptr_t)(slot + 8192 + wave * 1024), 16, 0, 0);
+    src.advance();
   };
 
-  // ---- fragment addresses
-  // K8 tile: row r (key), 8 units of 16 B; lane reads units 4 s + 2 hi + {0, 1} of key 32 kb + l31
-  const int ksw = (l31 >> 1) & 7;                          // (row >> 1) & 7 with row = 32 kb + l31
-  int k_off[2][2];
+  // ---- fragments
+  int k_off[2][2], v_off[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
-    for (int e = 0; e < 2; ++e) k_off[s][e] = l31 * HD8 + (((4 * s + 2 * hi + e) ^ ksw) << 4);
-  // V8T tile: row c (channel), 4 units; lane reads units 2 hi + {0, 1} of channel 32 cb + l31
-  const int vsw = (l31 >> 2) & 3;
-  int v_off[2];
+    for (int e = 0; e < 2; ++e) k_off[s][e] = k_frag_off(l31, hi, s, e);
 #pragma unroll
-  for (int e = 0; e < 2; ++e) v_off[e] = 8192 + l31 * 64 + (((2 * hi + e) ^ vsw) << 4);
-
+  for (int e = 0; e < 2; ++e) v_off[e] = v_frag_off(l31, hi, e);
   i32x8_t kf[2][2], vf[4];
+  auto read_k1 = [&](int tt, int kb, int s2) __attribute__((always_inline)) { kf[kb][s2] = read_k_frag(smem, tt, kb, k_off[s2][0], k_off[s2][1]); };
+  auto read_v1 = [&](int tt, int cb) __attribute__((always_inline)) { vf[cb] = read_v_frag(smem, tt, cb, v_off[0], v_off[1]); };
   auto read_k = [&](int tt) __attribute__((always_inline)) {
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + kb * 32 * HD8 + k_off[s][0]);
-        const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + kb * 32 * HD8 + k_off[s][1]);
-        kf[kb][s] = i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-      }
-  };
-  auto read_v1 = [&](int tt, int cb) __attribute__((always_inline)) {          // one V^T fragment (2 ds_read_b128)
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES;
-    const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + cb * 32 * 64 + v_off[0]);
-    const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + cb * 32 * 64 + v_off[1]);
-    vf[cb] = i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-  };
-  auto read_k1 = [&](int tt, int kb, int s2) __attribute__((always_inline)) {   // one K fragment (2 ds_read_b128)
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES;
-    const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + kb * 32 * HD8 + k_off[s2][0]);
-    const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + kb * 32 * HD8 + k_off[s2][1]);
-    kf[kb][s2] = i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
+      for (int s = 0; s < 2; ++s) read_k1(tt, kb, s);
   };
   auto read_v = [&](int tt) __attribute__((always_inline)) {
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES;
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + cb * 32 * 64 + v_off[0]);
-      const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + cb * 32 * 64 + v_off[1]);
-      vf[cb] = i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-    }
+    for (int cb = 0; cb < 4; ++cb) read_v1(tt, cb);
   };
 
   f32x16_t o[4], sc[2];
@@ -317,17 +422,11 @@ __global__ __launch_bounds__(512, 2) void attn_fp8_kernel(f8_args p) {
   // the scores already in registers.  m_run starts at P_SHIFT (binit = 0) and the first tile always re-bases.
   float m_run = P_SHIFT, l_run = 0.f;
   if (MODE == 2) {                                           // resume: (O, m, l) of this lane's row as the first pass left them
-    const float* sp = p.state + ((int64_t)sh * p.sq_pad + qrow) * F8_STATE_LD;
+    const float* sp = state_row(p, (int64_t)sh * p.sq_pad + qrow);
     m_run = sp[HD8];
     l_run = hi == 0 ? sp[HD8 + 1] : 0.f;                     // the two half-lanes' sums are joined at the end
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4_t t4 = *reinterpret_cast<const f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[cb][4 * g + i] = t4[i];
-      }
+    for (int cb = 0; cb < 4; ++cb) o[cb] = load_state_block(sp, cb, hi);
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) asm volatile("" : "+v"(o[cb]));      // landed before the first LDS-DMA piece is counted
     asm volatile("" : "+v"(m_run), "+v"(l_run));
@@ -478,28 +577,20 @@ __global__ __launch_bounds__(512, 2) void attn_fp8_kernel(f8_args p) {
   // ---- normalise and store: lane (row l31, half hi) holds channels 32 cb + 8 g + 4 hi .. + 3 in registers 4 g .. 4 g + 3
   l_run += other_half(l_run, hi);
   if (MODE == 1 || MODE == 3) {          // un-normalised (O, m, l): the state of the first pass / a partial of the split last block
-    float* sp = MODE == 1 ? p.state + ((int64_t)sh * p.sq_pad + qrow) * F8_STATE_LD
+    float* sp = MODE == 1 ? state_row(p, (int64_t)sh * p.sq_pad + qrow)
                           : p.part + (((int64_t)sh * gridDim.z + blockIdx.z) * 256 + (qrow - p.qblk_base * 256)) * F8_STATE_LD;
     if (MODE == 1 || qrow < p.sq) {
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi) = f32x4_t{o[cb][4 * g], o[cb][4 * g + 1], o[cb][4 * g + 2], o[cb][4 * g + 3]};
-      if (hi == 0) { sp[HD8] = m_run; sp[HD8 + 1] = l_run; }
+      for (int cb = 0; cb < 4; ++cb) store_state_block(sp, cb, hi, o[cb]);
+      store_state_ml(sp, hi, m_run, l_run);
     }
     return;
   }
   if (qrow < p.sq) {
     const float inv = 1.f / l_run;
-    bf16_t* op = p.O + ((int64_t)seq * p.sq + qrow) * p.ldo + head * HD8;
+    bf16_t* op = out_row(p, seq, head, qrow);
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const u32x2_t w = {pack_bf2(o[cb][4 * g] * inv, o[cb][4 * g + 1] * inv), pack_bf2(o[cb][4 * g + 2] * inv, o[cb][4 * g + 3] * inv)};
-        *reinterpret_cast<u32x2_t*>(op + cb * 32 + 8 * g + 4 * hi) = w;
-      }
+    for (int cb = 0; cb < 4; ++cb) store_out_block(op, cb, hi, o[cb], inv);
   }
 }
 
@@ -533,15 +624,9 @@ __global__ __launch_bounds__(512, 2) void attn_fp8_kernel(f8_args p) {
 #define X_PIN(x) asm volatile("" : "+v"(x))
 constexpr int X_AHEAD = 4;                 // tiles staged ahead of the one whose K is being multiplied
 
-__device__ __forceinline__ void x_pv(f32x16_t& o, const i32x8_t& v, const i32x8_t& p, int one) {            // o (AGPR) += v x p
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+a"(o) : "v"(v), "v"(p), "v"(one) : "memory");
-}
-__device__ __forceinline__ void x_qk_first(f32x16_t& d, const i32x8_t& k, const i32x8_t& q, const f32x16_t& c, int one) {   // d = k x q + c
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %3, %4, %4 op_sel_hi:[0,0,0]" : "=&v"(d) : "v"(k), "a"(q), "v"(c), "v"(one) : "memory");
-}
-__device__ __forceinline__ void x_qk_acc(f32x16_t& d, const i32x8_t& k, const i32x8_t& q, int one) {       // d += k x q
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(d) : "v"(k), "a"(q), "v"(one) : "memory");
-}
+__device__ __forceinline__ void x_pv(f32x16_t& o, const i32x8_t& v, const i32x8_t& p, int one) { mfma_av_acc(o, v, p, one, one); }           // o (AGPR) += v x p
+__device__ __forceinline__ void x_qk_first(f32x16_t& d, const i32x8_t& k, const i32x8_t& q, const f32x16_t& c, int one) { mfma_va_init(d, k, q, c, one, one); }   // d = k x q + c
+__device__ __forceinline__ void x_qk_acc(f32x16_t& d, const i32x8_t& k, const i32x8_t& q, int one) { mfma_va_acc(d, k, q, one, one); }       // d += k x q
 
 // row max of one 32-query block over the tile's 64 keys: 20 single-instruction steps (four v_max3 chains, the other half-lane)
 struct XRowMax {
@@ -626,26 +711,14 @@ __global__ __launch_bounds__(256, 1) void attn_fp8x64_kernel(f8_args p, unsigned
   const int qblk = p.qblk_base + blockIdx.x, sh = blockIdx.y;          // sh = seq * heads + head
   const int seq = sh / p.heads, head = sh - seq * p.heads;
   const int q0 = qblk * 256 + wave * 64;                               // block j: rows q0 + 32 j + l31
-  auto stamp = [&](int t, int slot) __attribute__((always_inline)) {
-    if (PROF && blockIdx.x == 0 && sh == 0 && t >= 64 && t < 72) {
-      unsigned long long c;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c));
-      if (lane == 0) prof[(wave * 8 + (t - 64)) * 8 + slot] = c;
-    }
-  };
+  const Stamp<PROF> stamp{prof, sh, wave, lane};
 
-  // ---- Q fragments of both blocks (B operand of QK^T), parked in AccVGPRs: lane (row l31, half hi), k-step s: channels 64 s + 32 hi ..
+  // ---- Q fragments of both blocks (B operand of QK^T), parked in AccVGPRs
   i32x8_t qf[2][2];
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const uint8_t* qp = p.Q + ((int64_t)sh * p.sq_pad + q0 + 32 * j + l31) * HD8 + hi * 32;
+  for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const u32x4_t a = *reinterpret_cast<const u32x4_t*>(qp + s * 64);
-      const u32x4_t b = *reinterpret_cast<const u32x4_t*>(qp + s * 64 + 16);
-      qf[j][s] = i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-    }
-  }
+    for (int s = 0; s < 2; ++s) qf[j][s] = q_frag(p.Q + ((int64_t)sh * p.sq_pad + q0 + 32 * j + l31) * HD8, hi, s);
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -663,17 +736,12 @@ __global__ __launch_bounds__(256, 1) void attn_fp8x64_kernel(f8_args p, unsigned
   if (MODE == 2) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const float* sp = p.state + ((int64_t)sh * p.sq_pad + q0 + 32 * j + l31) * F8_STATE_LD;
+      const float* sp = state_row(p, (int64_t)sh * p.sq_pad + q0 + 32 * j + l31);
       m_run[j] = sp[HD8];
       l_run[j] = hi == 0 ? sp[HD8 + 1] : 0.f;
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4_t t4 = *reinterpret_cast<const f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) o[j][cb][4 * g + i] = t4[i];
-        }
+        o[j][cb] = load_state_block(sp, cb, hi);
         asm volatile("" : "+a"(o[j][cb]));
       }
       asm volatile("" : "+v"(m_run[j]), "+v"(l_run[j]));
@@ -693,81 +761,28 @@ __global__ __launch_bounds__(256, 1) void attn_fp8x64_kernel(f8_args p, unsigned
     X_PIN(bs[j]);
   }
 
-  // ---- LDS-DMA: a tile = 8 pieces of K8 (8 key rows each) + 8 of V8T (16 channel rows each), 1 KiB per wave-instruction; wave w
-  // moves pieces w and w + 4 of each.  Lane-linear destination, swizzle on the source unit (K: unit ^ ((row >> 1) & 7), V^T:
-  // unit ^ ((row >> 2) & 3)) - both are the same for pieces w and w + 4, so one lane offset serves both.
+  // ---- LDS-DMA: a tile = 8 pieces of K8 + 8 of V8T; wave w moves pieces w and w + 4 of each (the swizzle is the same for both, so
+  // one lane offset serves both)
   const int all_tiles = p.nchunks * p.tiles_per_chunk;
-  const int kr = wave * 8 + (lane >> 3);
-  const uint32_t k_lane_off = (uint32_t)kr * HD8 + (uint32_t)(((lane & 7) ^ ((kr >> 1) & 7)) << 4);
-  const int vr = wave * 16 + (lane >> 2);
-  const uint32_t v_lane_off = (uint32_t)vr * (uint32_t)p.sk_pad + (uint32_t)(((lane & 3) ^ ((vr >> 2) & 3)) << 4);
-  const uint8_t* base_k = p.K + (int64_t)sh * p.sk_pad * HD8;
-  const uint8_t* base_v = p.Vt + (int64_t)sh * p.sk_pad * HD8;
-  int st_n = 0, st_ti = 0, st_pos = 0;
-  auto chunk_off = [&](int pos) __attribute__((always_inline)) {
-    int c = p.chunk_first + pos;
-    if (p.chunk_total > 0 && c >= p.chunk_total) c -= p.chunk_total;
-    return (int64_t)c * p.chunk_stride;
-  };
-  const uint8_t* st_k = base_k + chunk_off(0);
-  const uint8_t* st_v = base_v + chunk_off(0);
-  const unsigned smem_lds = (unsigned)reinterpret_cast<uintptr_t>((lds_ptr_t)smem);
-  auto uniform = [](const uint8_t* q) __attribute__((always_inline)) {
-    const uint64_t u = reinterpret_cast<uint64_t>(q);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hh = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-    return reinterpret_cast<const uint8_t*>(((uint64_t)hh << 32) | lo);
-  };
-  // one piece: scalar base + 32-bit lane offset -> LDS at (M0) + lane * 16; asm: hipcc neither tracks it nor pads it (the counted
-  // vmcnt in front of the tile barrier is the only wait there is)
-  auto dma_piece = [&](const uint8_t* src, uint32_t lane_off, unsigned lds_off) __attribute__((always_inline)) {
-    const unsigned lds = __builtin_amdgcn_readfirstlane(smem_lds + lds_off);
-    const uint8_t* s = uniform(src);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(s), "s"(lds) : "memory");
-  };
+  TileSource src(p, sh, wave, lane, 0, all_tiles);
   auto stage_k = [&](int i) __attribute__((always_inline)) {       // piece wave + 4 i of the K8 tile under the cursor
-    dma_piece(st_k + i * (32 * HD8), k_lane_off, (unsigned)((st_n & (NSTAGE - 1)) * STAGE_BYTES + (wave + 4 * i) * 1024));
+    dma_piece(src.st_k + i * (32 * HD8), src.k_lane_off, smem, (unsigned)(src.slot() + (wave + 4 * i) * 1024));
   };
   auto stage_v = [&](int i) __attribute__((always_inline)) {
-    dma_piece(st_v + (int64_t)i * 64 * p.sk_pad, v_lane_off, (unsigned)((st_n & (NSTAGE - 1)) * STAGE_BYTES + 8192 + (wave + 4 * i) * 1024));
+    dma_piece(src.st_v + (int64_t)i * 64 * p.sk_pad, src.v_lane_off, smem, (unsigned)(src.slot() + 8192 + (wave + 4 * i) * 1024));
   };
-  auto stage_advance = [&]() __attribute__((always_inline)) {      // past the end of the stream the cursor stays on the last tile
-    ++st_n;
-    if (st_n < all_tiles) {
-      if (st_ti == p.tiles_per_chunk - 1) {
-        st_ti = 0;
-        ++st_pos;
-        st_k = base_k + chunk_off(st_pos);
-        st_v = base_v + chunk_off(st_pos);
-      } else {
-        ++st_ti;
-        st_k += KT * HD8;
-        st_v += KT;
-      }
-    }
-  };
+  auto stage_advance = [&]() __attribute__((always_inline)) { src.advance(); };
 
-  // ---- fragment addresses (as in attn_fp8_kernel): K8 fragment n = (kb = n & 1, s = n >> 1): key 32 kb + l31, units 4 s + 2 hi + {0, 1};
-  // V8T fragment cb: channel 32 cb + l31, units 2 hi + {0, 1}
-  const int ksw = (l31 >> 1) & 7, vsw = (l31 >> 2) & 3;
+  // ---- fragments: K8 fragment n = (kb = n & 1, s = n >> 1), V8T fragment cb
   int k_off[2][2], v_off[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
-    for (int e = 0; e < 2; ++e) k_off[s][e] = l31 * HD8 + (((4 * s + 2 * hi + e) ^ ksw) << 4);
+    for (int e = 0; e < 2; ++e) k_off[s][e] = k_frag_off(l31, hi, s, e);
 #pragma unroll
-  for (int e = 0; e < 2; ++e) v_off[e] = 8192 + l31 * 64 + (((2 * hi + e) ^ vsw) << 4);
-  auto k_frag = [&](int tt, int n) __attribute__((always_inline)) {
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES + (n & 1) * 32 * HD8;
-    const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + k_off[n >> 1][0]);
-    const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + k_off[n >> 1][1]);
-    return i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-  };
-  auto v_frag = [&](int tt, int cb) __attribute__((always_inline)) {
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES + cb * 32 * 64;
-    const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + v_off[0]);
-    const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + v_off[1]);
-    return i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-  };
+  for (int e = 0; e < 2; ++e) v_off[e] = v_frag_off(l31, hi, e);
+  auto k_frag = [&](int tt, int n) __attribute__((always_inline)) { return read_k_frag(smem, tt, n & 1, k_off[n >> 1][0], k_off[n >> 1][1]); };
+  auto v_frag = [&](int tt, int cb) __attribute__((always_inline)) { return read_v_frag(smem, tt, cb, v_off[0], v_off[1]); };
 
   // ---- pipeline registers (arch file)
   f32x16_t s0[2];              // block 0: S(t) on entry of an iteration, S(t+1) on exit
@@ -808,15 +823,7 @@ __global__ __launch_bounds__(256, 1) void attn_fp8x64_kernel(f8_args p, unsigned
   for (int n = 0; n < 4; ++n) { fr[n] = zero8; X_PIN(fr[n]); }       // "V8T(-1)" = 0
 
   // rare: keys past the end of a chunk (its last tile), once per chunk
-  auto mask_tail = [&](f32x16_t& sa, f32x16_t& sb) __attribute__((always_inline)) {
-    int tv = tail_valid - 4 * hi;
-    asm volatile("" : "+v"(tv));          // the 32 lane masks are computed here, in the rare branch, not held in 64 SGPRs across the loop
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if ((r & 3) + 8 * (r >> 2) >= tv) sa[r] = -INFINITY;
-      if (32 + (r & 3) + 8 * (r >> 2) >= tv) sb[r] = -INFINITY;
-    }
-  };
+  auto mask_tail = [&](f32x16_t& sa, f32x16_t& sb) __attribute__((always_inline)) { mask_chunk_end(sa, sb, tail_valid, hi); };
   auto o_settle = [&](int j) __attribute__((always_inline)) {          // in-flight P.V results of block j have landed (asm MFMAs: nothing is padded)
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+a"(o[j][0]), "+a"(o[j][1]), "+a"(o[j][2]), "+a"(o[j][3]));
   };
@@ -983,25 +990,17 @@ __global__ __launch_bounds__(256, 1) void attn_fp8x64_kernel(f8_args p, unsigned
     float l = l_run[j];
     l += other_half(l, hi);
     if (MODE == 1) {
-      float* sp = p.state + ((int64_t)sh * p.sq_pad + qrow) * F8_STATE_LD;
+      float* sp = state_row(p, (int64_t)sh * p.sq_pad + qrow);
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi) = f32x4_t{o[j][cb][4 * g], o[j][cb][4 * g + 1], o[j][cb][4 * g + 2], o[j][cb][4 * g + 3]};
-      if (hi == 0) { sp[HD8] = m_run[j]; sp[HD8 + 1] = l; }
+      for (int cb = 0; cb < 4; ++cb) store_state_block(sp, cb, hi, o[j][cb]);
+      store_state_ml(sp, hi, m_run[j], l);
       continue;
     }
     if (qrow < p.sq) {
       const float inv = 1.f / l;
-      bf16_t* op = p.O + ((int64_t)seq * p.sq + qrow) * p.ldo + head * HD8;
+      bf16_t* op = out_row(p, seq, head, qrow);
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const u32x2_t w = {pack_bf2(o[j][cb][4 * g] * inv, o[j][cb][4 * g + 1] * inv), pack_bf2(o[j][cb][4 * g + 2] * inv, o[j][cb][4 * g + 3] * inv)};
-          *reinterpret_cast<u32x2_t*>(op + cb * 32 + 8 * g + 4 * hi) = w;
-        }
+      for (int cb = 0; cb < 4; ++cb) store_out_block(op, cb, hi, o[j][cb], inv);
     }
   }
 }
@@ -1019,17 +1018,8 @@ __global__ __launch_bounds__(256, 1) void attn_fp8x64_kernel(f8_args p, unsigned
 // Registers: 256 per wave; O (64) and Q (16) in AccVGPRs, scores ping-pong (S(t+1) is born while S(t) is exponentiated), P doubled,
 // four rotating fragment sets (V^T channel block i at MFMA i, K fragment i at MFMA 4 + i).
 // ==================================================================================================================
-// all-arch-VGPR forms of the MFMA wrappers for the two-waves-per-SIMD kernel below: as soon as a kernel names an AccVGPR hipcc splits a
-// 256-register budget 128 / 128 and spills the arch side into the accumulator side; without one it hands out all 256 as arch VGPRs
-__device__ __forceinline__ void p_pv(f32x16_t& o, const i32x8_t& v, const i32x8_t& p, int one) {
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(o) : "v"(v), "v"(p), "v"(one) : "memory");
-}
-__device__ __forceinline__ void p_qk_first(f32x16_t& d, const i32x8_t& k, const i32x8_t& q, const f32x16_t& c, int one) {
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %3, %4, %4 op_sel_hi:[0,0,0]" : "=&v"(d) : "v"(k), "v"(q), "v"(c), "v"(one) : "memory");
-}
-__device__ __forceinline__ void p_qk_acc(f32x16_t& d, const i32x8_t& k, const i32x8_t& q, int one) {
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(d) : "v"(k), "v"(q), "v"(one) : "memory");
-}
+// This kernel names NO AccVGPR (its MFMAs are the mfma_vv family): as soon as a kernel names one hipcc splits a 256-register budget
+// 128 / 128 and spills the arch side into the accumulator side; without one it hands out all 256 as arch VGPRs.
 // exp2 + e4m3 pack of one 16-score register set as single-instruction steps (the row sums are NOT here: they run on the matrix pipe,
 // l += ones x P^T, from the ROUNDED probabilities).  FAST = 0: 16 v_exp_f32 + 8 v_cvt_pk_fp8_f32, each pack a round behind its
 // exponentials.  FAST = 1 (attn_dtype "fp8_fast"): the scores are born as z = 8 (s - m_run + 5) + 56 and ONE v_cvt_pk_u8_f32 per score
@@ -1092,29 +1082,16 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
   const int qblk = p.qblk_base + blockIdx.x, sh = blockIdx.y;
   const int seq = sh / p.heads, head = sh - seq * p.heads;
   const int qrow = qblk * 256 + wave * 32 + l31;
-  auto stamp = [&](int t, int slot) __attribute__((always_inline)) {
-    if (PROF && blockIdx.x == 0 && sh == 0 && t >= 64 && t < 72) {
-      unsigned long long c;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c));
-      if (lane == 0) prof[(wave * 8 + (t - 64)) * 8 + slot] = c;
-    }
-  };
+  const Stamp<PROF> stamp{prof, sh, wave, lane};
   // score units: u = SC (s - m_run + P_SHIFT) + OFF  (exact: log2 units; fast: eighths of an octave, biased so that u IS the e4m3 byte)
   constexpr float SC = FAST ? 8.f : 1.f, OFF = FAST ? 56.f : 0.f;
   constexpr float TOP = SC * P_SHIFT + OFF, THR = SC * (P_SHIFT + DEFER_T) + OFF;
 
   i32x8_t qf[2];
-  {
-    const uint8_t* qp = p.Q + ((int64_t)sh * p.sq_pad + qrow) * HD8 + hi * 32;
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const u32x4_t a = *reinterpret_cast<const u32x4_t*>(qp + s * 64);
-      const u32x4_t b = *reinterpret_cast<const u32x4_t*>(qp + s * 64 + 16);
-      qf[s] = i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-    }
+  for (int s = 0; s < 2; ++s) qf[s] = q_frag(p.Q + ((int64_t)sh * p.sq_pad + qrow) * HD8, hi, s);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(qf[s]));
-  }
+  for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(qf[s]));
   f32x16_t o[4], lacc;                                       // lacc: every register = the row sum of this lane's query (ones x P^T)
   float m_run = P_SHIFT;
 #pragma unroll
@@ -1124,19 +1101,13 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
 #pragma unroll
   for (int r = 0; r < 16; ++r) lacc[r] = 0.f;
   if (MODE == 2) {
-    const float* sp = p.state + ((int64_t)sh * p.sq_pad + qrow) * F8_STATE_LD;
+    const float* sp = state_row(p, (int64_t)sh * p.sq_pad + qrow);
     m_run = sp[HD8];
     const float l0 = sp[HD8 + 1];
 #pragma unroll
     for (int r = 0; r < 16; ++r) lacc[r] = l0;
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4_t t4 = *reinterpret_cast<const f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[cb][4 * g + i] = t4[i];
-      }
+    for (int cb = 0; cb < 4; ++cb) o[cb] = load_state_block(sp, cb, hi);
     asm volatile("" : "+v"(m_run));
   }
 #pragma unroll
@@ -1150,75 +1121,30 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
   for (int r = 0; r < 16; ++r) bs[r] = SC * (P_SHIFT - m_run) + OFF;
   X_PIN(bs);
 
-  // ---- LDS-DMA: per tile every wave moves one 1 KiB piece of K8 (8 key rows) and one of V8T (16 channel rows)
+  // ---- LDS-DMA: per tile every wave moves one 1 KiB piece of K8 and one of V8T
   const int all_tiles = p.nchunks * p.tiles_per_chunk;
-  const int kr = wave * 8 + (lane >> 3);
-  const uint32_t k_lane_off = (uint32_t)kr * HD8 + (uint32_t)(((lane & 7) ^ ((kr >> 1) & 7)) << 4);
-  const int vr = wave * 16 + (lane >> 2);
-  const uint32_t v_lane_off = (uint32_t)vr * (uint32_t)p.sk_pad + (uint32_t)(((lane & 3) ^ ((vr >> 2) & 3)) << 4);
-  const uint8_t* base_k = p.K + (int64_t)sh * p.sk_pad * HD8;
-  const uint8_t* base_v = p.Vt + (int64_t)sh * p.sk_pad * HD8;
-  int st_n = 0, st_ti = 0, st_pos = 0;
-  auto chunk_off = [&](int pos) __attribute__((always_inline)) {
-    int c = p.chunk_first + pos;
-    if (p.chunk_total > 0 && c >= p.chunk_total) c -= p.chunk_total;
-    return (int64_t)c * p.chunk_stride;
-  };
-  const uint8_t* st_k = base_k + chunk_off(0);
-  const uint8_t* st_v = base_v + chunk_off(0);
-  const unsigned smem_lds = (unsigned)reinterpret_cast<uintptr_t>((lds_ptr_t)smem);
-  auto uniform = [](const uint8_t* q) __attribute__((always_inline)) {
-    const uint64_t u = reinterpret_cast<uint64_t>(q);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hh = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-    return reinterpret_cast<const uint8_t*>(((uint64_t)hh << 32) | lo);
-  };
-  auto dma_piece = [&](const uint8_t* src, uint32_t lane_off, unsigned lds_off) __attribute__((always_inline)) {
-    const unsigned lds = __builtin_amdgcn_readfirstlane(smem_lds + lds_off);
-    const uint8_t* s = uniform(src);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(s), "s"(lds) : "memory");
-  };
-  auto stage_k = [&]() __attribute__((always_inline)) { dma_piece(st_k, k_lane_off, (unsigned)((st_n & (NSTAGE - 1)) * STAGE_BYTES + wave * 1024)); };
-  auto stage_v = [&]() __attribute__((always_inline)) { dma_piece(st_v, v_lane_off, (unsigned)((st_n & (NSTAGE - 1)) * STAGE_BYTES + 8192 + wave * 1024)); };
-  auto stage_advance = [&]() __attribute__((always_inline)) {
-    ++st_n;
-    if (st_n < all_tiles) {
-      if (st_ti == p.tiles_per_chunk - 1) {
-        st_ti = 0;
-        ++st_pos;
-        st_k = base_k + chunk_off(st_pos);
-        st_v = base_v + chunk_off(st_pos);
-      } else {
-        ++st_ti;
-        st_k += KT * HD8;
-        st_v += KT;
-      }
-    }
-  };
+  TileSource src(p, sh, wave, lane, 0, all_tiles);
+  auto stage_k = [&]() __attribute__((always_inline)) { dma_piece(src.st_k, src.k_lane_off, smem, (unsigned)(src.slot() + wave * 1024)); };
+  auto stage_v = [&]() __attribute__((always_inline)) { dma_piece(src.st_v, src.v_lane_off, smem, (unsigned)(src.slot() + 8192 + wave * 1024)); };
+  auto stage_advance = [&]() __attribute__((always_inline)) { src.advance(); };
 
-  const int ksw = (l31 >> 1) & 7, vsw = (l31 >> 2) & 3;
   int k_off[2][2], v_off[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
-    for (int e = 0; e < 2; ++e) k_off[s][e] = l31 * HD8 + (((4 * s + 2 * hi + e) ^ ksw) << 4);
+    for (int e = 0; e < 2; ++e) k_off[s][e] = k_frag_off(l31, hi, s, e);
 #pragma unroll
-  for (int e = 0; e < 2; ++e) v_off[e] = 8192 + l31 * 64 + (((2 * hi + e) ^ vsw) << 4);
+  for (int e = 0; e < 2; ++e) v_off[e] = v_frag_off(l31, hi, e);
   bool in_loop = false;
   i32x8_t stale = {0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838};
   X_PIN(stale);
   auto k_frag = [&](int tt, int kb, int s2) __attribute__((always_inline)) {
     if ((ABL & 32) && in_loop) return stale;
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES + kb * 32 * HD8;
-    const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + k_off[s2][0]);
-    const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + k_off[s2][1]);
-    return i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
+    return read_k_frag(smem, tt, kb, k_off[s2][0], k_off[s2][1]);
   };
   auto v_frag = [&](int tt, int cb) __attribute__((always_inline)) {
     if ((ABL & 32) && in_loop) return stale;
-    const unsigned char* slot = smem + (tt & (NSTAGE - 1)) * STAGE_BYTES + cb * 32 * 64;
-    const u32x4_t a = *reinterpret_cast<const u32x4_t*>(slot + v_off[0]);
-    const u32x4_t b = *reinterpret_cast<const u32x4_t*>(slot + v_off[1]);
-    return i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
+    return read_v_frag(smem, tt, cb, v_off[0], v_off[1]);
   };
   auto ones_frag = [&]() __attribute__((always_inline)) {
     if ((ABL & 32) && in_loop) return stale;
@@ -1227,9 +1153,7 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
     // the 18 fragment reads of a tile two-way conflicted = the 10 % SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE the r04 PMC pass
     // showed where the bf16 kernel has ~0
     const unsigned char* q = smem + P_LDS_ONES;
-    const u32x4_t a = *reinterpret_cast<const u32x4_t*>(q);
-    const u32x4_t b = *reinterpret_cast<const u32x4_t*>(q + 16);
-    return i32x8_t{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
+    return frag32(*reinterpret_cast<const u32x4_t*>(q), *reinterpret_cast<const u32x4_t*>(q + 16));
   };
 
   // Scores: the kb = 0 half (keys 0-31 of the tile) lives in ONE register set - its next tile's QK^T MFMAs are issued behind the last
@@ -1250,25 +1174,20 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
   *reinterpret_cast<u32x4_t*>(smem + 7 * STAGE_BYTES + 8192 + tid * 16) = u32x4_t{0u, 0u, 0u, 0u};
   *reinterpret_cast<uint32_t*>(smem + P_LDS_ONES + tid * 4) = 0x38383838u;
   asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");        // tile 0 (tiles 1 .. 3 = 6 pieces stay in flight)
+  // QK^T of this lane's query: the K operand's block scale is qk_scale, Q's is 2^0
+  auto qk_first = [&](f32x16_t& d, const i32x8_t& k) __attribute__((always_inline)) { mfma_vv_init(d, k, qf[0], bs, qk_scale, one); };
+  auto qk_acc = [&](f32x16_t& d, const i32x8_t& k) __attribute__((always_inline)) { mfma_vv_acc(d, k, qf[1], qk_scale, one); };
   fa = k_frag(0, 0, 0); fb = k_frag(0, 1, 0); fc = k_frag(0, 0, 1);
-  {
-    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %3, %4, %5 op_sel_hi:[0,0,0]" : "=&v"(sa) : "v"(fa), "v"(qf[0]), "v"(bs), "v"(qk_scale), "v"(one) : "memory");
-    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %3, %4, %5 op_sel_hi:[0,0,0]" : "=&v"(sb[0]) : "v"(fb), "v"(qf[0]), "v"(bs), "v"(qk_scale), "v"(one) : "memory");
-    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(sa) : "v"(fc), "v"(qf[1]), "v"(qk_scale), "v"(one) : "memory");
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(fa), "+v"(fb), "+v"(fc));
-    fa = k_frag(0, 1, 1);
-    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(sb[0]) : "v"(fa), "v"(qf[1]), "v"(qk_scale), "v"(one) : "memory");
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(fa));
-  }
+  qk_first(sa, fa);
+  qk_first(sb[0], fb);
+  qk_acc(sa, fc);
+  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(fa), "+v"(fb), "+v"(fc));
+  fa = k_frag(0, 1, 1);
+  qk_acc(sb[0], fa);
+  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(fa));
   fa = zero8; fb = zero8; fc = zero8;                      // "V8T(-1)" channel blocks 0 .. 2
   X_PIN(fa); X_PIN(fb); X_PIN(fc);
 
-  auto qk_first = [&](f32x16_t& d, const i32x8_t& k) __attribute__((always_inline)) {
-    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %3, %4, %5 op_sel_hi:[0,0,0]" : "=&v"(d) : "v"(k), "v"(qf[0]), "v"(bs), "v"(qk_scale), "v"(one) : "memory");
-  };
-  auto qk_acc = [&](f32x16_t& d, const i32x8_t& k) __attribute__((always_inline)) {
-    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(d) : "v"(k), "v"(qf[1]), "v"(qk_scale), "v"(one) : "memory");
-  };
   auto o_settle = [&]() __attribute__((always_inline)) {
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(lacc));
   };
@@ -1286,15 +1205,7 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
     rm.mx = 0.f;
 #define STEPS_A(G) do { if (!(ABL & 8)) Half::template run<HN * (G) / 4, HN * ((G) + 1) / 4>(sa, pn, 0); } while (0)      /* share G of 4 of the kb = 0 half */
 #define STEPS_B(G) do { if (!(ABL & 8)) Half::template run<HN * (G) / 3, HN * ((G) + 1) / 3>(sbc, pn, 1); } while (0)     /* share G of 3 of the kb = 1 half */
-    if (last_of_chunk && tail_valid < KT) {                  // rare, wave-uniform: keys past the chunk's end
-      int tv = tail_valid - 4 * hi;
-      asm volatile("" : "+v"(tv));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if ((r & 3) + 8 * (r >> 2) >= tv) sa[r] = -INFINITY;
-        if (32 + (r & 3) + 8 * (r >> 2) >= tv) sbc[r] = -INFINITY;
-      }
-    }
+    if (last_of_chunk && tail_valid < KT) mask_chunk_end(sa, sbc, tail_valid, hi);      // rare, wave-uniform: keys past the chunk's end
     bool flag = false;
     float alpha = 1.f;
     if constexpr (FAST != 0) {
@@ -1304,27 +1215,27 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
       // rare path (a row max above the deferred threshold, or the first tile) shifts the scores and the splat, repeats the 16
       // conversions of the first half, and shifts the keys-32-63 scores of tile t+1 that j5 has already started on the old splat.
       X_FENCE();
-      p_pv(o[0], fa, pc, one);                      // j0
+      mfma_f8_acc(o[0], fa, pc, one);                      // j0
       if (!(ABL & 2)) stage_k();
       fa = v_frag(t + 7, 3);
       X_FENCE();
-      p_pv(o[1], fb, pc, one);                      // j1
+      mfma_f8_acc(o[1], fb, pc, one);                      // j1
       if (!(ABL & 2)) stage_v();
       fb = ones_frag();
       X_FENCE();
-      p_pv(o[2], fc, pc, one);                      // j2
+      mfma_f8_acc(o[2], fc, pc, one);                      // j2
       fc = k_frag(t + 1, 1, 0);
 #pragma unroll
       for (int n = 0; n < 5; ++n) if (!(ABL & 16)) rm.step(n, sa, sbc, hi);
       STEPS_A(0);
       X_FENCE();
-      p_pv(o[3], fa, pc, one);                      // j3
+      mfma_f8_acc(o[3], fa, pc, one);                      // j3
       fa = k_frag(t + 1, 0, 0);
 #pragma unroll
       for (int n = 5; n < 10; ++n) if (!(ABL & 16)) rm.step(n, sa, sbc, hi);
       STEPS_A(1);
       X_FENCE();
-      p_pv(lacc, fb, pc, one);                      // j4
+      mfma_f8_acc(lacc, fb, pc, one);                      // j4
       fb = k_frag(t + 1, 1, 1);
 #pragma unroll
       for (int n = 10; n < 15; ++n) if (!(ABL & 16)) rm.step(n, sa, sbc, hi);
@@ -1355,20 +1266,20 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
     // The four P.V MFMAs need nothing of this tile's softmax: they are issued first, so that they EXECUTE under the two LDS-DMA pieces
     // (~150 cycles of issue stall each) and under the dependent row-max chain - the wave's own stalls are covered by its own MFMAs.
     X_FENCE();
-    p_pv(o[0], fa, pc, one);                      // j0
+    mfma_f8_acc(o[0], fa, pc, one);                      // j0
     if (!(ABL & 2)) stage_k();
     fa = v_frag(t + 7, 3);                        // for j3: V8T(t-1) channel block 3  ((t - 1) & 7 == (t + 7) & 7)
     X_FENCE();
-    p_pv(o[1], fb, pc, one);                      // j1
+    mfma_f8_acc(o[1], fb, pc, one);                      // j1
     if (!(ABL & 2)) stage_v();
     fb = ones_frag();                             // for j4
     X_FENCE();
-    p_pv(o[2], fc, pc, one);                      // j2
+    mfma_f8_acc(o[2], fc, pc, one);                      // j2
     fc = k_frag(t + 1, 1, 0);                     // for j5
 #pragma unroll
     for (int n = 0; n < 10; ++n) if (!(ABL & 16)) rm.step(n, sa, sbc, hi);
     X_FENCE();
-    p_pv(o[3], fa, pc, one);                      // j3
+    mfma_f8_acc(o[3], fa, pc, one);                      // j3
     fa = k_frag(t + 1, 0, 0);                     // for j6
 #pragma unroll
     for (int n = 10; n < 20; ++n) if (!(ABL & 16)) rm.step(n, sa, sbc, hi);
@@ -1384,7 +1295,7 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
       flag = true;                                   // O and l are scaled at the end of the tile: their MFMAs of tile t-1 are in flight
     }
     X_FENCE();
-    p_pv(lacc, fb, pc, one);                      // j4: l += ones x P^T(t-1)
+    mfma_f8_acc(lacc, fb, pc, one);                      // j4: l += ones x P^T(t-1)
     fb = k_frag(t + 1, 1, 1);                     // for j7
     STEPS_A(0);
     X_FENCE();
@@ -1442,38 +1353,30 @@ __global__ __launch_bounds__(512, 2) void attn_fp8p_kernel(f8_args p, unsigned l
     i32x8_t plast;
 #pragma unroll
     for (int e = 0; e < 8; ++e) plast[e] = odd ? pf[1][e] : pf[0][e];       // by value: a select between two ADDRESSES keeps pf in memory
-    p_pv(o[0], fa, plast, one);
-    p_pv(o[1], fb, plast, one);
-    p_pv(o[2], fc, plast, one);
+    mfma_f8_acc(o[0], fa, plast, one);
+    mfma_f8_acc(o[1], fb, plast, one);
+    mfma_f8_acc(o[2], fc, plast, one);
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(fa), "+v"(fb));
     fa = v_frag(all_tiles - 1, 3);
     fb = ones_frag();
-    p_pv(o[3], fa, plast, one);
-    p_pv(lacc, fb, plast, one);
+    mfma_f8_acc(o[3], fa, plast, one);
+    mfma_f8_acc(lacc, fb, plast, one);
   }
   o_settle();
 
   const float l = lacc[0];
   if (MODE == 1) {
-    float* sp = p.state + ((int64_t)sh * p.sq_pad + qrow) * F8_STATE_LD;
+    float* sp = state_row(p, (int64_t)sh * p.sq_pad + qrow);
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<f32x4_t*>(sp + cb * 32 + 8 * g + 4 * hi) = f32x4_t{o[cb][4 * g], o[cb][4 * g + 1], o[cb][4 * g + 2], o[cb][4 * g + 3]};
-    if (hi == 0) { sp[HD8] = m_run; sp[HD8 + 1] = l; }
+    for (int cb = 0; cb < 4; ++cb) store_state_block(sp, cb, hi, o[cb]);
+    store_state_ml(sp, hi, m_run, l);
     return;
   }
   if (qrow < p.sq) {
     const float inv = 1.f / l;
-    bf16_t* op = p.O + ((int64_t)seq * p.sq + qrow) * p.ldo + head * HD8;
+    bf16_t* op = out_row(p, seq, head, qrow);
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const u32x2_t w = {pack_bf2(o[cb][4 * g] * inv, o[cb][4 * g + 1] * inv), pack_bf2(o[cb][4 * g + 2] * inv, o[cb][4 * g + 3] * inv)};
-        *reinterpret_cast<u32x2_t*>(op + cb * 32 + 8 * g + 4 * hi) = w;
-      }
+    for (int cb = 0; cb < 4; ++cb) store_out_block(op, cb, hi, o[cb], inv);
   }
 }
 
@@ -1512,34 +1415,28 @@ extern "C" int am_attention_quantize_fp8(const am_attn_args* a, uint8_t* q8, uin
   return AM_OK;
 }
 
-// One launcher per kernel.  Every instantiation needs more than 64 KiB of dynamic LDS; it raises its own limit the first time it is
-// launched on a device, so the switch statements below are the only list of instantiations.
+// One launcher.  Every instantiation needs more than 64 KiB of dynamic LDS; it raises its own limit the first time it is launched on
+// a device (the kernel is a template argument: one flag per instantiation), so the switch statements below are the only list of
+// instantiations.
+template <auto KERNEL, int BLOCK, int LDS_BYTES, typename... A>
+static int launch_f8(dim3 grid, hipStream_t st, A... args) {
+  AM_ONCE_PER_DEVICE({
+    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+  });
+  hipLaunchKernelGGL(KERNEL, grid, dim3(BLOCK), LDS_BYTES, st, args...);
+  return AM_OK;
+}
 template <int ABL, int MODE>
 static int launch_fp8(const f8_args& p, dim3 grid, hipStream_t st) {
-  AM_ONCE_PER_DEVICE({
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8_kernel<ABL, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               NSTAGE * STAGE_BYTES));
-  });
-  hipLaunchKernelGGL((attn_fp8_kernel<ABL, MODE>), grid, dim3(512), NSTAGE * STAGE_BYTES, st, p);
-  return AM_OK;
+  return launch_f8<attn_fp8_kernel<ABL, MODE>, 512, NSTAGE * STAGE_BYTES>(grid, st, p);
 }
 template <int ABL, int MODE, bool PROF = false>
 static int launch_fp8x64(const f8_args& p, dim3 grid, hipStream_t st, unsigned long long* prof = nullptr) {
-  AM_ONCE_PER_DEVICE({
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8x64_kernel<ABL, MODE, PROF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               NSTAGE * STAGE_BYTES));
-  });
-  hipLaunchKernelGGL((attn_fp8x64_kernel<ABL, MODE, PROF>), grid, dim3(256), NSTAGE * STAGE_BYTES, st, p, prof);
-  return AM_OK;
+  return launch_f8<attn_fp8x64_kernel<ABL, MODE, PROF>, 256, NSTAGE * STAGE_BYTES>(grid, st, p, prof);
 }
 template <int ABL, int MODE, int FAST = 0, bool PROF = false>
 static int launch_fp8p(const f8_args& p, dim3 grid, hipStream_t st, unsigned long long* prof = nullptr) {
-  AM_ONCE_PER_DEVICE({
-    AM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8p_kernel<ABL, MODE, FAST, PROF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               P_LDS_BYTES));
-  });
-  hipLaunchKernelGGL((attn_fp8p_kernel<ABL, MODE, FAST, PROF>), grid, dim3(512), P_LDS_BYTES, st, p, prof);
-  return AM_OK;
+  return launch_f8<attn_fp8p_kernel<ABL, MODE, FAST, PROF>, 512, P_LDS_BYTES>(grid, st, p, prof);
 }
 
 // the kernels' view of a call: all query blocks from block 0, no partials

@@ -37,7 +37,7 @@ KERNELS = {
     "wave8": ("exp2", "unrounded", "attn_fp8_kernel, softmax(): `ps2[0] += f32x2_t{e[0], e[1]}` adds the v_exp_f32 results; the "
                                    "v_cvt_pk_fp8_f32 of the same e[] comes after it"),
     "x64": ("exp2", "unrounded", "XExpSumPack::step: XES_AD adds get(sa, sb, a), the exponential left by XES_EX; XES_PK packs it a round later"),
-    "product": ("exp2", "rounded", "attn_fp8p_kernel, j4: `p_pv(lacc, fb, pc, one)` - l += ones x P^T on the packed e4m3 P; PHalf has no add"),
+    "product": ("exp2", "rounded", "attn_fp8p_kernel, j4: `mfma_f8_acc(lacc, fb, pc, one)` - l += ones x P^T on the packed e4m3 P; PHalf has no add"),
     "fast": ("byte", "rounded", "the same j4; P is the byte of PHalf<ABL, 1>::step (v_cvt_pk_u8_f32 of 8 (s - m_run + 5) + 56, saturating at 0)"),
 }
 # A key exponentiated against a running maximum `d` octaves above it reaches the numerator iff d < KEPT_BELOW: exp2 forms - e4m3(2^(5 - d))

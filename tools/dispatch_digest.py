@@ -11,7 +11,8 @@ the sha256 of every output, by call.  The table reaches every host-side branch t
     block that is not split (1, 2, 2320, 300, 1); the two-pass sequence rows = 1 / state_mode 1 -> state_mode 2 -> rows = 2 at
     (2, 2, 2320, 1100, 4); the forced kernels 28, 58, 60, 68, 78, 90, 98 at (1, 2, 520, 1100, 1)
   fp8 attention: forms 0, 100, 200, 400 at (1, 2, 2320, 2320, 1), (2, 1, 300, 4111, 2) and (1, 1, 256, 577, 1); a stream under 8 tiles
-    (1, 2, 300, 257, 1; not form 100, which the entry refuses there); the two-pass sequence; the split tail
+    (1, 2, 300, 257, 1; not form 100, which the entry refuses there); a key stream whose last tile is full, so that no key is masked,
+    (1, 1, 256, 576, 1) and under 8 tiles (1, 2, 300, 256, 1); the two-pass sequence; the split tail
   the partials scratch of either family: a split tail at nseq * H = 1 early, one at nseq * H = 4 later (the buffer grows: this process
     is fresh), then the first call again - asserted to give the first call's digest
   GEMM: every case of tests/_gemm_exact.CASES through the call tests/test_gemm_exact_gpu.py makes, in both libraries; ops.gemm_head_post
@@ -141,8 +142,10 @@ def main():
     for form in FP8_FORMS:
         for shape in ((1, 2, 2320, 2320, 1), (2, 1, 300, 4111, 2), (1, 1, 256, 577, 1)):
             attn8(f"form {form}", shape, ablate=form)
+        attn8(f"full last tile form {form}", (1, 1, 256, 576, 1), ablate=form)      # no key past the chunk's end: the mask branch is not taken
         if form != 100:      # the 4 x 64 form has no kernel for a stream under 8 tiles: the entry refuses the code there
             attn8(f"under 8 tiles form {form}", (1, 2, 300, 257, 1), ablate=form)
+            attn8(f"under 8 tiles, full last tile form {form}", (1, 2, 300, 256, 1), ablate=form)
         two_pass(ops.attention_fp8, f"attention fp8 two-pass form {form}", (2, 2, 2320, 1100, 4), torch.bfloat16, ablate=form)
     attn8("split tail", (1, 2, 2320, 4200, 1))
     attn8("split tail, nseq*H = 4", (2, 2, 2320, 4200, 1))
