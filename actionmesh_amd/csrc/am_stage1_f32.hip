@@ -1,0 +1,149 @@
+// The two row / elementwise kernels of the exact-fp32 Stage-I denoiser (HipDenoiser(dtype="float32"), actionmesh_amd/denoiser_f32.py)
+// that the exact-fp32 matrix path of am_f32.hip does not have:
+//   am_head_post_f32   qk-RMSNorm (+ RoPE) in place on a packed fp32 projection output      (attention_processor.py:121-130)
+//   am_flow_step_f32   classifier-free guidance + Euler step on an fp32 velocity             (guidance.py:95-118, scheduler.py:238-248)
+// fp32 and nothing narrower; every operation is rounded once, in the order include/actionmesh_amd.h writes it: the file is built
+// without the SLP vectoriser and WITHOUT contraction into fused multiply-adds (csrc/Makefile), so am_flow_step_f32 gives the bits of
+// the torch fp32 expression.  Nothing here depends on the 16-bit type: both library builds carry the same object code.
+// Both kernels are HBM-bound: 16-byte accesses, no LDS, no scratch.
+#include "am_common.h"
+
+namespace {
+
+constexpr int HP_D = 128;          // head_dim: one 128-float chunk = 32 lanes x float4 = half a wave
+constexpr int HP_CHUNKS = 8;       // chunks per 256-thread workgroup
+
+struct HeadPostF32 {
+  float* X; int64_t ldx; int off, head_stride;
+  int64_t chunks; int heads;
+  const float* w; float eps;
+  const float* rope_cos; const float* rope_sin; int rows_per_frame;
+};
+
+// One (row, head) chunk per half wave.  Sum of squares: the lane's four squares pairwise, then five xor-shuffle levels inside the
+// half wave - a tree of 1 (square) + 2 + 5 = 8 levels, the same tree for every chunk of every launch.
+__global__ __launch_bounds__(256) void head_post_f32_kernel(HeadPostF32 p) {
+  const int lane = threadIdx.x & 31;
+  const int64_t chunk = (int64_t)blockIdx.x * HP_CHUNKS + (threadIdx.x >> 5);
+  const bool valid = chunk < p.chunks;
+  const int64_t row = valid ? chunk / p.heads : 0;
+  const int head = valid ? (int)(chunk - row * p.heads) : 0;
+  float* xp = p.X + row * p.ldx + p.off + (int64_t)head * p.head_stride + 4 * lane;
+  f32x4_t x = valid ? *reinterpret_cast<const f32x4_t*>(xp) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float ss = (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+  const float r = 1.0f / sqrtf(ss * (1.0f / HP_D) + p.eps);          // torch.rsqrt(mean + eps); the division by 128 is exact
+  const f32x4_t wv = *reinterpret_cast<const f32x4_t*>(p.w + 4 * lane);
+  f32x4_t y;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) y[e] = x[e] * r * wv[e];
+  if (p.rope_cos) {
+    // the lane holds the interleaved pairs 2 lane and 2 lane + 1 of the chunk; every row of a frame shares the frame's angles
+    const int64_t t = (row / p.rows_per_frame) * (HP_D / 2) + 2 * lane;
+    const float c0 = p.rope_cos[t], c1 = p.rope_cos[t + 1], s0 = p.rope_sin[t], s1 = p.rope_sin[t + 1];
+    // rotary_embedding.py:72-124: out = x cos + rot(x) sin, rot(x)[2i] = -x[2i + 1], rot(x)[2i + 1] = x[2i]
+    const f32x4_t o = {y[0] * c0 + (-y[1]) * s0, y[1] * c0 + y[0] * s0, y[2] * c1 + (-y[3]) * s1, y[3] * c1 + y[2] * s1};
+    y = o;
+  }
+  if (valid) *reinterpret_cast<f32x4_t*>(xp) = y;
+}
+
+struct FlowF32 {
+  const float* v; float* lat; int nb; float scales[3]; float dt; int additive;
+  uint8_t unobs[256]; int64_t per_frame4, total4;       // in float4 units
+};
+
+__device__ __forceinline__ f32x4_t flow_f32(const FlowF32& a, f32x4_t lat, f32x4_t out, const f32x4_t* cur) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float o = out[e], prev = o;
+#pragma unroll
+    for (int b = 1; b < 4; ++b) {
+      if (b < a.nb) {
+        const float c = cur[b - 1][e];
+        o = o + a.scales[b - 1] * (c - prev);          // guidance.py:113-116: output += scale_i * (v_{i+1} - v_i)
+        prev = c;
+      }
+    }
+    const float step = a.dt * o;                       // scheduler.py:238-241: distances[i] * output_pred
+    lat[e] = a.additive ? lat[e] + step : lat[e] - step;
+  }
+  return lat;
+}
+
+// VEC: one float4 of the latents per thread; otherwise (a frame size that is no multiple of 4) one element per thread
+template <bool VEC>
+__global__ __launch_bounds__(256) void flow_step_f32_kernel(FlowF32 a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.total4) return;
+  if (!a.unobs[(int)(i / a.per_frame4)]) return;
+  if (VEC) {
+    const f32x4_t* v = reinterpret_cast<const f32x4_t*>(a.v);
+    f32x4_t* lat = reinterpret_cast<f32x4_t*>(a.lat);
+    f32x4_t cur[3];
+#pragma unroll
+    for (int b = 1; b < 4; ++b) cur[b - 1] = b < a.nb ? v[(int64_t)b * a.total4 + i] : f32x4_t{0.f, 0.f, 0.f, 0.f};
+    lat[i] = flow_f32(a, lat[i], v[i], cur);
+  } else {
+    float o = a.v[i], prev = o;
+    for (int b = 1; b < a.nb; ++b) {
+      const float c = a.v[(int64_t)b * a.total4 + i];
+      o = o + a.scales[b - 1] * (c - prev);
+      prev = c;
+    }
+    const float step = a.dt * o;
+    a.lat[i] = a.additive ? a.lat[i] + step : a.lat[i] - step;
+  }
+}
+
+inline bool al16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
+
+}  // namespace
+
+extern "C" int am_head_post_f32(float* X, int64_t ldx, int off, int head_stride, int64_t rows, int heads, const float* w, float eps,
+                                const float* rope_cos, const float* rope_sin, int frames, int rows_per_frame, void* stream) {
+  AM_CHECK(X && w, "am_head_post_f32: null operand");
+  AM_CHECK(rows > 0 && heads > 0 && heads <= 65535, "am_head_post_f32: bad shape rows=%lld heads=%d", (long long)rows, heads);
+  AM_CHECK(al16(X) && al16(w) && ldx % 4 == 0 && off % 4 == 0 && head_stride % 4 == 0,
+           "am_head_post_f32: X, w, ldx, off and head_stride must be 16-byte aligned");
+  AM_CHECK(off >= 0 && (heads == 1 || head_stride >= HP_D) && ldx >= off + (int64_t)(heads - 1) * head_stride + HP_D,
+           "am_head_post_f32: the heads' chunks overlap or run past the row (ldx=%lld off=%d head_stride=%d heads=%d)", (long long)ldx,
+           off, head_stride, heads);
+  AM_CHECK((rope_cos == nullptr) == (rope_sin == nullptr), "am_head_post_f32: rope tables must come in pairs");
+  if (rope_cos)
+    AM_CHECK(rows_per_frame > 0 && frames > 0 && (rows - 1) / rows_per_frame < frames,
+             "am_head_post_f32: rows=%lld / rows_per_frame=%d runs past the %d frames of the tables", (long long)rows, rows_per_frame, frames);
+  const int64_t chunks = rows * heads, blocks = (chunks + HP_CHUNKS - 1) / HP_CHUNKS;
+  AM_CHECK(blocks <= 0x7fffffff, "am_head_post_f32: too many rows");
+  HeadPostF32 p{X, ldx, off, head_stride, chunks, heads, w, eps, rope_cos, rope_sin, rope_cos ? rows_per_frame : 1};
+  hipLaunchKernelGGL(head_post_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+extern "C" int am_flow_step_f32(const float* v_dev, float* latents_dev, int n_branches, const float* scales_host, float dt,
+                                int is_additive, const uint8_t* unobserved_host, int T_local, int N, int Din, void* stream) {
+  AM_CHECK(v_dev && latents_dev, "am_flow_step_f32: null operand");
+  AM_CHECK(n_branches >= 1 && n_branches <= 4, "am_flow_step_f32: n_branches=%d", n_branches);
+  AM_CHECK(n_branches == 1 || scales_host, "am_flow_step_f32: scales required");
+  AM_CHECK(T_local > 0 && T_local <= 256 && N > 0 && Din > 0, "am_flow_step_f32: bad shape");
+  FlowF32 a;
+  a.v = v_dev;
+  a.lat = latents_dev;
+  a.nb = n_branches;
+  for (int i = 0; i < 3; ++i) a.scales[i] = (i < n_branches - 1) ? scales_host[i] : 0.f;
+  a.dt = dt;
+  a.additive = is_additive ? 1 : 0;
+  for (int f = 0; f < 256; ++f) a.unobs[f] = (f < T_local) ? (unobserved_host ? unobserved_host[f] : 1) : 0;
+  const int64_t per_frame = (int64_t)N * Din;
+  const bool vec = per_frame % 4 == 0 && al16(v_dev) && al16(latents_dev);
+  a.per_frame4 = vec ? per_frame / 4 : per_frame;
+  a.total4 = a.per_frame4 * T_local;
+  const int64_t blocks = (a.total4 + 255) / 256;
+  AM_CHECK(blocks <= 0x7fffffff, "am_flow_step_f32: too many elements");
+  if (vec) hipLaunchKernelGGL(flow_step_f32_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(flow_step_f32_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}

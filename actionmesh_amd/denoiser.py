@@ -5,7 +5,8 @@ Same constructor fields, same `forward(hidden_states, context, framestep,
 diffusion_time, mask=None, freqs_rot=None) -> (velocity, freqs_rot)`, `.device`,
 `.eval()`, `.to()`, `load_state_dict` with the reference's state-dict keys and
 `from_pretrained(dir)`.  Python here only marshals pointers; there is no torch
-arithmetic on the hot path and no CPU fallback.
+arithmetic on the hot path and no CPU fallback.  `dtype="float32"` swaps the engine
+for the exact-fp32 one of denoiser_f32.py (the device-side ground truth).
 """
 from __future__ import annotations
 
@@ -319,9 +320,21 @@ class HipDenoiser(nn.Module):
         # 16-bit storage / MFMA type.  None (default): follow the caller's autocast region like the reference module does - the reference
         # pipeline runs Stage I under torch.autocast("cuda", dtype) (pipeline.py:671) with dtype from the CLI's --dtype {bfloat16,
         # float16}; bfloat16 outside any autocast region.  "float16" / "bfloat16" (or the torch dtypes) pin it.
-        self.dtype_pinned = None if dtype is None else L.kind_of(dtype)
-        # HIP-graph replay of the single-rank forward (None: the ACTIONMESH_AMD_GRAPH environment variable, default off)
-        self.use_graph = (os.environ.get("ACTIONMESH_AMD_GRAPH", "0") == "1") if use_graph is None else bool(use_graph)
+        # "float32" (or torch.float32): the reference's own fp32 arithmetic on the exact-fp32 kernels (denoiser_f32.F32Engine) - the
+        # ground truth the 16-bit and fp8 modes are measured against, not a fast path; the velocity comes back as float32 and the
+        # caller's autocast region changes nothing.  One device, no captured graph, no fp8 attention: the options that cannot apply are refused.
+        self.fp32 = dtype is not None and L.is_f32(dtype)
+        self.dtype_pinned = "f32" if self.fp32 else None if dtype is None else L.kind_of(dtype)
+        if self.fp32:
+            if process_group is not None:
+                raise ValueError("HipDenoiser(dtype='float32'): process_group is not supported (the fp32 engine runs on one device)")
+            if use_graph:
+                raise ValueError("HipDenoiser(dtype='float32'): use_graph=True is not supported (the fp32 forward is not captured)")
+            if attn_dtype != "bf16":
+                raise ValueError(f"HipDenoiser(dtype='float32'): attn_dtype={attn_dtype!r} is not supported (every operation is fp32)")
+        self.f32_backend = None             # fp32 mode: the kernels' backend object (None: denoiser_f32.HipF32Backend)
+        # HIP-graph replay of the single-rank forward (None: the ACTIONMESH_AMD_GRAPH environment variable, default off; fp32: never)
+        self.use_graph = False if self.fp32 else (os.environ.get("ACTIONMESH_AMD_GRAPH", "0") == "1") if use_graph is None else bool(use_graph)
         self.attn_dtype = attn_dtype        # "fp8": inflated self-attention on the e4m3 MFMA kernel (BASELINE configs[4])
         if width != num_attention_heads * HEAD_DIM:
             raise ValueError("HipDenoiser supports head_dim 128 only (width = heads * 128), as the reference ships")
@@ -410,7 +423,8 @@ class HipDenoiser(nn.Module):
         return self._cfg_peer_groups[plan.cfg_groups][plan.rank % plan.group_size]
 
     def compute_kind(self) -> str:
-        """'bf16' or 'f16': the pinned dtype, else the autocast dtype of the calling region (float16 only when the caller asked for it)."""
+        """'bf16' or 'f16': the pinned dtype, else the autocast dtype of the calling region (float16 only when the caller asked for it).
+        'f32' for HipDenoiser(dtype="float32"), whatever the calling region."""
         return L.autocast_kind(self.dtype_pinned)
 
     def _ensure_engine(self, B: int, T_local: int, N: int, S: int, plan: FrameShardPlan) -> HipEngine:
@@ -423,6 +437,11 @@ class HipDenoiser(nn.Module):
             return e
         if e is not None:
             e.close()
+        if kind == "f32":
+            from .denoiser_f32 import F32Engine
+            self._engine = F32Engine(self.hyper_params(), self._host_sd, self.device, backend=self.f32_backend)
+            self._window = None
+            return self._engine
         kv_factory = None
         if plan.frame_world > 1 and os.environ.get("ACTIONMESH_AMD_EXCHANGE", "rccl") == "peer":
             from .sharding import PeerExchange
@@ -440,7 +459,7 @@ class HipDenoiser(nn.Module):
         `ctx_zero` (per batch row; None = find out with one device reduction) and `shared_prefix` enable the exact shortcuts of
         am_set_branch_hints; ACTIONMESH_AMD_NO_SHORTCUTS=1 turns both off."""
         B, T, S, _ = context.shape
-        if os.environ.get("ACTIONMESH_AMD_NO_SHORTCUTS", "0") == "1":
+        if self.fp32 or os.environ.get("ACTIONMESH_AMD_NO_SHORTCUTS", "0") == "1":      # the fp32 engine computes everything
             ctx_zero, shared_prefix = [False] * B, False
         elif ctx_zero is None:
             ctx_zero = [not bool(f) for f in context.reshape(B, -1).ne(0).any(dim=1).tolist()]

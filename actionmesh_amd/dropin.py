@@ -21,6 +21,8 @@ The reference builds its Stage-I objects in three places, none of which takes a 
     `ActionMeshPipeline.__init__` resolves in `actionmesh.pipeline`'s globals (pipeline.py:97), is rebound to HipImagePreprocessor,
     and the composed config's `model.image_encoder` (pipeline.py:164) is pointed at HipImageEncoder with `preprocess="hip"`
     (actionmesh_amd/image_preprocess.py, seam S8);
+  * optionally (`install_stage1_fp32()` after `install()`) that HipDenoiser in exact fp32: the bound class defaults to
+    dtype="float32" (actionmesh_amd/denoiser_f32.py; the ground truth for a 16-bit run of the same checkpoint, seam S2);
   * optionally (`install_mask_refine()` after `install()`) the mask refinement behind the background remover: `refine_mask`, a name
     `BackgroundRemover.forward` resolves in `actionmesh.preprocessing.background_removal`'s globals (background_removal.py:109), is
     rebound to the HIP labelling (actionmesh_amd/mask_refine.py, seam S9);
@@ -183,6 +185,8 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
         from . import render as R
         R.install_hook()
     _state["preprocess"] = False
+    _state["stage1_fp32"] = False
+    _state["denoiser_kw"] = kw
     _state["mask_refine"] = None
     _state["pointcloud"] = None
     _state["isosurface"] = None
@@ -210,6 +214,36 @@ def install_preprocess() -> None:
     _state["saved"]["ImagePreprocessor"] = P.ImagePreprocessor
     P.ImagePreprocessor = HipImagePreprocessor
     _state["preprocess"] = True
+
+
+def install_stage1_fp32() -> None:
+    """On top of `install()` (called with its defaults first if nothing is installed; idempotent): Stage I in exact fp32 -
+    `ActionMeshDenoiser` in `actionmesh.pipeline` becomes a HipDenoiser whose `dtype` defaults to "float32" (the reference calls
+    `from_pretrained(dir)` with no keyword), so the unmodified pipeline samples with the reference's own fp32 arithmetic on the
+    exact-fp32 kernels (actionmesh_amd/denoiser_f32.py): the ground truth to hold a 16-bit or fp8 run of the same checkpoint against,
+    many times slower than they are.  Needs an `install()` with attn_dtype="bf16" and without use_graph=True (the fp32 mode refuses
+    both).  `uninstall()` - and therefore a later `install()` - takes it back.  A call of its own, like `install_preprocess()`:
+    `install()` keeps its parameter list."""
+    if not _state.get("installed"):
+        install()
+    if _state.get("stage1_fp32"):
+        return
+    kw = _state["denoiser_kw"]
+    if kw["attn_dtype"] != "bf16" or kw["use_graph"]:
+        raise ValueError(f"actionmesh_amd.install_stage1_fp32(): install(attn_dtype={kw['attn_dtype']!r}, use_graph={kw['use_graph']!r}) "
+                         "cannot be combined with the exact-fp32 Stage I")
+    P = _state["module"]
+    base = P.ActionMeshDenoiser           # install()'s HipDenoiser subclass (the reference's own class is in _state["saved"] already)
+
+    class _Fp32HipDenoiser(base):
+        """HipDenoiser with dtype="float32" bound."""
+        def __init__(self, *a, **k):
+            k.setdefault("dtype", "float32")
+            super().__init__(*a, **k)
+    _Fp32HipDenoiser.__name__ = "HipDenoiser"
+    _Fp32HipDenoiser.__qualname__ = "HipDenoiser"
+    P.ActionMeshDenoiser = _Fp32HipDenoiser
+    _state["stage1_fp32"] = True
 
 
 def install_mask_refine() -> None:
@@ -266,6 +300,7 @@ def uninstall() -> None:
         I.uninstall_from(*_state["isosurface"])
         _state["isosurface"] = None
     _state["preprocess"] = False
+    _state["stage1_fp32"] = False
     _state["installed"] = False
 
 

@@ -472,7 +472,10 @@ def displacement(logits: torch.Tensor, out_dim: int, out: torch.Tensor) -> torch
 
 def flow_step(v: torch.Tensor, latents: torch.Tensor, scales: Sequence[float], dt: float,
               is_additive: bool, unobserved: Optional[Sequence[bool]]) -> None:
-    """In place: latents (T, N, D) fp32 += sign * bf16(dt * cfg(v)); v (n_branches, T, N, D) bf16."""
+    """In place: latents (T, N, D) fp32 += sign * bf16(dt * cfg(v)); v (n_branches, T, N, D) bf16 (or float16: that build's rounding).
+    An fp32 velocity - an exact-fp32 model's - takes am_flow_step_f32: the reference's fp32 arithmetic, nothing rounded to 16 bits."""
+    if v.dtype == torch.float32:
+        return flow_step_f32(v, latents, scales, dt, is_additive, unobserved)
     _need(v, H16, "v"); _need(latents, torch.float32, "latents")
     nb, T, N, D = v.shape
     sc = (C.c_float * max(1, len(scales)))(*[float(s) for s in scales])
@@ -1500,7 +1503,7 @@ def dmc_triangles(code: torch.Tensor, edge_mask: torch.Tensor, vertex_offset: to
     return out
 
 
-# ---- exact-fp32 path (csrc/am_f32.hip, am_elementwise.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----
+# ---- exact-fp32 path (csrc/am_f32.hip, am_stage1_f32.hip, am_elementwise.hip; both library builds carry it, `kind` picks which one runs it: same bits) ----
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              gelu: bool = False, out: Optional[torch.Tensor] = None, kind: str = "bf16") -> torch.Tensor:
     """am_gemm_f32: out = act(a @ w.T + bias) + residual, all fp32, fp32 MFMA.  a (M, K), w (N, K) (nn.Linear layout), bias (N,),
@@ -1581,6 +1584,46 @@ def layernorm_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float 
     _call(x, kind, "am_layernorm_f32", x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(),
             x.numel() // Cdim, Cdim, eps)
     return out
+
+
+def head_post_f32(x: torch.Tensor, heads: int, w: torch.Tensor, off: int = 0, head_stride: int = HEAD_DIM, eps: float = 1e-6,
+                  rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, rows_per_frame: int = 1, kind: str = "bf16") -> torch.Tensor:
+    """am_head_post_f32, in place: qk-RMSNorm (gain w (128,), eps) and - with `rope` = (cos, sin), each (frames, 64) fp32 - RoPE with the
+    angles of frame row // rows_per_frame, on the 128-wide chunks x[r, off + h * head_stride : + 128] of the packed projection output
+    x (rows, >= ...) fp32 (rows may be strided).  One chunk kind per call; the other columns of x are not touched.  Returns x."""
+    _need_rows(x, torch.float32, "x"); _need(w, torch.float32, "w")
+    if w.numel() != HEAD_DIM:
+        raise ValueError(f"head_post_f32: the gain has {w.numel()} elements, head_dim is {HEAD_DIM}")
+    if heads < 1 or off < 0 or head_stride < 0 or off + (heads - 1) * head_stride + HEAD_DIM > x.shape[1]:
+        raise ValueError(f"head_post_f32: x has {x.shape[1]} columns, head {heads - 1} ends at {off + (heads - 1) * head_stride + HEAD_DIM}")
+    cos = sin = None
+    frames = 0
+    if rope is not None:
+        cos, sin = rope
+        _need(cos, torch.float32, "rope cos"); _need(sin, torch.float32, "rope sin")
+        frames = cos.shape[0]
+        if cos.dim() != 2 or cos.shape[1] != HEAD_DIM // 2 or sin.shape != cos.shape:
+            raise ValueError(f"head_post_f32: rope tables must be (frames, {HEAD_DIM // 2}), got {tuple(cos.shape)} / {tuple(sin.shape)}")
+        if rows_per_frame < 1 or (x.shape[0] - 1) // rows_per_frame >= frames:
+            raise ValueError(f"head_post_f32: {x.shape[0]} rows of {rows_per_frame} per frame run past the {frames} frames of the tables")
+    _call(x, kind, "am_head_post_f32", x.data_ptr(), x.stride(0), off, head_stride, x.shape[0], heads, w.data_ptr(), eps,
+            _p(cos), _p(sin), frames, rows_per_frame)
+    return x
+
+
+def flow_step_f32(v: torch.Tensor, latents: torch.Tensor, scales: Sequence[float], dt: float, is_additive: bool,
+                  unobserved: Optional[Sequence[bool]], kind: str = "bf16") -> None:
+    """am_flow_step_f32, in place: latents (T, N, D) fp32 +- dt * cfg(v) on the unobserved frames, v (n_branches, T, N, D) fp32; every
+    operation rounded once to fp32 - the bits of the reference's fp32 expression (guidance.py:95-118, scheduler.py:238-248)."""
+    _need(v, torch.float32, "v"); _need(latents, torch.float32, "latents")
+    nb, T, N, D = v.shape
+    if tuple(latents.shape) != (T, N, D):
+        raise ValueError(f"flow_step_f32: latents {tuple(latents.shape)} != {(T, N, D)}")
+    if len(scales) < nb - 1 or (unobserved is not None and len(unobserved) != T):
+        raise ValueError(f"flow_step_f32: {len(scales)} scales for {nb} branches / a mask that does not cover the {T} frames")
+    sc = (C.c_float * max(1, len(scales)))(*[float(s) for s in scales])
+    un = None if unobserved is None else (C.c_uint8 * T)(*[1 if u else 0 for u in unobserved])
+    _call(v, kind, "am_flow_step_f32", v.data_ptr(), latents.data_ptr(), nb, sc, float(dt), 1 if is_additive else 0, un, T, N, D)
 
 
 def point_embed_f32(query: torch.Tensor, in_channels: int, extra_channels: int, num_freqs: int, include_pi: bool,

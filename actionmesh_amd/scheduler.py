@@ -77,7 +77,7 @@ class HipSchedulerFlow:
     # Not a reference field.  The reference's GPU path multiplies `distances[i]` (a 0-dim fp32 DEVICE tensor) with the bf16
     # velocity, and torch's type promotion rounds the distance to bf16 first (scheduler.py:238-241 under cuda autocast; its
     # fp32 CPU path does not).  False (default) keeps dt in fp32 = the reference's CPU arithmetic; True reproduces the
-    # cuda-autocast rounding bit for bit.
+    # cuda-autocast rounding bit for bit (a 16-bit model only: an exact-fp32 model has no such rounding, whatever this says).
     cuda_autocast_dt: bool = False
     # Not a reference field.  Two EXACT shortcuts of the CFG batch (am_set_branch_hints: bit-identical latents): the unconditional
     # branch's cross-attention is its to_out bias (zero context, bias-free to_k / to_v), and layer 0's self-attention branch is
@@ -170,8 +170,11 @@ class HipSchedulerFlow:
         for i in it:
             t = float(timesteps[i])
             dt = float(distances[i])
-            if self.cuda_autocast_dt:          # the 16-bit type the model computes in (bfloat16, or float16 under --dtype float16)
-                h16 = torch.float16 if diffusion_model.compute_kind() == "f16" else torch.bfloat16
+            # the 16-bit type the model computes in (bfloat16, or float16 under --dtype float16); an exact-fp32 model
+            # (HipDenoiser(dtype="float32")) keeps dt as it is: the reference in fp32 has no autocast region to round it
+            kind = diffusion_model.compute_kind() if self.cuda_autocast_dt else None
+            if kind in ("bf16", "f16"):
+                h16 = torch.float16 if kind == "f16" else torch.bfloat16
                 dt = float(torch.tensor(dt, dtype=torch.float32).to(h16))
             # every launch of the step goes to the denoiser's device and that device's current stream, whichever device is
             # current in the calling thread (the forward and the CFG+Euler kernel must share a stream to be ordered)

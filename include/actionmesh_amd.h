@@ -444,6 +444,34 @@ int am_patchify_f32(const float* pixels, int frames, int channels, int height, i
                     void* stream);
 int am_displacement_f32(const float* logits, int ld, int64_t rows, int out_dim, float* out, void* stream);
 
+/* ---- exact-fp32 Stage I (csrc/am_stage1_f32.hip): what HipDenoiser(dtype="float32") needs beside the matrix path above ----------
+ * fp32 and nothing narrower, every operation rounded once in the order written here (built without contraction into fused
+ * multiply-adds); deterministic; the same bits from both library builds.
+ *
+ * qk-RMSNorm (diffusers RMSNorm(dim_head, eps), attention_processor.py:121-124) and RoPE (rotary_embedding.py:72-124,
+ * attention_processor.py:127-130) IN PLACE on the 128-wide head chunks of a packed fp32 projection output, addressed as
+ * am_attention_f32 addresses them: the chunk of head h of row r is x = X[r * ldx + off + h * head_stride .. + 128].  Per chunk:
+ *   ss   = sum of x[d] * x[d]: per lane (x0 x0 + x1 x1) + (x2 x2 + x3 x3) of four consecutive d, then a binary tree over the 32 lanes
+ *          (8 levels in all, the same tree every launch)
+ *   r    = 1 / sqrt(ss / 128 + eps)
+ *   y[d] = (x[d] * r) * w[d]                                              w [128]
+ *   with tables (rope_cos, rope_sin: [frames][64] fp32, one value per interleaved pair, frame = r / rows_per_frame):
+ *   c = rope_cos[frame][i], s = rope_sin[frame][i]:   out[2i] = y[2i] * c + (-y[2i + 1]) * s,   out[2i + 1] = y[2i + 1] * c + y[2i] * s
+ * and out (or y, with NULL tables: frames and rows_per_frame are then ignored) is written back over x.  One launch handles ONE chunk
+ * kind: the caller launches it for q and for k (cross-attention: for q, and for the context's k).  No column outside the addressed
+ * chunks is read or written.  X, w 16-byte aligned; ldx, off, head_stride multiples of 4; head_stride >= 128 unless heads == 1;
+ * off + (heads - 1) * head_stride + 128 <= ldx; (rows - 1) / rows_per_frame < frames. */
+int am_head_post_f32(float* X, int64_t ldx, int off, int head_stride, int64_t rows, int heads, const float* w, float eps,
+                     const float* rope_cos, const float* rope_sin, int frames, int rows_per_frame, void* stream);
+/* The fp32 form of am_flow_step: ClassifierFreeGuidance.aggregate_cfg (guidance.py:95-118) and the Euler step with its masked write
+ * (scheduler.py:238-248) as the reference computes them in fp32 - the bits of the torch fp32 expression:
+ *   out = v_0;   out = out + scale_i * (v_{i+1} - v_i)   for i = 0 .. n_branches - 2   (a subtraction, a product, a sum: three roundings)
+ *   step = dt * out;   latents[f] = latents[f] + step (is_additive) or latents[f] - step   for frames with unobserved[f] != 0
+ * (unobserved_host NULL: every frame).  latents_dev fp32 (T_local, N, Din), v_dev fp32 (n_branches, T_local, N, Din); frames that are
+ * not unobserved are neither read nor written.  n_branches 1 .. 4, T_local <= 256. */
+int am_flow_step_f32(const float* v_dev, float* latents_dev, int n_branches, const float* scales_host, float dt, int is_additive,
+                     const uint8_t* unobserved_host, int T_local, int N, int Din, void* stream);
+
 /* ActionBench quality gate (actionbench/chamfer.py:13-86, actionbench/icp.py:94): exact nearest-neighbour
  * search, the arithmetic of scipy.spatial.KDTree(points).query(queries) and of pytorch3d's chamfer_distance.
  *   points  (batch, n_points, 3) fp32, batch stride points_bstride ELEMENTS (0 = one cloud shared by every batch entry);
