@@ -418,6 +418,7 @@ SYMBOLS = {
     "am_patchify_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "am_displacement_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P]),
     "am_head_post_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, _P, C.c_float, _P, _P, C.c_int, C.c_int, _P]),
+    "am_rope_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "am_flow_step_f32": (C.c_int, [_P, _P, C.c_int, _P, C.c_float, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "am_nn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "am_nn_search": (C.c_int, [C.POINTER(AmNnArgs), _P, C.c_size_t, _P]),
@@ -528,8 +529,8 @@ def lib(kind: str = "bf16") -> C.CDLL:
 def kind_of(dtype) -> str:
     """'bf16' / 'f16' for torch.bfloat16 / torch.float16 (or their names); anything else is an error.  These are the two builds of the
     library; float32 is not a third build: the exact-fp32 entry points (am_gemm_f32, am_attention_f32, ...) live in both, and the modules
-    that offer an fp32 mode (HipAutoencoder(cross_fp32=True), HipImageEncoder(dtype="float32"), HipDenoiser(dtype="float32")) handle it
-    before calling this (is_f32)."""
+    that offer an fp32 mode (HipAutoencoder(cross_fp32=True) / (exact_fp32=True), HipImageEncoder(dtype="float32"),
+    HipDenoiser(dtype="float32")) handle it before calling this (is_f32)."""
     name = str(dtype).replace("torch.", "")
     if name in ("bfloat16", "bf16"):
         return "bf16"

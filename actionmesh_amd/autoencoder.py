@@ -25,6 +25,10 @@ LayerNorm's 16-bit output (am_add_layernorm_f32).  By default the cross-attentio
 block, norm_out and proj_out - in exact fp32 (am_gemm_f32 / am_attention_f32 / am_layernorm_f32 on the fp32 MFMA) on the finished fp32
 kv stream, while the 16 self-attention blocks still follow the caller's 16-bit type (opt-in: it roughly doubles a window's time, the
 cross-attention at V vertices x T (N + 1) keys being the largest single cost).  `residual_fp32=False` is the round-5 all-16-bit stream.
+`exact_fp32=True` runs the WHOLE forward - the 16 self-attention blocks too - in the reference's fp32 arithmetic on the exact-fp32 kernels
+(autoencoder_f32.py; am_rope_f32 for the RoPE without a qk-norm): the device-side ground truth for the modes above, many times slower than
+they are; it implies the other two switches, ignores the caller's autocast region and reports compute_kind() 'f32'.  A keyword of its
+own and not a dtype: `dtype` names the 16-bit type of the library build, and float32 stays refused there.
 Tolerances: tests/test_autoencoder.py, tests/test_fp32_path_gpu.py.
 float16 range: activations above 65504 overflow in IEEE half; a float16 forward whose result is not finite raises.
 The 16-bit type follows the caller like the reference module's does: the reference pipeline calls Stage II inside
@@ -43,14 +47,17 @@ import torch
 from . import _lib as _L
 from . import ops
 from ._lib import lib
+from . import autoencoder_f32 as F32
 from .denoiser import rope_tables_host
+from .denoiser_f32 import HipF32Backend
 
 
 class HipAutoencoder:
     def __init__(self, temporal_context_size: int = 16, in_channels: int = 3, in_extra_channels: int = 3, out_dim: int = 3,
                  latent_channels: int = 64, width: int = 1024, num_layers: int = 16, num_attention_heads: int = 8,
                  embed_frequency: int = 8, embed_include_pi: bool = False, prediction_mode: str = "direct",
-                 verbose: bool = False, dtype=None, residual_fp32: bool = True, cross_fp32: bool = False, **_ignored):
+                 verbose: bool = False, dtype=None, residual_fp32: Optional[bool] = None, cross_fp32: Optional[bool] = None,
+                 exact_fp32: bool = False, **_ignored):
         if width % num_attention_heads or width // num_attention_heads != ops.HEAD_DIM:
             raise ValueError("HipAutoencoder: the kernels are built for head_dim 128 (width = 128 * heads)")
         if latent_channels % 64 or width % 64:
@@ -63,14 +70,24 @@ class HipAutoencoder:
         self.query_dim = in_channels * (2 * embed_frequency + 1) + in_extra_channels
         self.query_pad = ops.round_up(self.query_dim, 64)
         self.device = torch.device("cpu")
+        if dtype is not None and _L.is_f32(dtype):
+            # float32 is not a 16-bit type of the library: the exact mode is a keyword of its own, the dtype stays the 16-bit one
+            raise ValueError(f"HipAutoencoder: dtype must be bfloat16 or float16, got {dtype!r}; the exact-fp32 mode is exact_fp32=True")
         self.dtype_pinned = None if dtype is None else _L.kind_of(dtype)      # None: the caller's autocast dtype (compute_kind)
-        self.residual_fp32 = bool(residual_fp32)
-        self.cross_fp32 = bool(cross_fp32)
+        # exact_fp32: the whole forward - the self-attention stack too - in the reference's fp32 arithmetic on the exact-fp32 kernels
+        # (autoencoder_f32.py): the ground truth for the 16-bit modes, many times slower.  It implies the other two switches.
+        self.exact_fp32 = bool(exact_fp32)
+        if self.exact_fp32 and (residual_fp32 is False or cross_fp32 is False):
+            raise ValueError("HipAutoencoder: exact_fp32=True implies residual_fp32=True and cross_fp32=True; neither can be turned off with it")
+        self.residual_fp32 = True if residual_fp32 is None else bool(residual_fp32)      # None: the default, fp32 as the reference's
+        self.cross_fp32 = self.exact_fp32 if cross_fp32 is None else bool(cross_fp32)     # None: the default, off unless exact_fp32
+        self.f32_backend = None            # exact_fp32: the kernels' backend object (None: denoiser_f32.HipF32Backend)
         if self.cross_fp32 and not self.residual_fp32:
             raise ValueError("HipAutoencoder: cross_fp32=True needs residual_fp32=True (the fp32 block reads the fp32 kv stream)")
         self._sd: Optional[Dict[str, torch.Tensor]] = None
         self._w_kind: Dict[str, Dict[str, torch.Tensor]] = {}                 # "bf16" / "f16" -> device weights, uploaded on first use
         self._w32_cache: Optional[Dict[str, torch.Tensor]] = None             # fp32 copies of the cross_fp32 layers, uploaded on first use
+        self._w32_self_cache: Optional[Dict[str, torch.Tensor]] = None        # exact_fp32: fp32 copies of post_quant and the self-attention blocks
         lib()      # fail loudly here if libactionmesh_amd.so is missing
 
     # ---- nn.Module-like surface ---------------------------------------------------------------------------
@@ -96,11 +113,13 @@ class HipAutoencoder:
         self.device = torch.device(device)
         self._w_kind = {}
         self._w32_cache = None
+        self._w32_self_cache = None
         return self
 
     def compute_kind(self) -> str:
-        """'bf16' or 'f16' (HipDenoiser.compute_kind): the pinned dtype, else the autocast dtype of the calling region."""
-        return _L.autocast_kind(self.dtype_pinned)
+        """'bf16' or 'f16' (HipDenoiser.compute_kind): the pinned dtype, else the autocast dtype of the calling region; 'f32' for an
+        exact_fp32 model, whatever that region says."""
+        return "f32" if self.exact_fp32 else _L.autocast_kind(self.dtype_pinned)
 
     @property
     def _w(self) -> Dict[str, torch.Tensor]:
@@ -119,28 +138,22 @@ class HipAutoencoder:
         self._sd = {k: v.detach().to("cpu", torch.float32) for k, v in sd.items()}
         self._w_kind = {}
         self._w32_cache = None
+        self._w32_self_cache = None
         return self
 
     @property
     def _w32(self) -> Dict[str, torch.Tensor]:
         """fp32 device copies of what the reference runs with autocast off: proj_query, the cross-attention block, norm_out, proj_out."""
-        if self._w32_cache is None:
-            sd, dev, p = self._sd, self.device, f"blocks.{self.num_layers}."
-            f32 = lambda t: t.to(dev, torch.float32).contiguous()
-            pq = torch.zeros((self.width, self.query_pad))
-            pq[:, : self.query_dim] = sd["proj_query.weight"]                   # K padded to a multiple of 64 (zero columns)
-            w = {"proj_query": f32(pq), "proj_query_b": f32(sd["proj_query.bias"]),
-                 "q": f32(sd[p + "x_attn.to_q.weight"]),
-                 "kv": f32(torch.cat([sd[p + "x_attn.to_k.weight"], sd[p + "x_attn.to_v.weight"]], 0)),   # [to_k | to_v] output columns
-                 "o": f32(sd[p + "x_attn.to_out.0.weight"]), "o_b": f32(sd[p + "x_attn.to_out.0.bias"]),
-                 "ff1": f32(sd[p + "ff.net.0.proj.weight"]), "ff1_b": f32(sd[p + "ff.net.0.proj.bias"]),
-                 "ff2": f32(sd[p + "ff.net.2.weight"]), "ff2_b": f32(sd[p + "ff.net.2.bias"]),
-                 "proj_out": f32(sd["proj_out.weight"]), "proj_out_b": f32(sd["proj_out.bias"]),
-                 "norm_out.w": f32(sd["norm_out.weight"]), "norm_out.b": f32(sd["norm_out.bias"])}
-            for n, key in (("norm_x_attn", "norm_x_attn"), ("norm_cross", "x_attn.norm_cross"), ("norm_ff", "norm_ff")):
-                w[n + ".w"], w[n + ".b"] = f32(sd[p + key + ".weight"]), f32(sd[p + key + ".bias"])
-            self._w32_cache = w
+        if self._w32_cache is None:                                             # K of proj_query padded to a multiple of 64 (zero columns)
+            self._w32_cache = F32.pack_cross_weights_f32(self._sd, self.num_layers, self.query_dim, self.query_pad, self.device)
         return self._w32_cache
+
+    @property
+    def _w32_self(self) -> Dict[str, torch.Tensor]:
+        """exact_fp32: fp32 device copies of post_quant and the self-attention blocks, uploaded once."""
+        if self._w32_self_cache is None:
+            self._w32_self_cache = F32.pack_self_weights_f32(self._sd, self.num_layers, self.device)
+        return self._w32_self_cache
 
     def _upload(self, dt16: torch.dtype) -> Dict[str, torch.Tensor]:
         sd, dev, C = self._sd, self.device, self.width
@@ -249,22 +262,7 @@ class HipAutoencoder:
         """blocks[-1](queries, encoder_hidden_states=kv_cache) -> norm_out -> proj_out, all fp32.  kv32 (B*S, C): the finished residual
         stream (any key order per batch entry); qh32 (B*V, C): proj_query's output, used as the block's residual stream (modified in
         place).  Returns (B*V, out_dim) logits BEFORE the reference's * -1."""
-        w, H, hd = self._w32, self.heads, ops.HEAD_DIM
-        e = ops.layernorm_f32(kv32, w["norm_cross.w"], w["norm_cross.b"])             # nn.LayerNorm, eps 1e-5
-        kv = ops.gemm_f32(e, w["kv"])                                                 # (B*S, 2C) = [to_k | to_v]
-        del e
-        z = ops.layernorm_f32(qh32, w["norm_x_attn.w"], w["norm_x_attn.b"])
-        q = ops.gemm_f32(z, w["q"])
-        # attention_processor.py:111-115: head h of the concatenated projection is columns h*2hd (K) and h*2hd + hd (V)
-        a = ops.attention_f32(q, kv, kv, H, V, S, hd, q_hs=hd, k_hs=2 * hd, v_hs=2 * hd, v_off=hd)
-        del kv, q
-        ops.gemm_f32(a, w["o"], bias=w["o_b"], residual=qh32, out=qh32)
-        z = ops.layernorm_f32(qh32, w["norm_ff.w"], w["norm_ff.b"], out=z)
-        f = ops.gemm_f32(z, w["ff1"], bias=w["ff1_b"], gelu=True)
-        ops.gemm_f32(f, w["ff2"], bias=w["ff2_b"], residual=qh32, out=qh32)
-        del f
-        z = ops.layernorm_f32(qh32, w["norm_out.w"], w["norm_out.b"], out=z)
-        return ops.gemm_f32(z, w["proj_out"], bias=w["proj_out_b"])
+        return F32.cross_logits(HipF32Backend(), self._w32, kv32, qh32, self.heads, V, S)     # the launches are stated once, there
 
     @torch.no_grad()
     def fwd_cross_attn(self, kv_cache: torch.Tensor, queries: torch.Tensor) -> torch.Tensor:
@@ -294,6 +292,8 @@ class HipAutoencoder:
     def forward(self, latent: torch.Tensor, framestep: torch.Tensor, source_alpha: torch.Tensor,
                 target_alphas: torch.Tensor, query: torch.Tensor,
                 step_callback: Optional[Callable[[int, int], None]] = None) -> torch.Tensor:
+        if self.exact_fp32:
+            return self._forward_exact_f32(latent, framestep, source_alpha, target_alphas, query, step_callback)
         if self.device.type != "cuda" or self._sd is None:
             raise RuntimeError("HipAutoencoder: load_state_dict(...) and .to('cuda:N') first (there is no CPU path)")
         assert target_alphas.ndim == 2 and source_alpha.ndim == 1
@@ -362,6 +362,25 @@ class HipAutoencoder:
                 raise FloatingPointError("HipAutoencoder: the float16 forward produced non-finite displacements (activation overflow "
                                          "in IEEE half); run Stage II under autocast(bfloat16) / dtype='bfloat16'")
             return out
+
+    def _forward_exact_f32(self, latent, framestep, source_alpha, target_alphas, query, step_callback) -> torch.Tensor:
+        """exact_fp32: autoencoder_f32.forward_f32 through the model's backend object.  The caller's autocast region changes nothing:
+        every operand is fp32 and every launch an fp32 entry point.  Only a backend of the caller's (`f32_backend`: the CPU tests'
+        torch restatements) runs off the device."""
+        be = self.f32_backend
+        if self._sd is None or (be is None and self.device.type != "cuda"):
+            raise RuntimeError("HipAutoencoder: load_state_dict(...) and .to('cuda:N') first (there is no CPU path)")
+        assert target_alphas.ndim == 2 and source_alpha.ndim == 1
+        if be is None:
+            be = self.f32_backend = HipF32Backend()
+        if self.device.type != "cuda":
+            return F32.forward_f32(be, self._w32_self, self._w32, self, latent, framestep, source_alpha, target_alphas, query, step_callback)
+        with torch.cuda.device(self.device):
+            return F32.forward_f32(be, self._w32_self, self._w32, self, latent, framestep, source_alpha, target_alphas, query, step_callback)
+
+    def entry_counts(self) -> Dict[str, int]:
+        """exact_fp32: launches per C entry point of this model's forwards so far (HipF32Backend.calls)."""
+        return dict(self.f32_backend.calls) if self.f32_backend is not None else {}
 
     __call__ = forward
 

@@ -1,4 +1,4 @@
-"""`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage1-fp32] [--stage2-hip [--stage2-cross-fp32]]
+"""`python -m actionmesh_amd.cli [--backend {hip,reference}] [--attn-dtype {bf16,fp8,fp8_fast}] [--stage1-fp32] [--stage2-hip [--stage2-cross-fp32] [--stage2-fp32]]
                                  [--render {auto,hip,off}] [--pointcloud {hip,off}] [--preprocess {hip,off}]
                                  [--mask-refine {hip,off}] [--isosurface {hip,hip-dual,off}] [--script NAME] [--reference-root DIR] -- <the reference CLI's own arguments>`
 
@@ -45,6 +45,9 @@ def split_args(argv: List[str]) -> Tuple[argparse.Namespace, List[str]]:
     ap.add_argument("--stage2-hip", action="store_true", help="also decode Stage II on the HIP kernels (HipAutoencoder)")
     ap.add_argument("--stage2-cross-fp32", action="store_true",
                     help="with --stage2-hip: Stage II's query side and cross-attention block in exact fp32, as the reference runs them")
+    ap.add_argument("--stage2-fp32", action="store_true",
+                    help="with --stage2-hip: all of Stage II in exact fp32 (HipAutoencoder(exact_fp32=True)): the reference's fp32 arithmetic on "
+                         "the device, the ground truth for a 16-bit run of the same checkpoint - many times slower; implies --stage2-cross-fp32")
     ap.add_argument("--stage1-fp32", action="store_true",
                     help="with --backend hip: Stage I in exact fp32 (HipDenoiser(dtype='float32')): the reference's fp32 arithmetic on the "
                          "device, the ground truth for a 16-bit or fp8 run of the same checkpoint - many times slower; needs --attn-dtype bf16")
@@ -75,6 +78,8 @@ def split_args(argv: List[str]) -> Tuple[argparse.Namespace, List[str]]:
         raise SystemExit(0)
     if ours.stage2_cross_fp32 and not ours.stage2_hip:
         ap.error("--stage2-cross-fp32 needs --stage2-hip")
+    if ours.stage2_fp32 and not ours.stage2_hip:
+        ap.error("--stage2-fp32 needs --stage2-hip")
     if ours.stage1_fp32 and (ours.backend != "hip" or ours.attn_dtype != "bf16"):
         ap.error("--stage1-fp32 needs --backend hip and --attn-dtype bf16")
     return ours, rest
@@ -94,6 +99,8 @@ def main(argv: Optional[List[str]] = None) -> None:
                        pointcloud=ours.pointcloud == "hip")
         if ours.stage1_fp32:
             dropin.install_stage1_fp32()
+        if ours.stage2_fp32:
+            dropin.install_stage2_fp32()
         if ours.preprocess == "hip":
             dropin.install_preprocess()
         if ours.mask_refine == "hip":

@@ -1,11 +1,13 @@
-// The two row / elementwise kernels of the exact-fp32 Stage-I denoiser (HipDenoiser(dtype="float32"), actionmesh_amd/denoiser_f32.py)
-// that the exact-fp32 matrix path of am_f32.hip does not have:
+// The row / elementwise kernels of the exact-fp32 Stage-I denoiser (HipDenoiser(dtype="float32"), actionmesh_amd/denoiser_f32.py)
+// and of the exact-fp32 Stage-II decoder (HipAutoencoder(exact_fp32=True), actionmesh_amd/autoencoder_f32.py) that the exact-fp32
+// matrix path of am_f32.hip does not have:
 //   am_head_post_f32   qk-RMSNorm (+ RoPE) in place on a packed fp32 projection output      (attention_processor.py:121-130)
+//   am_rope_f32        RoPE alone, q and k chunks in one launch (Stage II has no qk-norm)     (attention_processor.py:127-130)
 //   am_flow_step_f32   classifier-free guidance + Euler step on an fp32 velocity             (guidance.py:95-118, scheduler.py:238-248)
 // fp32 and nothing narrower; every operation is rounded once, in the order include/actionmesh_amd.h writes it: the file is built
 // without the SLP vectoriser and WITHOUT contraction into fused multiply-adds (csrc/Makefile), so am_flow_step_f32 gives the bits of
-// the torch fp32 expression.  Nothing here depends on the 16-bit type: both library builds carry the same object code.
-// Both kernels are HBM-bound: 16-byte accesses, no LDS, no scratch.
+// the torch fp32 expression, and am_rope_f32 those of the unfused torch fp32 rotation.  Nothing here depends on the 16-bit type: both
+// library builds carry the same object code.  The kernels are HBM-bound: 16-byte accesses, no LDS, no scratch.
 #include "am_common.h"
 
 namespace {
@@ -47,6 +49,32 @@ __global__ __launch_bounds__(256) void head_post_f32_kernel(HeadPostF32 p) {
     y = o;
   }
   if (valid) *reinterpret_cast<f32x4_t*>(xp) = y;
+}
+
+struct RopeF32 {
+  float* X; int64_t ldx; int off[2]; int head_stride;
+  int64_t chunks; int heads, kinds;
+  const float* rope_cos; const float* rope_sin; int rows_per_frame;
+};
+
+// One (row, kind, head) chunk per half wave, kind 0 = the chunks at off[0] (q), kind 1 = those at off[1] (k): the chunks of one row are
+// neighbours in the grid.  No reduction, so a half wave past the last chunk simply leaves.
+__global__ __launch_bounds__(256) void rope_f32_kernel(RopeF32 p) {
+  const int lane = threadIdx.x & 31;
+  const int64_t chunk = (int64_t)blockIdx.x * HP_CHUNKS + (threadIdx.x >> 5);
+  if (chunk >= p.chunks) return;
+  const int per_row = p.kinds * p.heads;
+  const int64_t row = chunk / per_row;
+  const int in_row = (int)(chunk - row * per_row);
+  const int kind = in_row / p.heads, head = in_row - kind * p.heads;
+  float* xp = p.X + row * p.ldx + p.off[kind] + (int64_t)head * p.head_stride + 4 * lane;
+  const f32x4_t x = *reinterpret_cast<const f32x4_t*>(xp);
+  // the lane holds the interleaved pairs 2 lane and 2 lane + 1 of the chunk; every row of a frame shares the frame's angles
+  const int64_t t = (row / p.rows_per_frame) * (HP_D / 2) + 2 * lane;
+  const float c0 = p.rope_cos[t], c1 = p.rope_cos[t + 1], s0 = p.rope_sin[t], s1 = p.rope_sin[t + 1];
+  // rotary_embedding.py:72-124: out = x cos + rot(x) sin, rot(x)[2i] = -x[2i + 1], rot(x)[2i + 1] = x[2i]: two products, one sum, each rounded
+  const f32x4_t o = {x[0] * c0 + (-x[1]) * s0, x[1] * c0 + x[0] * s0, x[2] * c1 + (-x[3]) * s1, x[3] * c1 + x[2] * s1};
+  *reinterpret_cast<f32x4_t*>(xp) = o;
 }
 
 struct FlowF32 {
@@ -118,6 +146,42 @@ extern "C" int am_head_post_f32(float* X, int64_t ldx, int off, int head_stride,
   AM_CHECK(blocks <= 0x7fffffff, "am_head_post_f32: too many rows");
   HeadPostF32 p{X, ldx, off, head_stride, chunks, heads, w, eps, rope_cos, rope_sin, rope_cos ? rows_per_frame : 1};
   hipLaunchKernelGGL(head_post_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  AM_HIP(hipGetLastError());
+  return AM_OK;
+}
+
+extern "C" int am_rope_f32(float* X, int64_t ldx, int off_a, int off_b, int head_stride, int64_t rows, int heads, const float* rope_cos,
+                           const float* rope_sin, int frames, int rows_per_frame, void* stream) {
+  AM_CHECK((rope_cos == nullptr) == (rope_sin == nullptr), "am_rope_f32: rope tables must come in pairs");
+  AM_CHECK(X && rope_cos, "am_rope_f32: null operand");
+  AM_CHECK(rows > 0 && heads > 0 && heads <= 65535, "am_rope_f32: bad shape rows=%lld heads=%d", (long long)rows, heads);
+  const int kinds = off_b < 0 ? 1 : 2;
+  AM_CHECK(al16(X) && ldx % 4 == 0 && off_a % 4 == 0 && (kinds == 1 || off_b % 4 == 0) && head_stride % 4 == 0,
+           "am_rope_f32: X, ldx, off_a, off_b and head_stride must be 16-byte aligned");
+  const int64_t span = (int64_t)(heads - 1) * head_stride + HP_D;
+  AM_CHECK(off_a >= 0 && (heads == 1 || head_stride >= HP_D) && ldx >= off_a + span && (kinds == 1 || ldx >= off_b + span),
+           "am_rope_f32: the heads' chunks overlap or run past the row (ldx=%lld off_a=%d off_b=%d head_stride=%d heads=%d)",
+           (long long)ldx, off_a, off_b, head_stride, heads);
+  if (kinds == 2) {
+    // a q chunk and a k chunk overlap when off_b - off_a + m head_stride lies inside (-128, 128) for a head difference |m| < heads;
+    // with head_stride >= 128 only the two multiples around the difference can
+    const int64_t d = (int64_t)off_b - off_a;
+    bool overlap;
+    if (heads == 1) {
+      overlap = d > -HP_D && d < HP_D;
+    } else {
+      const int64_t fl = d >= 0 ? d / head_stride : -((-d + head_stride - 1) / head_stride);      // floor(d / head_stride)
+      const int64_t r = d - fl * head_stride;                                                     // in [0, head_stride)
+      overlap = (r < HP_D && fl < heads && -fl < heads) || (head_stride - r < HP_D && fl + 1 < heads && -(fl + 1) < heads);
+    }
+    AM_CHECK(!overlap, "am_rope_f32: the q and k chunks overlap (off_a=%d off_b=%d head_stride=%d heads=%d)", off_a, off_b, head_stride, heads);
+  }
+  AM_CHECK(rows_per_frame > 0 && frames > 0 && (rows - 1) / rows_per_frame < frames,
+           "am_rope_f32: rows=%lld / rows_per_frame=%d runs past the %d frames of the tables", (long long)rows, rows_per_frame, frames);
+  const int64_t chunks = rows * heads * kinds, blocks = (chunks + HP_CHUNKS - 1) / HP_CHUNKS;
+  AM_CHECK(blocks <= 0x7fffffff, "am_rope_f32: too many rows");
+  RopeF32 p{X, ldx, {off_a, kinds == 2 ? off_b : off_a}, head_stride, chunks, heads, kinds, rope_cos, rope_sin, rows_per_frame};
+  hipLaunchKernelGGL(rope_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

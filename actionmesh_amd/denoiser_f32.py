@@ -35,7 +35,8 @@ LN_EPS, RMS_EPS = 1e-5, 1e-6        # FP32LayerNorm / nn.LayerNorm (block.py:64,
 class HipF32Backend:
     """The kernels of the fp32 forward behind one object, so that the orchestration can be run on restatements of them (the CPU tests
     substitute torch ones; the fifth kernel of the mode, am_flow_step_f32, is the sampler's: ops.flow_step).  `calls` counts the
-    launches per C entry point: what really ran."""
+    launches per C entry point: what really ran.  The exact-fp32 Stage II (autoencoder_f32.py) runs through the same object: the four
+    methods of Stage I - head_post aside - and the three behind them."""
 
     def __init__(self, kind: str = "bf16"):
         self.kind = kind             # which build of the library runs the fp32 entry points (the same bits from both)
@@ -57,10 +58,24 @@ class HipF32Backend:
         return ops.head_post_f32(x, heads, w, off=off, head_stride=head_stride, eps=eps, rope=rope, rows_per_frame=rows_per_frame,
                                  kind=self.kind)
 
-    def attention(self, q, k, v, heads, sq, sk, q_hs, k_hs, v_hs, q_off, k_off, v_off):
+    def attention(self, q, k, v, heads, sq, sk, q_hs, k_hs, v_hs, q_off, k_off, v_off, out=None):
         self._count("am_attention_f32")
         return ops.attention_f32(q, k, v, heads, sq, sk, HEAD_DIM, q_hs=q_hs, k_hs=k_hs, v_hs=v_hs, q_off=q_off, k_off=k_off,
-                                 v_off=v_off, kind=self.kind)
+                                 v_off=v_off, out=out, kind=self.kind)
+
+    # what the exact-fp32 Stage II (autoencoder_f32.py) needs beside the four above
+    def rope(self, x, heads, rope, off_a, off_b, head_stride, rows_per_frame):
+        self._count("am_rope_f32")
+        return ops.rope_f32(x, heads, rope, off_a=off_a, off_b=off_b, head_stride=head_stride, rows_per_frame=rows_per_frame,
+                            kind=self.kind)
+
+    def point_embed(self, query, in_channels, extra_channels, num_freqs, include_pi, ld_out):
+        self._count("am_point_embed_f32")
+        return ops.point_embed_f32(query, in_channels, extra_channels, num_freqs, include_pi, ld_out, kind=self.kind)
+
+    def displacement(self, logits, out_dim, out):
+        self._count("am_displacement_f32")
+        return ops.displacement_f32(logits, out_dim, out, kind=self.kind)
 
 
 def timestep_sinusoid_host(t_bt: Sequence[float], dim: int) -> torch.Tensor:

@@ -23,6 +23,8 @@ The reference builds its Stage-I objects in three places, none of which takes a 
     (actionmesh_amd/image_preprocess.py, seam S8);
   * optionally (`install_stage1_fp32()` after `install()`) that HipDenoiser in exact fp32: the bound class defaults to
     dtype="float32" (actionmesh_amd/denoiser_f32.py; the ground truth for a 16-bit run of the same checkpoint, seam S2);
+  * optionally (`install_stage2_fp32()` after `install(stage2=True)`) that HipAutoencoder in exact fp32: the bound class defaults to
+    exact_fp32=True (actionmesh_amd/autoencoder_f32.py; the ground truth for a 16-bit run of the same checkpoint, seam S2c);
   * optionally (`install_mask_refine()` after `install()`) the mask refinement behind the background remover: `refine_mask`, a name
     `BackgroundRemover.forward` resolves in `actionmesh.preprocessing.background_removal`'s globals (background_removal.py:109), is
     rebound to the HIP labelling (actionmesh_amd/mask_refine.py, seam S9);
@@ -186,6 +188,8 @@ def install(attn_dtype: str = "bf16", stage2: bool = False, use_graph: Optional[
         R.install_hook()
     _state["preprocess"] = False
     _state["stage1_fp32"] = False
+    _state["stage2"] = bool(stage2)
+    _state["stage2_fp32"] = False
     _state["denoiser_kw"] = kw
     _state["mask_refine"] = None
     _state["pointcloud"] = None
@@ -246,6 +250,32 @@ def install_stage1_fp32() -> None:
     _state["stage1_fp32"] = True
 
 
+def install_stage2_fp32() -> None:
+    """On top of `install(stage2=True)` (idempotent): Stage II in exact fp32 - `ActionMeshAutoencoder` in `actionmesh.pipeline` becomes
+    a HipAutoencoder whose `exact_fp32` defaults to True (the reference calls `from_pretrained(dir)` with no keyword), so the
+    unmodified pipeline decodes with the reference's own fp32 arithmetic on the exact-fp32 kernels (actionmesh_amd/autoencoder_f32.py),
+    whatever autocast region it calls the decoder in: the ground truth to hold a 16-bit run of the same checkpoint against, many times
+    slower than it is.  It implies the fp32 cross-attention block (`stage2_cross_fp32`).  Needs an `install()` that put HipAutoencoder
+    there: without one, or after `install(stage2=False)`, it raises.  `uninstall()` - and therefore a later `install()` - takes it
+    back.  A call of its own, like `install_stage1_fp32()`: `install()` keeps its parameter list."""
+    if not _state.get("installed") or not _state.get("stage2"):
+        raise RuntimeError("actionmesh_amd.install_stage2_fp32(): call install(stage2=True) first (Stage II is not on HipAutoencoder)")
+    if _state.get("stage2_fp32"):
+        return
+    P = _state["module"]
+    base = P.ActionMeshAutoencoder        # install()'s HipAutoencoder (the reference's own class is in _state["saved"] already)
+
+    class _Fp32HipAutoencoder(base):
+        """HipAutoencoder with exact_fp32=True bound."""
+        def __init__(self, *a, **k):
+            k.setdefault("exact_fp32", True)
+            super().__init__(*a, **k)
+    _Fp32HipAutoencoder.__name__ = "HipAutoencoder"
+    _Fp32HipAutoencoder.__qualname__ = "HipAutoencoder"
+    P.ActionMeshAutoencoder = _Fp32HipAutoencoder
+    _state["stage2_fp32"] = True
+
+
 def install_mask_refine() -> None:
     """On top of `install()` (called with its defaults first if nothing is installed; idempotent): `refine_mask` in
     `actionmesh.preprocessing.background_removal` - Otsu threshold, connected components, removal of the small ones, on every frame
@@ -301,6 +331,8 @@ def uninstall() -> None:
         _state["isosurface"] = None
     _state["preprocess"] = False
     _state["stage1_fp32"] = False
+    _state["stage2"] = False
+    _state["stage2_fp32"] = False
     _state["installed"] = False
 
 

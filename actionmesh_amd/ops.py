@@ -1611,6 +1611,28 @@ def head_post_f32(x: torch.Tensor, heads: int, w: torch.Tensor, off: int = 0, he
     return x
 
 
+def rope_f32(x: torch.Tensor, heads: int, rope: Tuple[torch.Tensor, torch.Tensor], off_a: int = 0, off_b: int = -1,
+             head_stride: int = HEAD_DIM, rows_per_frame: int = 1, kind: str = "bf16") -> torch.Tensor:
+    """am_rope_f32, in place: RoPE without a qk-norm - `rope` = (cos, sin), each (frames, 64) fp32, the angles of frame
+    row // rows_per_frame - on the 128-wide chunks x[r, off_a + h * head_stride : + 128] (q) and, unless off_b < 0, x[r, off_b + h *
+    head_stride : + 128] (k) of the packed projection output x (rows, >= ...) fp32 (rows may be strided): both kinds in one launch, the
+    bits of the unfused torch fp32 rotation.  The other columns of x are not touched.  Returns x."""
+    _need_rows(x, torch.float32, "x")
+    cos, sin = rope
+    _need(cos, torch.float32, "rope cos"); _need(sin, torch.float32, "rope sin")
+    if cos.dim() != 2 or cos.shape[1] != HEAD_DIM // 2 or sin.shape != cos.shape:
+        raise ValueError(f"rope_f32: rope tables must be (frames, {HEAD_DIM // 2}), got {tuple(cos.shape)} / {tuple(sin.shape)}")
+    for off in (off_a,) if off_b < 0 else (off_a, off_b):
+        if heads < 1 or off < 0 or head_stride < 0 or off + (heads - 1) * head_stride + HEAD_DIM > x.shape[1]:
+            raise ValueError(f"rope_f32: x has {x.shape[1]} columns, head {heads - 1} ends at {off + (heads - 1) * head_stride + HEAD_DIM}")
+    frames = cos.shape[0]
+    if rows_per_frame < 1 or (x.shape[0] - 1) // rows_per_frame >= frames:
+        raise ValueError(f"rope_f32: {x.shape[0]} rows of {rows_per_frame} per frame run past the {frames} frames of the tables")
+    _call(x, kind, "am_rope_f32", x.data_ptr(), x.stride(0), off_a, off_b, head_stride, x.shape[0], heads, cos.data_ptr(), sin.data_ptr(),
+          frames, rows_per_frame)
+    return x
+
+
 def flow_step_f32(v: torch.Tensor, latents: torch.Tensor, scales: Sequence[float], dt: float, is_additive: bool,
                   unobserved: Optional[Sequence[bool]], kind: str = "bf16") -> None:
     """am_flow_step_f32, in place: latents (T, N, D) fp32 +- dt * cfg(v) on the unobserved frames, v (n_branches, T, N, D) fp32; every

@@ -463,6 +463,19 @@ int am_displacement_f32(const float* logits, int ld, int64_t rows, int out_dim, 
  * off + (heads - 1) * head_stride + 128 <= ldx; (rows - 1) / rows_per_frame < frames. */
 int am_head_post_f32(float* X, int64_t ldx, int off, int head_stride, int64_t rows, int heads, const float* w, float eps,
                      const float* rope_cos, const float* rope_sin, int frames, int rows_per_frame, void* stream);
+/* RoPE alone, for the self-attention of Stage II, which rotates q and k WITHOUT a qk-norm (attention_qk_norm=None,
+ * temporal_autoencoder.py:83-92; am_head_post_f32 always normalises and refuses a null gain).  IN PLACE on the 128-wide head chunks of a
+ * packed fp32 projection output, addressed as above, TWO chunk kinds in one launch: x = X[r * ldx + off_a + h * head_stride .. + 128]
+ * (q) and, unless off_b < 0 (one kind only), X[r * ldx + off_b + h * head_stride .. + 128] (k).  With c = rope_cos[frame][i],
+ * s = rope_sin[frame][i], frame = r / rows_per_frame (tables [frames][64] fp32, both required):
+ *   out[2i] = x[2i] * c + (-x[2i + 1]) * s,   out[2i + 1] = x[2i + 1] * c + x[2i] * s
+ * two products and one sum per element, each rounded once to fp32 in that order: the bits of the unfused torch fp32 expression
+ * x * cos + rot(x) * sin (rotary_embedding.py:72-124).  No column outside the addressed chunks - the v chunks, padding behind the last
+ * chunk - is read or written.  X 16-byte aligned; ldx, off_a, off_b, head_stride multiples of 4; head_stride >= 128 unless heads == 1;
+ * off_x + (heads - 1) * head_stride + 128 <= ldx for both kinds; no q chunk may overlap a k chunk; (rows - 1) / rows_per_frame < frames.
+ * A refused call launches nothing. */
+int am_rope_f32(float* X, int64_t ldx, int off_a, int off_b, int head_stride, int64_t rows, int heads, const float* rope_cos,
+                const float* rope_sin, int frames, int rows_per_frame, void* stream);
 /* The fp32 form of am_flow_step: ClassifierFreeGuidance.aggregate_cfg (guidance.py:95-118) and the Euler step with its masked write
  * (scheduler.py:238-248) as the reference computes them in fp32 - the bits of the torch fp32 expression:
  *   out = v_0;   out = out + scale_i * (v_{i+1} - v_i)   for i = 0 .. n_branches - 2   (a subtraction, a product, a sum: three roundings)

@@ -12,6 +12,9 @@ stays on the reference's CPU path (and is not timed here): background removal, T
 BASELINE.json's "end-to-end video->4D wall-clock" restricted to the stages this repository implements).
 
     python tools/e2e_synthetic.py [--frames 16] [--steps 30] [--vertices 50000] [--tiny]
+    python tools/e2e_synthetic.py --exact-fp32 [--steps 3]      the same chain twice on the same inputs and seeds - the default models, and
+                                                  encoder fp32 -> Stage I fp32 -> Stage II fp32 (exact_fp32=True) - and the default run's vertex
+                                                  error against the exact one, in the normalised mesh's units; a short step count, stated in the record
     python tools/e2e_synthetic.py --config 1      BASELINE.json configs[1]: the 16 davis_camel frames (tests/golden/frames/, preprocessed by the
                                                   reference's own ImagePreprocessor + BitImageProcessor geometry), 50-step scheduler, bf16
     python tools/e2e_synthetic.py --config 3      configs[3]: the panda clip; in the reference this path (pipeline_with_3d) differs from configs[1]
@@ -61,7 +64,8 @@ def rand_like_spec(shapes, g):
     return sd
 
 
-def build(tiny: bool, dev):
+def build(tiny: bool, dev, exact: bool = False):
+    """The three models on random-init weights; `exact`: each in its exact-fp32 mode, from the same weights."""
     from bench import random_state_dict
     from actionmesh_amd import ClassifierFreeGuidance, HipAutoencoder, HipDenoiser, HipImageEncoder, HipSchedulerFlow
     from actionmesh_amd import image_encoder as IE
@@ -78,12 +82,13 @@ def build(tiny: bool, dev):
                    inflated_layers=list(range(21)))
         ae = dict(width=1024, num_layers=16, num_attention_heads=8, latent_channels=64)
         n_tokens, window, side = 2048, 16, 224
-    enc = HipImageEncoder(config=dino, state_dict=rand_like_spec(IE.state_dict_shapes(dict(IE._CFG_DEFAULTS, **dino)), g)).to(dev)
-    denoiser = HipDenoiser(num_tokens_nominal=n_tokens, temporal_context_size=window, **den)
+    enc = HipImageEncoder(config=dino, state_dict=rand_like_spec(IE.state_dict_shapes(dict(IE._CFG_DEFAULTS, **dino)), g),
+                          **(dict(dtype="float32") if exact else {})).to(dev)
+    denoiser = HipDenoiser(num_tokens_nominal=n_tokens, temporal_context_size=window, **den, **(dict(dtype="float32") if exact else {}))
     denoiser.load_state_dict(random_state_dict(den, seed=0))
     denoiser.to(dev).eval()
     from oracle.autoencoder_oracle import AEConfig, state_dict_spec      # parameter names / shapes only
-    vae = HipAutoencoder(temporal_context_size=window, **ae)
+    vae = HipAutoencoder(temporal_context_size=window, **ae, exact_fp32=exact)
     vae.load_state_dict(rand_like_spec(dict(state_dict_spec(AEConfig(**ae))), g))
     vae.to(dev)
     return enc, denoiser, vae, HipSchedulerFlow, ClassifierFreeGuidance, n_tokens, window, side
@@ -284,10 +289,64 @@ def run(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44,
             "context_rms": round(float(context.float().pow(2).mean().sqrt()), 4), "latents_rms": round(float(lat[1:].float().pow(2).mean().sqrt()), 4)}
 
 
+def run_exact_fp32(frames: int, steps: int, vertices: int, tiny: bool, dev, seed: int = 44):
+    """How far the default pipeline's vertices are from the same pipeline in exact arithmetic: the chain context encoder -> Stage I
+    windows -> Stage II windows twice on the same pixels, anchor latent, anchor mesh and seeds (the noise is drawn on the device from
+    the window's seed in both) - the default models, then every stage in its exact-fp32 mode - and the vertex error of the first
+    against the second, in the units of the normalised mesh (the torus fills the 0.8 cube)."""
+    from actionmesh_amd import LatentBank, generate_3d_latents, generate_vertex_animation
+    from actionmesh_amd import mesh_prep as MP
+    clean_v, clean_f, _ = torus_mesh(vertices)
+    out, seconds = {}, {}
+    for mode in ("default", "exact_fp32"):
+        enc, denoiser, vae, Sched, CFG, n_tokens, window, side = build(tiny, dev, exact=mode == "exact_fp32")
+        g = torch.Generator().manual_seed(1)
+        pixels = torch.randn((frames, 3, side, side), generator=g).to(dev)
+        timesteps = torch.arange(frames, dtype=torch.float32)
+        anchor_latent = torch.randn((1, n_tokens, 64), generator=g).to(dev)
+        pts, faces = torch.from_numpy(clean_v).float().to(dev), torch.from_numpy(clean_f).to(dev)
+        features = MP.VertexFeatures(faces)
+        sched, cfg = Sched(num_inference_steps=steps, shift=3.0, is_additive=True), CFG(True, [[0, 1], [1, 1]], [7.5])
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        context = enc.encode_pixels(pixels)
+        bank = LatentBank(empty_dims=(n_tokens, 64), device=str(dev))
+        bank.update(timesteps[:1], anchor_latent)
+        generate_3d_latents(denoiser, sched, cfg, timesteps, context, bank, 0, window, window - 1, (n_tokens, 64), seed=seed, device=dev)
+        vbank = LatentBank(empty_dims=(vertices, 3), device=str(dev))
+        vbank.update(timesteps[:1], pts[None])
+        generate_vertex_animation(vae, bank, vbank, features, 0, window, window - 1, device=dev)
+        torch.cuda.synchronize(dev)
+        seconds[mode] = round(time.perf_counter() - t0, 3)
+        verts, ts = vbank.get_ordered()
+        assert ts.tolist() == timesteps.tolist() and bool(torch.isfinite(verts).all())
+        out[mode] = (verts.double().cpu(), bank.get_ordered()[0].double().cpu(), context.double().cpu())
+        denoiser.cpu(); vae.to("cpu")
+        del enc, denoiser, vae, bank, vbank, context
+        torch.cuda.empty_cache()
+    (v, lat, ctx), (v32, lat32, ctx32) = out["default"], out["exact_fp32"]
+    assert torch.equal(v[0], v32[0])                                     # the anchor mesh, kept by both
+    dist = (v[1:] - v32[1:]).norm(dim=-1)                                # (frames - 1, V): Euclidean, per vertex and frame
+    rel = lambda a, b: float((a - b).norm() / b.norm())
+    return {"metric": "default (bf16) pipeline's vertices against the exact-fp32 pipeline, same inputs and seeds", "value": rel(v[1:], v32[1:]),
+            "unit": "rel-L2", "higher_is_better": False, "n_gpus": 1, "data": "synthetic", "denoise_steps": steps,
+            "vertex_error": {"rel_l2": rel(v[1:], v32[1:]), "mean_euclidean": float(dist.mean()), "max_euclidean": float(dist.max()),
+                             "units": "normalised mesh (torus inside the 0.8 cube)",
+                             "per_frame_max_euclidean": [float(x) for x in dist.max(dim=1).values]},
+            "context_rel_l2": rel(ctx, ctx32), "latents_rel_l2": rel(lat[1:], lat32[1:]),
+            "seconds_gpu_stages": seconds,
+            "config": {"workload": f"{frames} frames, AR windows of {window}, {steps} denoise steps (short on purpose: the exact Stage I is many "
+                                   f"times slower), N={n_tokens} tokens, {vertices} vertices, {'tiny' if tiny else 'shipped'} model shapes, "
+                                   "random-init weights, random frames"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=None, help="denoise steps per window (default 30; 3 with --exact-fp32)")
+    ap.add_argument("--exact-fp32", action="store_true",
+                    help="run the chain in the default modes and in exact fp32 (encoder, Stage I, Stage II) on the same inputs and seeds, and "
+                         "report the default run's vertex error against the exact one")
     ap.add_argument("--vertices", type=int, default=50000)
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--clip", default=None, choices=["davis_camel", "panda"], help="frames of a reference example clip (tests/golden/frames/) instead of noise")
@@ -309,6 +368,10 @@ def main():
                          "triangles in front of the decimation)")
     ap.add_argument("--config", type=int, default=None, choices=[1, 3], help="BASELINE.json configs[1] / configs[3] as a plumbing record (see the module docstring)")
     a = ap.parse_args()
+    if a.steps is None:
+        a.steps = 3 if a.exact_fp32 else 30
+    if a.exact_fp32 and (a.clip or a.config or a.mesh_prep or a.face_decimation):
+        ap.error("--exact-fp32 runs the plain chain on random frames: no --clip, --config, --mesh-prep or --face-decimation")
     if a.raw_frames and not (a.clip or a.config):
         ap.error("--raw-frames needs --clip (or --config)")
     if a.face_decimation and not (a.mesh_prep or a.config == 3):
@@ -328,6 +391,9 @@ def main():
         label = ("configs[3]: {video+3D}->4D panda path, 16 frames, 1 x MI355X - PLUMBING on random-init weights; differs from configs[1] only in the "
                  "anchor latent's source (Stage 0, reference path), which is seeded noise in both records, and in the mesh glue around Stage II "
                  "(dirty mesh -> merge_and_clean_mesh -> normalize_mesh -> sample_surface; denormalize_mesh + expand_to_original at the end)")
+    if a.exact_fp32:
+        print(json.dumps(run_exact_fp32(a.frames, a.steps, a.vertices, a.tiny, dev)))
+        return
     print(json.dumps(run(a.frames, a.steps, a.vertices, a.tiny, dev, clip=a.clip, label=label, raw_frames=a.raw_frames,
                          features=a.features, mesh_prep=a.mesh_prep, face_decimation=a.face_decimation,
                          field_grid=a.field_grid, iso_method=a.iso_method, decimate_borders=a.decimate_borders)))
