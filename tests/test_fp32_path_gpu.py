@@ -115,6 +115,7 @@ def test_attention_f32_against_fp64(nseq, H, sq, sk, D, layout):
     """Operands read in place from packed projection outputs.  layout "cross": q (rows, H D), kv = [to_k | to_v] split per head as the
     reference does (K of head h at column 2 h D, V at 2 h D + D); layout "dinov2": transformers' split, h D inside each of q / k / v
     (one packed [q | k | v] tensor when sq == sk).  Bound: rel-L2 <= 2e-6, max abs <= 1e-5 max|V|.
+    Per element, on operands with one correct bit pattern: tests/test_attention_f32_exact_gpu.py.
     Measured on MI355X: rel-L2 <= 1.7e-6 (D = 128, sk = 2056), 5.0e-7 at sk = 4113.  A first version failed here (2.9e-6 at
     sk = 4113, D = 128): its rescale used the unrounded m * scale while the probabilities used the rounded one, so alpha was 1 + ulp
     instead of 1 on every block and the early blocks drifted; both now use the same rounded scaled max."""
