@@ -39,7 +39,7 @@ this wrapper used to compute bfloat16 whatever the caller asked for).
 """
 from __future__ import annotations
 
-import math
+import contextlib
 from typing import Callable, Dict, Optional
 
 import torch
@@ -49,7 +49,7 @@ from . import ops
 from ._lib import lib
 from . import autoencoder_f32 as F32
 from .denoiser import rope_tables_host
-from .denoiser_f32 import HipF32Backend
+from .f32_backend import HipF32Backend
 
 
 class HipAutoencoder:
@@ -81,7 +81,7 @@ class HipAutoencoder:
             raise ValueError("HipAutoencoder: exact_fp32=True implies residual_fp32=True and cross_fp32=True; neither can be turned off with it")
         self.residual_fp32 = True if residual_fp32 is None else bool(residual_fp32)      # None: the default, fp32 as the reference's
         self.cross_fp32 = self.exact_fp32 if cross_fp32 is None else bool(cross_fp32)     # None: the default, off unless exact_fp32
-        self.f32_backend = None            # exact_fp32: the kernels' backend object (None: denoiser_f32.HipF32Backend)
+        self.f32_backend = None            # cross_fp32 / exact_fp32: the kernels' backend object (None: f32_backend.HipF32Backend, on first use)
         if self.cross_fp32 and not self.residual_fp32:
             raise ValueError("HipAutoencoder: cross_fp32=True needs residual_fp32=True (the fp32 block reads the fp32 kv stream)")
         self._sd: Optional[Dict[str, torch.Tensor]] = None
@@ -252,17 +252,10 @@ class HipAutoencoder:
         y = ops.gemm(f, w[p + "ff2"], bias=w[p + "ff2_b"])
         return ops.add_layernorm_f32(qh32, y, w["norm_out.w"], w["norm_out.b"])
 
-    # the exact-fp32 query side and cross-attention block (cross_fp32; temporal_autoencoder.py:152-161 under autocast(enabled=False))
-    def _query_f32(self, query: torch.Tensor) -> torch.Tensor:
-        """FrequencyPositionalEmbedding (+ extra channels) of query (rows, 3|6) fp32 -> fp32 (rows, query_pad), zero padded (:240-243)."""
-        return ops.point_embed_f32(query, self.in_channels, self.in_extra_channels, self.embed_frequency, self.embed_include_pi,
-                                   self.query_pad)
-
-    def _cross_logits_f32(self, kv32: torch.Tensor, qh32: torch.Tensor, B: int, V: int, S: int) -> torch.Tensor:
-        """blocks[-1](queries, encoder_hidden_states=kv_cache) -> norm_out -> proj_out, all fp32.  kv32 (B*S, C): the finished residual
-        stream (any key order per batch entry); qh32 (B*V, C): proj_query's output, used as the block's residual stream (modified in
-        place).  Returns (B*V, out_dim) logits BEFORE the reference's * -1."""
-        return F32.cross_logits(HipF32Backend(), self._w32, kv32, qh32, self.heads, V, S)     # the launches are stated once, there
+    def _backend(self) -> HipF32Backend:
+        """The model's one backend object of the exact-fp32 kernels (cross_fp32, exact_fp32), created on first use."""
+        self.f32_backend = HipF32Backend() if self.f32_backend is None else self.f32_backend
+        return self.f32_backend
 
     @torch.no_grad()
     def fwd_cross_attn(self, kv_cache: torch.Tensor, queries: torch.Tensor) -> torch.Tensor:
@@ -278,13 +271,13 @@ class HipAutoencoder:
         if C != self.width or queries.shape[0] != B or Dq != self.query_dim:
             raise ValueError(f"HipAutoencoder.fwd_cross_attn: kv_cache {tuple(kv_cache.shape)} / queries {tuple(queries.shape)} do not "
                              f"match width {self.width}, query_dim {self.query_dim}")
-        dev, w = self.device, self._w32
+        dev, w, be = self.device, self._w32, self._backend()
         with torch.cuda.device(dev):
             kv32 = kv_cache.to(dev, torch.float32).reshape(B * S, C).contiguous()
             qe = torch.zeros((B * V, self.query_pad), dtype=torch.float32, device=dev)
             qe[:, :Dq] = queries.to(dev, torch.float32).reshape(B * V, Dq)           # zero-padded K (copy only)
-            qh32 = ops.gemm_f32(qe, w["proj_query"], bias=w["proj_query_b"])
-            lg = self._cross_logits_f32(kv32, qh32, B, V, S)
+            qh32 = be.gemm(qe, w["proj_query"], bias=w["proj_query_b"])
+            lg = F32.cross_logits(be, w, kv32, qh32, self.heads, V, S)
             return (-lg).view(B, V, self.out_dim)
 
     # ---- forward (temporal_autoencoder.py:160-267) --------------------------------------------------------------
@@ -308,19 +301,14 @@ class HipAutoencoder:
                      bias=w["post_quant_b"], out=base, c_map=(N, L, 1), M=B * T * N)
             cos, sin = rope_tables_host(framestep)                                # scale_timestep(center) (:198-209)
             rope = (cos.to(dev), sin.to(dev))
-            # alpha tokens: TimestepEmbedder(source, target) = [cos | sin](source) | [cos | sin](target), width/2 each (:232-235)
-            half = C // 4
-            freqs = torch.exp(-math.log(10_000) * torch.arange(half, dtype=torch.float32) / half)
-            src = source_alpha.detach().float().cpu()[:, None].expand_as(target_alphas)
-            emb = []
-            for t in (src, target_alphas.detach().float().cpu()):
-                arg = t[..., None] * freqs
-                emb += [torch.cos(arg), torch.sin(arg)]
-            alpha = torch.cat(emb, -1).to(dev, dt16)                              # (B, T_out, C)
+            # alpha tokens (B, T_out, C): the fp32 stream takes the embedding in fp32 (:232-235, :258), the 16-bit stream its rounding
+            alpha = F32.alpha_embedding_host(C, source_alpha, target_alphas).to(dev, torch.float32 if self.residual_fp32 else dt16)
             # query side, once: embed + proj_query
             q32 = query.to(dev, torch.float32).reshape(B * V, -1).contiguous()
             if self.cross_fp32:                                                 # the query side with autocast off (:240-243), once
-                qh32_0 = ops.gemm_f32(self._query_f32(q32), self._w32["proj_query"], bias=self._w32["proj_query_b"])
+                be, w32 = self._backend(), self._w32
+                qe = be.point_embed(q32, self.in_channels, self.in_extra_channels, self.embed_frequency, self.embed_include_pi, self.query_pad)
+                qh32_0 = be.gemm(qe, w32["proj_query"], bias=w32["proj_query_b"])
             else:
                 qe = ops.point_embed(q32, self.in_channels, self.in_extra_channels, self.embed_frequency, self.embed_include_pi,
                                      self.query_pad, dtype=dt16)
@@ -328,7 +316,6 @@ class HipAutoencoder:
             out = torch.empty((B, T_out, V, self.out_dim), dtype=torch.float32, device=dev)
             if self.residual_fp32:
                 base32 = base.float()                                           # am_bf16_to_f32 would do; once per window, torch moves rows
-                alpha32 = torch.cat(emb, -1).to(dev, torch.float32)             # the alpha embedding enters the stream in fp32 (:232-235, :258)
                 if not self.cross_fp32:
                     qh32_0 = qh.float()
             for i in range(T_out):
@@ -336,15 +323,15 @@ class HipAutoencoder:
                     step_callback(i + 1, T_out)
                 if self.cross_fp32:
                     h32 = base32.clone()
-                    h32.view(B, T, L, C)[:, :, 0] = alpha32[:, i][:, None]
+                    h32.view(B, T, L, C)[:, :, 0] = alpha[:, i][:, None]
                     kv32 = self._self_stack_f32(h32, dt16, B, T, L, rope, finish_fp32=True)
-                    lg = self._cross_logits_f32(kv32, qh32_0.clone(), B, V, T * L)
+                    lg = F32.cross_logits(be, w32, kv32, qh32_0.clone(), self.heads, V, T * L)     # blocks[-1] -> norm_out -> proj_out, fp32
                     for b in range(B):
-                        ops.displacement_f32(lg[b * V:(b + 1) * V], self.out_dim, out[b, i])
+                        be.displacement(lg[b * V:(b + 1) * V], self.out_dim, out[b, i])
                     continue
                 if self.residual_fp32:
                     h32 = base32.clone()
-                    h32.view(B, T, L, C)[:, :, 0] = alpha32[:, i][:, None]
+                    h32.view(B, T, L, C)[:, :, 0] = alpha[:, i][:, None]
                     e = self._self_stack_f32(h32, dt16, B, T, L, rope)
                     z = self._cross_block_f32(qh32_0.clone(), e, dt16, B, V, T * L)
                 else:
@@ -367,19 +354,15 @@ class HipAutoencoder:
         """exact_fp32: autoencoder_f32.forward_f32 through the model's backend object.  The caller's autocast region changes nothing:
         every operand is fp32 and every launch an fp32 entry point.  Only a backend of the caller's (`f32_backend`: the CPU tests'
         torch restatements) runs off the device."""
-        be = self.f32_backend
-        if self._sd is None or (be is None and self.device.type != "cuda"):
+        if self._sd is None or (self.f32_backend is None and self.device.type != "cuda"):
             raise RuntimeError("HipAutoencoder: load_state_dict(...) and .to('cuda:N') first (there is no CPU path)")
         assert target_alphas.ndim == 2 and source_alpha.ndim == 1
-        if be is None:
-            be = self.f32_backend = HipF32Backend()
-        if self.device.type != "cuda":
-            return F32.forward_f32(be, self._w32_self, self._w32, self, latent, framestep, source_alpha, target_alphas, query, step_callback)
-        with torch.cuda.device(self.device):
-            return F32.forward_f32(be, self._w32_self, self._w32, self, latent, framestep, source_alpha, target_alphas, query, step_callback)
+        with torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext():
+            return F32.forward_f32(self._backend(), self._w32_self, self._w32, self, latent, framestep, source_alpha, target_alphas, query,
+                                   step_callback)
 
     def entry_counts(self) -> Dict[str, int]:
-        """exact_fp32: launches per C entry point of this model's forwards so far (HipF32Backend.calls)."""
+        """Launches per fp32 C entry point so far (HipF32Backend.calls): an exact_fp32 model's all, a cross_fp32 one's query side and block."""
         return dict(self.f32_backend.calls) if self.f32_backend is not None else {}
 
     __call__ = forward

@@ -4,7 +4,7 @@ The reference's fp32 arithmetic (temporal_autoencoder.py:163-269 with autocast o
 restates), step for step, on the exact-fp32 kernels of the library: am_gemm_f32, am_attention_f32, am_layernorm_f32,
 am_point_embed_f32, am_displacement_f32 (csrc/am_f32.hip, am_elementwise.hip) and am_rope_f32 (csrc/am_stage1_f32.hip) - Stage II
 rotates q and k without a qk-norm (attention_qk_norm=None, temporal_autoencoder.py:83-92).  Python orchestrates the launches through
-ONE backend object (denoiser_f32.HipF32Backend; the CPU tests substitute torch restatements); torch owns the memory and moves rows,
+ONE backend object (f32_backend.HipF32Backend; the CPU tests substitute torch restatements); torch owns the memory and moves rows,
 and does no arithmetic on the device.  Like Stage I's fp32 engine this is the GROUND TRUTH the 16-bit modes are measured against,
 not a fast path: nothing is captured in a graph, nothing is sharded.
 

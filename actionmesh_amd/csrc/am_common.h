@@ -212,6 +212,11 @@ int am_head_post_check(const am_headpost_args* a);      // am_norm.hip: argument
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
+// Host checks of the exact-fp32 path.  Packed heads: head h of a row of ld floats is the D columns at off + h * hs, 16-byte aligned, inside the row.
+static inline bool al16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
+static inline bool heads_aligned(int64_t ld, int off, int hs) { return ((ld | off | hs) & 3) == 0; }
+static inline bool heads_fit(int64_t ld, int off, int hs, int heads, int D) { return off >= 0 && ld >= off + (int64_t)(heads - 1) * hs + D; }
+
 // Within every aligned group of 16 keys, V^T stores key k at position
 // perm16(k) = k with bits 2 and 3 swapped (an involution).  This makes the 8
 // keys a lane holds after the S^T = K Q^T MFMA ((r&3) + 8*(r>>2) + 4*hi, the

@@ -335,8 +335,6 @@ __global__ void displacement_f32_kernel(const float* __restrict__ logits, int ld
   out[i] = 2.0f / (1.0f + expf(logits[row * ld + (i - row * out_dim)])) - 1.0f;
 }
 
-inline bool al16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
-
 }  // namespace
 
 extern "C" int am_gemm_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* R, int64_t ldr,
@@ -362,12 +360,12 @@ extern "C" int am_attention_f32(const am_attn_f32_args* a, void* stream) {
   AM_CHECK(D == 64 || D == 128, "am_attention_f32: head_dim %d (64 or 128)", D);
   AM_CHECK(a->nseq > 0 && a->heads > 0 && a->sq > 0 && a->sk > 0 && a->nseq <= 65535 && a->heads <= 65535,
            "am_attention_f32: bad shape nseq=%d heads=%d sq=%d sk=%d", a->nseq, a->heads, a->sq, a->sk);
-  AM_CHECK(al16(a->Q) && al16(a->K) && al16(a->V) && al16(a->O) &&
-           ((a->ldq | a->ldk | a->ldv | a->ldo) & 3) == 0 && ((a->q_off | a->q_hs | a->k_off | a->k_hs | a->v_off | a->v_hs) & 3) == 0,
+  AM_CHECK(al16(a->Q) && al16(a->K) && al16(a->V) && al16(a->O) && (a->ldo & 3) == 0 && heads_aligned(a->ldq, a->q_off, a->q_hs) &&
+           heads_aligned(a->ldk, a->k_off, a->k_hs) && heads_aligned(a->ldv, a->v_off, a->v_hs),
            "am_attention_f32: operands, row strides, column offsets and head strides must be 16-byte aligned");
-  AM_CHECK(a->q_off >= 0 && a->k_off >= 0 && a->v_off >= 0 && a->q_hs >= 0 && a->k_hs >= 0 && a->v_hs >= 0 &&
-           a->ldq >= a->q_off + (int64_t)(a->heads - 1) * a->q_hs + D && a->ldk >= a->k_off + (int64_t)(a->heads - 1) * a->k_hs + D &&
-           a->ldv >= a->v_off + (int64_t)(a->heads - 1) * a->v_hs + D && a->ldo >= (int64_t)a->heads * D,
+  AM_CHECK(a->q_hs >= 0 && a->k_hs >= 0 && a->v_hs >= 0 && heads_fit(a->ldq, a->q_off, a->q_hs, a->heads, D) &&
+           heads_fit(a->ldk, a->k_off, a->k_hs, a->heads, D) && heads_fit(a->ldv, a->v_off, a->v_hs, a->heads, D) &&
+           a->ldo >= (int64_t)a->heads * D,
            "am_attention_f32: a head's columns run past its row (ld / offset / head stride)");
   AttnF32 p{a->Q, a->K, a->V, a->O, a->ldq, a->ldk, a->ldv, a->ldo, a->q_off, a->q_hs, a->k_off, a->k_hs, a->v_off, a->v_hs,
             a->nseq, a->heads, a->sq, a->sk, a->scale};

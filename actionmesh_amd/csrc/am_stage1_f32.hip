@@ -15,6 +15,20 @@ namespace {
 constexpr int HP_D = 128;          // head_dim: one 128-float chunk = 32 lanes x float4 = half a wave
 constexpr int HP_CHUNKS = 8;       // chunks per 256-thread workgroup
 
+// The lane's four floats of the chunk at column `col` of row `row`: the interleaved pairs 2 lane and 2 lane + 1 of the chunk.  *t: where
+// the angles of those two pairs stand in the (frames, 64) tables - every row of a frame shares the frame's angles.
+__device__ __forceinline__ float* chunk_ptr(float* X, int64_t ldx, int64_t row, int64_t col, int rows_per_frame, int lane, int64_t* t) {
+  *t = (row / rows_per_frame) * (HP_D / 2) + 2 * lane;
+  return X + row * ldx + col + 4 * lane;
+}
+
+// rotary_embedding.py:72-124 on the lane's two pairs: out = x cos + rot(x) sin, rot(x)[2i] = -x[2i + 1], rot(x)[2i + 1] = x[2i] - two
+// products and one sum per element, each rounded once (the file is built without contraction)
+__device__ __forceinline__ f32x4_t rotate_pairs(f32x4_t x, const float* rope_cos, const float* rope_sin, int64_t t) {
+  const float c0 = rope_cos[t], c1 = rope_cos[t + 1], s0 = rope_sin[t], s1 = rope_sin[t + 1];
+  return f32x4_t{x[0] * c0 + (-x[1]) * s0, x[1] * c0 + x[0] * s0, x[2] * c1 + (-x[3]) * s1, x[3] * c1 + x[2] * s1};
+}
+
 struct HeadPostF32 {
   float* X; int64_t ldx; int off, head_stride;
   int64_t chunks; int heads;
@@ -30,7 +44,8 @@ __global__ __launch_bounds__(256) void head_post_f32_kernel(HeadPostF32 p) {
   const bool valid = chunk < p.chunks;
   const int64_t row = valid ? chunk / p.heads : 0;
   const int head = valid ? (int)(chunk - row * p.heads) : 0;
-  float* xp = p.X + row * p.ldx + p.off + (int64_t)head * p.head_stride + 4 * lane;
+  int64_t t;
+  float* xp = chunk_ptr(p.X, p.ldx, row, p.off + (int64_t)head * p.head_stride, p.rows_per_frame, lane, &t);
   f32x4_t x = valid ? *reinterpret_cast<const f32x4_t*>(xp) : f32x4_t{0.f, 0.f, 0.f, 0.f};
   float ss = (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
 #pragma unroll
@@ -40,14 +55,7 @@ __global__ __launch_bounds__(256) void head_post_f32_kernel(HeadPostF32 p) {
   f32x4_t y;
 #pragma unroll
   for (int e = 0; e < 4; ++e) y[e] = x[e] * r * wv[e];
-  if (p.rope_cos) {
-    // the lane holds the interleaved pairs 2 lane and 2 lane + 1 of the chunk; every row of a frame shares the frame's angles
-    const int64_t t = (row / p.rows_per_frame) * (HP_D / 2) + 2 * lane;
-    const float c0 = p.rope_cos[t], c1 = p.rope_cos[t + 1], s0 = p.rope_sin[t], s1 = p.rope_sin[t + 1];
-    // rotary_embedding.py:72-124: out = x cos + rot(x) sin, rot(x)[2i] = -x[2i + 1], rot(x)[2i + 1] = x[2i]
-    const f32x4_t o = {y[0] * c0 + (-y[1]) * s0, y[1] * c0 + y[0] * s0, y[2] * c1 + (-y[3]) * s1, y[3] * c1 + y[2] * s1};
-    y = o;
-  }
+  if (p.rope_cos) y = rotate_pairs(y, p.rope_cos, p.rope_sin, t);
   if (valid) *reinterpret_cast<f32x4_t*>(xp) = y;
 }
 
@@ -67,14 +75,9 @@ __global__ __launch_bounds__(256) void rope_f32_kernel(RopeF32 p) {
   const int64_t row = chunk / per_row;
   const int in_row = (int)(chunk - row * per_row);
   const int kind = in_row / p.heads, head = in_row - kind * p.heads;
-  float* xp = p.X + row * p.ldx + p.off[kind] + (int64_t)head * p.head_stride + 4 * lane;
-  const f32x4_t x = *reinterpret_cast<const f32x4_t*>(xp);
-  // the lane holds the interleaved pairs 2 lane and 2 lane + 1 of the chunk; every row of a frame shares the frame's angles
-  const int64_t t = (row / p.rows_per_frame) * (HP_D / 2) + 2 * lane;
-  const float c0 = p.rope_cos[t], c1 = p.rope_cos[t + 1], s0 = p.rope_sin[t], s1 = p.rope_sin[t + 1];
-  // rotary_embedding.py:72-124: out = x cos + rot(x) sin, rot(x)[2i] = -x[2i + 1], rot(x)[2i + 1] = x[2i]: two products, one sum, each rounded
-  const f32x4_t o = {x[0] * c0 + (-x[1]) * s0, x[1] * c0 + x[0] * s0, x[2] * c1 + (-x[3]) * s1, x[3] * c1 + x[2] * s1};
-  *reinterpret_cast<f32x4_t*>(xp) = o;
+  int64_t t;
+  float* xp = chunk_ptr(p.X, p.ldx, row, p.off[kind] + (int64_t)head * p.head_stride, p.rows_per_frame, lane, &t);
+  *reinterpret_cast<f32x4_t*>(xp) = rotate_pairs(*reinterpret_cast<const f32x4_t*>(xp), p.rope_cos, p.rope_sin, t);
 }
 
 struct FlowF32 {
@@ -82,22 +85,20 @@ struct FlowF32 {
   uint8_t unobs[256]; int64_t per_frame4, total4;       // in float4 units
 };
 
-__device__ __forceinline__ f32x4_t flow_f32(const FlowF32& a, f32x4_t lat, f32x4_t out, const f32x4_t* cur) {
+// One element of the step: `lat` its latent, `v0` branch 0's velocity, branch(b) that of branch b = 1 .. nb - 1
+template <class Branch>
+__device__ __forceinline__ float flow_element(const FlowF32& a, float lat, float v0, Branch branch) {
+  float o = v0, prev = o;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float o = out[e], prev = o;
-#pragma unroll
-    for (int b = 1; b < 4; ++b) {
-      if (b < a.nb) {
-        const float c = cur[b - 1][e];
-        o = o + a.scales[b - 1] * (c - prev);          // guidance.py:113-116: output += scale_i * (v_{i+1} - v_i)
-        prev = c;
-      }
+  for (int b = 1; b < 4; ++b) {
+    if (b < a.nb) {
+      const float c = branch(b);
+      o = o + a.scales[b - 1] * (c - prev);            // guidance.py:113-116: output += scale_i * (v_{i+1} - v_i)
+      prev = c;
     }
-    const float step = a.dt * o;                       // scheduler.py:238-241: distances[i] * output_pred
-    lat[e] = a.additive ? lat[e] + step : lat[e] - step;
   }
-  return lat;
+  const float step = a.dt * o;                         // scheduler.py:238-241: distances[i] * output_pred
+  return a.additive ? lat + step : lat - step;
 }
 
 // VEC: one float4 of the latents per thread; otherwise (a frame size that is no multiple of 4) one element per thread
@@ -112,20 +113,20 @@ __global__ __launch_bounds__(256) void flow_step_f32_kernel(FlowF32 a) {
     f32x4_t cur[3];
 #pragma unroll
     for (int b = 1; b < 4; ++b) cur[b - 1] = b < a.nb ? v[(int64_t)b * a.total4 + i] : f32x4_t{0.f, 0.f, 0.f, 0.f};
-    lat[i] = flow_f32(a, lat[i], v[i], cur);
+    f32x4_t x = lat[i];
+    const f32x4_t v0 = v[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = flow_element(a, x[e], v0[e], [&](int b) { return cur[b - 1][e]; });
+    lat[i] = x;
   } else {
-    float o = a.v[i], prev = o;
-    for (int b = 1; b < a.nb; ++b) {
-      const float c = a.v[(int64_t)b * a.total4 + i];
-      o = o + a.scales[b - 1] * (c - prev);
-      prev = c;
-    }
-    const float step = a.dt * o;
-    a.lat[i] = a.additive ? a.lat[i] + step : a.lat[i] - step;
+    a.lat[i] = flow_element(a, a.lat[i], a.v[i], [&](int b) { return a.v[(int64_t)b * a.total4 + i]; });
   }
 }
 
-inline bool al16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
+// the (frames, 64) tables reach the frame of the last row
+inline bool frames_cover(int64_t rows, int rows_per_frame, int frames) {
+  return rows_per_frame > 0 && frames > 0 && (rows - 1) / rows_per_frame < frames;
+}
 
 }  // namespace
 
@@ -133,14 +134,14 @@ extern "C" int am_head_post_f32(float* X, int64_t ldx, int off, int head_stride,
                                 const float* rope_cos, const float* rope_sin, int frames, int rows_per_frame, void* stream) {
   AM_CHECK(X && w, "am_head_post_f32: null operand");
   AM_CHECK(rows > 0 && heads > 0 && heads <= 65535, "am_head_post_f32: bad shape rows=%lld heads=%d", (long long)rows, heads);
-  AM_CHECK(al16(X) && al16(w) && ldx % 4 == 0 && off % 4 == 0 && head_stride % 4 == 0,
+  AM_CHECK(al16(X) && al16(w) && heads_aligned(ldx, off, head_stride),
            "am_head_post_f32: X, w, ldx, off and head_stride must be 16-byte aligned");
-  AM_CHECK(off >= 0 && (heads == 1 || head_stride >= HP_D) && ldx >= off + (int64_t)(heads - 1) * head_stride + HP_D,
+  AM_CHECK((heads == 1 || head_stride >= HP_D) && heads_fit(ldx, off, head_stride, heads, HP_D),
            "am_head_post_f32: the heads' chunks overlap or run past the row (ldx=%lld off=%d head_stride=%d heads=%d)", (long long)ldx,
            off, head_stride, heads);
   AM_CHECK((rope_cos == nullptr) == (rope_sin == nullptr), "am_head_post_f32: rope tables must come in pairs");
   if (rope_cos)
-    AM_CHECK(rows_per_frame > 0 && frames > 0 && (rows - 1) / rows_per_frame < frames,
+    AM_CHECK(frames_cover(rows, rows_per_frame, frames),
              "am_head_post_f32: rows=%lld / rows_per_frame=%d runs past the %d frames of the tables", (long long)rows, rows_per_frame, frames);
   const int64_t chunks = rows * heads, blocks = (chunks + HP_CHUNKS - 1) / HP_CHUNKS;
   AM_CHECK(blocks <= 0x7fffffff, "am_head_post_f32: too many rows");
@@ -156,10 +157,10 @@ extern "C" int am_rope_f32(float* X, int64_t ldx, int off_a, int off_b, int head
   AM_CHECK(X && rope_cos, "am_rope_f32: null operand");
   AM_CHECK(rows > 0 && heads > 0 && heads <= 65535, "am_rope_f32: bad shape rows=%lld heads=%d", (long long)rows, heads);
   const int kinds = off_b < 0 ? 1 : 2;
-  AM_CHECK(al16(X) && ldx % 4 == 0 && off_a % 4 == 0 && (kinds == 1 || off_b % 4 == 0) && head_stride % 4 == 0,
+  AM_CHECK(al16(X) && heads_aligned(ldx, off_a, head_stride) && (kinds == 1 || heads_aligned(ldx, off_b, head_stride)),
            "am_rope_f32: X, ldx, off_a, off_b and head_stride must be 16-byte aligned");
-  const int64_t span = (int64_t)(heads - 1) * head_stride + HP_D;
-  AM_CHECK(off_a >= 0 && (heads == 1 || head_stride >= HP_D) && ldx >= off_a + span && (kinds == 1 || ldx >= off_b + span),
+  AM_CHECK((heads == 1 || head_stride >= HP_D) && heads_fit(ldx, off_a, head_stride, heads, HP_D) &&
+               (kinds == 1 || heads_fit(ldx, off_b, head_stride, heads, HP_D)),
            "am_rope_f32: the heads' chunks overlap or run past the row (ldx=%lld off_a=%d off_b=%d head_stride=%d heads=%d)",
            (long long)ldx, off_a, off_b, head_stride, heads);
   if (kinds == 2) {
@@ -176,7 +177,7 @@ extern "C" int am_rope_f32(float* X, int64_t ldx, int off_a, int off_b, int head
     }
     AM_CHECK(!overlap, "am_rope_f32: the q and k chunks overlap (off_a=%d off_b=%d head_stride=%d heads=%d)", off_a, off_b, head_stride, heads);
   }
-  AM_CHECK(rows_per_frame > 0 && frames > 0 && (rows - 1) / rows_per_frame < frames,
+  AM_CHECK(frames_cover(rows, rows_per_frame, frames),
            "am_rope_f32: rows=%lld / rows_per_frame=%d runs past the %d frames of the tables", (long long)rows, rows_per_frame, frames);
   const int64_t chunks = rows * heads * kinds, blocks = (chunks + HP_CHUNKS - 1) / HP_CHUNKS;
   AM_CHECK(blocks <= 0x7fffffff, "am_rope_f32: too many rows");

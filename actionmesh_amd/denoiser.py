@@ -332,7 +332,7 @@ class HipDenoiser(nn.Module):
                 raise ValueError("HipDenoiser(dtype='float32'): use_graph=True is not supported (the fp32 forward is not captured)")
             if attn_dtype != "bf16":
                 raise ValueError(f"HipDenoiser(dtype='float32'): attn_dtype={attn_dtype!r} is not supported (every operation is fp32)")
-        self.f32_backend = None             # fp32 mode: the kernels' backend object (None: denoiser_f32.HipF32Backend)
+        self.f32_backend = None             # fp32 mode: the kernels' backend object (None: f32_backend.HipF32Backend)
         # HIP-graph replay of the single-rank forward (None: the ACTIONMESH_AMD_GRAPH environment variable, default off; fp32: never)
         self.use_graph = False if self.fp32 else (os.environ.get("ACTIONMESH_AMD_GRAPH", "0") == "1") if use_graph is None else bool(use_graph)
         self.attn_dtype = attn_dtype        # "fp8": inflated self-attention on the e4m3 MFMA kernel (BASELINE configs[4])

@@ -3,7 +3,7 @@
 The forward is the reference's fp32 arithmetic (temporal_denoiser.py:151-249 with autocast off - what `oracle.denoiser_forward(...,
 "fp32")` restates), step for step, on the exact-fp32 kernels of the library: am_gemm_f32, am_attention_f32, am_layernorm_f32 (csrc/
 am_f32.hip) and am_head_post_f32 (csrc/am_stage1_f32.hip); the sampler's CFG + Euler step is am_flow_step_f32.  Python orchestrates
-the launches the way HipImageEncoder._forward_f32 and HipAutoencoder._cross_block_f32 do; torch owns the memory and moves rows (the
+the launches through ONE backend object (f32_backend.HipF32Backend; the CPU tests substitute torch restatements); torch owns the memory and moves rows (the
 time token's placement, the final [:, -N:] slice), and does no arithmetic on the device.  This engine is the GROUND TRUTH the 16-bit
 and fp8 paths are measured against, not a fast path: every operation is computed (the exact-shortcut hints of the 16-bit engine are
 accepted and ignored), nothing is captured in a graph, nothing is sharded.
@@ -26,56 +26,10 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import ops
+from .f32_backend import HipF32Backend
 
 HEAD_DIM = 128
 LN_EPS, RMS_EPS = 1e-5, 1e-6        # FP32LayerNorm / nn.LayerNorm (block.py:64,83,98,107); RMSNorm(dim_head, eps=1e-6) (block.py:49,72,91)
-
-
-class HipF32Backend:
-    """The kernels of the fp32 forward behind one object, so that the orchestration can be run on restatements of them (the CPU tests
-    substitute torch ones; the fifth kernel of the mode, am_flow_step_f32, is the sampler's: ops.flow_step).  `calls` counts the
-    launches per C entry point: what really ran.  The exact-fp32 Stage II (autoencoder_f32.py) runs through the same object: the four
-    methods of Stage I - head_post aside - and the three behind them."""
-
-    def __init__(self, kind: str = "bf16"):
-        self.kind = kind             # which build of the library runs the fp32 entry points (the same bits from both)
-        self.calls: Dict[str, int] = {}
-
-    def _count(self, name: str) -> None:
-        self.calls[name] = self.calls.get(name, 0) + 1
-
-    def gemm(self, a, w, bias=None, residual=None, gelu=False, out=None):
-        self._count("am_gemm_f32")
-        return ops.gemm_f32(a, w, bias=bias, residual=residual, gelu=gelu, out=out, kind=self.kind)
-
-    def layernorm(self, x, w, b, eps, out=None):
-        self._count("am_layernorm_f32")
-        return ops.layernorm_f32(x, w, b, eps=eps, out=out, kind=self.kind)
-
-    def head_post(self, x, heads, w, off, head_stride, eps, rope=None, rows_per_frame=1):
-        self._count("am_head_post_f32")
-        return ops.head_post_f32(x, heads, w, off=off, head_stride=head_stride, eps=eps, rope=rope, rows_per_frame=rows_per_frame,
-                                 kind=self.kind)
-
-    def attention(self, q, k, v, heads, sq, sk, q_hs, k_hs, v_hs, q_off, k_off, v_off, out=None):
-        self._count("am_attention_f32")
-        return ops.attention_f32(q, k, v, heads, sq, sk, HEAD_DIM, q_hs=q_hs, k_hs=k_hs, v_hs=v_hs, q_off=q_off, k_off=k_off,
-                                 v_off=v_off, out=out, kind=self.kind)
-
-    # what the exact-fp32 Stage II (autoencoder_f32.py) needs beside the four above
-    def rope(self, x, heads, rope, off_a, off_b, head_stride, rows_per_frame):
-        self._count("am_rope_f32")
-        return ops.rope_f32(x, heads, rope, off_a=off_a, off_b=off_b, head_stride=head_stride, rows_per_frame=rows_per_frame,
-                            kind=self.kind)
-
-    def point_embed(self, query, in_channels, extra_channels, num_freqs, include_pi, ld_out):
-        self._count("am_point_embed_f32")
-        return ops.point_embed_f32(query, in_channels, extra_channels, num_freqs, include_pi, ld_out, kind=self.kind)
-
-    def displacement(self, logits, out_dim, out):
-        self._count("am_displacement_f32")
-        return ops.displacement_f32(logits, out_dim, out, kind=self.kind)
 
 
 def timestep_sinusoid_host(t_bt: Sequence[float], dim: int) -> torch.Tensor:

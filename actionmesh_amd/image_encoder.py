@@ -32,6 +32,7 @@ packed [query | key | value] projection, LayerScale folded into the fp32 out-pro
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -39,6 +40,7 @@ import torch
 from . import _lib as L
 from . import ops
 from ._lib import lib
+from .f32_backend import HipF32Backend
 
 _CFG_DEFAULTS = dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, mlp_ratio=4, patch_size=14,
                      image_size=518, num_channels=3, layer_norm_eps=1e-6, qkv_bias=True, use_swiglu_ffn=False)
@@ -159,6 +161,7 @@ class HipImageEncoder:
         if self.kind == "f16":
             lib("f16")
         self.dt16 = torch.float32 if self.fp32 else L.torch_dtype(self.kind)
+        self.f32_backend = None            # dtype="float32": the kernels' backend object (None: f32_backend.HipF32Backend, on first use)
         self.pretrained_dino_feature_extractor = pretrained_dino_feature_extractor
         self.pretrained_dino_model = pretrained_dino_model
         self._device = torch.device("cpu")
@@ -207,7 +210,7 @@ class HipImageEncoder:
 
     def to(self, device):
         self._device = torch.device(device)
-        if self._packed is not None and self._device.type == "cuda":
+        if self._packed is not None and (self._device.type == "cuda" or self.fp32):
             self._upload()
         return self
 
@@ -221,7 +224,7 @@ class HipImageEncoder:
             raise ValueError(f"HipImageEncoder.load_state_dict: shape mismatch (key, got, expected): {bad[:4]}")
         self._packed = (pack_weights_f32 if self.fp32 else pack_weights)(sd, self.cfg)
         self._pos_cache.clear()
-        if self._device.type == "cuda":
+        if self._device.type == "cuda" or self.fp32:            # fp32 operands are also what a caller's backend takes off the device
             self._upload()
         return self
 
@@ -253,7 +256,9 @@ class HipImageEncoder:
     def encode_pixels(self, pixel_values: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """Dinov2Model(pixel_values).last_hidden_state: (T, 3, H, W) -> (T, 1 + (H/p)(W/p), C).
         `out_dtype=torch.bfloat16` (the encoder's own 16-bit type) hands the context over in the dtype `am_set_context` stores it in."""
-        if self._device.type != "cuda" or not self._w:
+        # only a backend of the caller's (`f32_backend` of a dtype="float32" model: the CPU tests' torch restatements) runs off the device
+        off_device = self._device.type != "cuda" and self.fp32 and self.f32_backend is not None
+        if not self._w or (self._device.type != "cuda" and not off_device):
             raise RuntimeError("HipImageEncoder: load_state_dict(...) and .to('cuda:N') first (there is no CPU path)")
         cfg, w, dev = self.cfg, self._w, self._device
         C, H, p, eps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["patch_size"], cfg["layer_norm_eps"]
@@ -263,7 +268,7 @@ class HipImageEncoder:
         n_h, n_w = Hi // p, Wi // p
         npatch, S = n_h * n_w, n_h * n_w + 1
         if self.fp32:
-            with torch.cuda.device(dev):
+            with contextlib.nullcontext() if off_device else torch.cuda.device(dev):
                 out = self._forward_f32(pixel_values.to(dev, torch.float32).contiguous(), T, n_h, n_w)
             return out if out_dtype == out.dtype else out.to(out_dtype)
         with torch.cuda.device(dev):
@@ -316,31 +321,36 @@ class HipImageEncoder:
             return y if out_dtype == y.dtype else y.to(out_dtype)
 
     def _forward_f32(self, pix: torch.Tensor, T: int, n_h: int, n_w: int) -> torch.Tensor:
-        """dtype="float32": Dinov2Model in fp32, every step on the exact-fp32 kernels.  Returns (T, S, C) fp32."""
+        """dtype="float32": Dinov2Model in fp32, every step on the exact-fp32 kernels through the backend.  Returns (T, S, C) fp32."""
+        be = self.f32_backend = HipF32Backend() if self.f32_backend is None else self.f32_backend
         cfg, w = self.cfg, self._w
         C, H, p, eps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["patch_size"], cfg["layer_norm_eps"]
         hd, npatch, S = C // H, n_h * n_w, n_h * n_w + 1
         # embeddings: h = [cls + pos_0 | conv(pixels) + bias + pos_1..] - the patch projection's residual operand is the position rows,
         # written in place behind each frame's class-token row
         h = self._pos_rows32(T, n_h, n_w).clone()
-        patches = ops.patchify_f32(pix, p, w["patch.w"].shape[1])
+        patches = be.patchify(pix, p, w["patch.w"].shape[1])
         for t in range(T):
             rows = h[t * S + 1:(t + 1) * S]
-            ops.gemm_f32(patches[t * npatch:(t + 1) * npatch], w["patch.w"], bias=w["patch.b"], residual=rows, out=rows)
+            be.gemm(patches[t * npatch:(t + 1) * npatch], w["patch.w"], bias=w["patch.b"], residual=rows, out=rows)
         del patches
         z = torch.empty_like(h)
         for i in range(cfg["num_hidden_layers"]):
             q = f"l{i}."
-            ops.layernorm_f32(h, w[q + "norm1.w"], w[q + "norm1.b"], eps=eps, out=z)
-            qkv = ops.gemm_f32(z, w[q + "qkv.w"], bias=w[q + "qkv.b"])                         # (T*S, 3C): q | k | v
-            a = ops.attention_f32(qkv, qkv, qkv, H, S, S, hd, q_off=0, k_off=C, v_off=2 * C)
+            be.layernorm(h, w[q + "norm1.w"], w[q + "norm1.b"], eps, out=z)
+            qkv = be.gemm(z, w[q + "qkv.w"], bias=w[q + "qkv.b"])                              # (T*S, 3C): q | k | v
+            a = be.attention(qkv, qkv, qkv, H, S, S, hd, hd, hd, 0, C, 2 * C, head_dim=hd)
             del qkv
-            ops.gemm_f32(a, w[q + "o.w"], bias=w[q + "o.b"], residual=h, out=h)                # LayerScale folded
-            ops.layernorm_f32(h, w[q + "norm2.w"], w[q + "norm2.b"], eps=eps, out=z)
-            f = ops.gemm_f32(z, w[q + "fc1.w"], bias=w[q + "fc1.b"], gelu=True)
-            ops.gemm_f32(f, w[q + "fc2.w"], bias=w[q + "fc2.b"], residual=h, out=h)
+            be.gemm(a, w[q + "o.w"], bias=w[q + "o.b"], residual=h, out=h)                     # LayerScale folded
+            be.layernorm(h, w[q + "norm2.w"], w[q + "norm2.b"], eps, out=z)
+            f = be.gemm(z, w[q + "fc1.w"], bias=w[q + "fc1.b"], gelu=True)
+            be.gemm(f, w[q + "fc2.w"], bias=w[q + "fc2.b"], residual=h, out=h)
             del f
-        return ops.layernorm_f32(h, w["norm.w"], w["norm.b"], eps=eps, out=z).view(T, S, C)
+        return be.layernorm(h, w["norm.w"], w["norm.b"], eps, out=z).view(T, S, C)
+
+    def entry_counts(self) -> Dict[str, int]:
+        """dtype="float32": launches per C entry point of this model's forwards so far (HipF32Backend.calls)."""
+        return dict(self.f32_backend.calls) if self.f32_backend is not None else {}
 
     def _preprocess_settings(self) -> Dict:
         """preprocessor_config.json of the feature extractor, validated by image_preprocess.processor_settings (no `transformers`)."""

@@ -79,6 +79,24 @@ def _need_rows(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     return t
 
 
+def _need_head_columns(who: str, name: str, t: torch.Tensor, heads: int, off: int, hs: int, head_dim: int) -> None:
+    """Packed heads of the fp32 path: head h of a row of `t` is columns [off + h * hs, + head_dim); the last one ends inside the row."""
+    end = off + (heads - 1) * hs + head_dim
+    if heads < 1 or off < 0 or hs < 0 or end > t.shape[1]:
+        raise ValueError(f"{who}: {name} has {t.shape[1]} columns, head {heads - 1} ends at {end}")
+
+
+def _need_rope_tables(who: str, rope: Tuple[torch.Tensor, torch.Tensor], rows: int, rows_per_frame: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`rope` = (cos, sin), each (frames, 64) fp32; row r takes frame r // rows_per_frame, and the rows stay inside the frames."""
+    cos, sin = rope
+    _need(cos, torch.float32, "rope cos"); _need(sin, torch.float32, "rope sin")
+    if cos.dim() != 2 or cos.shape[1] != HEAD_DIM // 2 or sin.shape != cos.shape:
+        raise ValueError(f"{who}: rope tables must be (frames, {HEAD_DIM // 2}), got {tuple(cos.shape)} / {tuple(sin.shape)}")
+    if rows_per_frame < 1 or (rows - 1) // rows_per_frame >= cos.shape[0]:
+        raise ValueError(f"{who}: {rows} rows of {rows_per_frame} per frame run past the {cos.shape[0]} frames of the tables")
+    return cos, sin
+
+
 def round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
@@ -1550,8 +1568,7 @@ def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
         raise ValueError(f"attention_f32: rows q {q.shape[0]} / k {k.shape[0]} / v {v.shape[0]} do not match sq={sq}, sk={sk}")
     q_hs, k_hs, v_hs = (head_dim if x is None else x for x in (q_hs, k_hs, v_hs))
     for name, t, off, hs in (("q", q, q_off, q_hs), ("k", k, k_off, k_hs), ("v", v, v_off, v_hs)):
-        if off < 0 or hs < 0 or off + (heads - 1) * hs + head_dim > t.shape[1]:
-            raise ValueError(f"attention_f32: {name} has {t.shape[1]} columns, head {heads - 1} ends at {off + (heads - 1) * hs + head_dim}")
+        _need_head_columns("attention_f32", name, t, heads, off, hs, head_dim)
     nseq = q.shape[0] // sq
     if out is None:
         out = torch.empty((nseq * sq, heads * head_dim), dtype=torch.float32, device=q.device)
@@ -1594,20 +1611,10 @@ def head_post_f32(x: torch.Tensor, heads: int, w: torch.Tensor, off: int = 0, he
     _need_rows(x, torch.float32, "x"); _need(w, torch.float32, "w")
     if w.numel() != HEAD_DIM:
         raise ValueError(f"head_post_f32: the gain has {w.numel()} elements, head_dim is {HEAD_DIM}")
-    if heads < 1 or off < 0 or head_stride < 0 or off + (heads - 1) * head_stride + HEAD_DIM > x.shape[1]:
-        raise ValueError(f"head_post_f32: x has {x.shape[1]} columns, head {heads - 1} ends at {off + (heads - 1) * head_stride + HEAD_DIM}")
-    cos = sin = None
-    frames = 0
-    if rope is not None:
-        cos, sin = rope
-        _need(cos, torch.float32, "rope cos"); _need(sin, torch.float32, "rope sin")
-        frames = cos.shape[0]
-        if cos.dim() != 2 or cos.shape[1] != HEAD_DIM // 2 or sin.shape != cos.shape:
-            raise ValueError(f"head_post_f32: rope tables must be (frames, {HEAD_DIM // 2}), got {tuple(cos.shape)} / {tuple(sin.shape)}")
-        if rows_per_frame < 1 or (x.shape[0] - 1) // rows_per_frame >= frames:
-            raise ValueError(f"head_post_f32: {x.shape[0]} rows of {rows_per_frame} per frame run past the {frames} frames of the tables")
+    _need_head_columns("head_post_f32", "x", x, heads, off, head_stride, HEAD_DIM)
+    cos, sin = (None, None) if rope is None else _need_rope_tables("head_post_f32", rope, x.shape[0], rows_per_frame)
     _call(x, kind, "am_head_post_f32", x.data_ptr(), x.stride(0), off, head_stride, x.shape[0], heads, w.data_ptr(), eps,
-            _p(cos), _p(sin), frames, rows_per_frame)
+            _p(cos), _p(sin), 0 if cos is None else cos.shape[0], rows_per_frame)
     return x
 
 
@@ -1618,18 +1625,11 @@ def rope_f32(x: torch.Tensor, heads: int, rope: Tuple[torch.Tensor, torch.Tensor
     head_stride : + 128] (k) of the packed projection output x (rows, >= ...) fp32 (rows may be strided): both kinds in one launch, the
     bits of the unfused torch fp32 rotation.  The other columns of x are not touched.  Returns x."""
     _need_rows(x, torch.float32, "x")
-    cos, sin = rope
-    _need(cos, torch.float32, "rope cos"); _need(sin, torch.float32, "rope sin")
-    if cos.dim() != 2 or cos.shape[1] != HEAD_DIM // 2 or sin.shape != cos.shape:
-        raise ValueError(f"rope_f32: rope tables must be (frames, {HEAD_DIM // 2}), got {tuple(cos.shape)} / {tuple(sin.shape)}")
     for off in (off_a,) if off_b < 0 else (off_a, off_b):
-        if heads < 1 or off < 0 or head_stride < 0 or off + (heads - 1) * head_stride + HEAD_DIM > x.shape[1]:
-            raise ValueError(f"rope_f32: x has {x.shape[1]} columns, head {heads - 1} ends at {off + (heads - 1) * head_stride + HEAD_DIM}")
-    frames = cos.shape[0]
-    if rows_per_frame < 1 or (x.shape[0] - 1) // rows_per_frame >= frames:
-        raise ValueError(f"rope_f32: {x.shape[0]} rows of {rows_per_frame} per frame run past the {frames} frames of the tables")
+        _need_head_columns("rope_f32", "x", x, heads, off, head_stride, HEAD_DIM)
+    cos, sin = _need_rope_tables("rope_f32", rope, x.shape[0], rows_per_frame)
     _call(x, kind, "am_rope_f32", x.data_ptr(), x.stride(0), off_a, off_b, head_stride, x.shape[0], heads, cos.data_ptr(), sin.data_ptr(),
-          frames, rows_per_frame)
+          cos.shape[0], rows_per_frame)
     return x
 
 

@@ -1,6 +1,6 @@
 """What tests/test_stage1_fp32_cpu.py and tests/test_stage1_fp32_gpu.py share: the tiny fixtures' cases, torch-CPU restatements of the five
-kernels - the four of the forward behind the interface of `actionmesh_amd.denoiser_f32.HipF32Backend`, and the sampler's CFG + Euler
-step - so that the orchestration of HipDenoiser(dtype="float32") runs without a device, and the assertions both files make on `tiny_inflated` / `tiny_mixed` - on the restatements in one, on the kernels in
+kernels - the four of the forward behind the interface of `actionmesh_amd.f32_backend.HipF32Backend`, and the sampler's CFG + Euler
+step (tests/_f32_backend.TorchBackend) - so that the orchestration of HipDenoiser(dtype="float32") runs without a device, and the assertions both files make on `tiny_inflated` / `tiny_mixed` - on the restatements in one, on the kernels in
 the other.
 
 The bound throughout is rel-L2 <= 2e-5 against the fp32 values of the reference's own modules (tests/golden/tiny_*.npz): the statement
@@ -9,10 +9,10 @@ import os
 
 import numpy as np
 import torch
-import torch.nn.functional as F
+
+from _f32_backend import HD, TorchBackend  # noqa: F401  (the one restatement; both test files reach it through this module)
 
 BOUND = 2e-5
-HD = 128
 CASES = {
     "tiny_inflated": dict(in_channels=64, num_layers=5, num_attention_heads=2, width=256,
                           mlp_ratio=4.0, cross_attention_dim=64, inflated_layers=(0, 1, 2, 3, 4)),
@@ -24,72 +24,6 @@ F32_ENTRIES = {"am_gemm_f32", "am_layernorm_f32", "am_head_post_f32", "am_attent
 
 def rel(a, b):
     return float((a.double() - b.double()).norm() / b.double().norm())
-
-
-class TorchBackend:
-    """HipF32Backend's four methods, and ops.flow_step for an fp32 velocity, as plain torch fp32 statements on CPU tensors, written
-    from the contracts in include/actionmesh_amd.h (same in-place and aliasing behaviour)."""
-
-    def __init__(self):
-        self.calls = {}
-
-    def _count(self, name):
-        self.calls[name] = self.calls.get(name, 0) + 1
-
-    def gemm(self, a, w, bias=None, residual=None, gelu=False, out=None):
-        self._count("am_gemm_f32")
-        y = F.linear(a, w, bias)
-        if gelu:
-            y = F.gelu(y, approximate="none")
-        if residual is not None:
-            y = y + residual
-        if out is None:
-            return y
-        out.copy_(y)
-        return out
-
-    def layernorm(self, x, w, b, eps, out=None):
-        self._count("am_layernorm_f32")
-        y = F.layer_norm(x, (x.shape[-1],), w, b, eps)
-        if out is None:
-            return y
-        assert out.data_ptr() != x.data_ptr()
-        out.copy_(y)
-        return out
-
-    def head_post(self, x, heads, w, off, head_stride, eps, rope=None, rows_per_frame=1):
-        self._count("am_head_post_f32")
-        rows = x.shape[0]
-        for h in range(heads):
-            c = x[:, off + h * head_stride: off + h * head_stride + HD]
-            y = c * torch.rsqrt(c.pow(2).mean(-1, keepdim=True) + eps) * w
-            if rope is not None:
-                frame = torch.arange(rows) // rows_per_frame
-                cs, sn = (t[frame].repeat_interleave(2, dim=1) for t in rope)
-                yr, yi = y.reshape(rows, HD // 2, 2).unbind(-1)
-                y = y * cs + torch.stack([-yi, yr], dim=-1).flatten(1) * sn
-            c.copy_(y)
-        return x
-
-    def attention(self, q, k, v, heads, sq, sk, q_hs, k_hs, v_hs, q_off, k_off, v_off):
-        self._count("am_attention_f32")
-        nseq = q.shape[0] // sq
-
-        def split(t, s, off, hs):
-            return torch.stack([t[:, off + h * hs: off + h * hs + HD] for h in range(heads)], 0).reshape(heads, nseq, s, HD).transpose(0, 1)
-        o = F.scaled_dot_product_attention(split(q, sq, q_off, q_hs), split(k, sk, k_off, k_hs), split(v, sk, v_off, v_hs))
-        return o.transpose(1, 2).reshape(nseq * sq, heads * HD).contiguous()
-
-    def flow_step(self, v, latents, scales, dt, is_additive, unobserved):
-        self._count("am_flow_step_f32")
-        assert v.dtype == torch.float32 and latents.dtype == torch.float32
-        out = v[0]
-        for i in range(v.shape[0] - 1):
-            out = out + float(scales[i]) * (v[i + 1] - v[i])
-        step = torch.tensor(dt, dtype=torch.float32) * out
-        flow = latents + step if is_additive else latents - step
-        sel = torch.ones(latents.shape[0], dtype=torch.bool) if unobserved is None else torch.tensor([bool(u) for u in unobserved])
-        latents[sel] = flow[sel]
 
 
 def setup(name, golden_dir, dev, backend=None, **model_kw):

@@ -1,6 +1,6 @@
 """What tests/test_stage2_fp32_cpu.py and tests/test_stage2_fp32_gpu.py share: torch-CPU restatements of the kernels behind the interface
-of `actionmesh_amd.denoiser_f32.HipF32Backend` as the exact-fp32 Stage II uses it (tests/_stage1_fp32.TorchBackend plus am_rope_f32,
-am_point_embed_f32 and am_displacement_f32, written from the contracts in include/actionmesh_amd.h), so that the orchestration of
+of `actionmesh_amd.f32_backend.HipF32Backend` as the exact-fp32 Stage II uses it (tests/_f32_backend.TorchBackend: Stage I's methods,
+am_rope_f32, am_point_embed_f32 and am_displacement_f32, written from the contracts in include/actionmesh_amd.h), so that the orchestration of
 HipAutoencoder(exact_fp32=True) runs without a device, and the assertions both files make - on the restatements in one, on the
 kernels in the other.
 
@@ -18,50 +18,10 @@ from oracle import autoencoder_oracle as AO
 
 BOUND = S1.BOUND
 HD = S1.HD
+TorchBackend = S1.TorchBackend
 rel = S1.rel
 F32_ENTRIES = {"am_gemm_f32", "am_layernorm_f32", "am_rope_f32", "am_attention_f32", "am_point_embed_f32", "am_displacement_f32"}
 SMALL = dict(width=256, num_layers=2, num_attention_heads=2, latent_channels=64)          # 2 + 1 blocks
-
-
-class TorchBackend(S1.TorchBackend):
-    """The Stage-I restatements plus the three methods Stage II adds to HipF32Backend, and the attention's `out`."""
-
-    def attention(self, q, k, v, heads, sq, sk, q_hs, k_hs, v_hs, q_off, k_off, v_off, out=None):
-        o = super().attention(q, k, v, heads, sq, sk, q_hs, k_hs, v_hs, q_off, k_off, v_off)
-        if out is None:
-            return o
-        out.copy_(o)
-        return out
-
-    def rope(self, x, heads, rope, off_a, off_b, head_stride, rows_per_frame):
-        self._count("am_rope_f32")
-        rows = x.shape[0]
-        frame = torch.arange(rows) // rows_per_frame
-        cs, sn = (t[frame].repeat_interleave(2, dim=1) for t in rope)
-        for off in (off_a,) if off_b < 0 else (off_a, off_b):
-            for h in range(heads):
-                c = x[:, off + h * head_stride: off + h * head_stride + HD]
-                xr, xi = c.reshape(rows, HD // 2, 2).unbind(-1)
-                c.copy_(c * cs + torch.stack([-xi, xr], dim=-1).flatten(1) * sn)
-        return x
-
-    def point_embed(self, query, in_channels, extra_channels, num_freqs, include_pi, ld_out):
-        self._count("am_point_embed_f32")
-        x = query[:, :in_channels]
-        freqs = 2.0 ** torch.arange(num_freqs, dtype=torch.float32)
-        if include_pi:
-            freqs = freqs * torch.pi
-        e = (x[..., None] * freqs).reshape(x.shape[0], -1)
-        cols = [x, e.sin(), e.cos(), query[:, in_channels:in_channels + extra_channels]]
-        out = torch.zeros((query.shape[0], ld_out))
-        cat = torch.cat(cols, -1)
-        out[:, :cat.shape[1]] = cat
-        return out
-
-    def displacement(self, logits, out_dim, out):
-        self._count("am_displacement_f32")
-        out.copy_(2 * torch.sigmoid(-logits[:, :out_dim]) - 1.0)
-        return out
 
 
 def fixture(golden_dir, name):

@@ -360,3 +360,11 @@ def test_encoder_float32_vitl_against_transformers(golden_dir):
     enc2 = IE.HipImageEncoder(state_dict=sd, dtype=torch.float32).to(DEV)
     o16 = enc2.encode_pixels(pixels.to(DEV), out_dtype=torch.bfloat16)
     assert o16.dtype == torch.bfloat16 and torch.equal(o16.cpu(), out.to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("name", ["head_dim_64", "head_dim_128"])
+def test_encoder_float32_tiny_cases_and_launch_counts(name):
+    """The two tiny encoders of tests/test_encoder_fp32_cpu.py (head_dim 64 and 128, non-square images) on the kernels: the same bound
+    against the oracle, the same launch counts."""
+    from test_encoder_fp32_cpu import check_case
+    check_case(name, torch.device(DEV))

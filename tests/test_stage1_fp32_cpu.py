@@ -1,5 +1,5 @@
 """HipDenoiser(dtype="float32") without a GPU: the orchestration of actionmesh_amd/denoiser_f32.py runs on torch-CPU restatements of its five
-kernels (tests/_stage1_fp32.TorchBackend) against the fp32 values of the reference's own modules, and the declarations, refusals and
+kernels (tests/_f32_backend.TorchBackend) against the fp32 values of the reference's own modules, and the declarations, refusals and
 switches that reach the mode are checked.  The same assertions run on the kernels in tests/test_stage1_fp32_gpu.py.
 
 Bound: rel-L2 <= 2e-5 (tests/_stage1_fp32.py).  Measured with the restatements (torch 2.x CPU kernels): 0.0 everywhere - tiny_inflated and

@@ -122,6 +122,42 @@ def test_head_post_f32_refuses_what_it_cannot_address(dev):
         ops.head_post_f32(x, 1, w, rope=(cos, cos), rows_per_frame=3)     # row 3 is frame 1, the tables hold one
 
 
+def test_head_post_f32_rotation_is_rope_f32_bit_for_bit(dev):
+    """The two kernels share one rotation: am_head_post_f32 with tables on the q chunks gives, bit for bit, am_head_post_f32 without
+    tables followed by am_rope_f32 (one kind) on the same chunks - the file is built without contraction, and the store and reload of
+    the normalised fp32 values between the two launches keeps their bits.  The packed [q | k | v] layout: 11 rows of 3 heads, head
+    stride 3 x 128, 4 rows per frame (three frames, the last partial), a row stride 4 floats wider than the row; 33 chunks over five
+    8-chunk workgroups, the last one partial.  X sits in a poisoned arena, the gain and the tables in arenas of their own, the values
+    are finite; the k and v chunks and the gap keep their bits."""
+    from actionmesh_amd import ops
+    from actionmesh_amd.denoiser import rope_tables_host
+    gen = torch.Generator().manual_seed(23)
+    rows, heads, hs, rpf = 11, 3, 3 * HD, 4
+    width = hs * heads
+    x = torch.randn((rows, width), generator=gen) * 3.0
+    w = 1.0 + 0.1 * torch.randn((HD,), generator=gen)
+    cos, sin = rope_tables_host(torch.arange(3, dtype=torch.float32)[None] * 1.5 + 2.0)
+    Wt, Cs, Sn = (Arena.flat_of(t.to(dev)) for t in (w, cos, sin))
+    tabs = (Cs.view, Sn.view)
+    fused, split = Arena.of(x.to(dev), ld=width + 4), Arena.of(x.to(dev), ld=width + 4)
+    ops.head_post_f32(fused.view, heads, Wt.view, off=0, head_stride=hs, rope=tabs, rows_per_frame=rpf)
+    ops.head_post_f32(split.view, heads, Wt.view, off=0, head_stride=hs)
+    normed = split.view.cpu()
+    ops.rope_f32(split.view, heads, tabs, off_a=0, off_b=-1, head_stride=hs, rows_per_frame=rpf)
+    torch.cuda.synchronize()
+    for a, what in ((fused, "X, one launch"), (split, "X, two launches"), (Wt, "w"), (Cs, "cos"), (Sn, "sin")):
+        a.assert_untouched(what)
+    assert torch.equal(Wt.view.cpu(), w) and torch.equal(Cs.view.cpu(), cos) and torch.equal(Sn.view.cpu(), sin)
+    got, two = fused.view.cpu(), split.view.cpu()
+    assert torch.isfinite(got).all()
+    assert torch.equal(got.view(torch.int32), two.view(torch.int32)), f"{int((got != two).sum())} element(s) differ"
+    q = torch.zeros((rows, width), dtype=torch.bool)
+    for h in range(heads):
+        q[:, h * hs: h * hs + HD] = True
+    assert torch.equal(got[~q].view(torch.int32), x[~q].view(torch.int32)), "a k or v chunk changed"
+    assert not torch.equal(got[q], normed[q]) and not torch.equal(normed[q], x[q])          # both steps did something
+
+
 # ---- am_flow_step_f32 ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("additive", [True, False])
 @pytest.mark.parametrize("nb", [1, 2, 3])

@@ -1,5 +1,5 @@
 """HipAutoencoder(exact_fp32=True) without a GPU: the orchestration of actionmesh_amd/autoencoder_f32.py runs on torch-CPU restatements of
-its six kernels (tests/_stage2_fp32.TorchBackend) against the reference's own fp32 displacement and the oracle, and the declarations,
+its six kernels (tests/_f32_backend.TorchBackend) against the reference's own fp32 displacement and the oracle, and the declarations,
 refusals and switches that reach the mode are checked.  The same assertions run on the kernels in tests/test_stage2_fp32_gpu.py.
 
 Bound: rel-L2 <= 2e-5 (tests/_stage2_fp32.py).  Measured with the restatements (torch CPU kernels): ae_tiny 5.0e-7, ae_arch 7.0e-7; the cases
@@ -44,7 +44,7 @@ def test_vertex_animation_passes_the_exact_mode_through():
 def test_entry_point_is_declared_and_bound():
     from actionmesh_amd import _lib as L
     from actionmesh_amd import ops
-    from actionmesh_amd.denoiser_f32 import HipF32Backend
+    from actionmesh_amd.f32_backend import HipF32Backend
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "actionmesh_amd.h")).read()
     assert "am_rope_f32" in L.SYMBOLS and re.search(r"\bam_rope_f32\(", hdr)
     assert L.ABI_VERSION == 2 and callable(ops.rope_f32)
